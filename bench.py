@@ -9,6 +9,14 @@ KS + blind-rotation launches -> result (repeat matches replay the cached plan;
 template plan with the new slots bound).  --matches M: each step is M matches of
 the pattern over M contents in shared launches (fr_has_match_batch).
 
+A plain run (`--gpus 1 --steps N --warmup W`) does what the headline figure needs: set-up
+(keys, encrypted content), W warm-up steps, the N timed steps, the result line.  The roofline
+block is read off the timed steps' own device timers.  --full adds every secondary record
+(fresh_content, inflight, inflight_1ctx, faithful, faithful_tree, kernel_saturated,
+latency_probe, power, cpu_baseline; N > 1: weak_matches, strong_starts, step_latency), each a
+run of its own after the timed steps; without --full they are null.  --dump-outputs DIR writes
+the last timed step's result ciphertexts and their decryption as .npy (dump_outputs).
+
 Workloads (--workload; BASELINE.json configs): metric = /abc/ on 256 printable
 chars with "abc" at 200; config2 = /abc/ on 64 chars (run it with --params
 k2n1024, BASELINE's "N=1024"); config3 = /^[a-z0-9]+$/ on 256 chars (grammar
@@ -315,6 +323,19 @@ def north_star_hbm(per_shape):
                     "algorithmic figure is not a physical rate (it exceeds 1.0 at >= 512 bootstraps per launch)"}
 
 
+def dump_outputs(out_dir: str, words, decrypted):
+    """--dump-outputs: what the last timed step returned to its caller, as float64 .npy files.
+    words: one (4, lwe_len) u64 radix ciphertext per result handle; a u64 does not fit a float64,
+    so its upper and lower 32 bits go to two arrays, each exact (the message sits in the upper
+    bits).  The inputs are seeded (content, encryptions, server key), so two builds given the same
+    arguments are compared array for array."""
+    os.makedirs(out_dir, exist_ok=True)
+    w = np.asarray(words, dtype=np.uint64).reshape(len(words), 4, -1)
+    np.save(os.path.join(out_dir, "result_words_hi32.npy"), (w >> np.uint64(32)).astype(np.float64))
+    np.save(os.path.join(out_dir, "result_words_lo32.npy"), (w & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    np.save(os.path.join(out_dir, "result_decrypted.npy"), np.asarray(decrypted, dtype=np.float64))
+
+
 class EnergyMeter:
     """Socket energy of this rank's GPU from the driver's energy accumulator (amdsmi; no HIP),
     read outside the timed regions: average power and energy per bootstrap of a region, and the
@@ -492,8 +513,17 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1,
                     help="GPUs (ranks); N > 1 without WORLD_SIZE set starts the N rank processes itself")
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every secondary measurement and check (fresh content, "
+                         "matches in flight, other lowerings, saturated kernel and latency probes, power, CPU "
+                         "baseline; N > 1: weak_matches, strong_starts, step_latency), each under its own option "
+                         "below; without --full those records are null")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step returned as DIR/<name>.npy (float64): the result "
+                         "ciphertexts' u64 words as result_words_hi32 / result_words_lo32 (upper / lower 32 bits, "
+                         "exact), and result_decrypted")
     ap.add_argument("--workload", default="metric", choices=sorted(WORKLOADS))
     ap.add_argument("--scaling", default="", choices=["", "strong", "weak"],
                     help="N>1: weak = per-GPU work fixed; strong = the workload's content split across ranks (one "
@@ -563,6 +593,9 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    full = args.full
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:], args.job_timeout))
@@ -820,7 +853,7 @@ def main():
         for h in o:
             ctx.release(h)
 
-    meter = EnergyMeter(torch.cuda.get_device_properties(device)) if rank == 0 and not args.no_power else None
+    meter = EnergyMeter(torch.cuda.get_device_properties(device)) if full and rank == 0 and not args.no_power else None
     ctx.set_profiling(True)
     t_before = ctx.device_timers()
     barrier()
@@ -890,9 +923,11 @@ def main():
         exp = expected if shard == "matches" else expected[:1]
         if result != exp:
             print(f"WARNING: decrypted results {result} != expected {exp}", file=sys.stderr)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, words, result)
 
     fresh = None
-    if args.fresh_steps and world == 1 and M == 1:
+    if full and args.fresh_steps and world == 1 and M == 1:
         # newly encrypted content for every match (device encryption before the timing): the
         # template plan is replayed with each content's slots bound; timed like the replay
         # (back-to-back matches, one synchronise at the end)
@@ -915,7 +950,7 @@ def main():
 
     weak_matches = None
     wm_steps = args.steps if args.weak_matches_steps < 0 else args.weak_matches_steps
-    if shard == "starts" and dist is not None and wm_steps > 0:
+    if full and shard == "starts" and dist is not None and wm_steps > 0:
         # secondary record: weak scaling by matches (every rank one full-length match of
         # the workload on its own content per step, no data-path collective)
         own = make_content(kind, chars, seed=rank)
@@ -951,7 +986,7 @@ def main():
     if starts and strong and dist is not None:
         strong_starts = {"same_as_value": True,
                          "note": "the timed region is already the named length split by start offsets"}
-    elif dist is not None and ss_steps > 0:
+    elif full and dist is not None and ss_steps > 0:
         # secondary record: the workload's NAMED length (256 chars for the metric, 1,024 for
         # config 4, ...) split by start offsets across the ranks -- north_star's split at
         # BASELINE's length, strong scaling -- beside a value on other terms; never `value`
@@ -994,7 +1029,7 @@ def main():
                 ctx.release(int(h))
 
     inflight = None
-    if args.inflight > 1 and world == 1 and M == 1 and rank == 0 and not starts:
+    if full and args.inflight > 1 and world == 1 and M == 1 and rank == 0 and not starts:
         # serving view: C independent single matches in flight, one per context (each context
         # its own stream, arena and copy of the keys), dealt round-robin; each match is the
         # full workload match, bit-identical to the timed region's
@@ -1031,7 +1066,7 @@ def main():
             c.close()
 
     inflight_1ctx = None
-    if args.lanes > 1 and world == 1 and M == 1 and rank == 0 and not starts:
+    if full and args.lanes > 1 and world == 1 and M == 1 and rank == 0 and not starts:
         # serving with ONE key: the same matches in flight on the lanes (streams) of this
         # context (fr_set_lanes), each lane its own plan copy; consecutive asynchronous
         # matches round-robin over the lanes, so a match's small levels share the chip with
@@ -1059,7 +1094,7 @@ def main():
                                  "one context (fr_set_lanes), each lane its own plan copy. Never `value`."}
 
     step_latency = None
-    if starts:
+    if full and starts:
         # latency of one start-sharded match end to end (match, export, gather, the OR on
         # rank 0), synchronised before and after; the timed region pipelines these
         lat_ms = []
@@ -1100,7 +1135,7 @@ def main():
                 "vs_threshold_ms": ms_per_step_local}
 
     faithful = faithful_tree = None
-    if world == 1 and M == 1 and rank == 0 and lowering == F.LOWER_THRESHOLD and not starts:
+    if full and world == 1 and M == 1 and rank == 0 and lowering == F.LOWER_THRESHOLD and not starts:
         if args.faithful_steps > 0:
             faithful = lowering_record(F.LOWER_FAITHFUL, args.faithful_steps,
                                        "faithful (FR_LOWER_FAITHFUL: eq/gt/le = 3 PBS, and/or = 1, not linear; the "
@@ -1115,7 +1150,7 @@ def main():
 
     kernel = None
     e_sat0 = e_sat1 = None
-    if args.saturate and rank == 0:
+    if full and args.saturate and rank == 0:
         src = [h for h in handles if h != F.NULL_CT]
         hs = [src[i % len(src)] for i in range(args.saturate)]
         ctx.dev_bench_pbs(hs, 1)  # warm-up, as the latency probe below
@@ -1128,7 +1163,7 @@ def main():
                   "br_pbs_per_s": it * args.saturate / (br_sat / 1e3)}
 
     probe = None
-    if args.probe.strip("' ") and rank == 0:
+    if full and args.probe.strip("' ") and rank == 0:
         src = [h for h in handles if h != F.NULL_CT]
         probe = {}
         for cnt in [int(x) for x in args.probe.replace("'", "").split(",") if x.strip("' ")]:
@@ -1186,7 +1221,7 @@ def main():
     br_avg_ms = br_ms / max(br_launches, 1)
     phys = pmc["traffic"] / (br_avg_ms / 1e3) / 1e9 if pmc and pmc.get("traffic") and br_avg_ms > 0 else None
     cpu = None
-    if args.cpu_sample > 0 and world == 1 and dist is None:  # its word check reads the plain match's output
+    if full and args.cpu_sample > 0 and world == 1 and dist is None:  # its word check reads the plain match's output
         cpu = cpu_baseline(params, content, pattern, grammar, engine, lowering, args.cpu_sample,
                            args.cpu_match_max_jobs, lwes0[0] if lwes0 else None, words0)
     ms_per_step = elapsed / args.steps * 1e3
@@ -1216,6 +1251,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": full,
         "ms_per_step": ms_per_step,
         "higher_is_better": True,
         "scaling": "strong" if strong else "weak",

@@ -148,13 +148,68 @@ def test_job_timeout_kills_stuck_ranks(tmp_path):
     assert rc == 124 and time.time() - t < 120
 
 
+def test_dump_outputs_splits_words_exactly(tmp_path):
+    """--dump-outputs: u64 ciphertext words leave as two float64 arrays (upper / lower 32 bits)
+    that recombine to the words bit for bit, beside the decrypted results"""
+    import numpy as np
+
+    import bench
+    rng = np.random.default_rng(3)
+    words = [rng.integers(0, 2 ** 64, (4, 11), dtype=np.uint64) for _ in range(2)]
+    words[0][0, 0], words[0][0, 1] = 2 ** 64 - 1, 2 ** 53 + 1  # neither fits a float64 whole
+    bench.dump_outputs(str(tmp_path / "o"), words, [1, 0])
+    hi = np.load(tmp_path / "o" / "result_words_hi32.npy")
+    lo = np.load(tmp_path / "o" / "result_words_lo32.npy")
+    assert hi.dtype == lo.dtype == np.float64 and hi.shape == lo.shape == (2, 4, 11)
+    back = (hi.astype(np.uint64) << np.uint64(32)) | lo.astype(np.uint64)
+    assert np.array_equal(back, np.stack(words))
+    dec = np.load(tmp_path / "o" / "result_decrypted.npy")
+    assert dec.dtype == np.float64 and dec.tolist() == [1.0, 0.0]
+
+
+def test_steps_must_be_positive():
+    res = subprocess.run([sys.executable, BENCH, "--steps", "0"], capture_output=True, text=True, timeout=120,
+                         env=_env())
+    assert res.returncode == 2 and "--steps must be >= 1" in res.stderr
+
+
+SECONDARY = ("fresh_content", "inflight", "inflight_1ctx", "faithful", "faithful_tree", "kernel_saturated",
+             "latency_probe", "power", "cpu_baseline", "weak_matches", "strong_starts", "step_latency")
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run times exactly --steps steps, leaves every secondary record null (they belong
+    to --full) and --dump-outputs writes the last step's result: the ciphertext words and a
+    decryption equal to the line's."""
+    import numpy as np
+
+    res = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path / "o")], capture_output=True, text=True, timeout=120,
+                         env=_env())
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert d["value"] == pytest.approx(d["blind_rotations_per_step"] / (d["ms_per_step"] / 1e3))
+    assert d["result_decrypted"] == d["result_expected"] == [1]
+    assert [k for k in SECONDARY if d[k] is not None] == []
+    assert d["roofline"]["br_launches"] > 0  # the timed steps' own timers
+    hi, lo, dec = (np.load(tmp_path / "o" / f"{f}.npy") for f in
+                   ("result_words_hi32", "result_words_lo32", "result_decrypted"))
+    assert dec.tolist() == [1.0]
+    assert hi.dtype == lo.dtype == np.float64 and hi.shape == lo.shape and hi.shape[:2] == (1, 4)
+    assert hi.max() < 2 ** 32 and lo.max() < 2 ** 32 and hi.any() and lo.any()
+
+
 @pytest.mark.gpu
 def test_one_rank_rccl_group_pipeline():
     """The N > 1 start-shard pipeline over a one-rank RCCL group on the GPU (bench.py
     --one-rank-group): process group, stream-ordered export, device all_gather, the OR on
     rank 0 and the all-reduces run, and every step's OR decrypts to the expected bit."""
-    res = subprocess.run([sys.executable, BENCH, "--one-rank-group", "--steps", "3", "--warmup", "1", "--cpu-sample", "0",
-                          "--inflight", "0", "--faithful-steps", "0", "--fresh-steps", "0", "--probe=", "--saturate", "0",
+    res = subprocess.run([sys.executable, BENCH, "--full", "--one-rank-group", "--steps", "3", "--warmup", "1",
+                          "--cpu-sample", "0", "--inflight", "0", "--faithful-steps", "0", "--fresh-steps", "0", "--probe=", "--saturate", "0",
                           "--weak-matches-steps", "2"], capture_output=True, text=True, timeout=300, env=_env())
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -173,8 +228,8 @@ def test_two_gloo_ranks_config4_named_length(parts):
     the named 1,024 characters split by start offsets (strong scaling), one JSON line, every
     step's OR decrypting to the expected bit, both ranks reporting; with each rank's parts
     (--start-parts 0: 16 // 2 = 8, fr_has_match_parts) and with one boolean per rank (1)"""
-    res = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dist-backend", "gloo", "--workload", "config4",
-                          "--steps", "2", "--warmup", "1", "--weak-matches-steps", "0", "--probe=", "--saturate", "0",
+    res = subprocess.run([sys.executable, BENCH, "--full", "--gpus", "2", "--dist-backend", "gloo",
+                          "--workload", "config4", "--steps", "2", "--warmup", "1", "--weak-matches-steps", "0", "--probe=", "--saturate", "0",
                           "--start-parts", str(parts), "--job-timeout", "280"], capture_output=True, text=True,
                          timeout=300, env=_env())
     assert res.returncode == 0, res.stderr[-3000:]

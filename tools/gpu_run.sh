@@ -43,36 +43,36 @@ for part in "${P[@]}"; do
     tail -2 "$out/profile.log" ;;
   bench)
     pmc=(); [ -f "$out/prof/pmc_summary.json" ] && pmc=(--pmc "$out/prof/pmc_summary.json")
-    step 500 "$out/bench.err" python3 bench.py --steps 20 --warmup 5 "${pmc[@]}" --out "$out/bench.json"
+    step 500 "$out/bench.err" python3 bench.py --full --steps 20 --warmup 5 "${pmc[@]}" --out "$out/bench.json"
     summ "$out/bench.json" ;;
   batch)
     for M in 8 16; do
-      step 300 "$out/bench_m$M.err" python3 bench.py --steps 5 --warmup 2 --matches $M --cpu-sample 0 --probe= \
+      step 300 "$out/bench_m$M.err" python3 bench.py --full --steps 5 --warmup 2 --matches $M --cpu-sample 0 --probe= \
         --fresh-steps 0 --saturate 0 --faithful-steps 0 --faithful-tree-steps 0 --out "$out/bench_m$M.json"
       summ "$out/bench_m$M.json"
     done ;;
   workloads)
     for w in "config2 --params k2n1024" "config2" "metric --params k2n1024" "config3" "config4" "config5"; do
       tag=$(echo $w | tr -d ' -')
-      step 400 "$out/bench_$tag.err" python3 bench.py --workload $w --steps 5 --warmup 2 --cpu-sample 0 --saturate 0 \
+      step 400 "$out/bench_$tag.err" python3 bench.py --full --workload $w --steps 5 --warmup 2 --cpu-sample 0 --saturate 0 \
         --faithful-steps 0 --faithful-tree-steps 0 --out "$out/bench_$tag.json"
       summ "$out/bench_$tag.json"
     done ;;
   rehearsal)
     for mode in "metric" "config4" "config5" "metric --shard matches"; do
       tag=$(echo $mode | sed 's/ --shard /_/')
-      step 500 "$out/rehearsal_2rank_$tag.err" python3 bench.py --gpus 2 --dist-backend gloo --workload $mode \
+      step 500 "$out/rehearsal_2rank_$tag.err" python3 bench.py --full --gpus 2 --dist-backend gloo --workload $mode \
         --steps 5 --warmup 1 --out "$out/rehearsal_2rank_$tag.json"
       summ "$out/rehearsal_2rank_$tag.json"
     done ;;
   rehearsal4)
     for mode in metric config4; do
-      step 600 "$out/rehearsal_4rank_$mode.err" python3 bench.py --gpus 4 --dist-backend gloo --workload $mode \
+      step 600 "$out/rehearsal_4rank_$mode.err" python3 bench.py --full --gpus 4 --dist-backend gloo --workload $mode \
         --steps 3 --warmup 1 --saturate 0 --probe= --out "$out/rehearsal_4rank_$mode.json"
       summ "$out/rehearsal_4rank_$mode.json"
     done ;;
   rccl1)
-    step 300 "$out/rccl1.err" python3 bench.py --one-rank-group --steps 10 --warmup 2 --cpu-sample 0 --inflight 0 \
+    step 300 "$out/rccl1.err" python3 bench.py --full --one-rank-group --steps 10 --warmup 2 --cpu-sample 0 --inflight 0 \
       --faithful-steps 0 --faithful-tree-steps 0 --out "$out/rccl1.json"
     summ "$out/rccl1.json" ;;
   *) echo "unknown part $part"; exit 2 ;;
