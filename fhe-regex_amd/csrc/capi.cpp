@@ -847,12 +847,39 @@ int fr_load_client_key(fr_ctx* ctx, const uint8_t* data, size_t len) {
     })
 }
 
+// Every draw below runs under one RngKey (chacha.h).  The seeded entry points build
+// theirs with from_seed and the keyed ones with from_bytes, or from_os for a NULL
+// key; both then share one body.  The host copy of the key is wiped on the way out.
+namespace {
+struct ScopedKey {
+    RngKey k;
+    explicit ScopedKey(uint64_t seed) : k(RngKey::from_seed(seed)) {}
+    explicit ScopedKey(const uint8_t* key32) : k(key32 ? RngKey::from_bytes(key32) : RngKey::from_os()) {}
+    ~ScopedKey() { wipe_key(k); }
+    ScopedKey(const ScopedKey&) = delete;
+    ScopedKey& operator=(const ScopedKey&) = delete;
+};
+}  // namespace
+
+static void gen_client_key_with(fr_ctx* ctx, const RngKey& key) {
+    ctx->ck = gen_client_key(ctx->p, key);
+    ctx->has_ck = true;
+    ctx->has_sk = false;
+}
+
 int fr_gen_client_key(fr_ctx* ctx, uint64_t seed) {
     FR_TRY({
         NEED(ctx);
-        ctx->ck = gen_client_key(ctx->p, seed);
-        ctx->has_ck = true;
-        ctx->has_sk = false;
+        ScopedKey key(seed);
+        gen_client_key_with(ctx, key.k);
+    })
+}
+
+int fr_gen_client_key_keyed(fr_ctx* ctx, const uint8_t* key32) {
+    FR_TRY({
+        NEED(ctx);
+        ScopedKey key(key32);
+        gen_client_key_with(ctx, key.k);
     })
 }
 
@@ -868,25 +895,44 @@ int fr_serialize_client_key(fr_ctx* ctx, uint8_t* buf, size_t cap, size_t* writt
     })
 }
 
+// where the server key is generated (fr_set_keygen); checked before a key is drawn
+static bool server_keygen_on_device(fr_ctx* ctx) {
+    if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
+    const bool on_dev = ctx->dev && ctx->p.ring == FR_RING_FFT && ctx->keygen != FR_KEYGEN_HOST;
+    if (ctx->keygen == FR_KEYGEN_DEVICE && !on_dev)
+        throw Error(ctx->dev ? FR_ERR_INVALID : FR_ERR_NO_DEVICE, "device keygen needs a device and the FFT ring");
+    return on_dev;
+}
+static void gen_server_key_with(fr_ctx* ctx, bool on_dev, const RngKey& key) {
+    ctx->has_sk = false;
+    if (on_dev) {
+        ctx->ksk.clear();
+        ctx->bsk.clear();
+        ctx->dev->gen_server_key(ctx->ck, key);
+    } else {
+        gen_ksk(ctx->p, ctx->ck, key, ctx->ksk);
+        gen_bsk(ctx->p, ctx->ck, key, ctx->bsk);
+        if (ctx->dev) ctx->dev->upload_keys(ctx->ksk, ctx->bsk);
+    }
+    ctx->sk_on_device = on_dev;
+    ctx->has_sk = true;
+}
+
 int fr_gen_server_key(fr_ctx* ctx, uint64_t seed) {
     FR_TRY({
         NEED(ctx);
-        if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
-        const bool on_dev = ctx->dev && ctx->p.ring == FR_RING_FFT && ctx->keygen != FR_KEYGEN_HOST;
-        if (ctx->keygen == FR_KEYGEN_DEVICE && !on_dev)
-            throw Error(ctx->dev ? FR_ERR_INVALID : FR_ERR_NO_DEVICE, "device keygen needs a device and the FFT ring");
-        ctx->has_sk = false;
-        if (on_dev) {
-            ctx->ksk.clear();
-            ctx->bsk.clear();
-            ctx->dev->gen_server_key(ctx->ck, seed);
-        } else {
-            gen_ksk(ctx->p, ctx->ck, seed, ctx->ksk);
-            gen_bsk(ctx->p, ctx->ck, seed, ctx->bsk);
-            if (ctx->dev) ctx->dev->upload_keys(ctx->ksk, ctx->bsk);
-        }
-        ctx->sk_on_device = on_dev;
-        ctx->has_sk = true;
+        const bool on_dev = server_keygen_on_device(ctx);
+        ScopedKey key(seed);
+        gen_server_key_with(ctx, on_dev, key.k);
+    })
+}
+
+int fr_gen_server_key_keyed(fr_ctx* ctx, const uint8_t* key32) {
+    FR_TRY({
+        NEED(ctx);
+        const bool on_dev = server_keygen_on_device(ctx);
+        ScopedKey key(key32);
+        gen_server_key_with(ctx, on_dev, key.k);
     })
 }
 
@@ -934,13 +980,28 @@ int fr_load_server_key(fr_ctx* ctx, const uint64_t* ksk, size_t ksk_len, const u
     })
 }
 
+// preconditions of fr_encrypt_blocks[_keyed], checked before a key is drawn
+static void check_encrypt_blocks(fr_ctx* ctx, const uint8_t* msgs, size_t count, const uint64_t* out) {
+    NEED(ctx && (msgs || !count) && (out || !count));
+    if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
+    for (size_t i = 0; i < count; ++i) NEED(msgs[i] < 16);
+}
+
 int fr_encrypt_blocks(fr_ctx* ctx, const uint8_t* msgs, size_t count, uint64_t seed, uint64_t first_block,
                       uint64_t* out) {
     FR_TRY({
-        NEED(ctx && (msgs || !count) && (out || !count));
-        if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
-        for (size_t i = 0; i < count; ++i) NEED(msgs[i] < 16);
-        encrypt_blocks(ctx->p, ctx->ck, msgs, count, seed, first_block, out);
+        check_encrypt_blocks(ctx, msgs, count, out);
+        ScopedKey key(seed);
+        encrypt_blocks(ctx->p, ctx->ck, msgs, count, key.k, first_block, out);
+    })
+}
+
+int fr_encrypt_blocks_keyed(fr_ctx* ctx, const uint8_t* msgs, size_t count, const uint8_t* key32,
+                            uint64_t first_block, uint64_t* out) {
+    FR_TRY({
+        check_encrypt_blocks(ctx, msgs, count, out);
+        ScopedKey key(key32);
+        encrypt_blocks(ctx->p, ctx->ck, msgs, count, key.k, first_block, out);
     })
 }
 
@@ -956,34 +1017,67 @@ static std::vector<uint8_t> str_blocks(const char* s, size_t len) {
     return msgs;
 }
 
+// radix messages of fr_encrypt_str[_keyed]'s string, after its preconditions
+static std::vector<uint8_t> check_encrypt_str(fr_ctx* ctx, const char* s, size_t len, const void* out) {
+    NEED(ctx && (s || !len) && (out || !len));
+    if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
+    return str_blocks(s, len);
+}
+
 int fr_encrypt_str(fr_ctx* ctx, const char* s, size_t len, uint64_t seed, uint64_t* out) {
     FR_TRY({
-        NEED(ctx && (s || !len) && (out || !len));
-        if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
-        const std::vector<uint8_t> msgs = str_blocks(s, len);
-        encrypt_blocks(ctx->p, ctx->ck, msgs.data(), msgs.size(), seed, 0, out);
+        const std::vector<uint8_t> msgs = check_encrypt_str(ctx, s, len, out);
+        ScopedKey key(seed);
+        encrypt_blocks(ctx->p, ctx->ck, msgs.data(), msgs.size(), key.k, 0, out);
     })
+}
+
+int fr_encrypt_str_keyed(fr_ctx* ctx, const char* s, size_t len, const uint8_t* key32, uint64_t* out) {
+    FR_TRY({
+        const std::vector<uint8_t> msgs = check_encrypt_str(ctx, s, len, out);
+        ScopedKey key(key32);
+        encrypt_blocks(ctx->p, ctx->ck, msgs.data(), msgs.size(), key.k, 0, out);
+    })
+}
+
+// preconditions of fr_encrypt_upload_str[_keyed] in the seeded call's order: client key,
+// device, ASCII content
+static std::vector<uint8_t> check_encrypt_upload_str(fr_ctx* ctx, const char* s, size_t len, const fr_ct* out) {
+    NEED(ctx && (s || !len) && (out || !len));
+    if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
+    (void)ctx->device();
+    return str_blocks(s, len);
+}
+static void encrypt_upload_with(fr_ctx* ctx, const std::vector<uint8_t>& msgs, const RngKey& key, fr_ct* out) {
+    Device& dev = ctx->device();
+    std::vector<int> slots(msgs.size());
+    for (auto& x : slots) x = dev.alloc_slot();
+    try {
+        dev.encrypt_to_slots(ctx->ck, msgs.data(), msgs.size(), key, 0, slots.data());
+    } catch (...) {
+        for (int x : slots) dev.free_slot(x);
+        throw;
+    }
+    for (size_t i = 0; i < msgs.size() / 4; ++i) {
+        HandleRec r;
+        for (int b = 0; b < 4; ++b) r.b[b].slot = slots[4 * i + b];
+        out[i] = ctx->new_handle(r);
+    }
 }
 
 int fr_encrypt_upload_str(fr_ctx* ctx, const char* s, size_t len, uint64_t seed, fr_ct* out) {
     FR_TRY({
-        NEED(ctx && (s || !len) && (out || !len));
-        if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
-        Device& dev = ctx->device();
-        const std::vector<uint8_t> msgs = str_blocks(s, len);
-        std::vector<int> slots(msgs.size());
-        for (auto& x : slots) x = dev.alloc_slot();
-        try {
-            dev.encrypt_to_slots(ctx->ck, msgs.data(), msgs.size(), seed, 0, slots.data());
-        } catch (...) {
-            for (int x : slots) dev.free_slot(x);
-            throw;
-        }
-        for (size_t i = 0; i < len; ++i) {
-            HandleRec r;
-            for (int b = 0; b < 4; ++b) r.b[b].slot = slots[4 * i + b];
-            out[i] = ctx->new_handle(r);
-        }
+        const std::vector<uint8_t> msgs = check_encrypt_upload_str(ctx, s, len, out);
+        ScopedKey key(seed);
+        encrypt_upload_with(ctx, msgs, key.k, out);
+    })
+}
+
+int fr_encrypt_upload_str_keyed(fr_ctx* ctx, const char* s, size_t len, const uint8_t* key32, fr_ct* out) {
+    FR_TRY({
+        const std::vector<uint8_t> msgs = check_encrypt_upload_str(ctx, s, len, out);
+        ScopedKey key(key32);
+        encrypt_upload_with(ctx, msgs, key.k, out);
     })
 }
 

@@ -43,6 +43,7 @@ struct DeviceTimers {
 };
 
 struct ClientKey;
+struct RngKey;
 
 class Device {
   public:
@@ -60,11 +61,11 @@ class Device {
     // server-key generation on the device (keygen.hip; FFT ring): the same keys
     // as gen_ksk + gen_bsk on the host, bit for bit; the torus keys stay on the
     // device for download_server_key
-    void gen_server_key(const ClientKey& ck, uint64_t seed);
+    void gen_server_key(const ClientKey& ck, const RngKey& key);
     void download_server_key(uint64_t* ksk, size_t ksk_len, uint64_t* bsk, size_t bsk_len);
     // fresh encryptions of block messages (encrypt_blocks, keys.h) written into
     // allocated arena slots, bit-identical to the host encryption
-    void encrypt_to_slots(const ClientKey& ck, const uint8_t* msgs, size_t count, uint64_t seed, uint64_t first_block,
+    void encrypt_to_slots(const ClientKey& ck, const uint8_t* msgs, size_t count, const RngKey& key, uint64_t first_block,
                           const int* slots);
 
     // arena of big-LWE slots

@@ -43,8 +43,12 @@ __device__ __forceinline__ uint64_t chacha_u64(const uint32_t* w, int q) {
     return (uint64_t)w[2 * q] | ((uint64_t)w[2 * q + 1] << 32);
 }
 
+// The generator key (RngKey, chacha.h) reaches every kernel below by value: a
+// kernel argument is wave-uniform, so its 8 words are scalar operands of the
+// ChaCha rounds and are never written to global memory.
+
 // ksk[row][t], row = i * L + j; masks are u64 numbers row * n + t of STREAM_KSK_MASK
-__global__ void __launch_bounds__(64) k_gen_ksk(uint64_t seed, int n, int L, int B, const uint64_t* __restrict__ s_small,
+__global__ void __launch_bounds__(64) k_gen_ksk(RngKey key, int n, int L, int B, const uint64_t* __restrict__ s_small,
                                                 const uint64_t* __restrict__ s_big, const int64_t* __restrict__ noise,
                                                 uint64_t* __restrict__ ksk) {
     const int row = blockIdx.x, lane = threadIdx.x;
@@ -54,7 +58,7 @@ __global__ void __launch_bounds__(64) k_gen_ksk(uint64_t seed, int n, int L, int
     uint64_t acc = 0;
     for (uint64_t b = (first >> 3) + lane; b <= ((last - 1) >> 3); b += 64) {
         uint32_t w[16];
-        chacha_block(seed, STREAM_KSK_MASK, b, w);
+        chacha_block(key, STREAM_KSK_MASK, b, w);
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             const uint64_t idx = b * 8 + q;
@@ -74,7 +78,7 @@ __global__ void __launch_bounds__(64) k_gen_ksk(uint64_t seed, int n, int L, int
 // one GGSW row (w, r) of the torus BSK [w][r][c][coef]; 256 threads, N / 256
 // coefficients per thread; LDS: the mask polynomial A_j (N u64)
 template <int N>
-__global__ void __launch_bounds__(256) k_gen_bsk(uint64_t seed, int k, const uint64_t* __restrict__ s_big,
+__global__ void __launch_bounds__(256) k_gen_bsk(RngKey key, int k,const uint64_t* __restrict__ s_big,
                                                  const uint8_t* __restrict__ msg, const int32_t* __restrict__ noise,
                                                  uint64_t gadget, uint64_t* __restrict__ bsk) {
     constexpr int PER = N / 256;
@@ -90,7 +94,7 @@ __global__ void __launch_bounds__(256) k_gen_bsk(uint64_t seed, int k, const uin
         const uint64_t base = (((uint64_t)w * kp1 + r) * k + j) * N;  // N % 8 == 0: whole ChaCha blocks
         for (int b = tid; b < N / 8; b += 256) {
             uint32_t wd[16];
-            chacha_block(seed, STREAM_BSK_MASK, (base >> 3) + b, wd);
+            chacha_block(key, STREAM_BSK_MASK, (base >> 3) + b, wd);
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 uint64_t v = chacha_u64(wd, q);
@@ -189,7 +193,7 @@ __global__ void __launch_bounds__(256) k_bsk_fourier(const uint64_t* __restrict_
 // arena slots (encrypt_str, src/regex/ciphertext.rs:32-40):
 // one wave per block; masks are u64 numbers qb * kN + t of STREAM_ENC_MASK
 // (kN % 8 == 0: whole ChaCha blocks), body = <mask, s_big> + m 2^59 + noise
-__global__ void __launch_bounds__(64) k_encrypt_blocks(uint64_t seed, int big, const uint64_t* __restrict__ s_big,
+__global__ void __launch_bounds__(64) k_encrypt_blocks(RngKey key, int big,const uint64_t* __restrict__ s_big,
                                                        const uint8_t* __restrict__ msgs,
                                                        const int64_t* __restrict__ noise, uint64_t first_block,
                                                        const int* __restrict__ slots, int stride,
@@ -200,7 +204,7 @@ __global__ void __launch_bounds__(64) k_encrypt_blocks(uint64_t seed, int big, c
     uint64_t acc = 0;
     for (int b = lane; b < big / 8; b += 64) {
         uint32_t w[16];
-        chacha_block(seed, STREAM_ENC_MASK, qb * (uint64_t)(big / 8) + b, w);
+        chacha_block(key, STREAM_ENC_MASK, qb * (uint64_t)(big / 8) + b, w);
 #pragma unroll
         for (int x = 0; x < 8; ++x) {
             const uint64_t v = chacha_u64(w, x);
@@ -212,7 +216,7 @@ __global__ void __launch_bounds__(64) k_encrypt_blocks(uint64_t seed, int big, c
     if (lane == 0) o[big] = acc + ((uint64_t)msgs[q] << DELTA_LOG) + (uint64_t)noise[q];
 }
 
-void Device::encrypt_to_slots(const ClientKey& ck, const uint8_t* msgs, size_t count, uint64_t seed,
+void Device::encrypt_to_slots(const ClientKey& ck, const uint8_t* msgs, size_t count, const RngKey& key,
                               uint64_t first_block, const int* slots) {
     if (!count) return;
     const int big = p_.big();
@@ -221,7 +225,7 @@ void Device::encrypt_to_slots(const ClientKey& ck, const uint8_t* msgs, size_t c
     for (size_t i = 0; i < count; ++i)
         if (slots[i] < 0 || (size_t)slots[i] >= next_slot_) throw Error(FR_ERR_INVALID, "device encryption: slot");
     std::vector<int64_t> noise;
-    enc_noise(p_, seed, first_block, count, noise);
+    enc_noise(p_, key, first_block, count, noise);
     const hipStream_t s = (hipStream_t)stream_;
     uint64_t* d_sb = nullptr;
     uint8_t* d_m = nullptr;
@@ -242,7 +246,7 @@ void Device::encrypt_to_slots(const ClientKey& ck, const uint8_t* msgs, size_t c
         KG_CHECK(hipMemcpyAsync(d_m, msgs, count, hipMemcpyHostToDevice, s));
         KG_CHECK(hipMemcpyAsync(d_n, noise.data(), 8 * count, hipMemcpyHostToDevice, s));
         KG_CHECK(hipMemcpyAsync(d_sl, slots, 4 * count, hipMemcpyHostToDevice, s));
-        k_encrypt_blocks<<<(unsigned)count, 64, 0, s>>>(seed, big, d_sb, d_m, d_n, first_block, d_sl, p_.slot_stride(),
+        k_encrypt_blocks<<<(unsigned)count, 64, 0, s>>>(key, big, d_sb, d_m, d_n, first_block, d_sl, p_.slot_stride(),
                                                        d_arena_);
         KG_CHECK(hipGetLastError());
         KG_CHECK(hipStreamSynchronize(s));
@@ -253,7 +257,7 @@ void Device::encrypt_to_slots(const ClientKey& ck, const uint8_t* msgs, size_t c
     cleanup();
 }
 
-void Device::gen_server_key(const ClientKey& ck, uint64_t seed) {
+void Device::gen_server_key(const ClientKey& ck, const RngKey& key) {
     if (p_.ring != FR_RING_FFT || !((p_.N == 2048 && p_.k == 1) || (p_.N == 1024 && p_.k == 2)))
         throw Error(FR_ERR_INVALID, "device keygen: FFT ring, (k, N) in {(1, 2048), (2, 1024)}");
     const int N = p_.N, M = N / 2, kp1 = p_.k + 1, n = p_.n, L = p_.ks_level;
@@ -264,8 +268,8 @@ void Device::gen_server_key(const ClientKey& ck, uint64_t seed) {
     // host: the noise draws and per-GGSW messages
     std::vector<int64_t> ksk_noise;
     std::vector<int32_t> bsk_noise;
-    gen_ksk_noise(p_, seed, ksk_noise);
-    gen_bsk_noise_torus(p_, seed, bsk_noise);
+    gen_ksk_noise(p_, key, ksk_noise);
+    gen_bsk_noise_torus(p_, key, bsk_noise);
     const std::vector<uint8_t> msg = ggsw_messages(p_, ck);
 
     uint64_t *d_ss = nullptr, *d_sb = nullptr;
@@ -296,7 +300,7 @@ void Device::gen_server_key(const ClientKey& ck, uint64_t seed) {
         (void)hipFree(d_ksk_);
         d_ksk_ = nullptr;
         KG_CHECK(hipMalloc(&d_ksk_, 8 * rows * (n + 1)));
-        k_gen_ksk<<<(unsigned)rows, 64, 0, s>>>(seed, n, L, p_.ks_base_log, d_ss, d_sb, d_kn, d_ksk_);
+        k_gen_ksk<<<(unsigned)rows, 64, 0, s>>>(key, n, L, p_.ks_base_log, d_ss, d_sb, d_kn, d_ksk_);
         KG_CHECK(hipGetLastError());
         build_ksk_limbs();
 
@@ -305,8 +309,8 @@ void Device::gen_server_key(const ClientKey& ck, uint64_t seed) {
         d_tbsk_ = nullptr;
         KG_CHECK(hipMalloc(&d_tbsk_, 8 * p_.bsk_len()));
         const uint64_t gadget = 1ULL << (64 - p_.pbs_base_log);
-        if (N == 2048) k_gen_bsk<2048><<<(unsigned)(nw * kp1), 256, 0, s>>>(seed, p_.k, d_sb, d_msg, d_bn, gadget, d_tbsk_);
-        else k_gen_bsk<1024><<<(unsigned)(nw * kp1), 256, 0, s>>>(seed, p_.k, d_sb, d_msg, d_bn, gadget, d_tbsk_);
+        if (N == 2048) k_gen_bsk<2048><<<(unsigned)(nw * kp1), 256, 0, s>>>(key, p_.k, d_sb, d_msg, d_bn, gadget, d_tbsk_);
+        else k_gen_bsk<1024><<<(unsigned)(nw * kp1), 256, 0, s>>>(key, p_.k, d_sb, d_msg, d_bn, gadget, d_tbsk_);
         KG_CHECK(hipGetLastError());
 
         // Fourier BSK in the lane layouts of the shapes in use (E = 4, and the throughput shape's)

@@ -9,7 +9,10 @@
 #include "chacha.h"
 #include "rns.h"
 
+#include <sys/random.h>
+
 #include <atomic>
+#include <cerrno>
 #include <climits>
 #include <cmath>
 #include <cstring>
@@ -17,11 +20,37 @@
 
 namespace fr {
 
+// ---------------------------------------------------------------- generator key
+void wipe_key(RngKey& k) { explicit_bzero(&k, sizeof k); }
+
+RngKey RngKey::from_os() {
+    uint8_t b[32];
+    size_t got = 0;
+    while (got < sizeof b) {
+        const ssize_t r = getrandom(b + got, sizeof b - got, 0);
+        if (r < 0) {
+            if (errno == EINTR) continue;
+            const int e = errno;
+            explicit_bzero(b, sizeof b);
+            throw Error(FR_ERR_RNG, std::string("getrandom: ") + std::strerror(e));
+        }
+        got += (size_t)r;
+    }
+    RngKey k = from_bytes(b);
+    explicit_bzero(b, sizeof b);
+    return k;
+}
+
+Rng::~Rng() {
+    wipe_key(key_);
+    explicit_bzero(w_, sizeof w_);
+}
+
 // ChaCha20: chacha.h (shared with the device key generator)
 uint64_t Rng::u64(uint64_t idx) {
     uint64_t blk = idx >> 3;
     if (!valid_ || blk != blk_) {
-        chacha_block(seed_, stream_, blk, w_);
+        chacha_block(key_, stream_, blk, w_);
         blk_ = blk;
         valid_ = true;
     }
@@ -138,7 +167,7 @@ std::vector<uint8_t> serialize_client_key(const ClientKey& ck) {
     return out;
 }
 
-ClientKey gen_client_key(const Params& p, uint64_t seed) {
+ClientKey gen_client_key(const Params& p, const RngKey& key) {
     auto bits = [](double x) {
         uint64_t v;
         std::memcpy(&v, &x, 8);
@@ -146,7 +175,7 @@ ClientKey gen_client_key(const Params& p, uint64_t seed) {
     };
     ClientKey ck;
     const size_t big = (size_t)p.big();
-    Rng r(seed, STREAM_CLIENT_KEY);
+    Rng r(key, STREAM_CLIENT_KEY);
     // tfhe-rs draws both secret keys as uniform binary vectors; bit 63 of ChaCha word i
     ck.s_big.resize(big);
     for (size_t i = 0; i < big; ++i) ck.s_big[i] = r.u64(i) >> 63;
@@ -264,11 +293,11 @@ static void parallel_for(int n, F&& fn) {
     for (auto& x : th) x.join();
 }
 
-void gen_ksk(const Params& p, const ClientKey& ck, uint64_t seed, std::vector<uint64_t>& ksk) {
+void gen_ksk(const Params& p, const ClientKey& ck, const RngKey& key, std::vector<uint64_t>& ksk) {
     const int big = p.big(), n = p.n, L = p.ks_level, B = p.ks_base_log;
     ksk.assign((size_t)big * L * (n + 1), 0);
     parallel_for(big, [&](int i) {
-        Rng rm(seed, STREAM_KSK_MASK), rn(seed, STREAM_KSK_NOISE);
+        Rng rm(key, STREAM_KSK_MASK), rn(key, STREAM_KSK_NOISE);
         for (int j = 0; j < L; ++j) {
             uint64_t row = (uint64_t)i * L + j;
             uint64_t* o = ksk.data() + row * (n + 1);
@@ -296,13 +325,13 @@ static uint64_t ggsw_msg(const Params& p, const ClientKey& ck, size_t w) {
 // 2^64 torus (mask uniform u64, body = sum_j A_j S_j + e, e ~ sigma_glwe 2^64),
 // plus m_w * 2^(64 - B) (the one-level gadget, B = pbs_base_log) on coefficient
 // 0 of component r.  A_j S_j (binary S) is summed exactly as rotations of A.
-static void gen_bsk_torus(const Params& p, const ClientKey& ck, uint64_t seed, std::vector<uint64_t>& bsk) {
+static void gen_bsk_torus(const Params& p, const ClientKey& ck, const RngKey& key, std::vector<uint64_t>& bsk) {
     const int k = p.k, N = p.N;
     const size_t kp1 = (size_t)k + 1, nw = p.bsk_ggsw();
     const uint64_t gadget = 1ULL << (64 - p.pbs_base_log);
     bsk.assign(p.bsk_len(), 0);
     parallel_for((int)nw, [&](int i) {
-        Rng rm(seed, STREAM_BSK_MASK), rn(seed, STREAM_BSK_NOISE);
+        Rng rm(key, STREAM_BSK_MASK), rn(key, STREAM_BSK_NOISE);
         const uint64_t msg = ggsw_msg(p, ck, (size_t)i);
         for (size_t r = 0; r < kp1; ++r) {
             uint64_t* row = bsk.data() + ((size_t)i * kp1 + r) * kp1 * N;
@@ -329,18 +358,18 @@ static void gen_bsk_torus(const Params& p, const ClientKey& ck, uint64_t seed, s
 // noise terms of the device key generator (keygen.hip): the same draws as
 // gen_ksk / gen_bsk_torus above (Box-Muller stays on the host, where libm is
 // the reference for the bits)
-void gen_ksk_noise(const Params& p, uint64_t seed, std::vector<int64_t>& e) {
+void gen_ksk_noise(const Params& p, const RngKey& key, std::vector<int64_t>& e) {
     const size_t rows = (size_t)p.big() * p.ks_level;
     e.resize(rows);
-    Rng rn(seed, STREAM_KSK_NOISE);
+    Rng rn(key, STREAM_KSK_NOISE);
     for (size_t row = 0; row < rows; ++row) e[row] = rn.gaussian(row, p.lwe_sigma);
 }
-void gen_bsk_noise_torus(const Params& p, uint64_t seed, std::vector<int32_t>& e) {
+void gen_bsk_noise_torus(const Params& p, const RngKey& key, std::vector<int32_t>& e) {
     const size_t polys = p.bsk_ggsw() * (size_t)(p.k + 1), N = (size_t)p.N;
     e.resize(polys * N);
     std::atomic<bool> ok{true};
     parallel_for((int)polys, [&](int q) {
-        Rng rn(seed, STREAM_BSK_NOISE);
+        Rng rn(key, STREAM_BSK_NOISE);
         for (size_t t = 0; t < N; ++t) {
             const int64_t v = rn.gaussian((uint64_t)q * N + t, p.glwe_sigma);
             if (v < INT32_MIN || v > INT32_MAX) ok = false;
@@ -349,9 +378,9 @@ void gen_bsk_noise_torus(const Params& p, uint64_t seed, std::vector<int32_t>& e
     });
     if (!ok) throw Error(FR_ERR_INVALID, "GLWE noise outside int32 (sigma too large for the device key generator)");
 }
-void enc_noise(const Params& p, uint64_t seed, uint64_t first_block, size_t count, std::vector<int64_t>& e) {
+void enc_noise(const Params& p, const RngKey& key, uint64_t first_block, size_t count, std::vector<int64_t>& e) {
     e.resize(count);
-    Rng rn(seed, STREAM_ENC_NOISE);
+    Rng rn(key, STREAM_ENC_NOISE);
     for (size_t q = 0; q < count; ++q) e[q] = rn.gaussian(first_block + q, p.glwe_sigma);
 }
 std::vector<uint8_t> ggsw_messages(const Params& p, const ClientKey& ck) {
@@ -360,9 +389,9 @@ std::vector<uint8_t> ggsw_messages(const Params& p, const ClientKey& ck) {
     return m;
 }
 
-void gen_bsk(const Params& p, const ClientKey& ck, uint64_t seed, std::vector<uint64_t>& bsk) {
+void gen_bsk(const Params& p, const ClientKey& ck, const RngKey& key, std::vector<uint64_t>& bsk) {
     if (p.ring == FR_RING_FFT) {
-        gen_bsk_torus(p, ck, seed, bsk);
+        gen_bsk_torus(p, ck, key, bsk);
         return;
     }
     const int k = p.k, N = p.N;
@@ -379,7 +408,7 @@ void gen_bsk(const Params& p, const ClientKey& ck, uint64_t seed, std::vector<ui
         }
     }
     parallel_for((int)nw, [&](int i) {
-        Rng rm(seed, STREAM_BSK_MASK), rn(seed, STREAM_BSK_NOISE);
+        Rng rm(key, STREAM_BSK_MASK), rn(key, STREAM_BSK_NOISE);
         std::vector<uint32_t> tmp(N), acc[2] = {std::vector<uint32_t>(N), std::vector<uint32_t>(N)};
         const uint64_t msg = ggsw_msg(p, ck, (size_t)i);
         for (size_t r = 0; r < kp1; ++r) {
@@ -411,10 +440,10 @@ void gen_bsk(const Params& p, const ClientKey& ck, uint64_t seed, std::vector<ui
 }
 
 // ---------------------------------------------------------------- client
-void encrypt_blocks(const Params& p, const ClientKey& ck, const uint8_t* msgs, size_t count, uint64_t seed,
+void encrypt_blocks(const Params& p, const ClientKey& ck, const uint8_t* msgs, size_t count, const RngKey& key,
                     uint64_t first_block, uint64_t* out) {
     const int big = p.big();
-    Rng rm(seed, STREAM_ENC_MASK), rn(seed, STREAM_ENC_NOISE);
+    Rng rm(key, STREAM_ENC_MASK), rn(key, STREAM_ENC_NOISE);
     for (size_t q = 0; q < count; ++q) {
         uint64_t* o = out + q * (big + 1);
         uint64_t qb = first_block + q, body = 0;

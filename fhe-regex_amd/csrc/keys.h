@@ -4,14 +4,16 @@
 #include <cstdint>
 #include <vector>
 
+#include "chacha.h"
 #include "common.h"
 
 namespace fr {
 
-// ChaCha20 (DJB layout: 64-bit block counter, 64-bit stream id); key words =
-// seed (2 words) + 6 fixed constants.  u64 number idx of a stream is words
-// 2*(idx%8), 2*(idx%8)+1 of block idx/8 — random access, so keygen is
-// parallel and deterministic.
+// ChaCha20 (DJB layout: 64-bit block counter, 64-bit stream id) under a 256-bit
+// RngKey (chacha.h): RngKey::from_seed for the reproducible draws of tests,
+// benchmarks and multi-rank keygen, from_bytes for a caller's key, from_os for the
+// OS CSPRNG.  u64 number idx of a stream is words 2*(idx%8), 2*(idx%8)+1 of
+// block idx/8 — random access, so keygen is parallel and deterministic.
 enum Stream : uint64_t {
     STREAM_KSK_MASK = 1,
     STREAM_KSK_NOISE = 2,
@@ -24,14 +26,18 @@ enum Stream : uint64_t {
 
 class Rng {
   public:
-    Rng(uint64_t seed, uint64_t stream) : seed_(seed), stream_(stream) {}
+    Rng(const RngKey& key, uint64_t stream) : key_(key), stream_(stream) {}
+    ~Rng();  // wipes its copy of the key and the last block
+    Rng(const Rng&) = delete;
+    Rng& operator=(const Rng&) = delete;
     uint64_t u64(uint64_t idx);
     // Box-Muller on words 2*idx, 2*idx+1; z * sigma * scale rounded to an
     // integer (scale 2^64: torus units; scale Q: units of Z_Q).
     int64_t gaussian(uint64_t idx, double sigma, double scale = 18446744073709551616.0);
 
   private:
-    uint64_t seed_, stream_, blk_ = 0;
+    RngKey key_;
+    uint64_t stream_, blk_ = 0;
     bool valid_ = false;
     uint32_t w_[16];
 };
@@ -59,28 +65,28 @@ ClientKey parse_client_key(const uint8_t* data, size_t len);
 std::vector<uint8_t> serialize_client_key(const ClientKey& ck);
 // A fresh RadixClientKey (gen_keys_radix(&PARAM_MESSAGE_2_CARRY_2, 4), ciphertext.rs:42-45):
 // uniform binary GLWE key of k*N bits (its flattening is the big LWE key) and uniform binary
-// LWE key of n bits, from a ChaCha20 stream of `seed` (STREAM_CLIENT_KEY); parameter block
+// LWE key of n bits, from the ChaCha20 stream STREAM_CLIENT_KEY of `key`; parameter block
 // from p (PARAM_MESSAGE_2_CARRY_2's words at the default params: pfks = (1, 2^23, glwe
 // sigma), cbs = (0, 0), message and carry modulus 4, 4 blocks).
-ClientKey gen_client_key(const Params& p, uint64_t seed);
+ClientKey gen_client_key(const Params& p, const RngKey& key);
 
 // KSK: [i in kN][level j][t in n+1], torus 2^64.
-void gen_ksk(const Params& p, const ClientKey& ck, uint64_t seed, std::vector<uint64_t>& ksk);
+void gen_ksk(const Params& p, const ClientKey& ck, const RngKey& key, std::vector<uint64_t>& ksk);
 // BSK: [GGSW w][row r in k+1][component c in k+1][coef], coefficient domain mod Q (rns.h);
 // GGSW w per Params::bsk_unroll (k = 1: 3 per pair of LWE coefficients).
-void gen_bsk(const Params& p, const ClientKey& ck, uint64_t seed, std::vector<uint64_t>& bsk);
+void gen_bsk(const Params& p, const ClientKey& ck, const RngKey& key, std::vector<uint64_t>& bsk);
 // Host parts of the device key generator (Device::gen_server_key): the
 // Box-Muller noise of every KSK row (lwe sigma, torus units), of every BSK
 // body coefficient ([w][r][coef], glwe sigma, torus units) and the message bit
 // of every GGSW.
-void gen_ksk_noise(const Params& p, uint64_t seed, std::vector<int64_t>& e);
-void gen_bsk_noise_torus(const Params& p, uint64_t seed, std::vector<int32_t>& e);
+void gen_ksk_noise(const Params& p, const RngKey& key, std::vector<int64_t>& e);
+void gen_bsk_noise_torus(const Params& p, const RngKey& key, std::vector<int32_t>& e);
 std::vector<uint8_t> ggsw_messages(const Params& p, const ClientKey& ck);
 // noise of encrypt_blocks for blocks first_block .. first_block + count - 1
-void enc_noise(const Params& p, uint64_t seed, uint64_t first_block, size_t count, std::vector<int64_t>& e);
+void enc_noise(const Params& p, const RngKey& key, uint64_t first_block, size_t count, std::vector<int64_t>& e);
 
 // Fresh LWE encryptions of block messages (Delta = 2^59) under the big key.
-void encrypt_blocks(const Params& p, const ClientKey& ck, const uint8_t* msgs, size_t count, uint64_t seed,
+void encrypt_blocks(const Params& p, const ClientKey& ck, const uint8_t* msgs, size_t count, const RngKey& key,
                     uint64_t first_block, uint64_t* out /* count * (kN+1) */);
 uint64_t lwe_phase(const Params& p, const ClientKey& ck, const uint64_t* lwe);
 // tfhe-rs shortint decrypt_message_and_carry: round(phase / Delta) mod 16

@@ -31,6 +31,7 @@ HEADER = os.path.join(REPO, "include", "fheregex.h")
 
 FR_OK = 0
 ERR_INVALID, ERR_PARSE, ERR_REF_PANIC, ERR_NO_DEVICE, ERR_HIP, ERR_NO_KEY, ERR_OOM, ERR_NON_ASCII = range(-1, -9, -1)
+ERR_RNG = -9
 LOWER_FAITHFUL, LOWER_THRESHOLD, LOWER_FAITHFUL_TREE = 0, 1, 2
 ENGINE_AUTO, ENGINE_ENUMERATE, ENGINE_MERGED = 0, 1, 2
 GRAMMAR_REFERENCE, GRAMMAR_EXT = 0, 1
@@ -108,6 +109,14 @@ _SIGS = {
     "fr_default_params": (C.c_int, [C.POINTER(Params)]),
     "fr_load_client_key": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
     "fr_gen_client_key": (C.c_int, [C.c_void_p, C.c_uint64]),
+    # *_keyed: key = 32 bytes, or None (NULL) for the OS CSPRNG
+    "fr_gen_client_key_keyed": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "fr_gen_server_key_keyed": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "fr_encrypt_str_keyed": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, u64p]),
+    "fr_encrypt_blocks_keyed": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, C.c_char_p, C.c_uint64,
+                                          u64p]),
+    "fr_encrypt_upload_str_keyed": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p,
+                                              C.POINTER(C.c_uint32)]),
     "fr_serialize_client_key": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "fr_gen_server_key": (C.c_int, [C.c_void_p, C.c_uint64]),
     "fr_set_keygen": (C.c_int, [C.c_void_p, C.c_int32]),
@@ -242,6 +251,29 @@ def _p(a: np.ndarray):
     return a.ctypes.data_as(u64p)
 
 
+def seed_key(seed: int) -> bytes:
+    """The 32-byte generator key that a 64-bit seed stands for (RngKey::from_seed):
+    the seed, then six fixed words.  A keyed call with it draws a seeded call's words."""
+    return (seed & 0xFFFFFFFFFFFFFFFF).to_bytes(8, "little") + b"".join(
+        w.to_bytes(4, "little") for w in (0x243F6A88, 0x85A308D3, 0x13198A2E, 0x03707344, 0xA4093822, 0x299F31D0))
+
+
+def _rng_arg(seed):
+    """The randomness argument of the key and encryption calls: (keyed, value).
+    int: a 64-bit seed (reproducible: tests, benchmarks); 32 bytes: a 256-bit generator
+    key; None: the OS CSPRNG (a NULL key)."""
+    if seed is None:
+        return True, None
+    if isinstance(seed, (bytes, bytearray, memoryview)):
+        key = bytes(seed)
+        if len(key) != 32:
+            raise ValueError(f"a generator key is 32 bytes, not {len(key)}")
+        return True, key
+    if isinstance(seed, (int, np.integer)):
+        return False, int(seed) & 0xFFFFFFFFFFFFFFFF
+    raise TypeError("seed: an int (seeded), 32 bytes (keyed) or None (OS randomness)")
+
+
 RING_RNS, RING_FFT = 0, 1  # fheregex.h FR_RING_*
 
 
@@ -352,10 +384,13 @@ class Context:
     def load_client_key(self, blob: bytes):
         _check(lib().fr_load_client_key(self.h, blob, len(blob)))
 
-    def gen_client_key(self, seed: int):
+    def gen_client_key(self, seed=None):
         """gen_keys_radix(&PARAM_MESSAGE_2_CARRY_2, 4) (ciphertext.rs:44): a fresh
-        uniform binary client key, reproducible from `seed`."""
-        _check(lib().fr_gen_client_key(self.h, seed & 0xFFFFFFFFFFFFFFFF))
+        uniform binary client key.  `seed`: None draws from the OS CSPRNG (as the
+        reference does), 32 bytes are a 256-bit generator key, an int is a 64-bit seed
+        (reproducible; tests and benchmarks)."""
+        keyed, v = _rng_arg(seed)
+        _check(lib().fr_gen_client_key_keyed(self.h, v) if keyed else lib().fr_gen_client_key(self.h, v))
 
     def serialize_client_key(self) -> bytes:
         """bincode RadixClientKey (engine.rs:238-246 generate_test_keys): the layout
@@ -366,10 +401,13 @@ class Context:
         _check(lib().fr_serialize_client_key(self.h, buf, n.value, C.byref(n)))
         return buf.raw
 
-    def gen_server_key(self, seed: int):
+    def gen_server_key(self, seed=None):
         """ServerKey::new (engine.rs:252): on the GPU for the FFT ring (KEYGEN_AUTO),
-        else on the host; both give the same key bit for bit."""
-        _check(lib().fr_gen_server_key(self.h, seed))
+        else on the host; both give the same key bit for bit.  `seed` as in
+        gen_client_key.  A server key from an int seed must not leave the client: whoever
+        guesses the seed recomputes the key's noise and solves for the client key."""
+        keyed, v = _rng_arg(seed)
+        _check(lib().fr_gen_server_key_keyed(self.h, v) if keyed else lib().fr_gen_server_key(self.h, v))
 
     def set_keygen(self, where: int):
         """KEYGEN_AUTO (device when present, FFT ring), KEYGEN_HOST or KEYGEN_DEVICE."""
@@ -433,17 +471,24 @@ class Context:
         _check(lib().fr_set_profiling(self.h, int(on)))
 
     # client side
-    def encrypt_str(self, s: bytes | str, seed: int) -> np.ndarray:
+    # `seed` of the three encryption calls: None draws masks and noise from the OS CSPRNG
+    # (as the reference does), 32 bytes are a 256-bit generator key, an int is a 64-bit
+    # seed (tests and benchmarks: two calls with one seed share masks and noise)
+    def encrypt_str(self, s: bytes | str, seed=None) -> np.ndarray:
         if isinstance(s, str):
             s = s.encode("latin-1")
+        keyed, v = _rng_arg(seed)
         out = np.zeros((len(s), 4, self.lwe_len), dtype=np.uint64)
-        _check(lib().fr_encrypt_str(self.h, s, len(s), seed, _p(out)))
+        f = lib().fr_encrypt_str_keyed if keyed else lib().fr_encrypt_str
+        _check(f(self.h, s, len(s), v, _p(out)))
         return out
 
-    def encrypt_blocks(self, msgs, seed: int, first_block: int = 0) -> np.ndarray:
+    def encrypt_blocks(self, msgs, seed=None, first_block: int = 0) -> np.ndarray:
         m = np.ascontiguousarray(np.asarray(msgs, dtype=np.uint8))
+        keyed, v = _rng_arg(seed)
         out = np.zeros((len(m), self.lwe_len), dtype=np.uint64)
-        _check(lib().fr_encrypt_blocks(self.h, m.ctypes.data_as(C.POINTER(C.c_uint8)), len(m), seed, first_block, _p(out)))
+        f = lib().fr_encrypt_blocks_keyed if keyed else lib().fr_encrypt_blocks
+        _check(f(self.h, m.ctypes.data_as(C.POINTER(C.c_uint8)), len(m), v, first_block, _p(out)))
         return out
 
     def decrypt_radix(self, blocks: np.ndarray) -> int:
@@ -465,12 +510,14 @@ class Context:
         _check(lib().fr_upload_radix(self.h, _p(b), b.shape[0], out))
         return list(out)
 
-    def encrypt_upload_str(self, s: bytes | str, seed: int) -> List[int]:
+    def encrypt_upload_str(self, s: bytes | str, seed=None) -> List[int]:
         """encrypt_str on the device into content handles (same words as encrypt_str)."""
         if isinstance(s, str):
             s = s.encode("latin-1")
+        keyed, v = _rng_arg(seed)
         out = (C.c_uint32 * len(s))()
-        _check(lib().fr_encrypt_upload_str(self.h, s, len(s), seed, out))
+        f = lib().fr_encrypt_upload_str_keyed if keyed else lib().fr_encrypt_upload_str
+        _check(f(self.h, s, len(s), v, out))
         return list(out)
 
     def serialize_radix(self, blocks: np.ndarray, degree: int = 3) -> bytes:
@@ -670,8 +717,10 @@ class Context:
 class ClientKey:
     ctx: Context
 
-    def encrypt_str(self, s: str, seed: int = 0) -> List[int]:
-        """encrypt_str (ciphertext.rs:32-40) + upload: one radix handle per char."""
+    def encrypt_str(self, s: str, seed=None) -> List[int]:
+        """encrypt_str (ciphertext.rs:32-40) + upload: one radix handle per char.  By
+        default the masks and noise come from the OS CSPRNG, fresh per call, as in the
+        reference; an int seed or a 32-byte key makes the call reproducible (tests)."""
         if any(ord(ch) > 127 for ch in s):
             raise ValueError("content contains non-ascii characters")
         return self.ctx.upload_radix(self.ctx.encrypt_str(s, seed))
@@ -705,19 +754,19 @@ class ServerKey:
         return ServerKey(ctx)
 
 
-def gen_keys(client_key_blob: Optional[bytes] = None, seed: int = 0, device: int = 0,
-             params: Optional[Params] = None, client_seed: Optional[int] = None):
+def gen_keys(client_key_blob: Optional[bytes] = None, seed=None, device: int = 0,
+             params: Optional[Params] = None, client_seed=None):
     """gen_keys (ciphertext.rs:42-45): (client key, server key).
 
     Without a blob the client key is fresh (gen_keys_radix(&PARAM_MESSAGE_2_CARRY_2, 4),
-    ciphertext.rs:44), drawn from `client_seed` (default: 64 bits of os.urandom, as the
-    reference draws from the OS); with a blob it is that bincode key (read_test_keys,
-    engine.rs:248-254).  The server key is derived deterministically from `seed`
-    (ServerKey::new, engine.rs:252)."""
+    ciphertext.rs:44), drawn under `client_seed`; with a blob it is that bincode key
+    (read_test_keys, engine.rs:248-254).  The server key's masks and noise
+    (ServerKey::new, engine.rs:252) are drawn under `seed`.  Both default to None: 256
+    bits of the OS CSPRNG each, as the reference draws.  32 bytes are a generator key, an
+    int a 64-bit seed; a server key from an int seed is reproducible (tests, benchmarks,
+    multi-rank keygen) and must not leave the client."""
     ctx = Context(device, params)
     if client_key_blob is None:
-        if client_seed is None:
-            client_seed = int.from_bytes(os.urandom(8), "little")
         ctx.gen_client_key(client_seed)
     else:
         ctx.load_client_key(client_key_blob)

@@ -60,6 +60,7 @@ enum {
     FR_ERR_NO_KEY = -6,       /* client or server key missing */
     FR_ERR_OOM = -7,          /* arena / allocation exhausted */
     FR_ERR_NON_ASCII = -8,    /* encrypt_str on non-ASCII content (ciphertext.rs:33-35) */
+    FR_ERR_RNG = -9,          /* the OS CSPRNG gave no randomness (a *_keyed call with a NULL key) */
 };
 
 /* Ring of the blind rotation.  FR_RING_FFT: GLWE/GGSW on the
@@ -113,14 +114,32 @@ const char* fr_last_error(void);
 int fr_default_params(fr_params* out); /* PARAM_MESSAGE_2_CARRY_2, k=1, N=2048 */
 
 /* ----- keys ----- */
+/* Randomness.  Every random draw (the client key, the server key's masks and noise, an
+ * encryption's masks and noise) is ChaCha20 under one 256-bit generator key.  The *_keyed
+ * entry points take it as `const uint8_t* key`: 32 bytes (the 8 little-endian key words),
+ * or NULL for 32 fresh bytes of the OS CSPRNG (getrandom(2)) per call, as the reference
+ * draws (ciphertext.rs:32-45, engine.rs:252); FR_ERR_RNG if the OS gives none, never a
+ * weaker source.  Production callers pass NULL.  A caller-supplied key must be secret,
+ * uniform and used for one call: two encryptions under one key share masks and noise
+ * block by block, and their difference exposes the plaintexts' difference.
+ * The entry points taking `uint64_t seed` run the same generator under the key
+ * (seed lo, seed hi, six fixed words).  They exist for tests, benchmarks and reproducible
+ * multi-rank keygen: a seed is at most 64 bits and usually known.  Whoever holds a
+ * server key and can guess its seed recomputes its noise and solves for the client key,
+ * so a server key generated from a known or guessable seed must never leave the client
+ * (fr_export_server_key -> fr_load_server_key). */
 /* bincode RadixClientKey (tfhe-rs 0.2 layout, reference test_data/client_key). */
 int fr_load_client_key(fr_ctx* ctx, const uint8_t* bincode, size_t len);
 /* A fresh client key (gen_keys_radix(&PARAM_MESSAGE_2_CARRY_2, 4), ciphertext.rs:44):
  * uniform binary GLWE key (k*N bits, flattened: the big LWE key) and LWE key (n bits)
  * drawn from a ChaCha20 stream of `seed` (the reference draws from the OS CSPRNG; a seed
  * makes the key reproducible), the parameter block of the context's params.  Replaces
- * any loaded client key and drops the server key. */
+ * any loaded client key and drops the server key.  For tests, benchmarks and reproducible
+ * multi-rank keygen: the key has the seed's 64 bits of entropy at most. */
 int fr_gen_client_key(fr_ctx* ctx, uint64_t seed);
+/* The same key generation under a 256-bit generator key (32 bytes), or under the OS
+ * CSPRNG (key == NULL): what gen_keys_radix does. */
+int fr_gen_client_key_keyed(fr_ctx* ctx, const uint8_t* key);
 /* bincode of the context's client key in the layout fr_load_client_key reads
  * (engine.rs:238-246 generate_test_keys): for a loaded key, the loaded bytes exactly.
  * buf == NULL: size query (*written = bytes needed). */
@@ -129,8 +148,14 @@ int fr_serialize_client_key(fr_ctx* ctx, uint8_t* buf, size_t cap, size_t* writt
  * ring, mod Q for the RNS ring) from the client key and a seed
  * (ServerKey::new, engine.rs:252; gen_keys_radix, ciphertext.rs:44).  With a
  * device and the FFT ring it is generated on the GPU (FR_KEYGEN_AUTO); the
- * host generator gives the same words bit for bit (fr_set_keygen). */
+ * host generator gives the same words bit for bit (fr_set_keygen).  For tests,
+ * benchmarks and reproducible multi-rank keygen: a server key generated from a known or
+ * guessable seed must never leave the client (see "Randomness" above). */
 int fr_gen_server_key(fr_ctx* ctx, uint64_t seed);
+/* The same server key generation (same preconditions, same fr_set_keygen placement)
+ * under a 256-bit generator key (32 bytes), or under the OS CSPRNG (key == NULL): the
+ * one to use for a server key that is exported. */
+int fr_gen_server_key_keyed(fr_ctx* ctx, const uint8_t* key);
 enum { FR_KEYGEN_AUTO = 0, FR_KEYGEN_HOST = 1, FR_KEYGEN_DEVICE = 2 };
 int fr_set_keygen(fr_ctx* ctx, int32_t where);
 /* Export the server key: ksk = kN*ks_level*(n+1) u64 ; bsk = W*(k+1)^2*N u64
@@ -151,10 +176,18 @@ int fr_server_key_sizes(fr_ctx* ctx, size_t* ksk_len, size_t* bsk_len);
  * not tfhe-rs's bincode ServerKey. */
 int fr_load_server_key(fr_ctx* ctx, const uint64_t* ksk, size_t ksk_len, const uint64_t* bsk, size_t bsk_len);
 
-/* ----- client side (tests / bench; not on the timed path) ----- */
+/* ----- client side (not on the timed path) ----- */
+/* Seeded encryption, for tests and benchmarks only: two calls with one seed share their
+ * masks and noise block by block (block q of a call draws at index first_block + q). */
 int fr_encrypt_str(fr_ctx* ctx, const char* s, size_t len, uint64_t seed, uint64_t* out /* len*4*(kN+1) */);
 int fr_encrypt_blocks(fr_ctx* ctx, const uint8_t* msgs, size_t count, uint64_t seed, uint64_t first_block,
                       uint64_t* out /* count*(kN+1) */);
+/* The same encryptions under a 256-bit generator key (32 bytes), or under the OS CSPRNG
+ * (key == NULL; what encrypt_str / RadixClientKey::encrypt do, ciphertext.rs:32-40).
+ * Errors as the seeded calls: FR_ERR_NO_KEY without a client key, FR_ERR_NON_ASCII. */
+int fr_encrypt_str_keyed(fr_ctx* ctx, const char* s, size_t len, const uint8_t* key, uint64_t* out /* len*4*(kN+1) */);
+int fr_encrypt_blocks_keyed(fr_ctx* ctx, const uint8_t* msgs, size_t count, const uint8_t* key, uint64_t first_block,
+                            uint64_t* out /* count*(kN+1) */);
 int fr_decrypt_radix(fr_ctx* ctx, const uint64_t* blocks /* 4*(kN+1) */, uint64_t* value);
 int fr_decode_block(fr_ctx* ctx, const uint64_t* lwe, uint32_t* msg_and_carry);
 
@@ -163,8 +196,14 @@ int fr_upload_radix(fr_ctx* ctx, const uint64_t* blocks /* n*4*(kN+1) */, size_t
 int fr_upload_bool(fr_ctx* ctx, const uint64_t* lwe /* n*(kN+1) */, size_t n, fr_ct* out);
 /* encrypt_str (ciphertext.rs:32-40) on the device, straight into n_chars
  * content handles: the same ciphertext words as fr_encrypt_str (same seed),
- * without the host encryption and the 64 KB-per-char upload. */
+ * without the host encryption and the 64 KB-per-char upload.  Seeded: tests and
+ * benchmarks only. */
 int fr_encrypt_upload_str(fr_ctx* ctx, const char* s, size_t len, uint64_t seed, fr_ct* out /* len */);
+/* The same under a 256-bit generator key (32 bytes; the words of fr_encrypt_str_keyed
+ * with that key), or under the OS CSPRNG (key == NULL).  The key travels to the kernel as
+ * an argument and is never stored in device memory.  FR_ERR_NO_KEY, FR_ERR_NO_DEVICE,
+ * FR_ERR_NON_ASCII as the seeded call. */
+int fr_encrypt_upload_str_keyed(fr_ctx* ctx, const char* s, size_t len, const uint8_t* key, fr_ct* out /* len */);
 /* Wire format of a radix ciphertext: bincode (fixint, little endian) of tfhe-rs
  * 0.2 RadixCiphertext — u64 n_blocks, then per block u64 len (= kN+1), the LWE
  * words, u64 degree, u64 message_modulus (4), u64 carry_modulus (4).  [ext]
