@@ -1,4 +1,5 @@
-// Device executor interface (HIP, gfx950).  Kernels live in device.hip.
+// Device executor interface (HIP, gfx950).  The host class is in device.hip; the kernels and
+// the methods that launch them in rns_br.hip, fft_br.hip, keyswitch.hip and keygen.hip.
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -171,7 +172,14 @@ class Device {
     void launch_ks(const DevGate* d_gates, size_t n, uint64_t* d_ks, void* ev_start = nullptr, void* ev_stop = nullptr);
     void launch_br(const DevGate* d_gates, const uint64_t* d_ks, size_t n, void* ev_start = nullptr,
                    void* ev_stop = nullptr);
-    // FR_RING_FFT (fft.hip)
+    void run_br_jobs(const uint64_t* ks_in, std::vector<DevGate>& gates, uint64_t* out);  // the blind_rotate_*_host hooks
+    // FR_RING_RNS (rns_br.hip)
+    void init_rns();
+    void upload_rns_bsk(const std::vector<uint64_t>& bsk);
+    void launch_br_rns(const DevGate* d_gates, const uint64_t* d_ks, size_t n, void* ev_start, void* ev_stop);
+    void free_rns();
+    void init_ks();  // keyswitch.hip: the FR_KS_* settings
+    // FR_RING_FFT (fft_br.hip)
     void init_fft();
     void upload_fft_bsk(const std::vector<uint64_t>& bsk);
     void launch_br_fft(const DevGate* d_gates, const uint64_t* d_ks, size_t n, void* stream, void* ev_start = nullptr,

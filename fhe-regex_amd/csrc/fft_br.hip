@@ -5,7 +5,7 @@
 //
 //   k_blind_rotate_fft<N,E>: modulus switch, test-polynomial accumulator (u64),
 //     the unrolled blind rotation (k = 1: one step per pair of LWE
-//     coefficients, three GGSWs, see device.hip), multi-value w-step and
+//     coefficients, three GGSWs, see rns_br.hip), multi-value w-step and
 //     sample extract -- outputs are already torus LWEs, no ring conversion.
 //
 // Geometry: one workgroup per bootstrap, 2 * M/E lanes (M = N/2 complex
@@ -22,19 +22,11 @@
 
 #include <cstring>
 
-#include "device.h"
+#include "device_impl.h"
 #include "fft.h"
 #include "geo.h"
 
 namespace fr {
-
-#define FFT_CHECK(x)                                                                         \
-    do {                                                                                     \
-        hipError_t _e = (x);                                                                 \
-        if (_e != hipSuccess)                                                                \
-            throw Error(FR_ERR_HIP, std::string("HIP error: ") + hipGetErrorString(_e) +     \
-                                        " at " __FILE__ ":" + std::to_string(__LINE__));     \
-    } while (0)
 
 template <int M, int E>
 using FGeo = NttGeo<M, E, 3, fft_layout_variant(ilog2c(M), ilog2c(E))>;
@@ -176,11 +168,6 @@ __device__ __forceinline__ void finv_phase(double2 (&x)[E], const double2* tw, i
 #ifndef FR_PAIR_CC
 #define FR_PAIR_CC 1
 #endif
-// latency shape: the MAC's key-only part and own-row product before the MAC barrier, the next
-// step's key prefetch with them (1), or all of the MAC after the barrier (0)
-#ifndef FR_MAC_EARLY
-#define FR_MAC_EARLY 0
-#endif
 // latency shape, k = 1: the lane's twiddles in registers (1) or read from LDS (0)
 #ifndef FR_LAT_TWR
 #define FR_LAT_TWR 1
@@ -194,7 +181,7 @@ __device__ __forceinline__ void finv_phase(double2 (&x)[E], const double2* tw, i
 //    the next step's key loaded right after them: 1.38 ms (ab_kearly.log);
 //  * k = 1 throughput shapes with E = 8 / 16 (two waves / one wave per polynomial): 12.0 /
 //    13.4 against 10.8 ms per 2048 bootstraps (ab_lane_elems_k1.log);
-//  * a 16-wave latency shape (E = 2, build with -DFR_LAT_E2): 2.03 ms with the twiddles
+//  * a 16-wave latency shape (E = 2): 2.03 ms with the twiddles
 //    from LDS, 2.27 with them in registers (spilled at the 128-VGPR cap of 4 waves per
 //    SIMD), against 1.34: nine exchanges per transform, three of them cross-wave
 //    (ab_lat_e2_16wave.log).
@@ -227,9 +214,6 @@ __device__ __forceinline__ double2 fwave_uniform(double2 v) {
 // schedule at 190 VGPRs), so it keeps the twiddles in VGPRs
 #ifndef FR_TW_SGPR_PAIR
 #define FR_TW_SGPR_PAIR 1
-#endif
-#ifndef FR_TW_SGPR_LAT
-#define FR_TW_SGPR_LAT 0
 #endif
 
 template <int M, int E>
@@ -305,7 +289,7 @@ __device__ __forceinline__ void finv_phase_r(double2 (&x)[E], const FTwr<M, E>& 
     }
 }
 
-// exchange between phase layouts stays inside each wave (see device.hip)
+// exchange between phase layouts stays inside each wave (see rns_br.hip)
 template <int M, int E, int PF, int PT>
 constexpr bool fwave_local() {
     using G = FGeo<M, E>;
@@ -339,9 +323,6 @@ constexpr int fperm_lane_bit(int j) {
 }
 template <int M, int E, int PF, int PT>
 constexpr bool fperm_ok() {
-#ifdef FR_FFT_NOPERM  // A/B switch: every exchange through LDS
-    return false;
-#else
     using G = FGeo<M, E>;
     if (PF == PT || (PF - PT != 1 && PT - PF != 1)) return false;
     for (int j = 0; j < G::e; ++j) {
@@ -355,7 +336,6 @@ constexpr bool fperm_ok() {
         if (!swapped && G::lane_bit(PF, b) != G::lane_bit(PT, b)) return false;
     }
     return true;
-#endif
 }
 template <int K>
 __device__ __forceinline__ void fperm_swap(double& a, double& b) {
@@ -417,30 +397,13 @@ __device__ __forceinline__ void fexchange(double2 (&x)[B][E], double2* row, int 
     if constexpr (fperm_ok<M, E, PF, PT>()) {
         // a pre-barrier would also order the next exchange's writes: keep the plan's barriers
         static_assert(!PRE, "register exchanges replace only exchanges without a pre-barrier");
-#ifndef FR_FFT_NOPERMX  // timing experiment only (wrong results): register exchanges skipped
 #pragma unroll
         for (int b = 0; b < B; ++b) fperm_exchange<M, E, PF, PT>(x[b]);
-#endif
     } else {
-#ifdef FR_FFT_NOXCHG  // timing experiment only (wrong results): LDS exchanges skipped
-        return;
-#endif
-#ifdef FR_FFT_NOXCHG_LOCAL  // timing experiment only: wave-local LDS exchanges skipped
-        if constexpr (fwave_local<M, E, PF, PT>()) return;
-#endif
-#ifdef FR_FFT_NOXCHG_CROSS  // timing experiment only: cross-wave LDS exchanges skipped
-        if constexpr (!fwave_local<M, E, PF, PT>()) return;
-#endif
         constexpr int X = PF < PT ? PF : PT;
         double2* rf = row + G::template at<X>(G::template base<PF>(tl));
         double2* rt = row + G::template at<X>(G::template base<PT>(tl));
         if constexpr (PRE) __syncthreads();
-#ifdef FR_XCHG_PRIO  // A/B experiment: a wave entering an exchange issues ahead of its SIMD partner
-        __builtin_amdgcn_s_setprio(FR_XCHG_PRIO);
-        struct PrioReset {
-            __device__ ~PrioReset() { __builtin_amdgcn_s_setprio(0); }
-        } prio_reset;
-#endif
         if constexpr (XK && fxkeep_ok<M, E, PF, PT>()) {  // the kept element: wave-uniform branches around its store and load
             const int q = __builtin_amdgcn_readfirstlane((tl >> 6) & (E - 1));
 #pragma unroll
@@ -468,7 +431,7 @@ __device__ __forceinline__ void fexchange(double2 (&x)[B][E], double2* row, int 
             for (int m = 0; m < E; ++m) x[b][m] = rt[b * BS + G::template at<X>(G::template moff<PT>(m))];
     }
 }
-// barrier plan as in device.hip: only the first exchange of a transform and
+// barrier plan as in rns_br.hip: only the first exchange of a transform and
 // exchanges writing a non-wave-top layout wait before writing
 template <int M, int E, int p>
 constexpr bool ffwd_pre() {
@@ -615,7 +578,7 @@ constexpr int fbr_tp_groups() {
 // waves per SIMD the register allocation must allow
 template <int N, int K, int E, bool LAT>
 constexpr int fbr_min_waves() {
-    if (LAT) return E == 2 ? 4 : 2;  // E = 2 (FR_LAT_E2 experiment): 16 waves, 4 per SIMD
+    if (LAT) return 2;
     if (K == 1) return E == 4 ? 4 : 2;
     return E == 4 ? 3 : 2;  // k = 2: 2 x 6 waves (E = 4); E = 8: the one-slot-ahead loads need > 168 VGPRs
 }
@@ -664,7 +627,7 @@ __device__ __forceinline__ uint64_t test_poly(int t, bool direct, const uint8_t*
     const int mm = (t + half) / box;
     return mm < 16 ? (uint64_t)lut0[mm] << DELTA_LOG : (uint64_t)0 - ((uint64_t)lut0[0] << DELTA_LOG);
 }
-// sum_t d_t (X^pos_t A)[j] mod 2^64 (multi-value w-step, terms as device.hip)
+// sum_t d_t (X^pos_t A)[j] mod 2^64 (multi-value w-step, terms of lut_terms)
 template <int N>
 __device__ __forceinline__ uint64_t w_step64(const uint64_t* row, const uint32_t* terms, int nt, int j) {
     uint64_t acc = 0;
@@ -681,6 +644,53 @@ __device__ __forceinline__ uint64_t w_step64(const uint64_t* row, const uint32_t
     return acc;
 }
 
+// ---- the tail of a bootstrap, after the step loop, shared by k_blind_rotate_fft and
+// k_blind_rotate_fft_dual (NT: threads of the workgroup, tid: this thread among them).
+// The prologue (LUT / abar / bbar staging, test-polynomial accumulator) stays written out in
+// both: every shared form tried changed the listing of the step loop (tools/isa_diff.py).
+// Tail: one accumulator polynomial as u64 [N] at arow
+template <int M, int E>
+__device__ __forceinline__ void fbr_publish(uint64_t* arow, const double (&alo)[E], const double (&ahi)[E], int tl) {
+#pragma unroll
+    for (int m = 0; m < E; ++m) {
+        const int j = FGeo<M, E>::template idx<0>(tl, m);
+        arow[j] = fft::torus_of_acc(alo[m]);
+        arow[j + M] = fft::torus_of_acc(ahi[m]);
+    }
+}
+// Tail: the multi-value terms of a gate's LUTs, one thread per output
+template <int N>
+__device__ __forceinline__ void fbr_terms(int tid, int n_out, int kind, const uint8_t* lut, uint32_t* wterms, int* wcnt) {
+    if (tid < n_out && kind == JOB_MULTI) wcnt[tid] = lut_terms<N>(lut + 16 * tid, wterms + 16 * tid);
+}
+// Tail: the gate's outputs from its published accumulator ab ([K+1][N]): sample extract under
+// the flattened key (sign gate: +-Delta/2 + Delta/2 -> {0, Delta}), or one w-step per output
+template <int N, int K, int NT>
+__device__ __forceinline__ void fbr_outputs(int tid, const uint64_t* ab, const DevGate& gate, int n_out, int kind,
+                                            const uint32_t* wterms, const int* wcnt, uint64_t* arena, int slot_stride) {
+    constexpr int big = K * N;
+    if (kind != JOB_MULTI) {
+        uint64_t* out = arena + (size_t)gate.out_slot[0] * slot_stride;
+        const uint64_t post = kind == JOB_SIGN ? (1ULL << (DELTA_LOG - 1)) : 0;
+        for (int c = tid; c <= big; c += NT) {
+            const ExtractIdx x = extract_index<N, K>(c);
+            const uint64_t v = ab[x.pp * N + x.j];
+            out[c] = (x.neg ? (uint64_t)0 - v : v) + (c == big ? post : 0);
+        }
+        return;
+    }
+    for (int f = 0; f < n_out; ++f) {
+        const uint32_t* tf = wterms + 16 * f;
+        const int nt = wcnt[f];
+        uint64_t* out = arena + (size_t)gate.out_slot[f] * slot_stride;
+        for (int c = tid; c <= big; c += NT) {
+            const ExtractIdx x = extract_index<N, K>(c);
+            const uint64_t v = w_step64<N>(ab + x.pp * N, tf, nt, x.j);
+            out[c] = x.neg ? (uint64_t)0 - v : v;
+        }
+    }
+}
+
 template <int N, int K, int E, bool LAT, int B = 1>
 __global__ void __launch_bounds__((fbr_threads<N, K, E>()), (fbr_min_waves<N, K, E, LAT>()))
 k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const DevGate* __restrict__ gates,
@@ -690,7 +700,7 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
     constexpr int M = N / 2;
     using G = FGeo<M, E>;
     static_assert(fexchanges_conflict_free<M, E>(), "LDS maps must make every exchange conflict-free");
-    static_assert(!LAT || E == 4 || E == 2, "the latency shape holds a step's GGSW values in registers: E = 4 (2: experiment)");
+    static_assert(!LAT || E == 4, "the latency shape holds a step's GGSW values in registers: E = 4");
     static_assert(B == 1 || (B == 2 && LAT && K == 1 && E == 4), "pair shape: the k = 1 latency geometry");
     constexpr int NB = E >= 4 ? E / 4 : 1;  // psi bases per lane (slots m >> 2 share one)
     constexpr int T = M / E, NT = (K + 1) * T, LAST = G::NPH - 1, XL = G::XL;
@@ -793,7 +803,7 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
     // and (k = 1) the lane's twiddles
     double2 gv[3][K + 1][LAT ? E : 1];
     FTwr<M, TWR ? E : 2> twr;
-    if constexpr (TWR) ftw_load_phase<M, E, 0, B == 1 ? FR_TW_SGPR_LAT : FR_TW_SGPR_PAIR>(twr, B == 1 ? tw : tw_g, tl);
+    if constexpr (TWR) ftw_load_phase<M, E, 0, B == 1 ? false : FR_TW_SGPR_PAIR>(twr, B == 1 ? tw : tw_g, tl);
 #ifdef FR_BR_TIMING
     uint64_t tseg[6] = {0, 0, 0, 0, 0, 0};
     uint64_t tlast = __builtin_amdgcn_s_memtime();
@@ -804,10 +814,6 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
         const uint32_t sb = (uint32_t)__builtin_amdgcn_readfirstlane(tt) * (3u * GG * 16u);
 #pragma unroll
         for (int m = 0; m < E; ++m) {
-#ifdef FR_FFT_NOBSK  // timing experiment only (wrong results): no GGSW traffic
-#pragma unroll
-            for (int r = 0; r <= K; ++r) gv[gg][r][m] = make_double2(tt + gg + r, m);
-#else
             gv[gg][0][m] =
                 bsk_load(rs, lane_off, sb + 16u * (gg * GG + (uint32_t)(P * (K + 1) + P) * M + (uint32_t)m * T));
 #pragma unroll
@@ -815,7 +821,6 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
                 gv[gg][1 + q][m] = bsk_load(
                     rs, lane_off,
                     sb + 16u * (gg * GG + (uint32_t)(other_row<K>(P, q) * (K + 1) + P) * M + (uint32_t)m * T));
-#endif
         }
     };
     // latency shape, LATPF: groups 0 .. NPF-1 of a step's key values are loaded one
@@ -845,19 +850,6 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
         const int t0 = __builtin_amdgcn_readfirstlane((int)nxt[0]);
         for (int gg = 0; gg < NPF; ++gg) load_ggsw(gg, t0 < steps ? t0 : 0);
     }
-#if defined(FR_PRIO_HALF_LAT) || defined(FR_PRIO_HALF_PAIR)
-    // A/B experiment (MI355X_MICROARCH.md "Two waves per SIMD", item 4): the second half of an
-    // 8-wave workgroup (waves 4-7: polynomial 1) loses VALU arbitration to its older SIMD
-    // partner at every segment head; one static s_setprio for that half before the loop
-    if constexpr (LAT) {
-#ifdef FR_PRIO_HALF_LAT
-        if (B == 1 && tid >= NT / 2) __builtin_amdgcn_s_setprio(FR_PRIO_HALF_LAT);
-#endif
-#ifdef FR_PRIO_HALF_PAIR
-        if (B == 2 && tid >= NT / 2) __builtin_amdgcn_s_setprio(FR_PRIO_HALF_PAIR);
-#endif
-    }
-#endif
     for (int t = 0; t < steps; ++t) {
         if (idle(t)) continue;  // (uniform branch)
         FBR_STAMP(0);
@@ -900,11 +892,7 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
                     for (int bb = 0; bb < NB; ++bb) {
                         const uint32_t k = __umul24(h == 0 ? ei[b] : ej[b], Lb[bb]) & (2 * N - 1);
                         if constexpr (!PSIQ) {  // psi^k, k < 2N, straight from the table
-#ifdef FR_FFT_NOPSI  // timing experiment only (wrong results): no table lookups
-                            const double2 c = make_double2((double)k, 0.5);
-#else
                             const double2 c = psi[psi_slot((int)k)];
-#endif
                             bre[b][h][bb] = c.x;
                             bim[b][h][bb] = c.y;
                         } else {
@@ -940,85 +928,17 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
         });
         FBR_STAMP(2);
         // 3. MAC with the three GGSWs of the pair and their monomial factors
-#ifndef FR_FFT_NOMACX  // timing experiment only (wrong results): no MAC exchange
 #pragma unroll
         for (int b = 0; b < B; ++b)
 #pragma unroll
             for (int m = 0; m < E; ++m) row_bl[b * BS + G::template at<XL>(G::template moff<LAST>(m))] = x[b][m];
-#endif
-        // FR_MAC_EARLY (latency shape): everything of the MAC that does not read the other
-        // polynomials -- slot factors, the key-only K_r and the own-row product D_P K_P -- runs
-        // between the row writes and the barrier (the writes' completion hides behind it), the
-        // key registers die there, so the next step's prefetch issues before the barrier too
-        // (its issue cost in the barrier's wait); after the barrier only the other rows' reads
-        // and one cmac each.  Every value's operation sequence is the one below: same bits.
-        constexpr bool MAC_EARLY = LAT && B == 1 && FR_MAC_EARLY;
-        if constexpr (MAC_EARLY) {
-            double kxr_e[E][K], kxi_e[E][K];
-#pragma unroll
-            for (int m = 0; m < E; ++m) {
-                const double2 own = x[0][m];
-                const uint32_t sm = ((m & 1) << 1) | ((m >> 1) & 1);  // brv2(m & 3)
-                double cr[3], ci[3];
-#pragma unroll
-                for (int h = 1; h < 3; ++h)
-                    slot_factor(bre[0][h - 1][m >> 2], bim[0][h - 1][m >> 2], h == 1 ? ei[0] : ej[0], sm, cr[h], ci[h]);
-                fft::cmul(cr[1], ci[1], cr[2], ci[2], cr[0], ci[0]);
-                double kor, koi;
-#pragma unroll
-                for (int gg = 0; gg < 3; ++gg) {
-                    const double c1r = cr[gg] - 1.0, c1i = ci[gg];
-                    const double2 Bo = gv[gg][0][m];
-                    if (gg == 0) fft::cmul(Bo.x, Bo.y, c1r, c1i, kor, koi);
-                    else fft::cmac(Bo.x, Bo.y, c1r, c1i, kor, koi);
-#pragma unroll
-                    for (int q = 0; q < K; ++q) {
-                        const double2 Bx = gv[gg][1 + q][m];
-                        if (gg == 0) fft::cmul(Bx.x, Bx.y, c1r, c1i, kxr_e[m][q], kxi_e[m][q]);
-                        else fft::cmac(Bx.x, Bx.y, c1r, c1i, kxr_e[m][q], kxi_e[m][q]);
-                    }
-                }
-                double zr, zi;
-                fft::cmul(own.x, own.y, kor, koi, zr, zi);
-                x[0][m] = make_double2(zr, zi);
-            }
-            if constexpr (LATPF && FR_MAC_EARLY == 1) {  // the next step's key, into the registers just freed
-                const int tn = __builtin_amdgcn_readfirstlane((int)nxt[t + 1]);
-                __builtin_amdgcn_sched_barrier(0);
-                for (int gg = 0; gg < NPF; ++gg) load_ggsw(gg, tn < steps ? tn : t);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            __syncthreads();
-#pragma unroll
-            for (int m = 0; m < E; ++m) {
-                double zr = x[0][m].x, zi = x[0][m].y;
-#pragma unroll
-                for (int q = 0; q < K; ++q) {
-                    const double2 oth = orow_bl[q][G::template at<XL>(G::template moff<LAST>(m))];
-                    fft::cmac(oth.x, oth.y, kxr_e[m][q], kxi_e[m][q], zr, zi);
-                }
-                x[0][m] = make_double2(zr, zi);
-            }
-            if constexpr (LATPF && FR_MAC_EARLY == 2) {  // (2: the prefetch after the cross terms, as without)
-                const int tn = __builtin_amdgcn_readfirstlane((int)nxt[t + 1]);
-                __builtin_amdgcn_sched_barrier(0);
-                for (int gg = 0; gg < NPF; ++gg) load_ggsw(gg, tn < steps ? tn : t);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        } else {
         // throughput shapes: slot m's GGSW values, loaded one slot ahead (E = 8) or
         // at the top of the slot (E = 4, 128 VGPRs: the other workgroup hides the wait)
         constexpr bool AHEAD = !LAT && E == 8;
-#ifdef FR_TP_NOPRE0  // A/B switch: E = 4 throughput shape loads slot 0 in-slot too
-        constexpr bool PRE0 = AHEAD;
-#else
         constexpr bool PRE0 = !LAT;  // slot 0 lands during the MAC barrier and row exchange
-#endif
         double2 Bc[3][K + 1];
         if constexpr (PRE0) load_slot<M, T, K>(Bc, rs, sbase, P, 0, lane_off);
-#ifndef FR_FFT_NOMACX
         __syncthreads();
-#endif
         // slot factors psi^(e L) for e = a_i, a_j and their product for a_i + a_j.
         // Slot m of this lane has L = Lb + M s_m: Lb = L mod M is shared by the
         // slots of equal m >> 2 (E/4 bases per lane) and s_m = brv2(m & 3) (fft.h: L(j) =
@@ -1041,21 +961,13 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
                 const double2 own = x[b][m];
                 double2 oth[K];
 #pragma unroll
-#ifdef FR_FFT_NOMACX
-                for (int q = 0; q < K; ++q) oth[q] = make_double2(own.y, own.x);
-#else
                 for (int q = 0; q < K; ++q) oth[q] = orow_bl[q][b * BS + G::template at<XL>(G::template moff<LAST>(m))];
-#endif
                 const uint32_t sm = ((m & 1) << 1) | ((m >> 1) & 1);  // brv2(m & 3)
                 double cr[3], ci[3];
 #pragma unroll
                 for (int h = 1; h < 3; ++h)  // uniform quarter turn
                     slot_factor(bre[b][h - 1][m >> 2], bim[b][h - 1][m >> 2], h == 1 ? ei[b] : ej[b], sm, cr[h], ci[h]);
-#ifdef FR_FFT_NOC0  // timing experiment only (wrong results): no pair-monomial product
-                cr[0] = cr[1] + cr[2], ci[0] = ci[1];
-#else
                 fft::cmul(cr[1], ci[1], cr[2], ci[2], cr[0], ci[0]);
-#endif
                 // per row r: K_r = sum_g B_g[r][P] (c_g - 1), g ascending; then
                 // z = D_P K_P + sum_(r != P, ascending) D_r K_r  (own row first).
                 // 16 (K + 1) VALU per slot (k = 1: 32, against 36 for sum_g (c_g - 1) y_g)
@@ -1096,7 +1008,6 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
             for (int gg = 0; gg < NPF; ++gg) load_ggsw(gg, tn < steps ? tn : t);
             __builtin_amdgcn_sched_barrier(0);
         }
-        }  // !MAC_EARLY
         FBR_STAMP(3);
         // 4. inverse FFT (times M; 1/M is in the key), accumulate, reduce mod 2^64
         finverse_from<M, E, LAST, LAT, TWR, B, BS>(x, irow, twr, tw, twc, tl);
@@ -1123,58 +1034,18 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
     // the inverse rows)
     __syncthreads();
     uint64_t* accs = (uint64_t*)xbuf;
-#pragma unroll
-    for (int b = 0; b < B; ++b)
-#pragma unroll
-        for (int m = 0; m < E; ++m) {
-            const int j = G::template idx<0>(tl, m);
-            accs[(b * (K + 1) + P) * N + j] = fft::torus_of_acc(alo[b][m]);
-            accs[(b * (K + 1) + P) * N + j + M] = fft::torus_of_acc(ahi[b][m]);
-        }
     static_assert(B == 1 || 8 * B * (K + 1) * N <= 16 * B * BS, "pair shape: u64 rows inside the forward rows");
 #pragma unroll
-    for (int b = 0; b < B; ++b)
-        if (tid < n_out[b] && kind[b] == JOB_MULTI) {
-            // multi-value terms (device.hip lut_terms)
-            constexpr int box = N / 16, half = box / 2;
-            const uint8_t* lf = lut + b * 16 * MAX_OUT + 16 * tid;
-            uint32_t* terms = wterms + b * 16 * MAX_OUT + 16 * tid;
-            int nt = 0;
-            for (int tt = 1; tt <= 16; ++tt) {
-                const int d = tt < 16 ? (int)lf[tt] - (int)lf[tt - 1] : -((int)lf[0] + (int)lf[15]);
-                if (d != 0) terms[nt++] = (uint32_t)(tt < 16 ? tt * box - half : N - half) | ((uint32_t)(d + 128) << 16);
-            }
-            wcnt[b * MAX_OUT + tid] = nt;
-        }
-    __syncthreads();
-    constexpr int big = K * N;
-#pragma unroll
     for (int b = 0; b < B; ++b) {
-        if (!has[b]) continue;
-        const uint64_t* ab = accs + b * (K + 1) * N;
-        if (kind[b] != JOB_MULTI) {
-            uint64_t* out = arena + (size_t)gates[gb[b]].out_slot[0] * slot_stride;
-            const uint64_t post = kind[b] == JOB_SIGN ? (1ULL << (DELTA_LOG - 1)) : 0;
-            for (int c = tid; c <= big; c += NT) {
-                const int pp = c < big ? c / N : K, t = c < big ? c % N : 0;
-                const int j = t == 0 ? 0 : N - t;
-                const uint64_t v = ab[pp * N + j];
-                out[c] = (t != 0 ? (uint64_t)0 - v : v) + (c == big ? post : 0);
-            }
-            continue;
-        }
-        for (int f = 0; f < n_out[b]; ++f) {
-            const uint32_t* tf = wterms + b * 16 * MAX_OUT + 16 * f;
-            const int nt = wcnt[b * MAX_OUT + f];
-            uint64_t* out = arena + (size_t)gates[gb[b]].out_slot[f] * slot_stride;
-            for (int c = tid; c <= big; c += NT) {
-                const int pp = c < big ? c / N : K, t = c < big ? c % N : 0;
-                const int j = t == 0 ? 0 : N - t;
-                const uint64_t v = w_step64<N>(ab + pp * N, tf, nt, j);
-                out[c] = t != 0 ? (uint64_t)0 - v : v;
-            }
-        }
+        fbr_publish<M, E>(accs + (b * (K + 1) + P) * N, alo[b], ahi[b], tl);
+        fbr_terms<N>(tid, n_out[b], kind[b], lut + b * 16 * MAX_OUT, wterms + b * 16 * MAX_OUT, wcnt + b * MAX_OUT);
     }
+    __syncthreads();
+#pragma unroll
+    for (int b = 0; b < B; ++b)
+        if (has[b])
+            fbr_outputs<N, K, NT>(tid, accs + b * (K + 1) * N, gates[gb[b]], n_out[b], kind[b], wterms + b * 16 * MAX_OUT,
+                                  wcnt + b * MAX_OUT, arena, slot_stride);
 }
 
 // The pair shape's one instantiation is compiled in its own translation unit,
@@ -1353,49 +1224,11 @@ k_blind_rotate_fft_dual(const uint64_t* __restrict__ ks, int ks_stride, int n, c
     uint64_t* accs = (uint64_t*)xbuf;
     static_assert(8 * B * N <= 16 * B * BS, "dual shape: u64 rows inside the exchange rows");
 #pragma unroll
-    for (int P = 0; P < B; ++P)
-#pragma unroll
-        for (int m = 0; m < E; ++m) {
-            const int j = G::template idx<0>(tl, m);
-            accs[P * N + j] = fft::torus_of_acc(alo[P][m]);
-            accs[P * N + j + M] = fft::torus_of_acc(ahi[P][m]);
-        }
-    if (tl < n_out && kind == JOB_MULTI) {
-        constexpr int box = N / 16, half = box / 2;
-        const uint8_t* lf = lut + 16 * tl;
-        uint32_t* terms = wterms + 16 * tl;
-        int nt = 0;
-        for (int tt = 1; tt <= 16; ++tt) {
-            const int d = tt < 16 ? (int)lf[tt] - (int)lf[tt - 1] : -((int)lf[0] + (int)lf[15]);
-            if (d != 0) terms[nt++] = (uint32_t)(tt < 16 ? tt * box - half : N - half) | ((uint32_t)(d + 128) << 16);
-        }
-        wcnt[tl] = nt;
-    }
+    for (int P = 0; P < B; ++P) fbr_publish<M, E>(accs + P * N, alo[P], ahi[P], tl);
+    fbr_terms<N>(tl, n_out, kind, lut, wterms, wcnt);
     __syncthreads();
     if (gi >= n_gates) return;
-    constexpr int big = K * N;
-    if (kind != JOB_MULTI) {
-        uint64_t* out = arena + (size_t)gates[gi].out_slot[0] * slot_stride;
-        const uint64_t post = kind == JOB_SIGN ? (1ULL << (DELTA_LOG - 1)) : 0;
-        for (int c = tl; c <= big; c += NT) {
-            const int pp = c < big ? c / N : K, t = c < big ? c % N : 0;
-            const int j = t == 0 ? 0 : N - t;
-            const uint64_t v = accs[pp * N + j];
-            out[c] = (t != 0 ? (uint64_t)0 - v : v) + (c == big ? post : 0);
-        }
-        return;
-    }
-    for (int f = 0; f < n_out; ++f) {
-        const uint32_t* tf = wterms + 16 * f;
-        const int nt = wcnt[f];
-        uint64_t* out = arena + (size_t)gates[gi].out_slot[f] * slot_stride;
-        for (int c = tl; c <= big; c += NT) {
-            const int pp = c < big ? c / N : K, t = c < big ? c % N : 0;
-            const int j = t == 0 ? 0 : N - t;
-            const uint64_t v = w_step64<N>(accs + pp * N, tf, nt, j);
-            out[c] = t != 0 ? (uint64_t)0 - v : v;
-        }
-    }
+    fbr_outputs<N, K, NT>(tl, accs, gates[gi], n_out, kind, wterms, wcnt, arena, slot_stride);
 }
 
 #ifndef FR_BR_PAIR_TU
@@ -1405,9 +1238,6 @@ k_blind_rotate_fft_dual(const uint64_t* __restrict__ ks, int ks_stride, int n, c
 // k = 1: E = 4 only (its transforms are radix-4 in the inverse, fradix4)
 template <int N, int K, int E>
 constexpr bool fft_shape_ok() {
-#ifdef FR_LAT_E2  // experiment: a 16-wave latency shape (E = 2) for k = 1; host keygen only
-    if (K == 1 && N == 2048 && E == 2) return true;
-#endif
     return (K == 1 && N == 2048 && E == 4) || (K == 2 && N == 1024 && (E == 4 || E == 8));
 }
 static bool fft_supported(int K, int N, int E) {
@@ -1418,7 +1248,7 @@ template <int N, int K, int E, bool LAT, int B = 1>
 static void fft_attr() {
     static_assert(fbr_smem_bytes<N, K, E, LAT, B>() <= (LAT ? 160 * 1024 : 160 * 1024 / fbr_tp_groups<K, E>()),
                   "LDS per workgroup of the shape");
-    FFT_CHECK(hipFuncSetAttribute((const void*)k_blind_rotate_fft<N, K, E, LAT, B>,
+    HIP_CHECK(hipFuncSetAttribute((const void*)k_blind_rotate_fft<N, K, E, LAT, B>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)fbr_smem_bytes<N, K, E, LAT, B>()));
 }
 
@@ -1446,24 +1276,21 @@ void Device::init_fft() {
         if constexpr (K == 1) {
             fft_attr<N, K, 4, true, 2>();
             static_assert(fbr_dual_smem_bytes<N>() <= 80 * 1024, "dual shape: two workgroups per CU");
-            FFT_CHECK(hipFuncSetAttribute((const void*)k_blind_rotate_fft_dual<N>,
+            HIP_CHECK(hipFuncSetAttribute((const void*)k_blind_rotate_fft_dual<N>,
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)fbr_dual_smem_bytes<N>()));
         }
-#ifdef FR_LAT_E2
-        if constexpr (fft_shape_ok<N, K, 2>()) fft_attr<N, K, 2, true>();
-#endif
         if constexpr (fft_shape_ok<N, K, 8>()) fft_attr<N, K, 8, false>();
     });
 
     fft::Tables T(p_.N);
-    FFT_CHECK(hipMalloc(&d_ftw_, 16 * (size_t)T.M));
+    HIP_CHECK(hipMalloc(&d_ftw_, 16 * (size_t)T.M));
     std::vector<fft::c64> psi(2 * (size_t)p_.N);
     for (int k = 0; k < 2 * p_.N; ++k) psi[k] = fft::psi_pow(p_.N, k);
-    FFT_CHECK(hipMalloc(&d_fqt_, 16 * psi.size()));
-    FFT_CHECK(hipMalloc(&d_fleaf_, 2 * (size_t)T.M));
-    FFT_CHECK(hipMemcpy(d_ftw_, T.tw.data(), 16 * (size_t)T.M, hipMemcpyHostToDevice));
-    FFT_CHECK(hipMemcpy(d_fqt_, psi.data(), 16 * psi.size(), hipMemcpyHostToDevice));
-    FFT_CHECK(hipMemcpy(d_fleaf_, T.leaf.data(), 2 * (size_t)T.M, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMalloc(&d_fqt_, 16 * psi.size()));
+    HIP_CHECK(hipMalloc(&d_fleaf_, 2 * (size_t)T.M));
+    HIP_CHECK(hipMemcpy(d_ftw_, T.tw.data(), 16 * (size_t)T.M, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_fqt_, psi.data(), 16 * psi.size(), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_fleaf_, T.leaf.data(), 2 * (size_t)T.M, hipMemcpyHostToDevice));
 }
 
 void Device::upload_fft_bsk(const std::vector<uint64_t>& bsk) {
@@ -1475,17 +1302,11 @@ void Device::upload_fft_bsk(const std::vector<uint64_t>& bsk) {
     // slot order -> per-lane order [poly][m][lane] (one copy per lane geometry E):
     // lane tl's element m is slot idx<LAST>(tl, m), so each load of a wave is 1 KB contiguous
     std::vector<fft::c64> lanes(four.size());
-    for (int E : {16, 8, 4, 2}) {
-#ifdef FR_LAT_E2
-        const bool e2 = E == 2 && p_.k == 1;  // the experiment's latency layout, in the E = 16 slot
-#else
-        const bool e2 = false;
-#endif
-        if (E == 2 && !e2) continue;
+    for (int E : {16, 8, 4}) {
         double*& dst = d_fbsk_[fbsk_index(E)];
         (void)hipFree(dst);
         dst = nullptr;
-        if (!e2 && (!fft_supported(p_.k, N, E) || !fbsk_needed(E))) continue;
+        if (!fft_supported(p_.k, N, E) || !fbsk_needed(E)) continue;
         const int T = M / E;
         int e = 0;
         while ((1 << e) < E) ++e;
@@ -1496,8 +1317,8 @@ void Device::upload_fft_bsk(const std::vector<uint64_t>& bsk) {
             for (int m = 0; m < E; ++m) slot[(size_t)m * T + tl] = geo_base(tabs.LOG, e, LAST, tl, V) + (m << L);
         for (size_t pq = 0; pq < polys; ++pq)
             for (size_t q = 0; q < (size_t)M; ++q) lanes[pq * M + q] = four[pq * M + slot[q]];
-        FFT_CHECK(hipMalloc(&dst, 16 * lanes.size()));
-        FFT_CHECK(hipMemcpy(dst, lanes.data(), 16 * lanes.size(), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMalloc(&dst, 16 * lanes.size()));
+        HIP_CHECK(hipMemcpy(dst, lanes.data(), 16 * lanes.size(), hipMemcpyHostToDevice));
     }
 }
 
@@ -1521,12 +1342,6 @@ void Device::launch_br_fft(const DevGate* d_gates, const uint64_t* d_ks, size_t 
         using I8 = std::integral_constant<int, 8>;
         using B1 = std::integral_constant<int, 1>;
         // small launches (at most one bootstrap per CU): the latency shape
-#ifdef FR_LAT_E2
-        if (n <= fft_small_ && K == 1) {
-            go(std::integral_constant<int, 2>{}, std::true_type{}, B1{});
-            return;
-        }
-#endif
         if (n <= fft_small_) go(I4{}, std::true_type{}, B1{});
         else if (n <= fft_pair_ && K == 1 && fft_dual_) {
             if constexpr (K == 1)
@@ -1539,7 +1354,7 @@ void Device::launch_br_fft(const DevGate* d_gates, const uint64_t* d_ks, size_t 
         else if (fft_e_ == 4) go(I4{}, std::false_type{}, B1{});
         else go(I8{}, std::false_type{}, B1{});
     });
-    FFT_CHECK(hipGetLastError());
+    HIP_CHECK(hipGetLastError());
 }
 
 void Device::free_fft() {

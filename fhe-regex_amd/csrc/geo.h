@@ -1,5 +1,5 @@
 // Lane geometry of the register-phase NTT/FFT kernels and their bank-conflict-
-// free LDS exchange maps (shared by device.hip: RNS NTT, and fft.hip: f64 FFT).
+// free LDS exchange maps (shared by rns_br.hip: RNS NTT, and fft_br.hip: f64 FFT).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -24,19 +24,12 @@
 #include <vector>
 
 #include "chacha.h"
-#include "device.h"
+#include "device_impl.h"
 #include "fft.h"
 #include "geo.h"
 #include "keys.h"
 
 namespace fr {
-
-#define KG_CHECK(x)                                                                          \
-    do {                                                                                     \
-        hipError_t _e = (x);                                                                 \
-        if (_e != hipSuccess)                                                                \
-            throw Error(FR_ERR_HIP, std::string("HIP error (keygen): ") + hipGetErrorString(_e)); \
-    } while (0)
 
 // u64 number 8*blk + q of a ChaCha stream: words (2q, 2q+1) of block blk
 __device__ __forceinline__ uint64_t chacha_u64(const uint32_t* w, int q) {
@@ -238,18 +231,18 @@ void Device::encrypt_to_slots(const ClientKey& ck, const uint8_t* msgs, size_t c
         (void)hipFree(d_sl);
     };
     try {
-        KG_CHECK(hipMalloc(&d_sb, 8 * (size_t)big));
-        KG_CHECK(hipMalloc(&d_m, count));
-        KG_CHECK(hipMalloc(&d_n, 8 * count));
-        KG_CHECK(hipMalloc(&d_sl, 4 * count));
-        KG_CHECK(hipMemcpyAsync(d_sb, ck.s_big.data(), 8 * (size_t)big, hipMemcpyHostToDevice, s));
-        KG_CHECK(hipMemcpyAsync(d_m, msgs, count, hipMemcpyHostToDevice, s));
-        KG_CHECK(hipMemcpyAsync(d_n, noise.data(), 8 * count, hipMemcpyHostToDevice, s));
-        KG_CHECK(hipMemcpyAsync(d_sl, slots, 4 * count, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMalloc(&d_sb, 8 * (size_t)big));
+        HIP_CHECK(hipMalloc(&d_m, count));
+        HIP_CHECK(hipMalloc(&d_n, 8 * count));
+        HIP_CHECK(hipMalloc(&d_sl, 4 * count));
+        HIP_CHECK(hipMemcpyAsync(d_sb, ck.s_big.data(), 8 * (size_t)big, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(d_m, msgs, count, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(d_n, noise.data(), 8 * count, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(d_sl, slots, 4 * count, hipMemcpyHostToDevice, s));
         k_encrypt_blocks<<<(unsigned)count, 64, 0, s>>>(key, big, d_sb, d_m, d_n, first_block, d_sl, p_.slot_stride(),
                                                        d_arena_);
-        KG_CHECK(hipGetLastError());
-        KG_CHECK(hipStreamSynchronize(s));
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(s));
     } catch (...) {
         cleanup();
         throw;
@@ -264,7 +257,7 @@ void Device::gen_server_key(const ClientKey& ck, const RngKey& key) {
     const size_t rows = (size_t)p_.big() * L, nw = p_.bsk_ggsw();
     const size_t bsk_polys = nw * kp1 * kp1;
     // every queued launch of every lane that reads the old keys has finished before they go
-    KG_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipDeviceSynchronize());
     // host: the noise draws and per-GGSW messages
     std::vector<int64_t> ksk_noise;
     std::vector<int32_t> bsk_noise;
@@ -285,48 +278,48 @@ void Device::gen_server_key(const ClientKey& ck, const RngKey& key) {
     };
     try {
         const hipStream_t s = (hipStream_t)stream_;
-        KG_CHECK(hipMalloc(&d_ss, 8 * ck.s_small.size()));
-        KG_CHECK(hipMalloc(&d_sb, 8 * ck.s_big.size()));
-        KG_CHECK(hipMalloc(&d_kn, 8 * ksk_noise.size()));
-        KG_CHECK(hipMalloc(&d_bn, 4 * bsk_noise.size()));
-        KG_CHECK(hipMalloc(&d_msg, msg.size()));
-        KG_CHECK(hipMemcpyAsync(d_ss, ck.s_small.data(), 8 * ck.s_small.size(), hipMemcpyHostToDevice, s));
-        KG_CHECK(hipMemcpyAsync(d_sb, ck.s_big.data(), 8 * ck.s_big.size(), hipMemcpyHostToDevice, s));
-        KG_CHECK(hipMemcpyAsync(d_kn, ksk_noise.data(), 8 * ksk_noise.size(), hipMemcpyHostToDevice, s));
-        KG_CHECK(hipMemcpyAsync(d_bn, bsk_noise.data(), 4 * bsk_noise.size(), hipMemcpyHostToDevice, s));
-        KG_CHECK(hipMemcpyAsync(d_msg, msg.data(), msg.size(), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMalloc(&d_ss, 8 * ck.s_small.size()));
+        HIP_CHECK(hipMalloc(&d_sb, 8 * ck.s_big.size()));
+        HIP_CHECK(hipMalloc(&d_kn, 8 * ksk_noise.size()));
+        HIP_CHECK(hipMalloc(&d_bn, 4 * bsk_noise.size()));
+        HIP_CHECK(hipMalloc(&d_msg, msg.size()));
+        HIP_CHECK(hipMemcpyAsync(d_ss, ck.s_small.data(), 8 * ck.s_small.size(), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(d_sb, ck.s_big.data(), 8 * ck.s_big.size(), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(d_kn, ksk_noise.data(), 8 * ksk_noise.size(), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(d_bn, bsk_noise.data(), 4 * bsk_noise.size(), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(d_msg, msg.data(), msg.size(), hipMemcpyHostToDevice, s));
 
         // KSK (torus) and its byte limbs
         (void)hipFree(d_ksk_);
         d_ksk_ = nullptr;
-        KG_CHECK(hipMalloc(&d_ksk_, 8 * rows * (n + 1)));
+        HIP_CHECK(hipMalloc(&d_ksk_, 8 * rows * (n + 1)));
         k_gen_ksk<<<(unsigned)rows, 64, 0, s>>>(key, n, L, p_.ks_base_log, d_ss, d_sb, d_kn, d_ksk_);
-        KG_CHECK(hipGetLastError());
+        HIP_CHECK(hipGetLastError());
         build_ksk_limbs();
 
         // torus BSK, kept for export
         (void)hipFree(d_tbsk_);
         d_tbsk_ = nullptr;
-        KG_CHECK(hipMalloc(&d_tbsk_, 8 * p_.bsk_len()));
+        HIP_CHECK(hipMalloc(&d_tbsk_, 8 * p_.bsk_len()));
         const uint64_t gadget = 1ULL << (64 - p_.pbs_base_log);
         if (N == 2048) k_gen_bsk<2048><<<(unsigned)(nw * kp1), 256, 0, s>>>(key, p_.k, d_sb, d_msg, d_bn, gadget, d_tbsk_);
         else k_gen_bsk<1024><<<(unsigned)(nw * kp1), 256, 0, s>>>(key, p_.k, d_sb, d_msg, d_bn, gadget, d_tbsk_);
-        KG_CHECK(hipGetLastError());
+        HIP_CHECK(hipGetLastError());
 
         // Fourier BSK in the lane layouts of the shapes in use (E = 4, and the throughput shape's)
         for (int E : {4, 8, 16}) {
             double*& dst = d_fbsk_[fbsk_index(E)];
             (void)hipFree(dst);
             dst = nullptr;
-            if (fbsk_needed(E) && (E < 16 || p_.k == 1)) KG_CHECK(hipMalloc(&dst, 16 * bsk_polys * M));
+            if (fbsk_needed(E) && (E < 16 || p_.k == 1)) HIP_CHECK(hipMalloc(&dst, 16 * bsk_polys * M));
         }
         double2 *o4 = (double2*)d_fbsk_[0], *o8 = (double2*)d_fbsk_[1], *o16 = (double2*)d_fbsk_[2];
         if (N == 2048)
             k_bsk_fourier<2048><<<(unsigned)bsk_polys, 256, 0, s>>>(d_tbsk_, (const double2*)d_ftw_, o4, o8, o16);
         else
             k_bsk_fourier<1024><<<(unsigned)bsk_polys, 256, 0, s>>>(d_tbsk_, (const double2*)d_ftw_, o4, o8, o16);
-        KG_CHECK(hipGetLastError());
-        KG_CHECK(hipStreamSynchronize(s));
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(s));
     } catch (...) {
         cleanup();
         throw;
@@ -338,11 +331,11 @@ void Device::download_server_key(uint64_t* ksk, size_t ksk_len, uint64_t* bsk, s
     if (!d_ksk_ || !d_tbsk_) throw Error(FR_ERR_NO_KEY, "no device-generated server key");
     if (ksk) {
         if (ksk_len != (size_t)p_.big() * p_.ks_level * (p_.n + 1)) throw Error(FR_ERR_INVALID, "ksk size");
-        KG_CHECK(hipMemcpy(ksk, d_ksk_, 8 * ksk_len, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(ksk, d_ksk_, 8 * ksk_len, hipMemcpyDeviceToHost));
     }
     if (bsk) {
         if (bsk_len != p_.bsk_len()) throw Error(FR_ERR_INVALID, "bsk size");
-        KG_CHECK(hipMemcpy(bsk, d_tbsk_, 8 * bsk_len, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(bsk, d_tbsk_, 8 * bsk_len, hipMemcpyDeviceToHost));
     }
 }
 

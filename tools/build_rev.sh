@@ -1,6 +1,7 @@
 #!/bin/bash
 # Build libfheregex.so of a git revision (A/B baseline) into fhe-regex_amd/build/exp/lib_NAME.so:
 #   tools/build_rev.sh NAME REV [-DFOO=1 ...]
+# (HIPFLAGS_EXTRA reaches revisions whose Makefile knows it)
 set -e
 cd "$(dirname "$0")/.."
 name=$1; rev=$2; shift 2

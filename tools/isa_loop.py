@@ -6,7 +6,7 @@ import sys
 
 def main():
     pat = sys.argv[1]
-    path = sys.argv[2] if len(sys.argv) > 2 else "fhe-regex_amd/build/asm/device-hip-amdgcn-amd-amdhsa-gfx950.s"
+    path = sys.argv[2] if len(sys.argv) > 2 else "fhe-regex_amd/build/asm/fft_br-hip-amdgcn-amd-amdhsa-gfx950.s"
     lines = open(path).read().split("\n")
     start = next(i for i, l in enumerate(lines) if re.match(r"^_Z\w*" + pat + r"\w*:", l))
     end = next(i for i in range(start, len(lines)) if lines[i].startswith("\t.size") or lines[i].startswith(".Lfunc_end"))
