@@ -1,0 +1,347 @@
+// C-ABI entries of the client side and the keys (include/fheregex.h): client and server
+// keys, encryption, the radix wire format, decryption.
+#include <cstring>
+#include <vector>
+
+#include "ctx.h"
+
+using namespace fr;
+
+extern "C" {
+
+int fr_load_client_key(fr_ctx* ctx, const uint8_t* data, size_t len) {
+    FR_TRY({
+        NEED(ctx && data);
+        ClientKey ck = parse_client_key(data, len);
+        if ((size_t)ctx->p.k * ctx->p.N != ck.s_big.size() || (size_t)ctx->p.n != ck.s_small.size())
+            throw Error(FR_ERR_INVALID, "client key dimensions do not match the context params");
+        // the radix encoding this build implements: PARAM_MESSAGE_2_CARRY_2, 4 blocks per
+        // character (ciphertext.rs:1,12-13,43-44); a key of other parameters would decode wrong
+        if (ck.message_modulus != MESSAGE_MODULUS || ck.carry_modulus != CARRY_MODULUS || ck.num_blocks != 4)
+            throw Error(FR_ERR_INVALID, "client key: message/carry modulus or block count other than "
+                                        "PARAM_MESSAGE_2_CARRY_2 with 4 blocks");
+        ctx->ck = std::move(ck);
+        ctx->has_ck = true;
+        ctx->has_sk = false;
+    })
+}
+
+// Every draw below runs under one RngKey (chacha.h).  The seeded entry points build
+// theirs with from_seed and the keyed ones with from_bytes, or from_os for a NULL
+// key; both then share one body.  The host copy of the key is wiped on the way out.
+namespace {
+struct ScopedKey {
+    RngKey k;
+    explicit ScopedKey(uint64_t seed) : k(RngKey::from_seed(seed)) {}
+    explicit ScopedKey(const uint8_t* key32) : k(key32 ? RngKey::from_bytes(key32) : RngKey::from_os()) {}
+    ~ScopedKey() { wipe_key(k); }
+    ScopedKey(const ScopedKey&) = delete;
+    ScopedKey& operator=(const ScopedKey&) = delete;
+};
+}  // namespace
+
+static void gen_client_key_with(fr_ctx* ctx, const RngKey& key) {
+    ctx->ck = gen_client_key(ctx->p, key);
+    ctx->has_ck = true;
+    ctx->has_sk = false;
+}
+
+int fr_gen_client_key(fr_ctx* ctx, uint64_t seed) {
+    FR_TRY({
+        NEED(ctx);
+        ScopedKey key(seed);
+        gen_client_key_with(ctx, key.k);
+    })
+}
+
+int fr_gen_client_key_keyed(fr_ctx* ctx, const uint8_t* key32) {
+    FR_TRY({
+        NEED(ctx);
+        ScopedKey key(key32);
+        gen_client_key_with(ctx, key.k);
+    })
+}
+
+int fr_serialize_client_key(fr_ctx* ctx, uint8_t* buf, size_t cap, size_t* written) {
+    FR_TRY({
+        NEED(ctx && written);
+        if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
+        const std::vector<uint8_t> b = serialize_client_key(ctx->ck);
+        *written = b.size();
+        if (!buf) return FR_OK;  // size query
+        NEED(cap >= b.size());
+        std::memcpy(buf, b.data(), b.size());
+    })
+}
+
+// where the server key is generated (fr_set_keygen); checked before a key is drawn
+static bool server_keygen_on_device(fr_ctx* ctx) {
+    if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
+    const bool on_dev = ctx->dev && ctx->p.ring == FR_RING_FFT && ctx->keygen != FR_KEYGEN_HOST;
+    if (ctx->keygen == FR_KEYGEN_DEVICE && !on_dev)
+        throw Error(ctx->dev ? FR_ERR_INVALID : FR_ERR_NO_DEVICE, "device keygen needs a device and the FFT ring");
+    return on_dev;
+}
+static void gen_server_key_with(fr_ctx* ctx, bool on_dev, const RngKey& key) {
+    ctx->has_sk = false;
+    if (on_dev) {
+        ctx->ksk.clear();
+        ctx->bsk.clear();
+        ctx->dev->gen_server_key(ctx->ck, key);
+    } else {
+        gen_ksk(ctx->p, ctx->ck, key, ctx->ksk);
+        gen_bsk(ctx->p, ctx->ck, key, ctx->bsk);
+        if (ctx->dev) ctx->dev->upload_keys(ctx->ksk, ctx->bsk);
+    }
+    ctx->sk_on_device = on_dev;
+    ctx->has_sk = true;
+}
+
+int fr_gen_server_key(fr_ctx* ctx, uint64_t seed) {
+    FR_TRY({
+        NEED(ctx);
+        const bool on_dev = server_keygen_on_device(ctx);
+        ScopedKey key(seed);
+        gen_server_key_with(ctx, on_dev, key.k);
+    })
+}
+
+int fr_gen_server_key_keyed(fr_ctx* ctx, const uint8_t* key32) {
+    FR_TRY({
+        NEED(ctx);
+        const bool on_dev = server_keygen_on_device(ctx);
+        ScopedKey key(key32);
+        gen_server_key_with(ctx, on_dev, key.k);
+    })
+}
+
+int fr_server_key_sizes(fr_ctx* ctx, size_t* ksk_len, size_t* bsk_len) {
+    FR_TRY({
+        NEED(ctx);
+        const Params& p = ctx->p;
+        if (ksk_len) *ksk_len = (size_t)p.big() * p.ks_level * (p.n + 1);
+        if (bsk_len) *bsk_len = p.bsk_len();
+    })
+}
+
+int fr_export_server_key(fr_ctx* ctx, uint64_t* ksk, size_t ksk_len, uint64_t* bsk, size_t bsk_len) {
+    FR_TRY({
+        NEED(ctx);
+        if (!ctx->has_sk) throw Error(FR_ERR_NO_KEY, "server key not generated");
+        if (ctx->sk_on_device) {
+            ctx->device().download_server_key(ksk, ksk_len, bsk, bsk_len);
+            return FR_OK;
+        }
+        if (ksk) {
+            NEED(ksk_len == ctx->ksk.size());
+            std::memcpy(ksk, ctx->ksk.data(), 8 * ksk_len);
+        }
+        if (bsk) {
+            NEED(bsk_len == ctx->bsk.size());
+            std::memcpy(bsk, ctx->bsk.data(), 8 * bsk_len);
+        }
+    })
+}
+
+int fr_load_server_key(fr_ctx* ctx, const uint64_t* ksk, size_t ksk_len, const uint64_t* bsk, size_t bsk_len) {
+    FR_TRY({
+        NEED(ctx && ksk && bsk);
+        const Params& p = ctx->p;
+        if (ksk_len != (size_t)p.big() * p.ks_level * (p.n + 1) || bsk_len != p.bsk_len())
+            throw Error(FR_ERR_INVALID, "server key lengths do not match the context params (fr_server_key_sizes)");
+        ctx->has_sk = false;
+        std::vector<uint64_t> k(ksk, ksk + ksk_len), b(bsk, bsk + bsk_len);
+        if (ctx->dev) ctx->dev->upload_keys(k, b);
+        ctx->ksk = std::move(k);
+        ctx->bsk = std::move(b);
+        ctx->sk_on_device = false;
+        ctx->has_sk = true;
+    })
+}
+
+// preconditions of fr_encrypt_blocks[_keyed], checked before a key is drawn
+static void check_encrypt_blocks(fr_ctx* ctx, const uint8_t* msgs, size_t count, const uint64_t* out) {
+    NEED(ctx && (msgs || !count) && (out || !count));
+    if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
+    for (size_t i = 0; i < count; ++i) NEED(msgs[i] < 16);
+}
+
+int fr_encrypt_blocks(fr_ctx* ctx, const uint8_t* msgs, size_t count, uint64_t seed, uint64_t first_block,
+                      uint64_t* out) {
+    FR_TRY({
+        check_encrypt_blocks(ctx, msgs, count, out);
+        ScopedKey key(seed);
+        encrypt_blocks(ctx->p, ctx->ck, msgs, count, key.k, first_block, out);
+    })
+}
+
+int fr_encrypt_blocks_keyed(fr_ctx* ctx, const uint8_t* msgs, size_t count, const uint8_t* key32,
+                            uint64_t first_block, uint64_t* out) {
+    FR_TRY({
+        check_encrypt_blocks(ctx, msgs, count, out);
+        ScopedKey key(key32);
+        encrypt_blocks(ctx->p, ctx->ck, msgs, count, key.k, first_block, out);
+    })
+}
+
+// radix messages of a string (ciphertext.rs:18-29: 4 blocks of 2 bits, least significant first)
+
+static std::vector<uint8_t> str_blocks(const char* s, size_t len) {
+    std::vector<uint8_t> msgs(4 * len);
+    for (size_t i = 0; i < len; ++i) {
+        const uint8_t c = (uint8_t)s[i];
+        if (c > 127) throw Error(FR_ERR_NON_ASCII, "content contains non-ascii characters");
+        for (int b = 0; b < 4; ++b) msgs[4 * i + b] = (c >> (2 * b)) & 3;
+    }
+    return msgs;
+}
+
+// radix messages of fr_encrypt_str[_keyed]'s string, after its preconditions
+static std::vector<uint8_t> check_encrypt_str(fr_ctx* ctx, const char* s, size_t len, const void* out) {
+    NEED(ctx && (s || !len) && (out || !len));
+    if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
+    return str_blocks(s, len);
+}
+
+int fr_encrypt_str(fr_ctx* ctx, const char* s, size_t len, uint64_t seed, uint64_t* out) {
+    FR_TRY({
+        const std::vector<uint8_t> msgs = check_encrypt_str(ctx, s, len, out);
+        ScopedKey key(seed);
+        encrypt_blocks(ctx->p, ctx->ck, msgs.data(), msgs.size(), key.k, 0, out);
+    })
+}
+
+int fr_encrypt_str_keyed(fr_ctx* ctx, const char* s, size_t len, const uint8_t* key32, uint64_t* out) {
+    FR_TRY({
+        const std::vector<uint8_t> msgs = check_encrypt_str(ctx, s, len, out);
+        ScopedKey key(key32);
+        encrypt_blocks(ctx->p, ctx->ck, msgs.data(), msgs.size(), key.k, 0, out);
+    })
+}
+
+// preconditions of fr_encrypt_upload_str[_keyed] in the seeded call's order: client key,
+// device, ASCII content
+static std::vector<uint8_t> check_encrypt_upload_str(fr_ctx* ctx, const char* s, size_t len, const fr_ct* out) {
+    NEED(ctx && (s || !len) && (out || !len));
+    if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
+    (void)ctx->device();
+    return str_blocks(s, len);
+}
+static void encrypt_upload_with(fr_ctx* ctx, const std::vector<uint8_t>& msgs, const RngKey& key, fr_ct* out) {
+    Device& dev = ctx->device();
+    std::vector<int> slots(msgs.size());
+    for (auto& x : slots) x = dev.alloc_slot();
+    try {
+        dev.encrypt_to_slots(ctx->ck, msgs.data(), msgs.size(), key, 0, slots.data());
+    } catch (...) {
+        for (int x : slots) dev.free_slot(x);
+        throw;
+    }
+    for (size_t i = 0; i < msgs.size() / 4; ++i) {
+        HandleRec r;
+        for (int b = 0; b < 4; ++b) r.b[b].slot = slots[4 * i + b];
+        out[i] = ctx->new_handle(r);
+    }
+}
+
+int fr_encrypt_upload_str(fr_ctx* ctx, const char* s, size_t len, uint64_t seed, fr_ct* out) {
+    FR_TRY({
+        const std::vector<uint8_t> msgs = check_encrypt_upload_str(ctx, s, len, out);
+        ScopedKey key(seed);
+        encrypt_upload_with(ctx, msgs, key.k, out);
+    })
+}
+
+int fr_encrypt_upload_str_keyed(fr_ctx* ctx, const char* s, size_t len, const uint8_t* key32, fr_ct* out) {
+    FR_TRY({
+        const std::vector<uint8_t> msgs = check_encrypt_upload_str(ctx, s, len, out);
+        ScopedKey key(key32);
+        encrypt_upload_with(ctx, msgs, key.k, out);
+    })
+}
+
+// bincode (fixint, little endian) of tfhe-rs 0.2 RadixCiphertext:
+//   u64 n_blocks, then per block: u64 len, len x u64 LWE words, u64 degree,
+//   u64 message_modulus, u64 carry_modulus
+int fr_radix_serialize(fr_ctx* ctx, const uint64_t* blocks, size_t n_blocks, uint64_t degree, uint8_t* buf,
+                       size_t cap, size_t* written) {
+    FR_TRY({
+        NEED(ctx && (blocks || !n_blocks) && written);
+        const size_t L = (size_t)ctx->p.lwe_len();
+        const size_t need = 8 + n_blocks * (8 * (L + 4));
+        *written = need;
+        if (!buf) return FR_OK;  // size query
+        NEED(cap >= need);
+        uint8_t* o = buf;
+        auto put = [&](uint64_t v) {
+            std::memcpy(o, &v, 8);
+            o += 8;
+        };
+        put(n_blocks);
+        for (size_t b = 0; b < n_blocks; ++b) {
+            put(L);
+            std::memcpy(o, blocks + b * L, 8 * L);
+            o += 8 * L;
+            put(degree);
+            put(MESSAGE_MODULUS);
+            put(CARRY_MODULUS);
+        }
+    })
+}
+
+int fr_radix_deserialize(fr_ctx* ctx, const uint8_t* buf, size_t len, uint64_t* blocks, size_t max_blocks,
+                         size_t* n_blocks) {
+    FR_TRY({
+        NEED(ctx && buf && n_blocks);
+        const size_t L = (size_t)ctx->p.lwe_len();
+        size_t off = 0;
+        auto get = [&]() -> uint64_t {
+            if (off + 8 > len) throw Error(FR_ERR_INVALID, "radix ciphertext: truncated");
+            uint64_t v;
+            std::memcpy(&v, buf + off, 8);
+            off += 8;
+            return v;
+        };
+        const uint64_t nb = get();
+        if (nb > (len - 8) / (8 * (L + 4))) throw Error(FR_ERR_INVALID, "radix ciphertext: bad block count");
+        *n_blocks = (size_t)nb;
+        if (!blocks) return FR_OK;  // size query
+        NEED(max_blocks >= nb);
+        for (uint64_t b = 0; b < nb; ++b) {
+            if (get() != L) throw Error(FR_ERR_INVALID, "radix ciphertext: LWE size does not match the parameters");
+            if (off + 8 * L > len) throw Error(FR_ERR_INVALID, "radix ciphertext: truncated");
+            std::memcpy(blocks + b * L, buf + off, 8 * L);
+            off += 8 * L;
+            // the comparison LUTs read clean 2-bit blocks (x0 + 4 x1 in [0, 16)); a block
+            // carrying a carry (degree > message_modulus - 1) would decode silently wrong
+            if (get() > MESSAGE_MODULUS - 1)
+                throw Error(FR_ERR_INVALID, "radix ciphertext: block degree exceeds message_modulus - 1 (carries not propagated)");
+            if (get() != MESSAGE_MODULUS || get() != CARRY_MODULUS)
+                throw Error(FR_ERR_INVALID, "radix ciphertext: message/carry modulus does not match the parameters");
+        }
+        if (off != len) throw Error(FR_ERR_INVALID, "radix ciphertext: trailing bytes");
+    })
+}
+
+int fr_decode_block(fr_ctx* ctx, const uint64_t* lwe, uint32_t* v) {
+    FR_TRY({
+        NEED(ctx && lwe && v);
+        if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
+        *v = decode16(lwe_phase(ctx->p, ctx->ck, lwe));
+    })
+}
+
+int fr_decrypt_radix(fr_ctx* ctx, const uint64_t* blocks, uint64_t* value) {
+    FR_TRY({
+        NEED(ctx && blocks && value);
+        if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
+        uint64_t v = 0;
+        for (int b = 0; b < 4; ++b) {
+            uint32_t d = decode16(lwe_phase(ctx->p, ctx->ck, blocks + (size_t)b * ctx->p.lwe_len()));
+            v += (uint64_t)(d % 4) << (2 * b);
+        }
+        *value = v & 0xFF;
+    })
+}
+
+}  // extern "C"

@@ -1,0 +1,157 @@
+// The context behind the C ABI's opaque fr_ctx (internal): parameters, keys, ciphertext
+// handles, the plan cache's storage, and the error boundary every entry point goes through.
+#pragma once
+#include <algorithm>
+#include <chrono>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "device.h"
+#include "fheregex.h"
+#include "keys.h"
+#include "plan.h"
+#include "regex.h"
+
+namespace fr {
+
+// PARAM_MESSAGE_2_CARRY_2 (ciphertext.rs:1): 2-bit message, 2-bit carry per block
+constexpr uint64_t MESSAGE_MODULUS = 4, CARRY_MODULUS = 4;
+
+struct Block {
+    int slot = -1;     // -1: trivial block
+    uint8_t triv = 0;  // value of a trivial block (message, < 16)
+};
+struct HandleRec {
+    bool live = false;
+    bool is_bool = false;  // block 0 carries 0/1, blocks 1..3 trivial zero
+    Block b[4];
+};
+
+static inline double now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// One cached match plan (match.cpp: the plan cache)
+struct CachedMatch {
+    std::string key;           // match_key: every numeric field first, the pattern last
+    size_t parts = 1;          // fr_has_match_parts' max_parts (also in the key)
+    int lane = 0;              // lane whose plan copy this is (0: lane 0; also in the key)
+    std::vector<int32_t> sig;  // canonical content shape (content_signature)
+    Plan plan;
+    size_t n_gates = 0;        // program gates of one match (copy m's gates start at m * n_gates)
+    std::vector<ProgOut> outs;  // one match's outputs (its parts, fr_has_match_parts)
+    Recorded rec;              // the recording's counters
+    uint64_t last_use = 0;
+};
+
+}  // namespace fr
+
+struct fr_plan_cache {
+    std::vector<std::unique_ptr<fr::CachedMatch>> entries;
+    size_t capacity = 8;
+    size_t slot_cap = (size_t)1 << 18;  // intermediate slots held by all cached plans
+    size_t slots_held = 0;
+    uint64_t clock = 0, hits = 0, misses = 0;
+
+    fr_plan_cache() {
+        if (const char* ev = std::getenv("FR_PLAN_CACHE")) capacity = (size_t)std::max(0, std::atoi(ev));
+        if (const char* ev = std::getenv("FR_PLAN_CACHE_SLOTS")) slot_cap = (size_t)std::max(0L, std::atol(ev));
+    }
+};
+
+struct fr_ctx {
+    fr::Params p;
+    std::unique_ptr<fr::Device> dev;
+    fr::ClientKey ck;
+    bool has_ck = false;
+    std::vector<uint64_t> ksk, bsk;
+    bool has_sk = false;
+    std::vector<fr::HandleRec> handles;
+    std::vector<uint32_t> free_handles;
+    int lowering = FR_LOWER_THRESHOLD;
+    int engine = FR_ENGINE_AUTO;
+    int grammar = FR_GRAMMAR_REFERENCE;
+    int keygen = FR_KEYGEN_AUTO;
+    bool sk_on_device = false;  // server key generated on the device (export downloads it)
+    bool multi_value = true;  // merge same-input small-norm LUTs into one blind rotation
+    bool async_match = true;  // has_match returns once its launches are enqueued (fr_set_async)
+    uint64_t next_lane = 0;   // fr_set_lanes: consecutive asynchronous matches round-robin over the lanes
+    fr_plan_cache plans;
+    // content_signature scratch: canonical id of an arena slot, valid while sig_gen[slot] == gen
+    std::vector<int32_t> sig_id;
+    std::vector<uint32_t> sig_gen;
+    uint32_t gen = 0;
+
+    // match.cpp: the cached plans give their slots and device batches back while the
+    // device is alive (the members above outlive this body)
+    ~fr_ctx();
+
+    fr::Device& device() {
+        if (!dev) throw fr::Error(FR_ERR_NO_DEVICE, "host-only context: no HIP device");
+        return *dev;
+    }
+    // the device, once it holds a server key (what every bootstrap needs)
+    fr::Device& keyed_device() {
+        fr::Device& d = device();
+        if (!has_sk || !d.has_keys()) throw fr::Error(FR_ERR_NO_KEY, "server key not generated");
+        return d;
+    }
+    fr_ct new_handle(const fr::HandleRec& r) {
+        uint32_t h;
+        if (!free_handles.empty()) {
+            h = free_handles.back();
+            free_handles.pop_back();
+            handles[h] = r;
+        } else {
+            h = (uint32_t)handles.size();
+            handles.push_back(r);
+        }
+        handles[h].live = true;
+        return h;
+    }
+    // a boolean handle: block 0 in arena slot `slot`, or (slot < 0) the trivial value triv
+    fr_ct new_bool(int slot, uint8_t triv = 0) {
+        fr::HandleRec r;
+        r.is_bool = true;
+        r.b[0].slot = slot;
+        r.b[0].triv = triv;
+        return new_handle(r);
+    }
+    fr::HandleRec& get(fr_ct h) {
+        if (h >= handles.size() || !handles[h].live) throw fr::Error(FR_ERR_INVALID, "invalid ciphertext handle");
+        return handles[h];
+    }
+    void release(fr_ct h) {
+        fr::HandleRec& r = get(h);
+        for (auto& b : r.b)
+            if (b.slot >= 0 && dev) dev->free_slot(b.slot);
+        r.live = false;
+        free_handles.push_back(h);
+    }
+};
+
+#define FR_TRY(...)                                   \
+    try {                                             \
+        __VA_ARGS__;                                       \
+        return FR_OK;                                 \
+    } catch (const fr::Error& e) {                    \
+        fr::set_last_error(e.what());                 \
+        return e.code;                                \
+    } catch (const std::bad_alloc&) {                 \
+        fr::set_last_error("out of memory");          \
+        return FR_ERR_OOM;                            \
+    } catch (const std::exception& e) {               \
+        fr::set_last_error(e.what());                 \
+        return FR_ERR_INVALID;                        \
+    } catch (...) {                                   \
+        fr::set_last_error("unknown error");          \
+        return FR_ERR_INVALID;                        \
+    }
+
+#define NEED(x)                                                               \
+    do {                                                                      \
+        if (!(x)) throw fr::Error(FR_ERR_INVALID, "invalid argument: " #x);   \
+    } while (0)

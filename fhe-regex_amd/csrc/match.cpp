@@ -1,0 +1,528 @@
+// The match engine behind the C ABI: the plan cache, has_match and its batch / range /
+// parts forms, the level-sharded match and the host-only schedule.
+#include <climits>
+
+#include "ctx.h"
+
+using namespace fr;
+
+namespace {
+
+// ------------------------------------------------------------ plan cache
+// The circuit of a match is data-oblivious: it depends on (pattern, grammar,
+// engine, lowering, multi-value, length, start range, batch size) and on the
+// content's *shape* -- which blocks are trivial and their values, and which
+// positions share a ciphertext (the multi-value merge compares inputs) -- never on
+// the ciphertexts themselves.  A cached plan is a template plan (Plan::n_refs):
+// its content inputs are references that each call binds to the call's arena
+// slots through a content map, so a fresh ciphertext of the same shape replays
+// the plan (the reference re-plans every call, engine.rs:8-42).  A cached plan
+// keeps its intermediate slots and a device copy of its gate batches; a repeat
+// call skips parse -> record -> lower -> compile and the descriptor uploads, and
+// only binds the content and enqueues the levels.  The cache is bounded by entries
+// (LRU, default 8, FR_PLAN_CACHE) and by the intermediate slots it holds (default
+// 2^18 = 4.3 GB at k = 1, FR_PLAN_CACHE_SLOTS); eviction runs before the new plan
+// allocates, and a plan larger than the slot budget runs uncached.
+
+// The key is a fixed number of '|'-terminated numeric fields followed by the pattern, so a
+// pattern's own text (which may contain '|' and digits) cannot make two keys collide.
+std::string match_key(fr_ctx* ctx, const char* pattern, size_t n, size_t M, size_t lo, size_t hi, size_t parts,
+                      int lane) {
+    std::string k;
+    for (size_t v : {(size_t)ctx->grammar, (size_t)ctx->engine, (size_t)ctx->lowering, (size_t)ctx->multi_value, n, M,
+                     lo, hi, parts, (size_t)lane})
+        k += std::to_string(v) + "|";
+    k += pattern;
+    return k;
+}
+// Canonical shape of the content: per position and block, the trivial value
+// (-1 - v), the index of the block's ciphertext in order of first appearance (>= 0:
+// equal indices = the same arena slot), or markers for an absent position / a
+// boolean handle.  Two contents with equal signatures lower, schedule and merge
+// identically.  cmap (if given) receives the content map: block r -> slot (-1: none).
+std::vector<int32_t> content_signature(fr_ctx* ctx, const fr_ct* content, size_t n, std::vector<int>* cmap) {
+    constexpr int32_t ABSENT = INT32_MIN, BOOL = INT32_MIN + 1;
+    std::vector<int32_t> sig;
+    sig.reserve(4 * n);
+    if (cmap) cmap->assign(4 * n, -1);
+    if (++ctx->gen == 0) {  // generation wrapped: forget every stamp
+        std::fill(ctx->sig_gen.begin(), ctx->sig_gen.end(), 0u);
+        ctx->gen = 1;
+    }
+    int32_t next_id = 0;
+    for (size_t q = 0; q < n; ++q) {
+        if (content[q] == 0xFFFFFFFFu) {
+            sig.insert(sig.end(), 4, ABSENT);
+            continue;
+        }
+        const HandleRec& h = ctx->get(content[q]);
+        for (int b = 0; b < 4; ++b) {
+            const int s = h.b[b].slot;
+            if (h.is_bool) {
+                sig.push_back(BOOL);
+            } else if (s < 0) {
+                sig.push_back(-1 - (int32_t)h.b[b].triv);
+            } else {
+                if ((size_t)s >= ctx->sig_id.size()) {
+                    ctx->sig_id.resize((size_t)s + 1024);
+                    ctx->sig_gen.resize((size_t)s + 1024, 0u);
+                }
+                if (ctx->sig_gen[s] != ctx->gen) {
+                    ctx->sig_gen[s] = ctx->gen;
+                    ctx->sig_id[s] = next_id++;
+                }
+                sig.push_back(ctx->sig_id[s]);
+            }
+            if (cmap) (*cmap)[4 * q + b] = s;
+        }
+    }
+    return sig;
+}
+
+void drop_cached(fr_ctx* ctx, CachedMatch& e) {
+    ctx->plans.slots_held -= std::min(ctx->plans.slots_held, e.plan.slot.size());
+    if (ctx->dev) release_plan(*ctx->dev, e.plan);
+}
+// drop least-recently-used plans until `entries` and `slots` more fit
+void evict_for(fr_ctx* ctx, size_t entries, size_t slots) {
+    fr_plan_cache& pc = ctx->plans;
+    while (!pc.entries.empty() &&
+           (pc.entries.size() + entries > pc.capacity || pc.slots_held + slots > pc.slot_cap)) {
+        size_t v = 0;
+        for (size_t i = 1; i < pc.entries.size(); ++i)
+            if (pc.entries[i]->last_use < pc.entries[v]->last_use) v = i;
+        drop_cached(ctx, *pc.entries[v]);
+        pc.entries.erase(pc.entries.begin() + (long)v);
+    }
+}
+
+// the content handles a program reads, for each of M matches over n positions
+// (content[m * n + q]): every one present and a radix character
+void check_content(fr_ctx* ctx, const Program& prog, const fr_ct* content, size_t n, size_t M) {
+    for (auto& g : prog.gates)
+        for (auto& in : g.ins)
+            if (in.src < 0) {
+                const size_t q = (size_t)((-in.src - 1) / 4);
+                for (size_t m = 0; m < M; ++m) {
+                    const fr_ct c = q < n ? content[m * n + q] : 0xFFFFFFFFu;
+                    if (c == 0xFFFFFFFFu) throw Error(FR_ERR_INVALID, "content position not provided");
+                    if (ctx->get(c).is_bool) throw Error(FR_ERR_INVALID, "content handle is not a radix character");
+                }
+            }
+}
+
+// the counters of a recording and of its plan, into zeroed stats
+void fill_stats(fr_match_stats& s, const Recorded& rec, const Plan& P) {
+    s.ct_ops = rec.ct_ops;
+    s.cache_hits = rec.cache_hits;
+    s.n_branches = rec.n_branches;
+    add_plan_stats(P, &s);
+}
+
+// M independent matches of one pattern over M contents of n positions each
+// (content[m * n + q]): one plan whose program is M copies of the match's lowered
+// program, so every level of the M matches shares its launches (M = 1: has_match).
+// parts > 1 (fr_has_match_parts): each match returns up to `parts` booleans whose OR is
+// its result, outs[m * P + j] with P = *n_parts (the same for every m).
+void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const char* pattern, size_t lo, size_t hi,
+                fr_ct* outs, fr_match_stats* st, size_t parts = 1, size_t* n_parts = nullptr) {
+    double t0 = now_ms();
+    pattern = pattern ? pattern : "";
+    Device& dev = ctx->keyed_device();
+    if (M == 0) throw Error(FR_ERR_INVALID, "no matches");
+    fr_plan_cache& pc = ctx->plans;
+    CachedMatch* hit = nullptr;
+    std::string key;
+    std::vector<int32_t> sig;
+    std::vector<int> cmap;
+    // lanes (fr_set_lanes): an asynchronous match of a cacheable plan runs on the next lane,
+    // with a plan of its own (its intermediate slots), so consecutive matches overlap
+    const int lane =
+        (ctx->async_match && dev.match_lanes() > 0 && pc.capacity) ? 1 + (int)(ctx->next_lane++ % dev.match_lanes()) : 0;
+    struct LaneScope {  // left on every exit, exceptions included
+        Device& d;
+        bool in = false;
+        void enter(int i) {
+            if (i > 0) d.enter_lane(i), in = true;
+        }
+        ~LaneScope() {
+            if (in) d.leave_lane();
+        }
+    } lane_scope{dev};
+    if (pc.capacity) {
+        key = match_key(ctx, pattern, n, M, lo, hi, parts, lane);
+        sig = content_signature(ctx, content, n * M, &cmap);
+        for (auto& e : pc.entries)
+            if (e->parts == parts && e->lane == lane && e->key == key && e->sig == sig) hit = e.get();
+    }
+    DeviceTimers before = dev.timers();
+    // 1. the plan and one match's outputs: the cached entry `c` (a hit, or this call's plan
+    // once kept), else the uncached plan `fresh` with the outputs of `prog`
+    CachedMatch* c = hit;
+    Recorded rec;
+    Program prog;
+    Plan fresh;
+    if (hit) {
+        ++pc.hits;
+        hit->last_use = ++pc.clock;
+        rec = hit->rec;
+    } else {
+        ++pc.misses;
+        ValueDag dag;
+        GrammarScope grammar(ctx->grammar);
+        rec = record_has_match_engine(dag, n, pattern, lo, hi, ctx->engine);
+        prog = lower(dag, rec.root, ctx->lowering, (int)parts);
+        check_content(ctx, prog, content, n, M);
+        // M copies: gate g of match m is m * G + g, content block cb of match m is 4 n m + cb
+        const size_t G = prog.gates.size();
+        std::vector<PGate> gates;
+        gates.reserve(G * M);
+        for (size_t m = 0; m < M; ++m)
+            for (const PGate& g0 : prog.gates) {
+                PGate g = g0;
+                for (auto& in : g.ins) in.src = in.src >= 0 ? in.src + (int)(m * G) : in.src - (int)(4 * n * m);
+                gates.push_back(std::move(g));
+            }
+        std::vector<fr_ct> inputs(content, content + n * M);
+        const bool keep = pc.capacity && G && G * M <= pc.slot_cap;
+        if (keep) evict_for(ctx, 1, G * M);  // before the new plan allocates its slots
+        fresh = compile_plan(ctx, gates, inputs, keep);
+        if (keep) {
+            // keep the plan: its slots stay allocated, its batches go to the device once
+            auto e = std::make_unique<CachedMatch>();
+            e->key = std::move(key);
+            e->parts = parts;
+            e->lane = lane;
+            e->sig = std::move(sig);
+            e->n_gates = G;
+            e->outs = prog.outs;
+            e->rec = rec;
+            e->last_use = ++pc.clock;
+            e->plan = std::move(fresh);
+            pc.slots_held += e->plan.slot.size();
+            c = e.get();
+            pc.entries.push_back(std::move(e));
+            c->plan.d_gates = dev.upload_gates(c->plan.gates.data(), c->plan.gates.size(), c->plan.n_refs);
+        }
+    }
+    // 2. launch and emit
+    Plan& plan = c ? c->plan : fresh;
+    const std::vector<ProgOut>& po = c ? c->outs : prog.outs;
+    const size_t G = c ? c->n_gates : prog.gates.size(), nO = po.size();
+    if (c) {
+        lane_scope.enter(lane);
+        dev.bind_content(cmap.data(), cmap.size());
+    }
+    double t1 = now_ms();
+    launch_plan(dev, plan);
+    if (hit && (nO < 1 || nO > parts))  // the caller's out buffer holds M * parts handles
+        throw Error(FR_ERR_INVALID, "cached plan has more outputs than the caller's parts");
+    // an uncached plan's one output takes its gate's slot; parts get copies (two parts may read one gate)
+    const bool take = !c && nO == 1;
+    for (size_t m = 0; m < M; ++m)
+        for (size_t j = 0; j < nO; ++j) {
+            ProgOut o = po[j];
+            if (o.gate >= 0) o.gate += (int)(m * G);
+            outs[m * nO + j] = make_output(ctx, o, plan.slot, take);
+        }
+    if (n_parts) *n_parts = nO;
+    if (!c) free_plan_slots(dev, plan.slot);  // later users of these slots are ordered after the launches (one stream)
+    if (!ctx->async_match) dev.sync();
+    double t2 = now_ms();
+    if (st) {
+        std::memset(st, 0, sizeof *st);
+        fill_stats(*st, rec, plan);
+        st->host_ms = t1 - t0;
+        st->device_ms = t2 - t1;
+        st->plan_cached = hit ? 1 : 0;
+        if (!ctx->async_match) {
+            // blocking call: this match's timers resolved at its sync.  An asynchronous
+            // call returns before its kernels ran, so its timers are left 0 here (read
+            // them with fr_device_timers after a synchronising call instead)
+            const DeviceTimers& after = dev.timers();
+            st->br_kernel_ms = after.br_ms - before.br_ms;
+            st->ks_kernel_ms = after.ks_ms - before.ks_ms;
+            st->br_launches = after.br_launches - before.br_launches;
+            st->br_gates = after.br_gates - before.br_gates;
+        }
+    }
+}
+
+}  // namespace
+
+// Cached plans go while the device is alive (fr_ctx's members are destroyed after this)
+fr_ctx::~fr_ctx() {
+    try {
+        for (auto& e : plans.entries) drop_cached(this, *e);
+    } catch (...) {
+    }
+}
+
+extern "C" {
+
+int fr_has_match(fr_ctx* ctx, const fr_ct* content, size_t n, const char* pattern, fr_ct* out, fr_match_stats* st) {
+    FR_TRY({
+        NEED(ctx && out && pattern && (content || !n));
+        match_impl(ctx, content, n, 1, pattern, 0, n, out, st);
+    })
+}
+
+int fr_set_plan_cache(fr_ctx* ctx, size_t capacity) {
+    FR_TRY({
+        NEED(ctx);
+        ctx->plans.capacity = capacity;
+        evict_for(ctx, 0, 0);  // drop the least recently used beyond the new capacity
+    })
+}
+
+int fr_set_lanes(fr_ctx* ctx, int32_t n) {
+    FR_TRY({
+        NEED(ctx && n >= 1 && n <= 8);
+        Device& dev = ctx->device();
+        if (n == 1 ? dev.match_lanes() == 0 : dev.match_lanes() == n) return FR_OK;
+        // the lanes' plan copies go with the lanes (their slots are held by the cache)
+        fr_plan_cache& pc = ctx->plans;
+        for (size_t i = pc.entries.size(); i-- > 0;)
+            if (pc.entries[i]->lane != 0) {
+                drop_cached(ctx, *pc.entries[i]);
+                pc.entries.erase(pc.entries.begin() + (long)i);
+            }
+        dev.set_lanes(n);
+        ctx->next_lane = 0;
+    })
+}
+
+int fr_set_async(fr_ctx* ctx, int32_t on) {
+    FR_TRY({
+        NEED(ctx);
+        ctx->async_match = on != 0;
+    })
+}
+
+int fr_set_plan_cache_slots(fr_ctx* ctx, size_t max_slots) {
+    FR_TRY({
+        NEED(ctx);
+        ctx->plans.slot_cap = max_slots;
+        evict_for(ctx, 0, 0);
+    })
+}
+
+int fr_plan_cache_stats(fr_ctx* ctx, uint64_t* entries, uint64_t* slots, uint64_t* hits, uint64_t* misses) {
+    FR_TRY({
+        NEED(ctx);
+        const fr_plan_cache& pc = ctx->plans;
+        if (entries) *entries = pc.entries.size();
+        if (slots) *slots = pc.slots_held;
+        if (hits) *hits = pc.hits;
+        if (misses) *misses = pc.misses;
+    })
+}
+
+int fr_has_match_batch(fr_ctx* ctx, const fr_ct* content, size_t n_chars, size_t n_matches, const char* pattern,
+                       fr_ct* out, fr_match_stats* st) {
+    FR_TRY({
+        NEED(ctx && out && pattern && n_matches && (content || !n_chars));
+        match_impl(ctx, content, n_chars, n_matches, pattern, 0, n_chars, out, st);
+    })
+}
+
+int fr_has_match_range(fr_ctx* ctx, const fr_ct* content, size_t n, const char* pattern, size_t lo, size_t hi,
+                       fr_ct* out, fr_match_stats* st) {
+    FR_TRY({
+        NEED(ctx && out && pattern && (content || !n) && lo <= hi);
+        match_impl(ctx, content, n, 1, pattern, lo, hi, out, st);
+    })
+}
+
+int fr_has_match_parts(fr_ctx* ctx, const fr_ct* content, size_t n, const char* pattern, size_t lo, size_t hi,
+                       size_t max_parts, fr_ct* out, size_t* n_parts, fr_match_stats* st) {
+    FR_TRY({
+        NEED(ctx && out && n_parts && pattern && (content || !n) && lo <= hi);
+        NEED(max_parts >= 1 && max_parts <= (size_t)MAX_FANIN);
+        match_impl(ctx, content, n, 1, pattern, lo, hi, out, st, max_parts, n_parts);
+    })
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------ level-sharded matches
+// One match split across ranks (the reference folds ct_or over the
+// start offsets of engine.rs:15-35, and anchored patterns have a single start,
+// engine.rs:51-57): every rank compiles the same plan over its own copy of the
+// content, runs a contiguous slice of every level's rotation jobs, and all-gathers
+// the level's output LWEs device to device (fr_shard_export / fr_shard_import into
+// the caller's device buffers, e.g. RCCL all_gather); every rank then holds the
+// level's outputs and goes on to the next.  The plan keeps its slots and a device
+// copy of its batches, so repeat runs only enqueue.
+struct fr_shard {
+    Plan plan;
+    ProgOut out;
+    std::vector<std::vector<int>> out_slots;     // per level: output slots in job order
+    std::vector<std::vector<uint32_t>> out_off;  // per level: first output of each job (+ total)
+    fr_match_stats stats{};
+};
+
+static const std::vector<int>& shard_level_range(const fr_shard* sh, uint32_t level, uint32_t b, uint32_t e,
+                                                 uint32_t& first, uint32_t& count) {
+    if (level >= sh->out_off.size()) throw Error(FR_ERR_INVALID, "shard: level out of range");
+    const auto& off = sh->out_off[level];
+    if (b > e || e + 1 > off.size()) throw Error(FR_ERR_INVALID, "shard: job range out of range");
+    first = off[b];
+    count = off[e] - off[b];
+    return sh->out_slots[level];
+}
+
+extern "C" {
+
+int fr_shard_plan(fr_ctx* ctx, const fr_ct* content, size_t n, const char* pattern, size_t lo, size_t hi,
+                  fr_shard** out, fr_match_stats* st) {
+    FR_TRY({
+        NEED(ctx && out && pattern && (content || !n) && lo <= hi);
+        Device& dev = ctx->keyed_device();
+        const double t0 = now_ms();
+        ValueDag dag;
+        GrammarScope grammar(ctx->grammar);
+        Recorded rec = record_has_match_engine(dag, n, pattern, lo, hi, ctx->engine);
+        Program prog = lower(dag, rec.root, ctx->lowering);
+        check_content(ctx, prog, content, n, 1);
+        auto sh = std::make_unique<fr_shard>();
+        sh->plan = compile_plan(ctx, prog.gates, std::vector<fr_ct>(content, content + n));
+        struct Guard {
+            fr_ctx* ctx;
+            fr_shard* sh;
+            ~Guard() {
+                if (sh) free_plan_slots(ctx->device(), sh->plan.slot);
+            }
+        } guard{ctx, sh.get()};
+        Plan& P = sh->plan;
+        P.d_gates = dev.upload_gates(P.gates.data(), P.gates.size());
+        sh->out = ProgOut{prog.out_gate, prog.out_w, prog.out_const};
+        for (size_t l = 0; l + 1 < P.level_off.size(); ++l) {
+            std::vector<int> slots;
+            std::vector<uint32_t> off{0};
+            for (size_t j = P.level_off[l]; j < P.level_off[l + 1]; ++j) {
+                for (int f = 0; f < P.gates[j].n_out; ++f) slots.push_back(P.gates[j].out_slot[f]);
+                off.push_back((uint32_t)slots.size());
+            }
+            sh->out_slots.push_back(std::move(slots));
+            sh->out_off.push_back(std::move(off));
+        }
+        fill_stats(sh->stats, rec, P);
+        sh->stats.host_ms = now_ms() - t0;
+        if (st) *st = sh->stats;
+        guard.sh = nullptr;
+        *out = sh.release();
+    })
+}
+int fr_shard_levels(const fr_shard* sh, uint32_t* levels) {
+    FR_TRY({
+        NEED(sh && levels);
+        *levels = (uint32_t)sh->out_off.size();
+    })
+}
+int fr_shard_jobs(const fr_shard* sh, uint32_t level, uint32_t* jobs) {
+    FR_TRY({
+        NEED(sh && jobs && level < sh->out_off.size());
+        *jobs = (uint32_t)sh->out_off[level].size() - 1;
+    })
+}
+int fr_shard_outputs(const fr_shard* sh, uint32_t level, uint32_t begin, uint32_t end, uint32_t* n_lwe) {
+    FR_TRY({
+        NEED(sh && n_lwe);
+        uint32_t first, count;
+        shard_level_range(sh, level, begin, end, first, count);
+        *n_lwe = count;
+    })
+}
+int fr_shard_run(fr_ctx* ctx, fr_shard* sh, uint32_t level, uint32_t begin, uint32_t end) {
+    FR_TRY({
+        NEED(ctx && sh);
+        uint32_t first, count;
+        shard_level_range(sh, level, begin, end, first, count);
+        const Plan& P = sh->plan;
+        const size_t a = P.level_off[level] + begin;
+        ctx->device().run_level_resident(P.d_gates + a, P.gates.data() + a, end - begin);
+    })
+}
+int fr_shard_export(fr_ctx* ctx, fr_shard* sh, uint32_t level, uint32_t begin, uint32_t end, uint64_t* dev_dst) {
+    FR_TRY({
+        NEED(ctx && sh);
+        uint32_t first, count;
+        const std::vector<int>& slots = shard_level_range(sh, level, begin, end, first, count);
+        NEED(dev_dst || !count);
+        ctx->device().slots_to_device(slots.data() + first, count, dev_dst);
+    })
+}
+int fr_shard_import(fr_ctx* ctx, fr_shard* sh, uint32_t level, uint32_t begin, uint32_t end, const uint64_t* dev_src) {
+    FR_TRY({
+        NEED(ctx && sh);
+        uint32_t first, count;
+        const std::vector<int>& slots = shard_level_range(sh, level, begin, end, first, count);
+        NEED(dev_src || !count);
+        ctx->device().device_to_slots(slots.data() + first, count, dev_src);
+    })
+}
+int fr_shard_finish(fr_ctx* ctx, fr_shard* sh, fr_ct* out, fr_match_stats* st) {
+    FR_TRY({
+        NEED(ctx && sh && out);
+        *out = finish_output(ctx, sh->out, sh->plan.slot, false);
+        if (st) *st = sh->stats;
+    })
+}
+int fr_shard_free(fr_ctx* ctx, fr_shard* sh) {
+    FR_TRY({
+        NEED(ctx);
+        if (!sh) return FR_OK;
+        std::unique_ptr<fr_shard> own(sh);
+        if (ctx->dev) release_plan(*ctx->dev, sh->plan);
+    })
+}
+
+// The same schedule without a device (CPU evaluators, tests): every content
+// position of [0, n_chars) is taken as an encrypted radix character.
+int fr_schedule_match(size_t n_chars, const char* pattern, size_t lo, size_t hi, int32_t lowering, int32_t engine,
+                      int32_t grammar, int32_t multi_value, fr_job* jobs, size_t jobs_cap, size_t* n_jobs,
+                      uint32_t* level_off, size_t level_cap, size_t* n_levels, int32_t* out3) {
+    size_t n_parts = 0;
+    return fr_schedule_match_parts(n_chars, pattern, lo, hi, lowering, engine, grammar, multi_value, 1, jobs, jobs_cap,
+                                   n_jobs, level_off, level_cap, n_levels, out3, &n_parts);
+}
+
+int fr_schedule_match_parts(size_t n_chars, const char* pattern, size_t lo, size_t hi, int32_t lowering,
+                            int32_t engine, int32_t grammar, int32_t multi_value, size_t max_parts, fr_job* jobs,
+                            size_t jobs_cap, size_t* n_jobs, uint32_t* level_off, size_t level_cap, size_t* n_levels,
+                            int32_t* outs3, size_t* n_parts) {
+    FR_TRY({
+        NEED(pattern && n_jobs && n_levels && outs3 && n_parts && lo <= hi);
+        NEED(max_parts >= 1 && max_parts <= (size_t)MAX_FANIN);
+        ValueDag dag;
+        GrammarScope gs(grammar);
+        Recorded rec = record_has_match_engine(dag, n_chars, pattern, lo, hi, engine);
+        Program prog = lower(dag, rec.root, lowering, (int)max_parts);
+        Schedule S = build_schedule(prog.gates, n_chars, multi_value != 0, [](int cb, int& key, int&) {
+            key = cb;
+            return true;
+        });
+        *n_jobs = S.jobs.size();
+        *n_levels = S.level_off.size() - 1;
+        *n_parts = prog.outs.size();
+        for (size_t j = 0; j < prog.outs.size(); ++j) {
+            outs3[3 * j] = prog.outs[j].gate;
+            outs3[3 * j + 1] = prog.outs[j].w;
+            outs3[3 * j + 2] = prog.outs[j].cst;
+        }
+        if (jobs) {
+            NEED(jobs_cap >= S.jobs.size());
+            static_assert(sizeof(fr_job) == sizeof(DevGate), "fr_job mirrors DevGate");
+            // (an empty schedule's vector has no storage: memcpy's source must not be null,
+            // UBSan finding of tests/test_fuzz_inputs.py)
+            if (!S.jobs.empty()) std::memcpy(jobs, S.jobs.data(), sizeof(DevGate) * S.jobs.size());
+        }
+        if (level_off) {
+            NEED(level_cap >= S.level_off.size());
+            for (size_t l = 0; l < S.level_off.size(); ++l) level_off[l] = (uint32_t)S.level_off[l];
+        }
+    })
+}
+
+}  // extern "C"

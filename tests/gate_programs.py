@@ -4,7 +4,7 @@
 A seeded Program is plain data: input values and gates.  From that one description come
 (a) the fheregex.Gate array for Context.run_gates, (b) the oracle's job list for
 Oracle.gates, level by level, and (c) the plaintext value of every gate.  The job list
-restates the executor's merge rule (capi.cpp build_schedule) in Program.jobs; a wrong
+restates the executor's merge rule (plan.h build_schedule) in Program.jobs; a wrong
 restatement shows as a failing word comparison, never as a silent pass.
 
 The norm^2 of a LUT's multi-value factor w_f is always even: its coefficients sum to

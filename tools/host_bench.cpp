@@ -1,7 +1,8 @@
 // Host-side cost of one has_match before the first launch: record the
 // reference's op DAG (parse + build_branches + Execution) and lower it to the
-// PBS program.  g++ -O2 -std=c++17 -Iinclude -Ifhe-regex_amd/csrc tools/host_bench.cpp
-//   fhe-regex_amd/build/{regex,merged,lower,capi,keys,fft}.o ... (see tools/host_bench.sh)
+// PBS program.  After `make -C fhe-regex_amd` has built the host objects:
+//   g++ -O2 -std=c++17 -Iinclude -Ifhe-regex_amd/csrc tools/host_bench.cpp
+//     fhe-regex_amd/build/{regex,merged,lower}.o -o tools/host_bench
 #include <chrono>
 #include <cstdio>
 #include <random>
