@@ -82,18 +82,31 @@ static bool server_keygen_on_device(fr_ctx* ctx) {
         throw Error(ctx->dev ? FR_ERR_INVALID : FR_ERR_NO_DEVICE, "device keygen needs a device and the FFT ring");
     return on_dev;
 }
-static void gen_server_key_with(fr_ctx* ctx, bool on_dev, const RngKey& key) {
+static void gen_server_key_with(fr_ctx* ctx, bool on_dev, const RngKey& key, bool compact = false) {
+    if (compact && ctx->p.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "compact server key: FFT ring only");
     ctx->has_sk = false;
+    ctx->sk_compact = false;
     if (on_dev) {
         ctx->ksk.clear();
         ctx->bsk.clear();
-        ctx->dev->gen_server_key(ctx->ck, key);
+        if (compact) {
+            // only the public mask key goes to the device; the noise is drawn here under `key`
+            ctx->mask_key = derive_mask_key(key);
+            ctx->dev->gen_server_key(ctx->ck, key, &ctx->mask_key);
+        } else {
+            ctx->dev->gen_server_key(ctx->ck, key);
+        }
     } else {
-        gen_ksk(ctx->p, ctx->ck, key, ctx->ksk);
-        gen_bsk(ctx->p, ctx->ck, key, ctx->bsk);
+        if (compact) {
+            gen_server_key_compact(ctx->p, ctx->ck, key, ctx->ksk, ctx->bsk, ctx->mask_key);
+        } else {
+            gen_ksk(ctx->p, ctx->ck, key, ctx->ksk);
+            gen_bsk(ctx->p, ctx->ck, key, ctx->bsk);
+        }
         if (ctx->dev) ctx->dev->upload_keys(ctx->ksk, ctx->bsk);
     }
     ctx->sk_on_device = on_dev;
+    ctx->sk_compact = compact;
     ctx->has_sk = true;
 }
 
@@ -112,6 +125,24 @@ int fr_gen_server_key_keyed(fr_ctx* ctx, const uint8_t* key32) {
         const bool on_dev = server_keygen_on_device(ctx);
         ScopedKey key(key32);
         gen_server_key_with(ctx, on_dev, key.k);
+    })
+}
+
+int fr_gen_server_key_compact(fr_ctx* ctx, uint64_t seed) {
+    FR_TRY({
+        NEED(ctx);
+        const bool on_dev = server_keygen_on_device(ctx);
+        ScopedKey key(seed);
+        gen_server_key_with(ctx, on_dev, key.k, true);
+    })
+}
+
+int fr_gen_server_key_compact_keyed(fr_ctx* ctx, const uint8_t* key32) {
+    FR_TRY({
+        NEED(ctx);
+        const bool on_dev = server_keygen_on_device(ctx);
+        ScopedKey key(key32);
+        gen_server_key_with(ctx, on_dev, key.k, true);
     })
 }
 
@@ -150,11 +181,71 @@ int fr_load_server_key(fr_ctx* ctx, const uint64_t* ksk, size_t ksk_len, const u
         if (ksk_len != (size_t)p.big() * p.ks_level * (p.n + 1) || bsk_len != p.bsk_len())
             throw Error(FR_ERR_INVALID, "server key lengths do not match the context params (fr_server_key_sizes)");
         ctx->has_sk = false;
+        ctx->sk_compact = false;
         std::vector<uint64_t> k(ksk, ksk + ksk_len), b(bsk, bsk + bsk_len);
         if (ctx->dev) ctx->dev->upload_keys(k, b);
         ctx->ksk = std::move(k);
         ctx->bsk = std::move(b);
         ctx->sk_on_device = false;
+        ctx->has_sk = true;
+    })
+}
+
+int fr_server_key_compact_size(fr_ctx* ctx, size_t* bytes) {
+    FR_TRY({
+        NEED(ctx && bytes);
+        if (ctx->p.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "compact server key: FFT ring only");
+        *bytes = compact_size(ctx->p);
+    })
+}
+
+int fr_export_server_key_compact(fr_ctx* ctx, uint8_t* buf, size_t cap, size_t* written) {
+    FR_TRY({
+        NEED(ctx && written);
+        if (!ctx->has_sk) throw Error(FR_ERR_NO_KEY, "server key not generated");
+        if (!ctx->sk_compact)
+            throw Error(FR_ERR_INVALID, "the installed server key was not generated in compact form: its masks are "
+                                        "not expandable from a mask key (fr_gen_server_key_compact)");
+        const size_t need = compact_size(ctx->p);
+        *written = need;
+        if (!buf) return FR_OK;  // size query
+        NEED(cap >= need);
+        std::vector<uint8_t> blob;
+        if (ctx->sk_on_device) {
+            size_t kl = 0, bl = 0;
+            fr_server_key_sizes(ctx, &kl, &bl);
+            std::vector<uint64_t> k(kl), b(bl);
+            ctx->device().download_server_key(k.data(), kl, b.data(), bl);
+            blob = pack_compact(ctx->p, ctx->mask_key, k, b);
+        } else {
+            blob = pack_compact(ctx->p, ctx->mask_key, ctx->ksk, ctx->bsk);
+        }
+        std::memcpy(buf, blob.data(), need);
+    })
+}
+
+int fr_load_server_key_compact(fr_ctx* ctx, const uint8_t* blob, size_t len) {
+    FR_TRY({
+        NEED(ctx && blob);
+        // length, magic and parameters are checked before the installed key is touched
+        const RngKey mk = check_compact(ctx->p, blob, len);
+        if (ctx->dev) {
+            ctx->has_sk = false;
+            ctx->dev->load_server_key_compact(mk, blob + COMPACT_HEADER);
+            ctx->ksk.clear();
+            ctx->bsk.clear();
+            ctx->sk_on_device = true;
+        } else {
+            std::vector<uint64_t> k, b;
+            RngKey m;
+            expand_compact(ctx->p, blob, len, k, b, m);
+            ctx->has_sk = false;
+            ctx->ksk = std::move(k);
+            ctx->bsk = std::move(b);
+            ctx->sk_on_device = false;
+        }
+        ctx->mask_key = mk;
+        ctx->sk_compact = true;
         ctx->has_sk = true;
     })
 }

@@ -76,6 +76,8 @@ struct fr_ctx {
     int grammar = FR_GRAMMAR_REFERENCE;
     int keygen = FR_KEYGEN_AUTO;
     bool sk_on_device = false;  // server key generated on the device (export downloads it)
+    bool sk_compact = false;    // the server key is in compact form (keys.h): mask_key expands its masks
+    fr::RngKey mask_key{};      // public by design
     bool multi_value = true;  // merge same-input small-norm LUTs into one blind rotation
     bool async_match = true;  // has_match returns once its launches are enqueued (fr_set_async)
     uint64_t next_lane = 0;   // fr_set_lanes: consecutive asynchronous matches round-robin over the lanes

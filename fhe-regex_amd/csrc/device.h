@@ -62,7 +62,17 @@ class Device {
     // server-key generation on the device (keygen.hip; FFT ring): the same keys
     // as gen_ksk + gen_bsk on the host, bit for bit; the torus keys stay on the
     // device for download_server_key
-    void gen_server_key(const ClientKey& ck, const RngKey& key);
+    // mask_key != nullptr: the compact form (keys.h) -- every kernel runs under the public
+    // mask key, `key` only draws the noise on the host and is no kernel argument
+    void gen_server_key(const ClientKey& ck, const RngKey& key, const RngKey* mask_key = nullptr);
+    // install a compact server key (FFT ring): `bodies` are the blob's KSK bodies
+    // [kN * ks_level] then BSK bodies [W][k+1][N] (u64, little endian, any alignment); one
+    // H2D copy, the masks expanded from mask_key on the device, then the transforms of
+    // gen_server_key.  The torus keys stay on the device for download_server_key.
+    void load_server_key_compact(const RngKey& mask_key, const uint8_t* bodies);
+    // stages of the last load_server_key_compact under fr_set_profiling, HIP events, ms:
+    // H2D copy, k_expand_ksk, k_expand_bsk, KSK limbs, k_bsk_fourier
+    const double* key_load_ms() const { return key_load_ms_; }
     void download_server_key(uint64_t* ksk, size_t ksk_len, uint64_t* bsk, size_t bsk_len);
     // fresh encryptions of block messages (encrypt_blocks, keys.h) written into
     // allocated arena slots, bit-identical to the host encryption
@@ -186,6 +196,8 @@ class Device {
                        void* ev_stop = nullptr);
     void free_fft();
     void build_ksk_limbs();  // d_kl_ from d_ksk_
+    void build_fourier_bsk();  // keygen.hip: d_fbsk_ (every lane layout in use) from d_tbsk_
+    double key_load_ms_[5] = {0, 0, 0, 0, 0};
     void stage_slot_list(const int* slots, size_t n);  // -> d_slot_list_ (stream order)
     int* d_slot_list_ = nullptr;
     size_t slot_list_cap_ = 0;
@@ -204,7 +216,7 @@ class Device {
     size_t small_batch_ = 256;
     void* stream_ = nullptr;  // hipStream_t
     uint64_t* d_ksk_ = nullptr;
-    uint64_t* d_tbsk_ = nullptr;  // torus BSK of a device-generated key (export)
+    uint64_t* d_tbsk_ = nullptr;  // torus BSK of a device-generated or device-expanded key (export)
     int8_t* d_kl_ = nullptr;      // KSK as balanced byte limbs [col*8 + limb][k] (MFMA keyswitch)
     int kl_cols_ = 0;
     bool ks_mfma_ = true;         // FR_KS_MFMA=0: the VALU lincomb+keyswitch kernel

@@ -13,7 +13,12 @@
 //   k_gen_bsk      one workgroup per GGSW row (w, r): masks A_j from ChaCha into
 //                  LDS, body = sum_j A_j * S_j (negacyclic, binary S: one
 //                  add/sub per set bit of S per coefficient) + noise, gadget m_w
-//                  2^(64 - pbs_base_log) on coefficient 0 of component r
+//                  2^(64 - pbs_base_log) on coefficient 0 of component r; COMPACT
+//                  (keys.h): rows r < k carry the gadget in the body, -m_w g S_r
+//   k_expand_ksk   compact key load, one wave per KSK row: the mask words from ChaCha
+//                  blocks of the public mask key, the body from the uploaded blob
+//   k_expand_bsk   the same for one GGSW row (w, r) per workgroup: k mask polynomials
+//                  and the body row.  Both are pure store streams, 16 bytes a store
 //   k_bsk_fourier  one workgroup per polynomial: fold, forward negacyclic FFT in
 //                  LDS (fft.h butterflies, host twiddles), scale 2^-log2(M),
 //                  written in the lane layouts of the blind-rotation kernels
@@ -21,6 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "chacha.h"
@@ -69,8 +75,10 @@ __global__ void __launch_bounds__(64) k_gen_ksk(RngKey key, int n, int L, int B,
 }
 
 // one GGSW row (w, r) of the torus BSK [w][r][c][coef]; 256 threads, N / 256
-// coefficients per thread; LDS: the mask polynomial A_j (N u64)
-template <int N>
+// coefficients per thread; LDS: the mask polynomial A_j (N u64).  COMPACT: `key` is the
+// public mask key, so no mask word may carry the gadget (word - ChaCha word would show
+// m_w): rows r < k subtract it from the body at every set bit of S_r instead.
+template <int N, bool COMPACT>
 __global__ void __launch_bounds__(256) k_gen_bsk(RngKey key, int k,const uint64_t* __restrict__ s_big,
                                                  const uint8_t* __restrict__ msg, const int32_t* __restrict__ noise,
                                                  uint64_t gadget, uint64_t* __restrict__ bsk) {
@@ -93,7 +101,7 @@ __global__ void __launch_bounds__(256) k_gen_bsk(RngKey key, int k,const uint64_
                 uint64_t v = chacha_u64(wd, q);
                 A[8 * b + q] = v;
                 // the gadget lands on coefficient 0 of component r after the body used A
-                if (j == r && b == 0 && q == 0 && msg[w]) v += gadget;
+                if (!COMPACT && j == r && b == 0 && q == 0 && msg[w]) v += gadget;
                 row[(size_t)j * N + 8 * b + q] = v;
             }
         }
@@ -128,8 +136,76 @@ __global__ void __launch_bounds__(256) k_gen_bsk(RngKey key, int k,const uint64_
         const int t = tid + 256 * q;
         uint64_t v = acc[q] + (uint64_t)(int64_t)e[t];
         if (r == k && t == 0 && msg[w]) v += gadget;
+        if (COMPACT && r < k && msg[w]) v -= gadget * (s_big[(size_t)r * N + t] & 1);
         row[(size_t)k * N + t] = v;
     }
+}
+
+// Compact-key expansion: masks are u64 numbers of the public mask key's streams at the
+// generator's indices, bodies come from the blob.  No sums, no LDS: store streams.
+
+// The u64 of ChaCha block b in a KSK row whose first mask word is stream number `first`:
+// word q is the row's element t0 + q, t0 = 8b - first (negative or past n where the block
+// straddles a neighbouring row: first = row * n is no multiple of 8).  The element's
+// address is ksk + row + 8b + q words, so pairs starting at a q of the row's parity are
+// 16-byte aligned and go out as one store; ODD rows store q = 0 and q = 7 alone.
+template <int ODD>
+__device__ __forceinline__ void expand_ksk_block(uint64_t* __restrict__ o, const uint32_t* w, int t0, int n) {
+    auto one = [&](int q) {
+        const int t = t0 + q;
+        if (t >= 0 && t < n) o[t] = chacha_u64(w, q);
+    };
+    if (ODD) one(0);
+#pragma unroll
+    for (int q = ODD; q + 1 < 8; q += 2) {
+        const int t = t0 + q;
+        if (t >= 0 && t + 1 < n) {
+            *reinterpret_cast<ulonglong2*>(o + t) = make_ulonglong2(chacha_u64(w, q), chacha_u64(w, q + 1));
+        } else {
+            one(q);
+            one(q + 1);
+        }
+    }
+    if (ODD) one(7);
+}
+
+// ksk[row][t] for t < n from the mask key, ksk[row][n] = body[row]; grid = rows, so every
+// store is inside row's n + 1 words
+__global__ void __launch_bounds__(64) k_expand_ksk(RngKey mask_key, int n, const uint64_t* __restrict__ body,
+                                                   uint64_t* __restrict__ ksk) {
+    const int row = blockIdx.x, lane = threadIdx.x;
+    const uint64_t first = (uint64_t)row * n, last = first + n;
+    uint64_t* o = ksk + (size_t)row * (n + 1);
+    for (uint64_t b = (first >> 3) + lane; b <= ((last - 1) >> 3); b += 64) {
+        uint32_t w[16];
+        chacha_block(mask_key, STREAM_KSK_MASK, b, w);
+        const int t0 = (int)((int64_t)(b * 8) - (int64_t)first);
+        if (row & 1) expand_ksk_block<1>(o, w, t0, n);
+        else expand_ksk_block<0>(o, w, t0, n);
+    }
+    if (lane == 0) o[n] = body[row];
+}
+
+// one GGSW row (w, r) of the torus BSK: k mask polynomials (kN / 8 whole ChaCha blocks,
+// 64 aligned bytes each) and the body polynomial from the blob; grid = W (k + 1) rows of
+// (k + 1) N words, so every store is inside bsk_len()
+template <int N>
+__global__ void __launch_bounds__(256) k_expand_bsk(RngKey mask_key, int k, const uint64_t* __restrict__ body,
+                                                    uint64_t* __restrict__ bsk) {
+    const int tid = threadIdx.x;
+    const size_t gr = blockIdx.x;  // w * (k + 1) + r
+    uint64_t* row = bsk + gr * (size_t)(k + 1) * N;
+    const uint64_t base = gr * (uint64_t)k * N;  // mask polynomial j starts at base + j N
+    for (int b = tid; b < k * (N / 8); b += 256) {
+        uint32_t wd[16];
+        chacha_block(mask_key, STREAM_BSK_MASK, (base >> 3) + b, wd);
+        ulonglong2* o = reinterpret_cast<ulonglong2*>(row + 8 * (size_t)b);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) o[q] = make_ulonglong2(chacha_u64(wd, 2 * q), chacha_u64(wd, 2 * q + 1));
+    }
+    const ulonglong2* src = reinterpret_cast<const ulonglong2*>(body + gr * N);
+    ulonglong2* dst = reinterpret_cast<ulonglong2*>(row + (size_t)k * N);
+    for (int x = tid; x < N / 2; x += 256) dst[x] = src[x];
 }
 
 // element m of lane tl in the last-phase layout of lane geometry E (slot order, geo.h)
@@ -250,12 +326,36 @@ void Device::encrypt_to_slots(const ClientKey& ck, const uint8_t* msgs, size_t c
     cleanup();
 }
 
-void Device::gen_server_key(const ClientKey& ck, const RngKey& key) {
-    if (p_.ring != FR_RING_FFT || !((p_.N == 2048 && p_.k == 1) || (p_.N == 1024 && p_.k == 2)))
-        throw Error(FR_ERR_INVALID, "device keygen: FFT ring, (k, N) in {(1, 2048), (2, 1024)}");
-    const int N = p_.N, M = N / 2, kp1 = p_.k + 1, n = p_.n, L = p_.ks_level;
+static void need_device_keygen_point(const Params& p, const char* what) {
+    if (p.ring != FR_RING_FFT || !((p.N == 2048 && p.k == 1) || (p.N == 1024 && p.k == 2)))
+        throw Error(FR_ERR_INVALID, std::string(what) + ": FFT ring, (k, N) in {(1, 2048), (2, 1024)}");
+}
+
+// Fourier BSK in the lane layouts of the shapes in use (E = 4, and the throughput shape's)
+void Device::build_fourier_bsk() {
+    const int N = p_.N, M = N / 2, kp1 = p_.k + 1;
+    const size_t bsk_polys = p_.bsk_ggsw() * kp1 * kp1;
+    const hipStream_t s = (hipStream_t)stream_;
+    for (int E : {4, 8, 16}) {
+        double*& dst = d_fbsk_[fbsk_index(E)];
+        (void)hipFree(dst);
+        dst = nullptr;
+        if (fbsk_needed(E) && (E < 16 || p_.k == 1)) HIP_CHECK(hipMalloc(&dst, 16 * bsk_polys * M));
+    }
+    double2 *o4 = (double2*)d_fbsk_[0], *o8 = (double2*)d_fbsk_[1], *o16 = (double2*)d_fbsk_[2];
+    if (N == 2048)
+        k_bsk_fourier<2048><<<(unsigned)bsk_polys, 256, 0, s>>>(d_tbsk_, (const double2*)d_ftw_, o4, o8, o16);
+    else
+        k_bsk_fourier<1024><<<(unsigned)bsk_polys, 256, 0, s>>>(d_tbsk_, (const double2*)d_ftw_, o4, o8, o16);
+    HIP_CHECK(hipGetLastError());
+}
+
+void Device::gen_server_key(const ClientKey& ck, const RngKey& key, const RngKey* mask_key) {
+    need_device_keygen_point(p_, "device keygen");
+    const int N = p_.N, kp1 = p_.k + 1, n = p_.n, L = p_.ks_level;
     const size_t rows = (size_t)p_.big() * L, nw = p_.bsk_ggsw();
-    const size_t bsk_polys = nw * kp1 * kp1;
+    const bool compact = mask_key != nullptr;
+    const RngKey& kkey = compact ? *mask_key : key;  // the key the kernels see
     // every queued launch of every lane that reads the old keys has finished before they go
     HIP_CHECK(hipDeviceSynchronize());
     // host: the noise draws and per-GGSW messages
@@ -293,7 +393,7 @@ void Device::gen_server_key(const ClientKey& ck, const RngKey& key) {
         (void)hipFree(d_ksk_);
         d_ksk_ = nullptr;
         HIP_CHECK(hipMalloc(&d_ksk_, 8 * rows * (n + 1)));
-        k_gen_ksk<<<(unsigned)rows, 64, 0, s>>>(key, n, L, p_.ks_base_log, d_ss, d_sb, d_kn, d_ksk_);
+        k_gen_ksk<<<(unsigned)rows, 64, 0, s>>>(kkey, n, L, p_.ks_base_log, d_ss, d_sb, d_kn, d_ksk_);
         HIP_CHECK(hipGetLastError());
         build_ksk_limbs();
 
@@ -302,24 +402,73 @@ void Device::gen_server_key(const ClientKey& ck, const RngKey& key) {
         d_tbsk_ = nullptr;
         HIP_CHECK(hipMalloc(&d_tbsk_, 8 * p_.bsk_len()));
         const uint64_t gadget = 1ULL << (64 - p_.pbs_base_log);
-        if (N == 2048) k_gen_bsk<2048><<<(unsigned)(nw * kp1), 256, 0, s>>>(key, p_.k, d_sb, d_msg, d_bn, gadget, d_tbsk_);
-        else k_gen_bsk<1024><<<(unsigned)(nw * kp1), 256, 0, s>>>(key, p_.k, d_sb, d_msg, d_bn, gadget, d_tbsk_);
+        const unsigned grid = (unsigned)(nw * kp1);
+        if (N == 2048 && !compact) k_gen_bsk<2048, false><<<grid, 256, 0, s>>>(kkey, p_.k, d_sb, d_msg, d_bn, gadget, d_tbsk_);
+        else if (N == 2048) k_gen_bsk<2048, true><<<grid, 256, 0, s>>>(kkey, p_.k, d_sb, d_msg, d_bn, gadget, d_tbsk_);
+        else if (!compact) k_gen_bsk<1024, false><<<grid, 256, 0, s>>>(kkey, p_.k, d_sb, d_msg, d_bn, gadget, d_tbsk_);
+        else k_gen_bsk<1024, true><<<grid, 256, 0, s>>>(kkey, p_.k, d_sb, d_msg, d_bn, gadget, d_tbsk_);
         HIP_CHECK(hipGetLastError());
 
-        // Fourier BSK in the lane layouts of the shapes in use (E = 4, and the throughput shape's)
-        for (int E : {4, 8, 16}) {
-            double*& dst = d_fbsk_[fbsk_index(E)];
-            (void)hipFree(dst);
-            dst = nullptr;
-            if (fbsk_needed(E) && (E < 16 || p_.k == 1)) HIP_CHECK(hipMalloc(&dst, 16 * bsk_polys * M));
-        }
-        double2 *o4 = (double2*)d_fbsk_[0], *o8 = (double2*)d_fbsk_[1], *o16 = (double2*)d_fbsk_[2];
-        if (N == 2048)
-            k_bsk_fourier<2048><<<(unsigned)bsk_polys, 256, 0, s>>>(d_tbsk_, (const double2*)d_ftw_, o4, o8, o16);
-        else
-            k_bsk_fourier<1024><<<(unsigned)bsk_polys, 256, 0, s>>>(d_tbsk_, (const double2*)d_ftw_, o4, o8, o16);
-        HIP_CHECK(hipGetLastError());
+        build_fourier_bsk();
         HIP_CHECK(hipStreamSynchronize(s));
+    } catch (...) {
+        cleanup();
+        throw;
+    }
+    cleanup();
+}
+
+void Device::load_server_key_compact(const RngKey& mask_key, const uint8_t* bodies) {
+    need_device_keygen_point(p_, "device load of a compact server key");
+    const int N = p_.N, kp1 = p_.k + 1, n = p_.n;
+    const size_t rows = compact_ksk_bodies(p_), brows = p_.bsk_ggsw() * kp1, words = rows + compact_bsk_bodies(p_);
+    // the BSK bodies follow the KSK bodies in one staging buffer and are read 16 bytes a lane
+    if (rows % 2 || N % 8) throw Error(FR_ERR_INVALID, "device load of a compact server key: alignment");
+    // every queued launch of every lane that reads the old keys has finished before they go
+    HIP_CHECK(hipDeviceSynchronize());
+    const hipStream_t s = (hipStream_t)stream_;
+    uint64_t* d_body = nullptr;
+    hipEvent_t ev[6] = {};
+    const bool timed = profiling_ != 0;
+    auto cleanup = [&] {
+        (void)hipFree(d_body);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    };
+    auto mark = [&](int i) {
+        if (timed) HIP_CHECK(hipEventRecord(ev[i], s));
+    };
+    try {
+        if (timed)
+            for (hipEvent_t& e : ev) HIP_CHECK(hipEventCreate(&e));
+        (void)hipFree(d_ksk_);
+        d_ksk_ = nullptr;
+        HIP_CHECK(hipMalloc(&d_ksk_, 8 * rows * (n + 1)));
+        (void)hipFree(d_tbsk_);
+        d_tbsk_ = nullptr;
+        HIP_CHECK(hipMalloc(&d_tbsk_, 8 * p_.bsk_len()));
+        HIP_CHECK(hipMalloc(&d_body, 8 * words));
+        mark(0);
+        HIP_CHECK(hipMemcpyAsync(d_body, bodies, 8 * words, hipMemcpyHostToDevice, s));
+        mark(1);
+        k_expand_ksk<<<(unsigned)rows, 64, 0, s>>>(mask_key, n, d_body, d_ksk_);
+        HIP_CHECK(hipGetLastError());
+        mark(2);
+        if (N == 2048) k_expand_bsk<2048><<<(unsigned)brows, 256, 0, s>>>(mask_key, p_.k, d_body + rows, d_tbsk_);
+        else k_expand_bsk<1024><<<(unsigned)brows, 256, 0, s>>>(mask_key, p_.k, d_body + rows, d_tbsk_);
+        HIP_CHECK(hipGetLastError());
+        mark(3);
+        build_ksk_limbs();
+        mark(4);
+        build_fourier_bsk();
+        mark(5);
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (timed)
+            for (int i = 0; i < 5; ++i) {
+                float ms = 0;
+                HIP_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+                key_load_ms_[i] = ms;
+            }
     } catch (...) {
         cleanup();
         throw;

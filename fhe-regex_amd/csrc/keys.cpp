@@ -294,10 +294,15 @@ static void parallel_for(int n, F&& fn) {
 }
 
 void gen_ksk(const Params& p, const ClientKey& ck, const RngKey& key, std::vector<uint64_t>& ksk) {
+    gen_ksk(p, ck, key, key, ksk);
+}
+
+void gen_ksk(const Params& p, const ClientKey& ck, const RngKey& mask_key, const RngKey& noise_key,
+             std::vector<uint64_t>& ksk) {
     const int big = p.big(), n = p.n, L = p.ks_level, B = p.ks_base_log;
     ksk.assign((size_t)big * L * (n + 1), 0);
     parallel_for(big, [&](int i) {
-        Rng rm(key, STREAM_KSK_MASK), rn(key, STREAM_KSK_NOISE);
+        Rng rm(mask_key, STREAM_KSK_MASK), rn(noise_key, STREAM_KSK_NOISE);
         for (int j = 0; j < L; ++j) {
             uint64_t row = (uint64_t)i * L + j;
             uint64_t* o = ksk.data() + row * (n + 1);
@@ -325,13 +330,16 @@ static uint64_t ggsw_msg(const Params& p, const ClientKey& ck, size_t w) {
 // 2^64 torus (mask uniform u64, body = sum_j A_j S_j + e, e ~ sigma_glwe 2^64),
 // plus m_w * 2^(64 - B) (the one-level gadget, B = pbs_base_log) on coefficient
 // 0 of component r.  A_j S_j (binary S) is summed exactly as rotations of A.
-static void gen_bsk_torus(const Params& p, const ClientKey& ck, const RngKey& key, std::vector<uint64_t>& bsk) {
+// compact (keys.h): the masks stay pure ChaCha words of mask_key and rows r < k carry the
+// gadget in the body, as -m_w 2^(64 - B) S_r.
+static void gen_bsk_torus(const Params& p, const ClientKey& ck, const RngKey& mask_key, const RngKey& noise_key,
+                          bool compact, std::vector<uint64_t>& bsk) {
     const int k = p.k, N = p.N;
     const size_t kp1 = (size_t)k + 1, nw = p.bsk_ggsw();
     const uint64_t gadget = 1ULL << (64 - p.pbs_base_log);
     bsk.assign(p.bsk_len(), 0);
     parallel_for((int)nw, [&](int i) {
-        Rng rm(key, STREAM_BSK_MASK), rn(key, STREAM_BSK_NOISE);
+        Rng rm(mask_key, STREAM_BSK_MASK), rn(noise_key, STREAM_BSK_NOISE);
         const uint64_t msg = ggsw_msg(p, ck, (size_t)i);
         for (size_t r = 0; r < kp1; ++r) {
             uint64_t* row = bsk.data() + ((size_t)i * kp1 + r) * kp1 * N;
@@ -350,7 +358,13 @@ static void gen_bsk_torus(const Params& p, const ClientKey& ck, const RngKey& ke
             }
             const uint64_t nb = ((uint64_t)i * kp1 + r) * N;
             for (int t = 0; t < N; ++t) Bp[t] += (uint64_t)rn.gaussian(nb + t, p.glwe_sigma);
-            if (msg) row[r * N] += gadget;
+            if (!msg) continue;
+            if (!compact || r == (size_t)k) {
+                row[r * N] += gadget;
+            } else {
+                const uint64_t* S = ck.s_big.data() + r * N;
+                for (int t = 0; t < N; ++t) Bp[t] -= gadget * S[t];
+            }
         }
     });
 }
@@ -391,7 +405,7 @@ std::vector<uint8_t> ggsw_messages(const Params& p, const ClientKey& ck) {
 
 void gen_bsk(const Params& p, const ClientKey& ck, const RngKey& key, std::vector<uint64_t>& bsk) {
     if (p.ring == FR_RING_FFT) {
-        gen_bsk_torus(p, ck, key, bsk);
+        gen_bsk_torus(p, ck, key, key, false, bsk);
         return;
     }
     const int k = p.k, N = p.N;
@@ -436,6 +450,100 @@ void gen_bsk(const Params& p, const ClientKey& ck, const RngKey& key, std::vecto
                 Bp[t] = q_add(rns::crt(acc[0][t], acc[1][t]), zq_from_i64(rn.gaussian(nb + t, p.glwe_sigma, (double)Q)));
             if (msg) row[r * N] = q_add(row[r * N], rns::G);
         }
+    });
+}
+
+// ---------------------------------------------------------------- compact server key
+RngKey derive_mask_key(const RngKey& key) {
+    uint32_t w[16];
+    chacha_block(key, STREAM_MASK_KEY, 0, w);
+    RngKey m;
+    for (int i = 0; i < 8; ++i) m.w[i] = w[i];
+    explicit_bzero(w, sizeof w);
+    return m;
+}
+
+static void need_fft_ring(const Params& p) {
+    if (p.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "compact server key: FFT ring only");
+}
+
+void gen_server_key_compact(const Params& p, const ClientKey& ck, const RngKey& key, std::vector<uint64_t>& ksk,
+                            std::vector<uint64_t>& bsk, RngKey& mask_key) {
+    need_fft_ring(p);
+    mask_key = derive_mask_key(key);
+    gen_ksk(p, ck, mask_key, key, ksk);
+    gen_bsk_torus(p, ck, mask_key, key, true, bsk);
+}
+
+size_t compact_ksk_bodies(const Params& p) { return (size_t)p.big() * p.ks_level; }
+size_t compact_bsk_bodies(const Params& p) { return p.bsk_ggsw() * (size_t)(p.k + 1) * p.N; }
+size_t compact_size(const Params& p) { return COMPACT_HEADER + 8 * (compact_ksk_bodies(p) + compact_bsk_bodies(p)); }
+
+static const char COMPACT_MAGIC[9] = "FRCSKEY1";
+static void compact_params(const Params& p, int32_t v[8]) {
+    const int32_t w[8] = {p.k, p.N, p.n, p.ks_base_log, p.ks_level, p.pbs_base_log, p.pbs_level, p.ring};
+    std::memcpy(v, w, sizeof w);
+}
+static void put_le32(uint8_t* o, uint32_t v) {
+    for (int i = 0; i < 4; ++i) o[i] = (uint8_t)(v >> (8 * i));
+}
+static uint32_t get_le32(const uint8_t* o) {
+    return (uint32_t)o[0] | ((uint32_t)o[1] << 8) | ((uint32_t)o[2] << 16) | ((uint32_t)o[3] << 24);
+}
+
+RngKey check_compact(const Params& p, const uint8_t* blob, size_t len) {
+    need_fft_ring(p);
+    if (!blob || len != compact_size(p))
+        throw Error(FR_ERR_INVALID, "compact server key: length does not match the context params "
+                                    "(fr_server_key_compact_size)");
+    if (std::memcmp(blob, COMPACT_MAGIC, 8)) throw Error(FR_ERR_INVALID, "compact server key: bad magic");
+    int32_t want[8];
+    compact_params(p, want);
+    for (int i = 0; i < 8; ++i)
+        if (get_le32(blob + 8 + 4 * i) != (uint32_t)want[i])
+            throw Error(FR_ERR_INVALID, "compact server key: parameters do not match the context params");
+    return RngKey::from_bytes(blob + 40);
+}
+
+std::vector<uint8_t> pack_compact(const Params& p, const RngKey& mask_key, const std::vector<uint64_t>& ksk,
+                                  const std::vector<uint64_t>& bsk) {
+    need_fft_ring(p);
+    const size_t rows = compact_ksk_bodies(p), n = (size_t)p.n, N = (size_t)p.N, kp1 = (size_t)p.k + 1;
+    const size_t brows = p.bsk_ggsw() * kp1;
+    if (ksk.size() != rows * (n + 1) || bsk.size() != p.bsk_len())
+        throw Error(FR_ERR_INVALID, "compact server key: key array sizes");
+    std::vector<uint8_t> out(compact_size(p));
+    std::memcpy(out.data(), COMPACT_MAGIC, 8);
+    int32_t v[8];
+    compact_params(p, v);
+    for (int i = 0; i < 8; ++i) put_le32(out.data() + 8 + 4 * i, (uint32_t)v[i]);
+    for (int i = 0; i < 8; ++i) put_le32(out.data() + 40 + 4 * i, mask_key.w[i]);
+    uint8_t* o = out.data() + COMPACT_HEADER;
+    for (size_t row = 0; row < rows; ++row, o += 8) std::memcpy(o, &ksk[row * (n + 1) + n], 8);
+    for (size_t q = 0; q < brows; ++q, o += 8 * N) std::memcpy(o, &bsk[(q * kp1 + (kp1 - 1)) * N], 8 * N);
+    return out;
+}
+
+void expand_compact(const Params& p, const uint8_t* blob, size_t len, std::vector<uint64_t>& ksk,
+                    std::vector<uint64_t>& bsk, RngKey& mask_key) {
+    mask_key = check_compact(p, blob, len);
+    const size_t rows = compact_ksk_bodies(p), n = (size_t)p.n, N = (size_t)p.N, k = (size_t)p.k, kp1 = k + 1;
+    const size_t brows = p.bsk_ggsw() * kp1;
+    const uint8_t* kb = blob + COMPACT_HEADER;
+    const uint8_t* bb = kb + 8 * rows;
+    ksk.resize(rows * (n + 1));
+    bsk.resize(p.bsk_len());
+    parallel_for((int)rows, [&](int row) {
+        Rng rm(mask_key, STREAM_KSK_MASK);
+        uint64_t* o = ksk.data() + (size_t)row * (n + 1);
+        for (size_t t = 0; t < n; ++t) o[t] = rm.u64((uint64_t)row * n + t);
+        std::memcpy(o + n, kb + 8 * (size_t)row, 8);
+    });
+    parallel_for((int)brows, [&](int q) {
+        Rng rm(mask_key, STREAM_BSK_MASK);
+        uint64_t* o = bsk.data() + (size_t)q * kp1 * N;
+        for (size_t t = 0; t < k * N; ++t) o[t] = rm.u64((uint64_t)q * k * N + t);
+        std::memcpy(o + k * N, bb + 8 * (size_t)q * N, 8 * N);
     });
 }
 

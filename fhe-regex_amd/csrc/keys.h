@@ -22,6 +22,7 @@ enum Stream : uint64_t {
     STREAM_ENC_MASK = 5,
     STREAM_ENC_NOISE = 6,
     STREAM_CLIENT_KEY = 7,
+    STREAM_MASK_KEY = 8,  // block 0, words 0..7: the public mask key of a compact server key
 };
 
 class Rng {
@@ -72,6 +73,9 @@ ClientKey gen_client_key(const Params& p, const RngKey& key);
 
 // KSK: [i in kN][level j][t in n+1], torus 2^64.
 void gen_ksk(const Params& p, const ClientKey& ck, const RngKey& key, std::vector<uint64_t>& ksk);
+// the same rows with the masks drawn under mask_key and the noise under noise_key
+void gen_ksk(const Params& p, const ClientKey& ck, const RngKey& mask_key, const RngKey& noise_key,
+             std::vector<uint64_t>& ksk);
 // BSK: [GGSW w][row r in k+1][component c in k+1][coef], coefficient domain mod Q (rns.h);
 // GGSW w per Params::bsk_unroll (k = 1: 3 per pair of LWE coefficients).
 void gen_bsk(const Params& p, const ClientKey& ck, const RngKey& key, std::vector<uint64_t>& bsk);
@@ -82,6 +86,32 @@ void gen_bsk(const Params& p, const ClientKey& ck, const RngKey& key, std::vecto
 void gen_ksk_noise(const Params& p, const RngKey& key, std::vector<int64_t>& e);
 void gen_bsk_noise_torus(const Params& p, const RngKey& key, std::vector<int32_t>& e);
 std::vector<uint8_t> ggsw_messages(const Params& p, const ClientKey& ck);
+
+// Compact (seeded) server key, FFT ring.  Every mask word is a ChaCha20
+// word of a public mask key, words 0..7 of chacha_block(K, STREAM_MASK_KEY, 0) for the
+// call's secret generator key K, at the index the standard generator uses; the noise is
+// the standard generator's under K.  No secret touches a mask: the gadget term m_w g
+// that the standard form adds to coefficient 0 of mask polynomial r (rows r < k) sits in
+// the body as -m_w g S_r, so the phase B - sum_j A_j S_j of every row is the standard
+// form's polynomial.  The key is then its bodies and the 32 bytes of the mask key.
+RngKey derive_mask_key(const RngKey& key);
+// the full arrays (gen_ksk's and gen_bsk's layouts) and the mask key
+void gen_server_key_compact(const Params& p, const ClientKey& ck, const RngKey& key, std::vector<uint64_t>& ksk,
+                            std::vector<uint64_t>& bsk, RngKey& mask_key);
+// Wire blob (include/fheregex.h): "FRCSKEY1", eight int32 parameters, the mask key, the
+// KSK bodies [kN * ks_level], the BSK bodies [W][k+1][N]; little endian
+constexpr size_t COMPACT_HEADER = 72;
+size_t compact_ksk_bodies(const Params& p);  // u64 counts
+size_t compact_bsk_bodies(const Params& p);
+size_t compact_size(const Params& p);        // bytes
+// Error(FR_ERR_INVALID) unless len, the magic and the eight parameters are p's; the mask key
+RngKey check_compact(const Params& p, const uint8_t* blob, size_t len);
+std::vector<uint8_t> pack_compact(const Params& p, const RngKey& mask_key, const std::vector<uint64_t>& ksk,
+                                  const std::vector<uint64_t>& bsk);
+// check_compact, then every mask from the mask key around the blob's bodies
+void expand_compact(const Params& p, const uint8_t* blob, size_t len, std::vector<uint64_t>& ksk,
+                    std::vector<uint64_t>& bsk, RngKey& mask_key);
+
 // noise of encrypt_blocks for blocks first_block .. first_block + count - 1
 void enc_noise(const Params& p, const RngKey& key, uint64_t first_block, size_t count, std::vector<int64_t>& e);
 

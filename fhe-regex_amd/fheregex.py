@@ -123,6 +123,12 @@ _SIGS = {
     "fr_export_server_key": (C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p, C.c_size_t]),
     "fr_server_key_sizes": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "fr_load_server_key": (C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p, C.c_size_t]),
+    "fr_gen_server_key_compact": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "fr_gen_server_key_compact_keyed": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "fr_server_key_compact_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
+    "fr_export_server_key_compact": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fr_load_server_key_compact": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
+    "fr_device_timers_key_load": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "fr_encrypt_str": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint64, u64p]),
     "fr_encrypt_blocks": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, C.c_uint64, C.c_uint64, u64p]),
     "fr_decrypt_radix": (C.c_int, [C.c_void_p, u64p, u64p]),
@@ -401,13 +407,20 @@ class Context:
         _check(lib().fr_serialize_client_key(self.h, buf, n.value, C.byref(n)))
         return buf.raw
 
-    def gen_server_key(self, seed=None):
+    def gen_server_key(self, seed=None, compact=False):
         """ServerKey::new (engine.rs:252): on the GPU for the FFT ring (KEYGEN_AUTO),
         else on the host; both give the same key bit for bit.  `seed` as in
         gen_client_key.  A server key from an int seed must not leave the client: whoever
-        guesses the seed recomputes the key's noise and solves for the client key."""
+        guesses the seed recomputes the key's noise and solves for the client key.
+        compact=True (FFT ring): the compact form, whose masks are ChaCha20 words of a
+        public mask key, so that export_server_key_compact ships the bodies only."""
         keyed, v = _rng_arg(seed)
-        _check(lib().fr_gen_server_key_keyed(self.h, v) if keyed else lib().fr_gen_server_key(self.h, v))
+        L = lib()
+        if compact:
+            f = L.fr_gen_server_key_compact_keyed if keyed else L.fr_gen_server_key_compact
+        else:
+            f = L.fr_gen_server_key_keyed if keyed else L.fr_gen_server_key
+        _check(f(self.h, v))
 
     def set_keygen(self, where: int):
         """KEYGEN_AUTO (device when present, FFT ring), KEYGEN_HOST or KEYGEN_DEVICE."""
@@ -427,6 +440,33 @@ class Context:
         k = np.ascontiguousarray(ksk, dtype=np.uint64)
         b = np.ascontiguousarray(bsk, dtype=np.uint64)
         _check(lib().fr_load_server_key(self.h, _p(k), len(k), _p(b), len(b)))
+
+    def server_key_compact_size(self) -> int:
+        n = C.c_size_t()
+        _check(lib().fr_server_key_compact_size(self.h, C.byref(n)))
+        return n.value
+
+    def export_server_key_compact(self) -> bytes:
+        """the compact wire blob (fheregex.h: magic, parameters, mask key, bodies) of a key
+        generated with compact=True or loaded from such a blob"""
+        n = C.c_size_t()
+        _check(lib().fr_export_server_key_compact(self.h, None, 0, C.byref(n)))
+        buf = C.create_string_buffer(n.value)
+        _check(lib().fr_export_server_key_compact(self.h, buf, n.value, C.byref(n)))
+        return buf.raw[:n.value]
+
+    def load_server_key_compact(self, blob: bytes):
+        """install a compact server key: no client key needed; a device context uploads
+        the bodies and expands the masks on the GPU"""
+        blob = bytes(blob)
+        _check(lib().fr_load_server_key_compact(self.h, blob, len(blob)))
+
+    def key_load_timers(self) -> List[float]:
+        """ms of the last load_server_key_compact's stages under set_profiling: H2D copy,
+        KSK expansion, BSK expansion, KSK limbs, BSK Fourier transform"""
+        ms = (C.c_double * 5)()
+        _check(lib().fr_device_timers_key_load(self.h, ms))
+        return list(ms)
 
     def set_lowering(self, mode: int):
         _check(lib().fr_set_lowering(self.h, mode))
@@ -753,9 +793,32 @@ class ServerKey:
             ctx.load_server_key(z["ksk"], z["bsk"])
         return ServerKey(ctx)
 
+    def save_compact(self, path: str):
+        """the raw compact blob (fr_export_server_key_compact) of a compact-form key"""
+        with open(path, "wb") as f:
+            f.write(self.ctx.export_server_key_compact())
+
+    @staticmethod
+    def load_compact(path: str, device: int = 0, params: Optional[Params] = None) -> "ServerKey":
+        """a server context holding only the server key of a compact blob"""
+        ctx = Context(device, params)
+        with open(path, "rb") as f:
+            ctx.load_server_key_compact(f.read())
+        return ServerKey(ctx)
+
+
+COMPACT_MAGIC = b"FRCSKEY1"
+
+
+def compact_mask_key(blob: bytes) -> bytes:
+    """the public 32-byte mask key of a compact server-key blob (bytes 40..71)"""
+    if len(blob) < 72 or bytes(blob[:8]) != COMPACT_MAGIC:
+        raise ValueError("not a compact server key blob")
+    return bytes(blob[40:72])
+
 
 def gen_keys(client_key_blob: Optional[bytes] = None, seed=None, device: int = 0,
-             params: Optional[Params] = None, client_seed=None):
+             params: Optional[Params] = None, client_seed=None, compact: bool = False):
     """gen_keys (ciphertext.rs:42-45): (client key, server key).
 
     Without a blob the client key is fresh (gen_keys_radix(&PARAM_MESSAGE_2_CARRY_2, 4),
@@ -764,13 +827,14 @@ def gen_keys(client_key_blob: Optional[bytes] = None, seed=None, device: int = 0
     (ServerKey::new, engine.rs:252) are drawn under `seed`.  Both default to None: 256
     bits of the OS CSPRNG each, as the reference draws.  32 bytes are a generator key, an
     int a 64-bit seed; a server key from an int seed is reproducible (tests, benchmarks,
-    multi-rank keygen) and must not leave the client."""
+    multi-rank keygen) and must not leave the client.  compact=True: the server key in
+    compact form (ServerKey.save_compact ships it)."""
     ctx = Context(device, params)
     if client_key_blob is None:
         ctx.gen_client_key(client_seed)
     else:
         ctx.load_client_key(client_key_blob)
-    ctx.gen_server_key(seed)
+    ctx.gen_server_key(seed, compact=compact)
     return ClientKey(ctx), ServerKey(ctx)
 
 

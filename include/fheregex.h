@@ -127,7 +127,13 @@ int fr_default_params(fr_params* out); /* PARAM_MESSAGE_2_CARRY_2, k=1, N=2048 *
  * multi-rank keygen: a seed is at most 64 bits and usually known.  Whoever holds a
  * server key and can guess its seed recomputes its noise and solves for the client key,
  * so a server key generated from a known or guessable seed must never leave the client
- * (fr_export_server_key -> fr_load_server_key). */
+ * (fr_export_server_key -> fr_load_server_key).
+ * A compact server key (fr_gen_server_key_compact*) splits the two uses of the key K of
+ * its call: the masks are ChaCha20 words of a mask key, words 0..7 of block 0 of K's
+ * stream 8, and the noise stays under K.  The mask key is public by design: it travels in
+ * the blob, and the block function is a PRF, so it says nothing about K's other streams.
+ * No secret touches a mask word.  The seed caveat stands: the noise of a compact key from
+ * a guessable seed is as recomputable as a standard key's, so it must not leave the client. */
 /* bincode RadixClientKey (tfhe-rs 0.2 layout, reference test_data/client_key). */
 int fr_load_client_key(fr_ctx* ctx, const uint8_t* bincode, size_t len);
 /* A fresh client key (gen_keys_radix(&PARAM_MESSAGE_2_CARRY_2, 4), ciphertext.rs:44):
@@ -175,6 +181,41 @@ int fr_server_key_sizes(fr_ctx* ctx, size_t* ksk_len, size_t* bsk_len);
  * other than fr_server_key_sizes' -> FR_ERR_INVALID.  This is the build's own layout,
  * not tfhe-rs's bincode ServerKey. */
 int fr_load_server_key(fr_ctx* ctx, const uint64_t* ksk, size_t ksk_len, const uint64_t* bsk, size_t bsk_len);
+/* Compact (seeded) server key, FFT ring (FR_RING_RNS -> FR_ERR_INVALID).  A server key in
+ * the layouts above whose mask words are all ChaCha20 words of a public 32-byte mask key
+ * (see "Randomness"), so that only the bodies and the mask key travel: 3.7x (k = 1,
+ * N = 2048) and 5.2x (k = 2, N = 1024) fewer bytes than fr_export_server_key's arrays.
+ * KSK mask word row*n + t is u64 number row*n + t of stream 1 under the mask key, BSK mask
+ * polynomial j of row (w, r) u64 numbers ((w(k+1) + r)k + j)N + t of stream 3: the
+ * standard generator's indices.  The gadget term m_w * 2^(64 - pbs_base_log) that the
+ * standard form adds to coefficient 0 of mask polynomial r (rows r < k) would make that
+ * word differ from its ChaCha word by a secret, so here it sits in the body:
+ * B = sum_j A_j S_j + e - m_w g S_r for r < k, B = sum_j A_j S_j + e + m_w g for r = k.
+ * Every row has the phase of the standard form, and every kernel runs on it unchanged.
+ * Same preconditions and fr_set_keygen placement as fr_gen_server_key[_keyed]; host and
+ * device give the same words.  The installed key is a full server key:
+ * fr_export_server_key returns it expanded, valid for fr_load_server_key. */
+int fr_gen_server_key_compact(fr_ctx* ctx, uint64_t seed);
+int fr_gen_server_key_compact_keyed(fr_ctx* ctx, const uint8_t* key /* NULL: OS CSPRNG */);
+/* The wire blob, little endian, exactly fr_server_key_compact_size bytes
+ * = 72 + 8*(kN*ks_level + W*(k+1)*N):
+ *   bytes 0-7    ASCII "FRCSKEY1"
+ *   bytes 8-39   eight int32: k, N, n, ks_base_log, ks_level, pbs_base_log, pbs_level, ring
+ *   bytes 40-71  the mask key (8 words)
+ *   bytes 72...  KSK bodies [kN*ks_level] u64, then BSK bodies [W][k+1][N] u64
+ * fr_export_server_key_compact: buf == NULL is a size query (*written = bytes needed).
+ * FR_ERR_NO_KEY without a server key; FR_ERR_INVALID if the installed key was not
+ * generated compact or loaded from a blob (a standard key's masks are not expandable
+ * from a mask key). */
+int fr_server_key_compact_size(fr_ctx* ctx, size_t* bytes);
+int fr_export_server_key_compact(fr_ctx* ctx, uint8_t* buf, size_t cap, size_t* written);
+/* Install a compact server key: needs no client key, any client key stays.  The length,
+ * the magic and all eight integers are checked against the context's params before the
+ * installed key is touched; anything else -> FR_ERR_INVALID and the context keeps the key
+ * it had.  A device context uploads the bodies only, expands the masks on the GPU and
+ * transforms the key there; a host-only context expands on the host.  The context can
+ * then export both forms. */
+int fr_load_server_key_compact(fr_ctx* ctx, const uint8_t* blob, size_t len);
 
 /* ----- client side (not on the timed path) ----- */
 /* Seeded encryption, for tests and benchmarks only: two calls with one seed share their
@@ -332,6 +373,10 @@ int fr_device_timers_latency(fr_ctx* ctx, double* br_ms, uint64_t* br_launches, 
 /* ... and in pair-shape launches (FFT ring, k = 1: two bootstraps per workgroup in the
  * latency geometry, for batches above the latency shape's limit). */
 int fr_device_timers_pair(fr_ctx* ctx, double* br_ms, uint64_t* br_launches, uint64_t* br_gates);
+/* The stages of the last fr_load_server_key_compact made under fr_set_profiling, by HIP
+ * events: ms[0..4] = H2D copy of the bodies, KSK mask expansion, BSK mask expansion, KSK
+ * byte limbs, Fourier transform of the BSK. */
+int fr_device_timers_key_load(fr_ctx* ctx, double* ms /* 5 */);
 
 /* ----- one match split across ranks ----- */
 /* The reference folds ct_or over the branches of every start offset
