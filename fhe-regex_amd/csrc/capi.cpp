@@ -638,6 +638,12 @@ int fr_device_timers_key_load(fr_ctx* ctx, double* ms) {
         std::memcpy(ms, ctx->device().key_load_ms(), 5 * sizeof(double));
     })
 }
+int fr_device_timers_content(fr_ctx* ctx, double* ms) {
+    FR_TRY({
+        NEED(ctx && ms);
+        *ms = ctx->device().expand_ms();
+    })
+}
 int fr_device_timers(fr_ctx* ctx, double* br_ms, double* ks_ms, uint64_t* br_launches, uint64_t* br_gates) {
     return device_timers(ctx, &DeviceTimers::br_ms, &DeviceTimers::br_launches, &DeviceTimers::br_gates, br_ms, ks_ms,
                          br_launches, br_gates);

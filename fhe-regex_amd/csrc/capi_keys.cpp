@@ -351,6 +351,101 @@ int fr_encrypt_upload_str_keyed(fr_ctx* ctx, const char* s, size_t len, const ui
     })
 }
 
+// ---- compact (seeded) content (keys.h): the client packs bodies + mask key, the server
+// expands them on the host or straight into arena slots
+
+int fr_compact_content_size(fr_ctx* ctx, size_t n_blocks, size_t* bytes) {
+    FR_TRY({
+        NEED(ctx && bytes);
+        *bytes = content_blob_size(n_blocks);
+    })
+}
+
+// the blob of `msgs` under `key32` (NULL: OS CSPRNG), after the caller's preconditions;
+// the size is answered before a key is drawn
+static void encrypt_compact_with(fr_ctx* ctx, const std::vector<uint8_t>& msgs, const uint8_t* key32,
+                                 uint64_t first_block, uint8_t* buf, size_t cap, size_t* written) {
+    if (first_block > CONTENT_MAX_BLOCK || first_block + msgs.size() > CONTENT_MAX_BLOCK)
+        throw Error(FR_ERR_INVALID, "compact content: first_block + n_blocks exceeds 2^40");
+    const size_t need = content_blob_size(msgs.size());
+    *written = need;
+    if (!buf) return;  // size query
+    NEED(cap >= need);
+    ScopedKey key(key32);
+    const std::vector<uint8_t> blob = encrypt_content_blob(ctx->p, ctx->ck, msgs.data(), msgs.size(), key.k, first_block);
+    std::memcpy(buf, blob.data(), need);
+}
+
+int fr_encrypt_str_compact_keyed(fr_ctx* ctx, const char* s, size_t len, const uint8_t* key32, uint8_t* buf,
+                                 size_t cap, size_t* written) {
+    FR_TRY({
+        NEED(ctx && (s || !len) && written);
+        if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
+        const std::vector<uint8_t> msgs = str_blocks(s, len);
+        encrypt_compact_with(ctx, msgs, key32, 0, buf, cap, written);
+    })
+}
+
+int fr_encrypt_blocks_compact_keyed(fr_ctx* ctx, const uint8_t* msgs, size_t count, const uint8_t* key32,
+                                    uint64_t first_block, uint8_t* buf, size_t cap, size_t* written) {
+    FR_TRY({
+        NEED(ctx && (msgs || !count) && written);
+        if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
+        for (size_t i = 0; i < count; ++i) NEED(msgs[i] < 16);
+        const std::vector<uint8_t> m(msgs, msgs + count);
+        encrypt_compact_with(ctx, m, key32, first_block, buf, cap, written);
+    })
+}
+
+int fr_expand_compact_content(fr_ctx* ctx, const uint8_t* blob, size_t len, uint64_t* out, size_t out_words,
+                              size_t* n_blocks) {
+    FR_TRY({
+        NEED(ctx && blob && n_blocks);
+        const ContentBlob c = check_content_blob(ctx->p, blob, len, false);
+        *n_blocks = c.n_blocks;
+        if (!out) return FR_OK;  // size query
+        // (n_blocks <= (len - 64) / 8: the product cannot wrap)
+        NEED(out_words >= c.n_blocks * (size_t)ctx->p.lwe_len());
+        expand_content(ctx->p, blob, len, out);
+    })
+}
+
+// the blob and cap are checked before the device is asked for and before anything is allocated
+static void upload_compact(fr_ctx* ctx, const uint8_t* blob, size_t len, bool radix, fr_ct* out, size_t cap,
+                           size_t* n) {
+    NEED(ctx && blob && n);
+    const ContentBlob c = check_content_blob(ctx->p, blob, len, radix);
+    const size_t handles = radix ? c.n_blocks / 4 : c.n_blocks;
+    *n = handles;
+    NEED((out || !handles) && cap >= handles);
+    Device& dev = ctx->device();
+    std::vector<int> slots(c.n_blocks);
+    dev.expand_to_slots(c.mask_key, c.first_block, c.bodies, c.n_blocks, slots.data());
+    try {
+        ctx->handles.reserve(ctx->handles.size() + handles);  // new_handle cannot fail below
+    } catch (...) {
+        for (int x : slots) dev.free_slot(x);
+        throw;
+    }
+    for (size_t i = 0; i < handles; ++i) {
+        if (radix) {
+            HandleRec r;
+            for (int b = 0; b < 4; ++b) r.b[b].slot = slots[4 * i + b];
+            out[i] = ctx->new_handle(r);
+        } else {
+            out[i] = ctx->new_bool(slots[i]);
+        }
+    }
+}
+
+int fr_upload_compact_str(fr_ctx* ctx, const uint8_t* blob, size_t len, fr_ct* out, size_t cap, size_t* n_chars) {
+    FR_TRY(upload_compact(ctx, blob, len, true, out, cap, n_chars))
+}
+
+int fr_upload_compact_blocks(fr_ctx* ctx, const uint8_t* blob, size_t len, fr_ct* out, size_t cap, size_t* n) {
+    FR_TRY(upload_compact(ctx, blob, len, false, out, cap, n))
+}
+
 // bincode (fixint, little endian) of tfhe-rs 0.2 RadixCiphertext:
 //   u64 n_blocks, then per block: u64 len, len x u64 LWE words, u64 degree,
 //   u64 message_modulus, u64 carry_modulus

@@ -79,6 +79,17 @@ class Device {
     void encrypt_to_slots(const ClientKey& ck, const uint8_t* msgs, size_t count, const RngKey& key, uint64_t first_block,
                           const int* slots);
 
+    // compact content (keys.h): allocates `count` arena slots (returned in `slots`) and
+    // rebuilds block q's LWE in slots[q] -- the masks from mask_key on the device, the body
+    // from `bodies` (count u64, little endian, any alignment; copied before the call
+    // returns).  Lane 0; stream-ordered: returns once enqueued.  The bodies and the slot
+    // list travel in one H2D copy from a pinned staging ring owned by the device (no
+    // allocation per call).  On an error no slot stays allocated.
+    void expand_to_slots(const RngKey& mask_key, uint64_t first_block, const uint8_t* bodies, size_t count, int* slots);
+    // ms of the last expand_to_slots' kernel under fr_set_profiling (HIP events; a profiled
+    // call waits for its kernel)
+    double expand_ms() const { return expand_ms_; }
+
     // arena of big-LWE slots
     int alloc_slot();
     void free_slot(int s);
@@ -198,6 +209,14 @@ class Device {
     void build_ksk_limbs();  // d_kl_ from d_ksk_
     void build_fourier_bsk();  // keygen.hip: d_fbsk_ (every lane layout in use) from d_tbsk_
     double key_load_ms_[5] = {0, 0, 0, 0, 0};
+    // expand_to_slots: device staging buffer (reused in stream order) and its pinned ring;
+    // a pinned buffer is rewritten only after its previous H2D copy completed
+    uint8_t* d_xstage_ = nullptr;
+    uint8_t* h_xstage_[2] = {nullptr, nullptr};
+    void* xstage_ev_[2] = {nullptr, nullptr};
+    size_t xstage_cap_ = 0;  // bytes
+    int xstage_ = 0;
+    double expand_ms_ = 0;
     void stage_slot_list(const int* slots, size_t n);  // -> d_slot_list_ (stream order)
     int* d_slot_list_ = nullptr;
     size_t slot_list_cap_ = 0;

@@ -73,6 +73,11 @@ Device::~Device() {
     (void)hipFree(d_gates_);
     (void)hipFree(d_ks_);
     (void)hipFree(d_slot_list_);
+    (void)hipFree(d_xstage_);
+    for (auto* h : h_xstage_)
+        if (h) (void)hipHostFree(h);
+    for (auto* e : xstage_ev_)
+        if (e) (void)hipEventDestroy((hipEvent_t)e);
     for (auto* h : h_stage_)
         if (h) (void)hipHostFree(h);
     for (auto* e : stage_ev_)

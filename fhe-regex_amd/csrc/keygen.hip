@@ -19,6 +19,9 @@
 //                  blocks of the public mask key, the body from the uploaded blob
 //   k_expand_bsk   the same for one GGSW row (w, r) per workgroup: k mask polynomials
 //                  and the body row.  Both are pure store streams, 16 bytes a store
+//   k_expand_blocks  compact content, one workgroup per LWE block: the mask words from
+//                  ChaCha blocks of the blob's mask key straight into the block's arena
+//                  slot, the body from the staged bodies; the same 16-byte store stream
 //   k_bsk_fourier  one workgroup per polynomial: fold, forward negacyclic FFT in
 //                  LDS (fft.h butterflies, host twiddles), scale 2^-log2(M),
 //                  written in the lane layouts of the blind-rotation kernels
@@ -324,6 +327,99 @@ void Device::encrypt_to_slots(const ClientKey& ck, const uint8_t* msgs, size_t c
         throw;
     }
     cleanup();
+}
+
+// Compact content (keys.h): the LWEs of `grid` blocks rebuilt in their arena slots, one
+// workgroup per LWE.  Mask word t of block q is u64 number (first_block + q) kN + t of
+// STREAM_ENC_MASK under the public mask key (k_encrypt_blocks's indices; kN % 8 == 0: whole
+// ChaCha blocks); thread t owns ChaCha block (first_block + q) kN / 8 + t, 64 aligned bytes
+// of the slot (slot stride: a multiple of 64 B), stored 16 bytes at a time as k_expand_bsk
+// does.  The body word comes from the staged bodies.  Every store is inside the slot's
+// big + 1 words; the host checked slots[q] < next_slot_.
+__global__ void __launch_bounds__(256) k_expand_blocks(RngKey mask_key, int big, uint64_t first_block,
+                                                       const uint64_t* __restrict__ bodies,
+                                                       const int* __restrict__ slots, int stride,
+                                                       uint64_t* __restrict__ arena) {
+    const int q = blockIdx.x, tid = threadIdx.x;
+    const uint64_t base = (first_block + q) * (uint64_t)(big / 8);
+    uint64_t* o = arena + (size_t)slots[q] * stride;
+    for (int b = tid; b < big / 8; b += 256) {
+        uint32_t w[16];
+        chacha_block(mask_key, STREAM_ENC_MASK, base + b, w);
+        ulonglong2* d = reinterpret_cast<ulonglong2*>(o + 8 * (size_t)b);
+#pragma unroll
+        for (int x = 0; x < 4; ++x) d[x] = make_ulonglong2(chacha_u64(w, 2 * x), chacha_u64(w, 2 * x + 1));
+    }
+    if (tid == 0) o[big] = bodies[q];
+}
+
+void Device::expand_to_slots(const RngKey& mask_key, uint64_t first_block, const uint8_t* bodies, size_t count,
+                             int* slots) {
+    if (!count) return;
+    const int big = p_.big();
+    if (big % 8) throw Error(FR_ERR_INVALID, "device expansion: kN must be a multiple of 8");
+    if (lane_ != 0) throw Error(FR_ERR_INVALID, "device expansion: lane 0 only");
+    if (count > (size_t)1 << 30) throw Error(FR_ERR_INVALID, "device expansion: too many blocks");
+    // every slot first: alloc_slot may grow the arena, which moves it (ensure_arena)
+    size_t got = 0;
+    try {
+        for (; got < count; ++got) slots[got] = alloc_slot();
+        // staging: the bodies [count] u64, then the slot list [count] int, in one H2D copy
+        const size_t need = 12 * count;
+        if (need > xstage_cap_) {
+            size_t cap = xstage_cap_ ? xstage_cap_ : 12 * 4096;
+            while (cap < need) cap *= 2;
+            HIP_CHECK(hipStreamSynchronize(STREAM));  // no copy or kernel may still use the old buffers
+            (void)hipFree(d_xstage_);
+            d_xstage_ = nullptr;
+            xstage_cap_ = 0;
+            for (int i = 0; i < 2; ++i) {
+                if (h_xstage_[i]) (void)hipHostFree(h_xstage_[i]);
+                h_xstage_[i] = nullptr;
+                if (!xstage_ev_[i]) {
+                    hipEvent_t ev;
+                    HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+                    xstage_ev_[i] = ev;  // never recorded: complete
+                }
+            }
+            HIP_CHECK(hipMalloc(&d_xstage_, cap));
+            for (auto& h : h_xstage_) HIP_CHECK(hipHostMalloc(&h, cap));
+            xstage_cap_ = cap;
+        }
+        const hipStream_t s = STREAM;
+        xstage_ ^= 1;
+        // the pinned buffer is rewritten only after its previous copy completed
+        HIP_CHECK(hipEventSynchronize((hipEvent_t)xstage_ev_[xstage_]));
+        uint8_t* h = h_xstage_[xstage_];
+        std::memcpy(h, bodies, 8 * count);
+        std::memcpy(h + 8 * count, slots, 4 * count);
+        HIP_CHECK(hipMemcpyAsync(d_xstage_, h, need, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipEventRecord((hipEvent_t)xstage_ev_[xstage_], s));
+        // d_xstage_ is reused in stream order: the next call's copy runs after this kernel
+        hipEvent_t t0 = nullptr, t1 = nullptr;
+        if (profiling_) {
+            t0 = (hipEvent_t)take_event();
+            t1 = (hipEvent_t)take_event();
+            HIP_CHECK(hipEventRecord(t0, s));
+        }
+        k_expand_blocks<<<(unsigned)count, 256, 0, s>>>(mask_key, big, first_block, (const uint64_t*)d_xstage_,
+                                                       (const int*)(d_xstage_ + 8 * count), p_.slot_stride(),
+                                                       d_arena_);
+        HIP_CHECK(hipGetLastError());
+        if (profiling_) {
+            // the probe's figure (fr_device_timers_content): a profiled call waits for its kernel
+            HIP_CHECK(hipEventRecord(t1, s));
+            HIP_CHECK(hipEventSynchronize(t1));
+            float ms = 0;
+            HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
+            expand_ms_ = ms;
+            event_pool_.push_back(t0);
+            event_pool_.push_back(t1);
+        }
+    } catch (...) {
+        for (size_t i = 0; i < got; ++i) free_slot(slots[i]);
+        throw;
+    }
 }
 
 static void need_device_keygen_point(const Params& p, const char* what) {

@@ -550,8 +550,13 @@ void expand_compact(const Params& p, const uint8_t* blob, size_t len, std::vecto
 // ---------------------------------------------------------------- client
 void encrypt_blocks(const Params& p, const ClientKey& ck, const uint8_t* msgs, size_t count, const RngKey& key,
                     uint64_t first_block, uint64_t* out) {
+    encrypt_blocks(p, ck, msgs, count, key, key, first_block, out);
+}
+
+void encrypt_blocks(const Params& p, const ClientKey& ck, const uint8_t* msgs, size_t count, const RngKey& mask_key,
+                    const RngKey& noise_key, uint64_t first_block, uint64_t* out) {
     const int big = p.big();
-    Rng rm(key, STREAM_ENC_MASK), rn(key, STREAM_ENC_NOISE);
+    Rng rm(mask_key, STREAM_ENC_MASK), rn(noise_key, STREAM_ENC_NOISE);
     for (size_t q = 0; q < count; ++q) {
         uint64_t* o = out + q * (big + 1);
         uint64_t qb = first_block + q, body = 0;
@@ -562,6 +567,76 @@ void encrypt_blocks(const Params& p, const ClientKey& ck, const uint8_t* msgs, s
         body += (uint64_t)msgs[q] << DELTA_LOG;
         body += (uint64_t)rn.gaussian(qb, p.glwe_sigma);
         o[big] = body;
+    }
+}
+
+// ---------------------------------------------------------------- compact content
+static const char CONTENT_MAGIC[9] = "FRCCTXT1";
+static void put_le64(uint8_t* o, uint64_t v) {
+    for (int i = 0; i < 8; ++i) o[i] = (uint8_t)(v >> (8 * i));
+}
+static uint64_t get_le64(const uint8_t* o) {
+    uint64_t v = 0;
+    for (int i = 0; i < 8; ++i) v |= (uint64_t)o[i] << (8 * i);
+    return v;
+}
+
+size_t content_blob_size(size_t n_blocks) {
+    if (n_blocks > CONTENT_MAX_BLOCK) throw Error(FR_ERR_INVALID, "compact content: more than 2^40 blocks");
+    return CONTENT_HEADER + 8 * n_blocks;
+}
+
+ContentBlob check_content_blob(const Params& p, const uint8_t* blob, size_t len, bool radix) {
+    if (!blob || len < CONTENT_HEADER || (len - CONTENT_HEADER) % 8)
+        throw Error(FR_ERR_INVALID, "compact content: length is not 64 + 8 n_blocks (fr_compact_content_size)");
+    if (std::memcmp(blob, CONTENT_MAGIC, 8)) throw Error(FR_ERR_INVALID, "compact content: bad magic");
+    if (get_le32(blob + 8) != (uint32_t)p.k || get_le32(blob + 12) != (uint32_t)p.N)
+        throw Error(FR_ERR_INVALID, "compact content: k, N do not match the context params");
+    ContentBlob c;
+    c.first_block = get_le64(blob + 16);
+    const uint64_t nb = get_le64(blob + 24);
+    if (nb != (len - CONTENT_HEADER) / 8)
+        throw Error(FR_ERR_INVALID, "compact content: n_blocks does not match the length");
+    // (each term first: the sum of two u64 could wrap)
+    if (c.first_block > CONTENT_MAX_BLOCK || nb > CONTENT_MAX_BLOCK || c.first_block + nb > CONTENT_MAX_BLOCK)
+        throw Error(FR_ERR_INVALID, "compact content: first_block + n_blocks exceeds 2^40");
+    if (radix && nb % 4) throw Error(FR_ERR_INVALID, "compact content: a string is 4 blocks per character");
+    c.n_blocks = (size_t)nb;
+    c.mask_key = RngKey::from_bytes(blob + 32);
+    c.bodies = blob + CONTENT_HEADER;
+    return c;
+}
+
+std::vector<uint8_t> encrypt_content_blob(const Params& p, const ClientKey& ck, const uint8_t* msgs, size_t count,
+                                          const RngKey& key, uint64_t first_block) {
+    if (first_block > CONTENT_MAX_BLOCK || count > CONTENT_MAX_BLOCK || first_block + count > CONTENT_MAX_BLOCK)
+        throw Error(FR_ERR_INVALID, "compact content: first_block + n_blocks exceeds 2^40");
+    const size_t big = (size_t)p.big();
+    const RngKey mk = derive_mask_key(key);  // public
+    std::vector<uint8_t> out(content_blob_size(count));
+    std::memcpy(out.data(), CONTENT_MAGIC, 8);
+    put_le32(out.data() + 8, (uint32_t)p.k);
+    put_le32(out.data() + 12, (uint32_t)p.N);
+    put_le64(out.data() + 16, first_block);
+    put_le64(out.data() + 24, count);
+    for (int i = 0; i < 8; ++i) put_le32(out.data() + 32 + 4 * i, mk.w[i]);
+    std::vector<uint64_t> lwe(big + 1);  // one block at a time: only its body is kept
+    for (size_t q = 0; q < count; ++q) {
+        encrypt_blocks(p, ck, msgs + q, 1, mk, key, first_block + q, lwe.data());
+        put_le64(out.data() + CONTENT_HEADER + 8 * q, lwe[big]);
+    }
+    return out;
+}
+
+void expand_content(const Params& p, const uint8_t* blob, size_t len, uint64_t* out) {
+    const ContentBlob c = check_content_blob(p, blob, len, false);
+    const uint64_t big = (uint64_t)p.big();
+    Rng rm(c.mask_key, STREAM_ENC_MASK);
+    for (size_t q = 0; q < c.n_blocks; ++q) {
+        uint64_t* o = out + q * (big + 1);
+        const uint64_t qb = c.first_block + q;
+        for (uint64_t t = 0; t < big; ++t) o[t] = rm.u64(qb * big + t);
+        o[big] = get_le64(c.bodies + 8 * q);
     }
 }
 

@@ -22,7 +22,7 @@ enum Stream : uint64_t {
     STREAM_ENC_MASK = 5,
     STREAM_ENC_NOISE = 6,
     STREAM_CLIENT_KEY = 7,
-    STREAM_MASK_KEY = 8,  // block 0, words 0..7: the public mask key of a compact server key
+    STREAM_MASK_KEY = 8,  // block 0, words 0..7: the public mask key of a compact server key or content blob
 };
 
 class Rng {
@@ -118,6 +118,35 @@ void enc_noise(const Params& p, const RngKey& key, uint64_t first_block, size_t 
 // Fresh LWE encryptions of block messages (Delta = 2^59) under the big key.
 void encrypt_blocks(const Params& p, const ClientKey& ck, const uint8_t* msgs, size_t count, const RngKey& key,
                     uint64_t first_block, uint64_t* out /* count * (kN+1) */);
+// the same blocks with the masks drawn under mask_key and the noise under noise_key
+void encrypt_blocks(const Params& p, const ClientKey& ck, const uint8_t* msgs, size_t count, const RngKey& mask_key,
+                    const RngKey& noise_key, uint64_t first_block, uint64_t* out /* count * (kN+1) */);
+
+// Compact (seeded) content ciphertexts, both rings.  The masks of the blocks
+// are ChaCha20 words of the public mask key derive_mask_key(K) at the standard encryptor's
+// indices (u64 number (first_block + q) kN + t of STREAM_ENC_MASK); the noise is the standard
+// encryptor's under the call's secret key K.  An LWE mask is public anyway, so no secret
+// touches a mask word, and the ciphertexts are their bodies and the 32 bytes of the mask key.
+// Wire blob (include/fheregex.h): "FRCCTXT1", int32 k, N, u64 first_block, u64 n_blocks, the
+// mask key, n_blocks u64 bodies; little endian, exactly 64 + 8 n_blocks bytes.
+constexpr size_t CONTENT_HEADER = 64;
+constexpr uint64_t CONTENT_MAX_BLOCK = (uint64_t)1 << 40;  // first_block + n_blocks: (f + q) kN / 8 cannot wrap
+struct ContentBlob {
+    RngKey mask_key;
+    uint64_t first_block = 0;
+    size_t n_blocks = 0;
+    const uint8_t* bodies = nullptr;  // n_blocks u64, little endian, any alignment
+};
+size_t content_blob_size(size_t n_blocks);  // bytes; Error(FR_ERR_INVALID) past CONTENT_MAX_BLOCK blocks
+// Error(FR_ERR_INVALID) unless len is exact, the magic matches, k and N are p's,
+// first_block + n_blocks <= 2^40 and (radix: the string entries) n_blocks % 4 == 0
+ContentBlob check_content_blob(const Params& p, const uint8_t* blob, size_t len, bool radix);
+// encrypt_blocks under (derive_mask_key(key), key), packed; `key` is the caller's to wipe
+std::vector<uint8_t> encrypt_content_blob(const Params& p, const ClientKey& ck, const uint8_t* msgs, size_t count,
+                                          const RngKey& key, uint64_t first_block);
+// check_content_blob (radix = false), then every mask from the mask key around the blob's
+// bodies; out has n_blocks * (kN+1) words.  Needs no client key.
+void expand_content(const Params& p, const uint8_t* blob, size_t len, uint64_t* out);
 uint64_t lwe_phase(const Params& p, const ClientKey& ck, const uint64_t* lwe);
 // tfhe-rs shortint decrypt_message_and_carry: round(phase / Delta) mod 16
 uint32_t decode16(uint64_t phase);

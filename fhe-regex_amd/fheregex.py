@@ -129,6 +129,18 @@ _SIGS = {
     "fr_export_server_key_compact": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "fr_load_server_key_compact": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
     "fr_device_timers_key_load": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "fr_compact_content_size": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fr_encrypt_str_compact_keyed": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t,
+                                               C.POINTER(C.c_size_t)]),
+    "fr_encrypt_blocks_compact_keyed": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, C.c_char_p,
+                                                  C.c_uint64, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fr_expand_compact_content": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, u64p, C.c_size_t,
+                                            C.POINTER(C.c_size_t)]),
+    "fr_upload_compact_str": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t,
+                                        C.POINTER(C.c_size_t)]),
+    "fr_upload_compact_blocks": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t,
+                                           C.POINTER(C.c_size_t)]),
+    "fr_device_timers_content": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "fr_encrypt_str": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint64, u64p]),
     "fr_encrypt_blocks": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, C.c_uint64, C.c_uint64, u64p]),
     "fr_decrypt_radix": (C.c_int, [C.c_void_p, u64p, u64p]),
@@ -560,6 +572,72 @@ class Context:
         _check(f(self.h, s, len(s), v, out))
         return list(out)
 
+    # compact (seeded) content (fheregex.h): the bodies and a public mask key travel, the
+    # server rebuilds the masks.  The C-ABI is keyed only: an int seed stands for seed_key(seed).
+    @staticmethod
+    def _compact_key(seed):
+        keyed, v = _rng_arg(seed)
+        return v if keyed else seed_key(v)
+
+    def compact_content_size(self, n_blocks: int) -> int:
+        n = C.c_size_t()
+        _check(lib().fr_compact_content_size(self.h, n_blocks, C.byref(n)))
+        return n.value
+
+    def encrypt_str_compact(self, s: bytes | str, seed=None) -> bytes:
+        """encrypt_str as a compact blob of 64 + 32 len(s) bytes (4 blocks per char)"""
+        if isinstance(s, str):
+            s = s.encode("latin-1")
+        key = self._compact_key(seed)
+        n = C.c_size_t()
+        _check(lib().fr_encrypt_str_compact_keyed(self.h, s, len(s), key, None, 0, C.byref(n)))
+        buf = C.create_string_buffer(n.value)
+        _check(lib().fr_encrypt_str_compact_keyed(self.h, s, len(s), key, buf, n.value, C.byref(n)))
+        return buf.raw[:n.value]
+
+    def encrypt_blocks_compact(self, msgs, seed=None, first_block: int = 0) -> bytes:
+        """encrypt_blocks as a compact blob of 64 + 8 len(msgs) bytes"""
+        m = np.ascontiguousarray(np.asarray(msgs, dtype=np.uint8))
+        mp = m.ctypes.data_as(C.POINTER(C.c_uint8))
+        key = self._compact_key(seed)
+        n = C.c_size_t()
+        _check(lib().fr_encrypt_blocks_compact_keyed(self.h, mp, len(m), key, first_block, None, 0, C.byref(n)))
+        buf = C.create_string_buffer(n.value)
+        _check(lib().fr_encrypt_blocks_compact_keyed(self.h, mp, len(m), key, first_block, buf, n.value, C.byref(n)))
+        return buf.raw[:n.value]
+
+    def expand_compact_content(self, blob: bytes) -> np.ndarray:
+        """the full LWE words [n_blocks, lwe_len] of a compact blob, on the host; no key needed"""
+        blob = bytes(blob)
+        n = C.c_size_t()
+        _check(lib().fr_expand_compact_content(self.h, blob, len(blob), None, 0, C.byref(n)))
+        out = np.zeros((n.value, self.lwe_len), dtype=np.uint64)
+        _check(lib().fr_expand_compact_content(self.h, blob, len(blob), _p(out), out.size, C.byref(n)))
+        return out
+
+    def _upload_compact(self, fn, blob, per_handle) -> List[int]:
+        blob = bytes(blob)
+        cap = max(0, len(blob) - 64) // (8 * per_handle)
+        out = (C.c_uint32 * max(cap, 1))()
+        n = C.c_size_t()
+        _check(fn(self.h, blob, len(blob), out, cap, C.byref(n)))
+        return list(out)[:n.value]
+
+    def upload_compact_str(self, blob: bytes) -> List[int]:
+        """a compact string blob expanded on the device into radix handles (as upload_radix);
+        no client key needed; returns once enqueued"""
+        return self._upload_compact(lib().fr_upload_compact_str, blob, 4)
+
+    def upload_compact_blocks(self, blob: bytes) -> List[int]:
+        """a compact blob expanded on the device into boolean handles (as upload_bool)"""
+        return self._upload_compact(lib().fr_upload_compact_blocks, blob, 1)
+
+    def content_expand_timer(self) -> float:
+        """ms of the last upload_compact_*'s expansion kernel under set_profiling"""
+        ms = C.c_double()
+        _check(lib().fr_device_timers_content(self.h, C.byref(ms)))
+        return ms.value
+
     def serialize_radix(self, blocks: np.ndarray, degree: int = 3) -> bytes:
         """bincode RadixCiphertext (tfhe-rs 0.2 layout, [ext] unverified) of one radix (4 blocks)."""
         b = np.ascontiguousarray(blocks.reshape(-1, self.lwe_len), dtype=np.uint64)
@@ -765,6 +843,13 @@ class ClientKey:
             raise ValueError("content contains non-ascii characters")
         return self.ctx.upload_radix(self.ctx.encrypt_str(s, seed))
 
+    def encrypt_str_compact(self, s: str, seed=None) -> bytes:
+        """encrypt_str as the compact wire blob (64 + 32 len(s) bytes) that
+        ServerKey.upload_str expands on the server's GPU; `seed` as in encrypt_str"""
+        if any(ord(ch) > 127 for ch in s):
+            raise ValueError("content contains non-ascii characters")
+        return self.ctx.encrypt_str_compact(s, seed)
+
     def decrypt(self, ct: int) -> int:
         return self.ctx.decrypt_radix(self.ctx.download_radix(ct))
 
@@ -779,6 +864,11 @@ class ServerKey:
 
     def create_trivial_radix(self, msg: int) -> int:
         return self.ctx.trivial(msg)
+
+    def upload_str(self, blob: bytes) -> List[int]:
+        """content handles of a client's compact blob (ClientKey.encrypt_str_compact): the
+        masks are rebuilt on the GPU, only the bodies cross the bus; no client key needed"""
+        return self.ctx.upload_compact_str(blob)
 
     def save(self, path: str):
         """the server key as an .npz of its (ksk, bsk) arrays (fr_export_server_key's layout)"""
@@ -815,6 +905,16 @@ def compact_mask_key(blob: bytes) -> bytes:
     if len(blob) < 72 or bytes(blob[:8]) != COMPACT_MAGIC:
         raise ValueError("not a compact server key blob")
     return bytes(blob[40:72])
+
+
+COMPACT_CONTENT_MAGIC = b"FRCCTXT1"
+
+
+def compact_content_mask_key(blob: bytes) -> bytes:
+    """the public 32-byte mask key of a compact content blob (bytes 32..63)"""
+    if len(blob) < 64 or bytes(blob[:8]) != COMPACT_CONTENT_MAGIC:
+        raise ValueError("not a compact content blob")
+    return bytes(blob[32:64])
 
 
 def gen_keys(client_key_blob: Optional[bytes] = None, seed=None, device: int = 0,

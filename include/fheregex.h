@@ -245,6 +245,48 @@ int fr_encrypt_upload_str(fr_ctx* ctx, const char* s, size_t len, uint64_t seed,
  * an argument and is never stored in device memory.  FR_ERR_NO_KEY, FR_ERR_NO_DEVICE,
  * FR_ERR_NON_ASCII as the seeded call. */
 int fr_encrypt_upload_str_keyed(fr_ctx* ctx, const char* s, size_t len, const uint8_t* key, fr_ct* out /* len */);
+/* Compact (seeded) content ciphertexts, both rings.  All but one word of an LWE block is
+ * pseudo-random mask, so the client ships the bodies and a public 32-byte mask key and the
+ * server rebuilds the masks: 64 + 8*n_blocks bytes instead of 8*(kN+1)*n_blocks (256
+ * chars: 8,256 B instead of 16,785,408 B).  With K the call's generator key (see
+ * "Randomness"): the mask key M is words 0..7 of block 0 of K's stream 8, as for a compact
+ * server key; mask word t of block q is u64 number (first_block + q)*kN + t of stream 5
+ * under M (the standard encryptor's indices under another key); the body is
+ * <mask, s_big> + m*2^59 + the standard encryptor's noise, which stays under K.  An LWE
+ * mask is public in the ordinary form too; no secret touches a mask word.  The keyed
+ * calls' caveat stands: two blobs made under one K share masks and noise block by block.
+ * The wire blob, little endian, exactly fr_compact_content_size bytes = 64 + 8*n_blocks:
+ *   bytes 0-7    ASCII "FRCCTXT1"
+ *   bytes 8-15   int32 k, int32 N
+ *   bytes 16-23  u64 first_block
+ *   bytes 24-31  u64 n_blocks
+ *   bytes 32-63  the mask key (8 words)
+ *   bytes 64...  n_blocks u64 bodies
+ * A blob is refused with FR_ERR_INVALID, before anything is allocated, unless its length
+ * is exact, the magic matches, k and N are the context's, first_block + n_blocks <= 2^40
+ * and, for fr_upload_compact_str, n_blocks % 4 == 0.
+ * Encryption (client): key == NULL draws K from the OS CSPRNG (production), else the
+ * caller's 32 bytes; buf == NULL is a size query (*written = bytes needed); FR_ERR_NO_KEY
+ * without a client key, FR_ERR_NON_ASCII, FR_ERR_RNG, FR_ERR_INVALID for cap too small. */
+int fr_compact_content_size(fr_ctx* ctx, size_t n_blocks, size_t* bytes);
+int fr_encrypt_str_compact_keyed(fr_ctx* ctx, const char* s, size_t len, const uint8_t* key, uint8_t* buf, size_t cap,
+                                 size_t* written); /* 4 blocks per char, first_block 0 */
+int fr_encrypt_blocks_compact_keyed(fr_ctx* ctx, const uint8_t* msgs, size_t count, const uint8_t* key,
+                                    uint64_t first_block, uint8_t* buf, size_t cap, size_t* written);
+/* Host expansion to the full LWE words; needs no key.  out has room for
+ * out_words >= n_blocks*(kN+1) (else FR_ERR_INVALID); out == NULL: *n_blocks only. */
+int fr_expand_compact_content(fr_ctx* ctx, const uint8_t* blob, size_t len, uint64_t* out, size_t out_words,
+                              size_t* n_blocks);
+/* Device expansion straight into fresh arena slots; needs no client key.  The handles are
+ * ordinary content: radix handles as fr_upload_radix's (4 blocks per character), boolean
+ * handles as fr_upload_bool's (one block each).  Only the bodies and the slot list cross
+ * the bus, in one copy; the call returns once the expansion is enqueued on the context's
+ * stream, the blob may be freed on return, and every later operation of the context, on
+ * any lane, is ordered after it.  *n_chars / *n = handles needed; cap smaller than that,
+ * or a bad blob -> FR_ERR_INVALID with no slot or handle left allocated;
+ * FR_ERR_NO_DEVICE on a host-only context (after the checks of the blob and of cap). */
+int fr_upload_compact_str(fr_ctx* ctx, const uint8_t* blob, size_t len, fr_ct* out, size_t cap, size_t* n_chars);
+int fr_upload_compact_blocks(fr_ctx* ctx, const uint8_t* blob, size_t len, fr_ct* out, size_t cap, size_t* n);
 /* Wire format of a radix ciphertext: bincode (fixint, little endian) of tfhe-rs
  * 0.2 RadixCiphertext — u64 n_blocks, then per block u64 len (= kN+1), the LWE
  * words, u64 degree, u64 message_modulus (4), u64 carry_modulus (4).  [ext]
@@ -377,6 +419,9 @@ int fr_device_timers_pair(fr_ctx* ctx, double* br_ms, uint64_t* br_launches, uin
  * events: ms[0..4] = H2D copy of the bodies, KSK mask expansion, BSK mask expansion, KSK
  * byte limbs, Fourier transform of the BSK. */
 int fr_device_timers_key_load(fr_ctx* ctx, double* ms /* 5 */);
+/* The expansion kernel of the last fr_upload_compact_* made under fr_set_profiling, by HIP
+ * events, ms.  A profiled upload waits for its kernel; an unprofiled one does not. */
+int fr_device_timers_content(fr_ctx* ctx, double* ms);
 
 /* ----- one match split across ranks ----- */
 /* The reference folds ct_or over the branches of every start offset
