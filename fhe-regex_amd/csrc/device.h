@@ -1,10 +1,14 @@
-// Device executor interface (HIP, gfx950).  The host class is in device.hip; the kernels and
-// the methods that launch them in rns_br.hip, fft_br.hip, keyswitch.hip and keygen.hip.
+// Device executor interface (HIP, gfx950), free of HIP headers: the engine compiles it with
+// g++.  The host class is in device.hip; the kernels and the methods that launch them in
+// rns_br.hip, fft_br.hip, keyswitch.hip and keygen.hip.  Every GPU resource of the class is
+// held by an owner from owned.h, so ~Device only synchronises and the members release
+// themselves in reverse order of declaration.
 #pragma once
 #include <cstdint>
 #include <vector>
 
 #include "common.h"
+#include "owned.h"
 
 namespace fr {
 
@@ -102,7 +106,7 @@ class Device {
     // stream-ordered slots_to_device for n <= 16 (the slot list travels as a kernel
     // argument): returns once enqueued; order other streams after it with an event on stream()
     void slots_to_device_async(const int* slots, size_t n, uint64_t* dst);
-    void* stream() const { return stream_; }
+    void* stream() const { return cur().stream.get(); }
     void zero_slot(int slot);
 
     // run one dependency level of gates (all independent), async on the stream
@@ -149,94 +153,75 @@ class Device {
     std::string info() const;
 
   private:
+    // Everything a lane owns.  Lane 0 is lane0_, lanes 1..n are lanes_; cur() is the one
+    // launches go to.  The stream is declared first: it outlives what is used on it.
     struct LaneState {
-        void* stream = nullptr;
-        uint64_t* d_ks = nullptr;
-        size_t batch_cap = 0;
-        int8_t* d_dig = nullptr;
-        size_t dig_cap = 0;
-        int* d_cmap = nullptr;
-        int* h_cmap[2] = {nullptr, nullptr};
-        void* cmap_ev[2] = {nullptr, nullptr};
-        size_t cmap_cap = 0, cmap_n = 0;
-        int cmap_stage = 0;
-        void* done_ev = nullptr;  // recorded on the lane's stream when it is left
-        bool pending = false;     // work enqueued since lane 0 last waited for it
+        gpu::Stream stream;
+        gpu::DevBuf<uint64_t> ks;    // keyswitch outputs [gates][ks_stride]
+        gpu::DevBuf<int8_t> dig;     // keyswitch digits [rows][kN*ks_level]
+        gpu::StagingRing<int> cmap;  // content map (bind_content)
+        size_t cmap_n = 0;           // entries bound
+        gpu::Event done_ev;          // recorded on the lane's stream when it is left
+        bool pending = false;        // work enqueued since lane 0 last waited for it
     };
+    // The lanes come before every other resource, so their streams are destroyed last.
+    LaneState lane0_;
     std::vector<LaneState> lanes_;  // lanes 1..n
     int lane_ = 0;                  // current lane
+    LaneState& cur() { return lane_ ? lanes_[lane_ - 1] : lane0_; }
+    const LaneState& cur() const { return lane_ ? lanes_[lane_ - 1] : lane0_; }
     bool lanes_pending_ = false;
     bool lanes_unsynced_ = false;   // lane work not yet host-synchronised (deferred frees)
-    void* main_ev_ = nullptr;       // lane 0's progress, waited for by a lane on entry
+    gpu::Event main_ev_;            // lane 0's progress, waited for by a lane on entry
     std::vector<int> deferred_free_;
-    void swap_lane(LaneState& l);
     // the stream of the current lane; on lane 0 it first waits (device-side) for the lanes
-    void* cur_stream();
+    hipStream_t cur_stream();
     void join_lanes();
     void sync_all();  // host-synchronise every lane, recycle the deferred slots
-    void free_lane(LaneState& l);
     void ensure_arena(size_t slots);
-    void ensure_batch(size_t n);
-    // pinned staging ring for gate descriptors: a buffer is rewritten only after
-    // its previous H2D copy completed (no stream-wide sync between levels)
-    DevGate* stage_acquire();
-    void stage_copy(size_t n);
+    void ensure_ks(size_t n);     // the current lane's keyswitch scratch for n gates
+    void ensure_gates(size_t n);  // the gate ring for n descriptors
     void validate_gates(const DevGate* gates, size_t n, size_t n_refs = 0) const;
     void launch_level(const DevGate* d_gates, const DevGate* host, size_t n);
     // profiling: per-level event triples resolved at sync() (no sync per level)
-    void* take_event();
+    gpu::Event take_event();
     void resolve_timers();
     void ensure_digits(size_t rows);
     // ev_start / ev_stop (profiling): HIP events stamped by the kernels' own dispatch
     // (hipExtLaunchKernel) -- the first kernel's start and the last one's end -- so timing
     // adds no marker packets between dependent launches (each cost ~5 us of gap)
-    void launch_ks(const DevGate* d_gates, size_t n, uint64_t* d_ks, void* ev_start = nullptr, void* ev_stop = nullptr);
-    void launch_br(const DevGate* d_gates, const uint64_t* d_ks, size_t n, void* ev_start = nullptr,
-                   void* ev_stop = nullptr);
+    void launch_ks(const DevGate* d_gates, size_t n, uint64_t* d_ks, hipEvent_t ev_start = nullptr,
+                   hipEvent_t ev_stop = nullptr);
+    void launch_br(const DevGate* d_gates, const uint64_t* d_ks, size_t n, hipEvent_t ev_start = nullptr,
+                   hipEvent_t ev_stop = nullptr);
     void run_br_jobs(const uint64_t* ks_in, std::vector<DevGate>& gates, uint64_t* out);  // the blind_rotate_*_host hooks
     // FR_RING_RNS (rns_br.hip)
     void init_rns();
     void upload_rns_bsk(const std::vector<uint64_t>& bsk);
-    void launch_br_rns(const DevGate* d_gates, const uint64_t* d_ks, size_t n, void* ev_start, void* ev_stop);
-    void free_rns();
+    void launch_br_rns(const DevGate* d_gates, const uint64_t* d_ks, size_t n, hipEvent_t ev_start, hipEvent_t ev_stop);
     void init_ks();  // keyswitch.hip: the FR_KS_* settings
     // FR_RING_FFT (fft_br.hip)
     void init_fft();
     void upload_fft_bsk(const std::vector<uint64_t>& bsk);
-    void launch_br_fft(const DevGate* d_gates, const uint64_t* d_ks, size_t n, void* stream, void* ev_start = nullptr,
-                       void* ev_stop = nullptr);
-    void free_fft();
+    void launch_br_fft(const DevGate* d_gates, const uint64_t* d_ks, size_t n, hipStream_t stream,
+                       hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
     void build_ksk_limbs();  // d_kl_ from d_ksk_
     void build_fourier_bsk();  // keygen.hip: d_fbsk_ (every lane layout in use) from d_tbsk_
     double key_load_ms_[5] = {0, 0, 0, 0, 0};
-    // expand_to_slots: device staging buffer (reused in stream order) and its pinned ring;
-    // a pinned buffer is rewritten only after its previous H2D copy completed
-    uint8_t* d_xstage_ = nullptr;
-    uint8_t* h_xstage_[2] = {nullptr, nullptr};
-    void* xstage_ev_[2] = {nullptr, nullptr};
-    size_t xstage_cap_ = 0;  // bytes
-    int xstage_ = 0;
+    // expand_to_slots: the bodies and the slot list of a call, one copy (lane 0)
+    gpu::StagingRing<uint8_t> xstage_;
     double expand_ms_ = 0;
     void stage_slot_list(const int* slots, size_t n);  // -> d_slot_list_ (stream order)
-    int* d_slot_list_ = nullptr;
-    size_t slot_list_cap_ = 0;
-    // content map (bind_content): device copy (rewritten in stream order), pinned
-    // staging ring, entries bound
-    int* d_cmap_ = nullptr;
-    int* h_cmap_[2] = {nullptr, nullptr};
-    void* cmap_ev_[2] = {nullptr, nullptr};
-    size_t cmap_cap_ = 0, cmap_n_ = 0;
-    int cmap_stage_ = 0;
+    gpu::DevBuf<int> d_slot_list_;
 
     Params p_;
     int dev_;
     int e_ = 8;        // residues per lane in the NTT kernels (8 or 16; measured: 8 wins for k=1 and k=2)
     int e_small_ = 8;  // ... for launches of at most small_batch_ bootstraps
     size_t small_batch_ = 256;
-    void* stream_ = nullptr;  // hipStream_t
-    uint64_t* d_ksk_ = nullptr;
-    uint64_t* d_tbsk_ = nullptr;  // torus BSK of a device-generated or device-expanded key (export)
-    int8_t* d_kl_ = nullptr;      // KSK as balanced byte limbs [col*8 + limb][k] (MFMA keyswitch)
+    gpu::DevBuf<uint64_t> d_ksk_;
+    gpu::DevBuf<uint64_t> d_tbsk_;  // torus BSK of a device-generated or device-expanded key (export)
+    gpu::DevBuf<int8_t> d_kl_;      // KSK as balanced byte limbs [col*8 + limb][k] (MFMA keyswitch)
     int kl_cols_ = 0;
     bool ks_mfma_ = true;         // FR_KS_MFMA=0: the VALU lincomb+keyswitch kernel
     size_t ks_mr4_min_ = 96;      // FR_KS_MR4_MIN: batches from this size use 4 row tiles per wave (k_ks_glds; ab_ks_glds.log: 100 gates 44 -> 37 us, 64 gates no gain)
@@ -245,10 +230,8 @@ class Device {
     int ks_xcd_ = 1;              // FR_KS_XCD=0: plain workgroup order of the MFMA keyswitch (k_ks_mfma)
     bool ks_dig16_ = true;        // FR_KS_DIG16=0: the digit pass with byte stores (k_ks_digits)
     bool ks_lds_ = true;          // FR_KS_LDS=0: four-row-tile keyswitch without the LDS-DMA ring (k_ks_mfma<4, 1>)
-    int8_t* d_dig_ = nullptr;     // keyswitch digits [rows][kN*ks_level]
-    size_t dig_cap_ = 0;
-    uint32_t* d_bsk_ = nullptr;  // NTT domain [i][r][c][prime][slot], Montgomery form, scaled by 1/N
-    uint32_t* d_tw_ = nullptr;   // Montgomery zeta per prime [2][N]
+    gpu::DevBuf<uint32_t> d_bsk_;  // NTT domain [i][r][c][prime][slot], Montgomery form, scaled by 1/N
+    gpu::DevBuf<uint32_t> d_tw_;   // Montgomery zeta per prime [2][N]
     // FR_RING_FFT: Fourier BSK [w][r][c][m][lane] (complex f64, scaled by 1/M), twiddles,
     // psi quadrant table, leaf exponents (fft.h)
     int fft_e_ = 4;           // complex points per lane in the throughput shape (4, 8 or 16)
@@ -259,22 +242,20 @@ class Device {
     bool fft_dual_ = false;  // FR_FFT_DUAL=1: the dual shape instead of the pair (experiment)
     // Fourier BSK, one copy per lane geometry in use: [0] E = 4 (latency shape, always),
     // [1] E = 8, [2] E = 16 (the throughput shape's when fft_e_ is that)
-    double* d_fbsk_[3] = {nullptr, nullptr, nullptr};
+    gpu::DevBuf<double> d_fbsk_[3];
     static int fbsk_index(int E) { return E == 4 ? 0 : E == 8 ? 1 : 2; }
     bool fbsk_needed(int E) const { return E == 4 || E == fft_e_; }
-    double* d_ftw_ = nullptr;
-    double* d_fqt_ = nullptr;   // psi^k, k < 2N
-    uint16_t* d_fleaf_ = nullptr;
-    uint64_t* d_arena_ = nullptr;
-    size_t arena_cap_ = 0;
+    gpu::DevBuf<double> d_ftw_;
+    gpu::DevBuf<double> d_fqt_;   // psi^k, k < 2N
+    gpu::DevBuf<uint16_t> d_fleaf_;
+    gpu::DevBuf<uint64_t> d_arena_;  // [slots][slot_stride]
     std::vector<int> free_slots_;
     size_t next_slot_ = 0;
-    DevGate* d_gates_ = nullptr;
-    DevGate* h_stage_[2] = {nullptr, nullptr};  // pinned staging ring
-    void* stage_ev_[2] = {nullptr, nullptr};
-    int stage_ = 0;
+    // gate descriptors of a staged level (lane 0: lanes run resident plans only); no
+    // stream-wide sync between levels
+    gpu::StagingRing<DevGate> gates_;
     struct PendingTimer {
-        void* ev[4];  // KS start, KS end, BR start, BR end
+        gpu::Event ev[4];  // KS start, KS end, BR start, BR end
         size_t gates, outs;
         bool lat, pair, ks;
         bool chain;  // BR timed from the keyswitch's end event (no start event on the BR launch)
@@ -282,13 +263,11 @@ class Device {
     bool latency_shape(size_t n) const;  // launch_br's shape choice for n bootstraps
     bool pair_shape(size_t n) const;     // (FFT ring, k = 1: the pair shape)
     std::vector<PendingTimer> pending_;
-    std::vector<void*> event_pool_;
-    uint64_t* d_ks_ = nullptr;
-    size_t batch_cap_ = 0;
+    std::vector<gpu::Event> event_pool_;
     int profiling_ = 0;  // fr_set_profiling level
     bool timer_chain_ = true;  // level 1: stop events only (FR_TIMER_CHAIN=0: start + stop on the BR launch)
     DeviceTimers timers_;
-    void* ev_[4] = {nullptr, nullptr, nullptr, nullptr};
+    gpu::Event ev_[4];  // bench_pbs
 };
 
 }  // namespace fr

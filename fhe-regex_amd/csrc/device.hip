@@ -1,4 +1,5 @@
-// The Device host class (HIP, gfx950): context construction, streams and lanes, the arena
+// The Device host class (HIP, gfx950): the HIP side of the resource owners (owned.h) and the
+// staging ring, context construction, streams and lanes, the arena
 // of big-LWE slots and its packed slot copies, gate staging and validation, running a
 // dependency level (keyswitch + blind rotation), timers, and the single-stage entry points
 // of the parity tests.  The kernels of a level live with the methods that launch them:
@@ -21,6 +22,61 @@ static bool supported(const Params& p) {
     return (p.N == 2048 && p.k == 1) || (p.N == 1024 && p.k == 2) || (p.N == 1024 && p.k == 1);
 }
 
+// ---------------------------------------------------------------- owners (owned.h)
+namespace gpu {
+void* dev_alloc(size_t bytes) {
+    void* p = nullptr;
+    HIP_CHECK(hipMalloc(&p, bytes));
+    return p;
+}
+void dev_free(void* p) noexcept { (void)hipFree(p); }
+void* pinned_alloc(size_t bytes) {
+    void* p = nullptr;
+    HIP_CHECK(hipHostMalloc(&p, bytes));
+    return p;
+}
+void pinned_free(void* p) noexcept { (void)hipHostFree(p); }
+hipEvent_t event_create(unsigned flags) {
+    hipEvent_t e = nullptr;
+    HIP_CHECK(hipEventCreateWithFlags(&e, flags));
+    return e;
+}
+void event_destroy(hipEvent_t e) noexcept { (void)hipEventDestroy(e); }
+hipStream_t stream_create() {
+    hipStream_t s = nullptr;
+    HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    return s;
+}
+void stream_destroy(hipStream_t s) noexcept { (void)hipStreamDestroy(s); }
+
+void StagingBytes::reserve(size_t bytes, size_t first, hipStream_t s) {
+    if (bytes <= d_.size()) return;
+    size_t cap = d_.size() ? d_.size() : first;
+    while (cap < bytes) cap *= 2;
+    HIP_CHECK(hipStreamSynchronize(s));  // no copy or kernel may still use the old buffers
+    d_.reset();
+    for (auto& h : h_) h.reset();
+    try {
+        for (auto& e : ev_)
+            if (!e) e = Event(hipEventDisableTiming);
+        for (auto& h : h_) h.alloc(cap);
+        d_.alloc(cap);
+    } catch (...) {
+        for (auto& h : h_) h.reset();
+        throw;
+    }
+}
+void* StagingBytes::acquire() {
+    side_ ^= 1;
+    HIP_CHECK(hipEventSynchronize(ev_[side_].get()));
+    return h_[side_].get();
+}
+void StagingBytes::commit(size_t bytes, hipStream_t s) {
+    HIP_CHECK(hipMemcpyAsync(d_.get(), h_[side_].get(), bytes, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipEventRecord(ev_[side_].get(), s));
+}
+}  // namespace gpu
+
 Device::Device(const Params& p, int device) : p_(p), dev_(device) {
     if (!supported(p)) throw Error(FR_ERR_INVALID, "device: unsupported (k, N)");
     if (p.ks_base_log != 3 || p.ks_level != 5 || p.pbs_base_log != 23 || p.pbs_level != 1)
@@ -30,97 +86,26 @@ Device::Device(const Params& p, int device) : p_(p), dev_(device) {
     if (hipGetDeviceCount(&count) != hipSuccess || count <= device || device < 0)
         throw Error(FR_ERR_NO_DEVICE, "no usable HIP device " + std::to_string(device));
     HIP_CHECK(hipSetDevice(device));
-    hipStream_t s;
-    HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    stream_ = s;
-    for (auto& e : ev_) {
-        hipEvent_t ev;
-        HIP_CHECK(hipEventCreate(&ev));
-        e = ev;
-    }
-    for (auto* evs : {&stage_ev_, &cmap_ev_})
-        for (auto& e : *evs) {
-            hipEvent_t ev;
-            HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            HIP_CHECK(hipEventRecord(ev, s));  // complete before first use
-            e = ev;
-        }
+    lane0_.stream.create();
+    for (auto& e : ev_) e = gpu::Event(hipEventDefault);
     init_rns();  // (an FFT-ring context too: twiddles and kernel attributes)
     init_ks();
     if (const char* ev = std::getenv("FR_TIMER_CHAIN")) timer_chain_ = std::atoi(ev) != 0;
     if (p.ring == FR_RING_FFT) init_fft();
     ensure_arena(1024);
-    ensure_batch(1024);
+    ensure_ks(1024);
+    ensure_gates(1024);
 }
 
+// Nothing may be released while a launch could still use it, and a stream not before the work
+// on it ended: wait for every lane, then the members go (device.h: the lanes last).
 Device::~Device() {
     (void)hipSetDevice(dev_);
-    if (lane_ != 0) leave_lane();
-    for (auto& l : lanes_) {
-        if (l.stream) (void)hipStreamSynchronize((hipStream_t)l.stream);
-        free_lane(l);
-    }
-    lanes_.clear();
-    if (main_ev_) (void)hipEventDestroy((hipEvent_t)main_ev_);
-    if (stream_) (void)hipStreamSynchronize((hipStream_t)stream_);
-    (void)hipFree(d_ksk_);
-    (void)hipFree(d_tbsk_);
-    (void)hipFree(d_kl_);
-    (void)hipFree(d_dig_);
-    free_rns();
-    free_fft();
-    (void)hipFree(d_arena_);
-    (void)hipFree(d_gates_);
-    (void)hipFree(d_ks_);
-    (void)hipFree(d_slot_list_);
-    (void)hipFree(d_xstage_);
-    for (auto* h : h_xstage_)
-        if (h) (void)hipHostFree(h);
-    for (auto* e : xstage_ev_)
-        if (e) (void)hipEventDestroy((hipEvent_t)e);
-    for (auto* h : h_stage_)
-        if (h) (void)hipHostFree(h);
-    for (auto* e : stage_ev_)
-        if (e) (void)hipEventDestroy((hipEvent_t)e);
-    for (auto* e : cmap_ev_)
-        if (e) (void)hipEventDestroy((hipEvent_t)e);
-    (void)hipFree(d_cmap_);
-    for (auto* h : h_cmap_)
-        if (h) (void)hipHostFree(h);
-    for (auto& t : pending_)
-        for (auto* e : t.ev) (void)hipEventDestroy((hipEvent_t)e);
-    for (auto* e : event_pool_) (void)hipEventDestroy((hipEvent_t)e);
-    for (auto e : ev_)
-        if (e) (void)hipEventDestroy((hipEvent_t)e);
-    if (stream_) (void)hipStreamDestroy((hipStream_t)stream_);
+    for (auto& l : lanes_) (void)hipStreamSynchronize(l.stream.get());
+    if (lane0_.stream) (void)hipStreamSynchronize(lane0_.stream.get());
 }
 
 // ---------------------------------------------------------------- lanes
-void Device::swap_lane(LaneState& l) {
-    std::swap(stream_, l.stream);
-    std::swap(d_ks_, l.d_ks);
-    std::swap(batch_cap_, l.batch_cap);
-    std::swap(d_dig_, l.d_dig);
-    std::swap(dig_cap_, l.dig_cap);
-    std::swap(d_cmap_, l.d_cmap);
-    std::swap(h_cmap_, l.h_cmap);
-    std::swap(cmap_ev_, l.cmap_ev);
-    std::swap(cmap_cap_, l.cmap_cap);
-    std::swap(cmap_n_, l.cmap_n);
-    std::swap(cmap_stage_, l.cmap_stage);
-}
-void Device::free_lane(LaneState& l) {
-    (void)hipFree(l.d_ks);
-    (void)hipFree(l.d_dig);
-    (void)hipFree(l.d_cmap);
-    for (auto* h : l.h_cmap)
-        if (h) (void)hipHostFree(h);
-    for (auto* e : l.cmap_ev)
-        if (e) (void)hipEventDestroy((hipEvent_t)e);
-    if (l.done_ev) (void)hipEventDestroy((hipEvent_t)l.done_ev);
-    if (l.stream) (void)hipStreamDestroy((hipStream_t)l.stream);
-    l = LaneState{};
-}
 void Device::set_lanes(int n) {
     if (n < 1 || n > 8) throw Error(FR_ERR_INVALID, "lanes: 1..8");
     if (lane_ != 0) throw Error(FR_ERR_INVALID, "lanes: changed inside a lane");
@@ -128,34 +113,16 @@ void Device::set_lanes(int n) {
     // n >= 2: n lanes besides lane 0 (matches go to them only: a match on lane 0 would wait
     // for the other lanes at its first launch)
     const int extra = n >= 2 ? n : 0;
-    while ((int)lanes_.size() > extra) {
-        free_lane(lanes_.back());
-        lanes_.pop_back();
-    }
-    if (!main_ev_ && extra) {
-        hipEvent_t ev;
-        HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        main_ev_ = ev;
-    }
+    while ((int)lanes_.size() > extra) lanes_.pop_back();
+    if (!main_ev_ && extra) main_ev_ = gpu::Event(hipEventDisableTiming);
     while ((int)lanes_.size() < extra) {
         LaneState l;
-        hipStream_t st;
-        HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        l.stream = st;
-        for (auto*& e : l.cmap_ev) {
-            hipEvent_t ev;
-            HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            HIP_CHECK(hipEventRecord(ev, st));  // complete before first use
-            e = ev;
-        }
-        hipEvent_t dv;
-        HIP_CHECK(hipEventCreateWithFlags(&dv, hipEventDisableTiming));
-        l.done_ev = dv;
-        lanes_.push_back(l);
-        // the lane's keyswitch scratch at the main lane's size (ensure_batch on entry grows it)
-        const int i = (int)lanes_.size();
-        enter_lane(i);
-        ensure_batch(1024);
+        l.stream.create();
+        l.done_ev = gpu::Event(hipEventDisableTiming);
+        lanes_.push_back(std::move(l));
+        // the lane's keyswitch scratch at the main lane's size (ensure_ks on entry grows it)
+        enter_lane((int)lanes_.size());
+        ensure_ks(1024);
         leave_lane();
     }
 }
@@ -166,16 +133,14 @@ void Device::enter_lane(int i) {
     // the lane waits for lane 0's own work so far -- not for the other lanes (no join here:
     // that would chain every lane behind the previous one); lane 0 waited for the lanes at
     // its last operation, so their results that operation consumed are covered too
-    HIP_CHECK(hipEventRecord((hipEvent_t)main_ev_, (hipStream_t)stream_));
-    swap_lane(lanes_[i - 1]);
+    HIP_CHECK(hipEventRecord(main_ev_.get(), lane0_.stream.get()));
+    HIP_CHECK(hipStreamWaitEvent(lanes_[i - 1].stream.get(), main_ev_.get(), 0));
     lane_ = i;
-    HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream_, (hipEvent_t)main_ev_, 0));
 }
 void Device::leave_lane() {
     if (lane_ == 0) return;
-    LaneState& l = lanes_[lane_ - 1];
-    HIP_CHECK(hipEventRecord((hipEvent_t)l.done_ev, (hipStream_t)stream_));
-    swap_lane(l);
+    LaneState& l = cur();
+    HIP_CHECK(hipEventRecord(l.done_ev.get(), l.stream.get()));
     l.pending = true;
     lanes_pending_ = true;
     lanes_unsynced_ = true;
@@ -185,19 +150,18 @@ void Device::join_lanes() {
     if (!lanes_pending_ || lane_ != 0) return;
     for (auto& l : lanes_)
         if (l.pending) {
-            HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream_, (hipEvent_t)l.done_ev, 0));
+            HIP_CHECK(hipStreamWaitEvent(lane0_.stream.get(), l.done_ev.get(), 0));
             l.pending = false;
         }
     lanes_pending_ = false;
 }
-void* Device::cur_stream() {
+hipStream_t Device::cur_stream() {
     if (lane_ == 0 && lanes_pending_) join_lanes();
-    return stream_;
+    return cur().stream.get();
 }
 void Device::sync_all() {
-    HIP_CHECK(hipStreamSynchronize((hipStream_t)stream_));
-    for (auto& l : lanes_)
-        if (l.stream) HIP_CHECK(hipStreamSynchronize((hipStream_t)l.stream));
+    HIP_CHECK(hipStreamSynchronize(lane0_.stream.get()));
+    for (auto& l : lanes_) HIP_CHECK(hipStreamSynchronize(l.stream.get()));
     if (lane_ == 0) {
         for (auto& l : lanes_) l.pending = false;
         lanes_pending_ = false;
@@ -218,39 +182,26 @@ std::string Device::info() const {
 }
 
 void Device::ensure_arena(size_t slots) {
-    if (slots <= arena_cap_) return;
-    size_t cap = arena_cap_ ? arena_cap_ : 1024;
+    const size_t stride = p_.slot_stride(), have = d_arena_.size() / stride;
+    if (slots <= have) return;
+    size_t cap = have ? have : 1024;
     while (cap < slots) cap *= 2;
-    uint64_t* nb = nullptr;
-    HIP_CHECK(hipMalloc(&nb, (size_t)8 * p_.slot_stride() * cap));
+    gpu::DevBuf<uint64_t> nb(stride * cap);
     if (d_arena_) {
         sync_all();  // no launch of any lane may still use the old arena
-        HIP_CHECK(hipMemcpyAsync(nb, d_arena_, (size_t)8 * p_.slot_stride() * arena_cap_, hipMemcpyDeviceToDevice, STREAM));
+        HIP_CHECK(hipMemcpyAsync(nb.get(), d_arena_.get(), 8 * d_arena_.size(), hipMemcpyDeviceToDevice, STREAM));
         HIP_CHECK(hipStreamSynchronize(STREAM));
-        HIP_CHECK(hipFree(d_arena_));
     }
-    d_arena_ = nb;
-    arena_cap_ = cap;
+    d_arena_ = std::move(nb);
 }
 
-void Device::ensure_batch(size_t n) {
-    if (n <= batch_cap_) return;
-    size_t cap = batch_cap_ ? batch_cap_ : 1024;
-    while (cap < n) cap *= 2;
+void Device::ensure_ks(size_t n) {
+    const size_t row = p_.ks_stride();
+    if (n * row <= cur().ks.size()) return;
     HIP_CHECK(hipStreamSynchronize(STREAM));
-    (void)hipFree(d_ks_);
-    if (lane_ == 0) {  // the gate staging ring belongs to lane 0 (lanes run resident plans only)
-        (void)hipFree(d_gates_);
-        for (auto& h : h_stage_) {
-            if (h) (void)hipHostFree(h);
-            h = nullptr;
-        }
-        HIP_CHECK(hipMalloc(&d_gates_, sizeof(DevGate) * cap));
-        for (auto& h : h_stage_) HIP_CHECK(hipHostMalloc(&h, sizeof(DevGate) * cap));
-    }
-    HIP_CHECK(hipMalloc(&d_ks_, (size_t)8 * p_.ks_stride() * cap));
-    batch_cap_ = cap;
+    cur().ks.grow(n * row, 1024 * row);
 }
+void Device::ensure_gates(size_t n) { gates_.reserve(n, 1024, STREAM); }
 
 int Device::alloc_slot() {
     if (!free_slots_.empty()) {
@@ -305,32 +256,29 @@ void Device::slots_to_device_async(const int* slots, size_t n, uint64_t* dst) {
         if (slots[i] < 0 || (size_t)slots[i] >= next_slot_) throw Error(FR_ERR_INVALID, "slot list: slot out of range");
         a.s[i] = slots[i];
     }
-    k_slots_to_buf_arg<<<(unsigned)n, 256, 0, STREAM>>>(d_arena_, p_.slot_stride(), a, p_.lwe_len(), dst);
+    k_slots_to_buf_arg<<<(unsigned)n, 256, 0, STREAM>>>(d_arena_.get(), p_.slot_stride(), a, p_.lwe_len(), dst);
     HIP_CHECK(hipGetLastError());
 }
 void Device::stage_slot_list(const int* slots, size_t n) {
     for (size_t i = 0; i < n; ++i)
         if (slots[i] < 0 || (size_t)slots[i] >= next_slot_) throw Error(FR_ERR_INVALID, "slot list: slot out of range");
-    if (n > slot_list_cap_) {
+    if (n > d_slot_list_.size()) {
         HIP_CHECK(hipStreamSynchronize(STREAM));
-        (void)hipFree(d_slot_list_);
-        d_slot_list_ = nullptr;
-        slot_list_cap_ = std::max<size_t>(n, 1024);
-        HIP_CHECK(hipMalloc(&d_slot_list_, 4 * slot_list_cap_));
+        d_slot_list_.alloc(std::max<size_t>(n, 1024));
     }
-    HIP_CHECK(hipMemcpyAsync(d_slot_list_, slots, 4 * n, hipMemcpyHostToDevice, STREAM));
+    HIP_CHECK(hipMemcpyAsync(d_slot_list_.get(), slots, 4 * n, hipMemcpyHostToDevice, STREAM));
 }
 void Device::slots_to_device(const int* slots, size_t n, uint64_t* dst) {
     if (!n) return;
     stage_slot_list(slots, n);
-    k_slots_to_buf<<<(unsigned)n, 256, 0, STREAM>>>(d_arena_, p_.slot_stride(), d_slot_list_, p_.lwe_len(), dst);
+    k_slots_to_buf<<<(unsigned)n, 256, 0, STREAM>>>(d_arena_.get(), p_.slot_stride(), d_slot_list_.get(), p_.lwe_len(), dst);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(STREAM));  // the caller's stream may read dst now
 }
 void Device::device_to_slots(const int* slots, size_t n, const uint64_t* src) {
     if (!n) return;
     stage_slot_list(slots, n);
-    k_buf_to_slots<<<(unsigned)n, 256, 0, STREAM>>>(src, p_.lwe_len(), d_slot_list_, p_.slot_stride(), d_arena_);
+    k_buf_to_slots<<<(unsigned)n, 256, 0, STREAM>>>(src, p_.lwe_len(), d_slot_list_.get(), p_.slot_stride(), d_arena_.get());
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(STREAM));  // the caller may reuse src now
 }
@@ -338,16 +286,16 @@ void Device::device_to_slots(const int* slots, size_t n, const uint64_t* src) {
 void Device::write_slots(const int* slots, size_t n, const uint64_t* host) {
     const int L = p_.lwe_len(), S = p_.slot_stride();
     for (size_t i = 0; i < n; ++i)
-        HIP_CHECK(hipMemcpyAsync(d_arena_ + (size_t)slots[i] * S, host + i * L, 8 * (size_t)L, hipMemcpyHostToDevice, STREAM));
+        HIP_CHECK(hipMemcpyAsync(d_arena_.get() + (size_t)slots[i] * S, host + i * L, 8 * (size_t)L, hipMemcpyHostToDevice, STREAM));
     HIP_CHECK(hipStreamSynchronize(STREAM));
 }
 void Device::read_slot(int slot, uint64_t* host) {
-    HIP_CHECK(hipMemcpyAsync(host, d_arena_ + (size_t)slot * p_.slot_stride(), 8 * (size_t)p_.lwe_len(),
+    HIP_CHECK(hipMemcpyAsync(host, d_arena_.get() + (size_t)slot * p_.slot_stride(), 8 * (size_t)p_.lwe_len(),
                              hipMemcpyDeviceToHost, STREAM));
     sync_all();
 }
 void Device::zero_slot(int slot) {
-    HIP_CHECK(hipMemsetAsync(d_arena_ + (size_t)slot * p_.slot_stride(), 0, 8 * (size_t)p_.lwe_len(), STREAM));
+    HIP_CHECK(hipMemsetAsync(d_arena_.get() + (size_t)slot * p_.slot_stride(), 0, 8 * (size_t)p_.lwe_len(), STREAM));
 }
 
 void Device::upload_keys(const std::vector<uint64_t>& ksk, const std::vector<uint64_t>& bsk) {
@@ -355,14 +303,11 @@ void Device::upload_keys(const std::vector<uint64_t>& ksk, const std::vector<uin
     if (bsk.size() != p_.bsk_len()) throw Error(FR_ERR_INVALID, "bsk size");
     // every queued launch of every lane that reads the old keys has finished before they go
     HIP_CHECK(hipDeviceSynchronize());
-    (void)hipFree(d_ksk_);
-    (void)hipFree(d_bsk_);
-    d_ksk_ = nullptr;
-    d_bsk_ = nullptr;
-    HIP_CHECK(hipMalloc(&d_ksk_, 8 * ksk.size()));
-    HIP_CHECK(hipMemcpy(d_ksk_, ksk.data(), 8 * ksk.size(), hipMemcpyHostToDevice));
-    (void)hipFree(d_tbsk_);  // host-generated keys: export reads the host copy
-    d_tbsk_ = nullptr;
+    d_ksk_.reset();
+    d_bsk_.reset();
+    d_tbsk_.reset();  // host-generated keys: export reads the host copy
+    d_ksk_.alloc(ksk.size());
+    HIP_CHECK(hipMemcpy(d_ksk_.get(), ksk.data(), 8 * ksk.size(), hipMemcpyHostToDevice));
     build_ksk_limbs();
     if (p_.ring == FR_RING_FFT) upload_fft_bsk(bsk);
     else upload_rns_bsk(bsk);
@@ -371,8 +316,8 @@ void Device::upload_keys(const std::vector<uint64_t>& ksk, const std::vector<uin
 bool Device::latency_shape(size_t n) const { return n <= (p_.ring == FR_RING_FFT ? fft_small_ : small_batch_); }
 bool Device::pair_shape(size_t n) const { return p_.ring == FR_RING_FFT && !latency_shape(n) && n <= fft_pair_; }
 
-void Device::launch_br(const DevGate* d_gates, const uint64_t* d_ks, size_t n, void* ev_start, void* ev_stop) {
-    if (p_.ring == FR_RING_FFT) launch_br_fft(d_gates, d_ks, n, stream_, ev_start, ev_stop);
+void Device::launch_br(const DevGate* d_gates, const uint64_t* d_ks, size_t n, hipEvent_t ev_start, hipEvent_t ev_stop) {
+    if (p_.ring == FR_RING_FFT) launch_br_fft(d_gates, d_ks, n, cur().stream.get(), ev_start, ev_stop);
     else launch_br_rns(d_gates, d_ks, n, ev_start, ev_stop);
 }
 
@@ -396,29 +341,18 @@ void Device::bind_content(const int* cmap, size_t n) {
     for (size_t i = 0; i < n; ++i)
         if (cmap[i] < -1 || (cmap[i] >= 0 && (size_t)cmap[i] >= next_slot_))
             throw Error(FR_ERR_INVALID, "content map: slot out of range");
-    if (n > cmap_cap_) {
-        HIP_CHECK(hipStreamSynchronize(STREAM));  // no launch may still read the old map
-        (void)hipFree(d_cmap_);
-        d_cmap_ = nullptr;
-        for (auto& h : h_cmap_) {
-            if (h) (void)hipHostFree(h);
-            h = nullptr;
-        }
-        size_t cap = cmap_cap_ ? cmap_cap_ : 4096;
-        while (cap < n) cap *= 2;
-        HIP_CHECK(hipMalloc(&d_cmap_, 4 * cap));
-        for (auto& h : h_cmap_) HIP_CHECK(hipHostMalloc(&h, 4 * cap));
-        cmap_cap_ = cap;
-    }
+    LaneState& l = cur();
+    const size_t bound = l.cmap_n;
+    l.cmap_n = 0;  // (an error below leaves no map bound)
+    if (!n) return;
+    const hipStream_t s = STREAM;
+    l.cmap.reserve(n, 4096, s);  // (after a reallocation no launch reads the old map)
     // the map bound last is still in place (a replay of the same content): nothing to copy
-    if (n == cmap_n_ && n && std::memcmp(h_cmap_[cmap_stage_], cmap, 4 * n) == 0) return;
-    cmap_stage_ ^= 1;
-    // the pinned buffer is rewritten only after its previous copy completed
-    HIP_CHECK(hipEventSynchronize((hipEvent_t)cmap_ev_[cmap_stage_]));
-    std::memcpy(h_cmap_[cmap_stage_], cmap, 4 * n);
-    if (n) HIP_CHECK(hipMemcpyAsync(d_cmap_, h_cmap_[cmap_stage_], 4 * n, hipMemcpyHostToDevice, STREAM));
-    HIP_CHECK(hipEventRecord((hipEvent_t)cmap_ev_[cmap_stage_], STREAM));
-    cmap_n_ = n;
+    if (n != bound || std::memcmp(l.cmap.last(), cmap, 4 * n) != 0) {
+        std::memcpy(l.cmap.acquire(), cmap, 4 * n);
+        l.cmap.commit(n, s);
+    }
+    l.cmap_n = n;
 }
 
 void Device::run_level(const DevGate* gates, size_t n) {
@@ -426,34 +360,34 @@ void Device::run_level(const DevGate* gates, size_t n) {
     if (!has_keys()) throw Error(FR_ERR_NO_KEY, "server key not uploaded");
     if (lane_ != 0) throw Error(FR_ERR_INVALID, "staged gate batches run on lane 0 only");
     validate_gates(gates, n);
-    ensure_batch(n);
-    // d_gates_ / d_ks_ are reused in stream order (this level's copy runs after
-    // the previous level's kernels); only the host staging buffer needs a wait
-    std::memcpy(stage_acquire(), gates, sizeof(DevGate) * n);
-    stage_copy(n);
-    launch_level(d_gates_, gates, n);
+    ensure_ks(n);
+    ensure_gates(n);
+    // the device copy and the keyswitch scratch are reused in stream order (this level's
+    // copy runs after the previous level's kernels); only the host staging buffer needs a wait
+    std::memcpy(gates_.acquire(), gates, sizeof(DevGate) * n);
+    gates_.commit(n, STREAM);
+    launch_level(gates_.device(), gates, n);
 }
 
 void Device::run_level_resident(const DevGate* d_gates, const DevGate* host, size_t n, size_t n_refs) {
     if (!n) return;
     if (!has_keys()) throw Error(FR_ERR_NO_KEY, "server key not uploaded");
-    if (n_refs > cmap_n_) throw Error(FR_ERR_INVALID, "template plan: content map not bound");
-    ensure_batch(n);
+    if (n_refs > cur().cmap_n) throw Error(FR_ERR_INVALID, "template plan: content map not bound");
+    ensure_ks(n);
     launch_level(d_gates, host, n);
 }
 
 DevGate* Device::upload_gates(const DevGate* gates, size_t n, size_t n_refs) {
     validate_gates(gates, n, n_refs);
-    DevGate* d = nullptr;
-    HIP_CHECK(hipMalloc(&d, sizeof(DevGate) * std::max<size_t>(n, 1)));
-    HIP_CHECK(hipMemcpy(d, gates, sizeof(DevGate) * n, hipMemcpyHostToDevice));
-    return d;
+    gpu::DevBuf<DevGate> d(std::max<size_t>(n, 1));
+    HIP_CHECK(hipMemcpy(d.get(), gates, sizeof(DevGate) * n, hipMemcpyHostToDevice));
+    return d.release();  // the plan's, until free_gates
 }
 
 void Device::free_gates(DevGate* d) {
     if (!d) return;
     HIP_CHECK(hipStreamSynchronize(STREAM));
-    HIP_CHECK(hipFree(d));
+    gpu::dev_free(d);
 }
 
 void Device::launch_level(const DevGate* d_gates, const DevGate* host, size_t n) {
@@ -467,9 +401,10 @@ void Device::launch_level(const DevGate* d_gates, const DevGate* host, size_t n)
     // launch opened a ~6.6 us gap before it and the stop events ~4.7 us after it under the
     // kernel trace (profiles/r04/gaps/).
     t.chain = profiling_ == 1 && timer_chain_;
-    if (profiling_ >= 2) launch_ks(d_gates, n, d_ks_, t.ev[0], t.ev[1]);
-    else launch_ks(d_gates, n, d_ks_, nullptr, t.chain ? t.ev[1] : nullptr);
-    launch_br(d_gates, d_ks_, n, t.chain ? nullptr : t.ev[2], t.ev[3]);
+    uint64_t* d_ks = cur().ks.get();
+    if (profiling_ >= 2) launch_ks(d_gates, n, d_ks, t.ev[0].get(), t.ev[1].get());
+    else launch_ks(d_gates, n, d_ks, nullptr, t.chain ? t.ev[1].get() : nullptr);
+    launch_br(d_gates, d_ks, n, t.chain ? nullptr : t.ev[2].get(), t.ev[3].get());
     HIP_CHECK(hipGetLastError());
     if (profiling_) {
         t.gates = n;
@@ -478,22 +413,13 @@ void Device::launch_level(const DevGate* d_gates, const DevGate* host, size_t n)
         t.ks = profiling_ >= 2;
         t.outs = 0;
         for (size_t i = 0; i < n; ++i) t.outs += host[i].n_out;
-        pending_.push_back(t);
+        pending_.push_back(std::move(t));
     }
 }
 
-DevGate* Device::stage_acquire() {
-    stage_ ^= 1;
-    HIP_CHECK(hipEventSynchronize((hipEvent_t)stage_ev_[stage_]));  // never-recorded events are complete
-    return h_stage_[stage_];
-}
-void Device::stage_copy(size_t n) {
-    HIP_CHECK(hipMemcpyAsync(d_gates_, h_stage_[stage_], sizeof(DevGate) * n, hipMemcpyHostToDevice, STREAM));
-    HIP_CHECK(hipEventRecord((hipEvent_t)stage_ev_[stage_], STREAM));
-}
-void* Device::take_event() {
+gpu::Event Device::take_event() {
     if (!event_pool_.empty()) {
-        void* e = event_pool_.back();
+        gpu::Event e = std::move(event_pool_.back());
         event_pool_.pop_back();
         return e;
     }
@@ -501,20 +427,21 @@ void* Device::take_event() {
     // the system-scope fence, so recording one between two launches costs no cache
     // writeback (with the default fence each record opened a ~5 us gap in the level chain)
     // (the first flag set this runtime accepts)
-    hipEvent_t ev = nullptr;
-    for (unsigned fl : {(unsigned)hipEventReleaseToDevice, (unsigned)hipEventDisableSystemFence, (unsigned)hipEventDefault})
-        if (hipEventCreateWithFlags(&ev, fl) == hipSuccess) return ev;
-        else (void)hipGetLastError();
-    HIP_CHECK(hipEventCreate(&ev));
-    return ev;
+    for (unsigned fl : {(unsigned)hipEventReleaseToDevice, (unsigned)hipEventDisableSystemFence})
+        try {
+            return gpu::Event(fl);
+        } catch (const Error&) {
+            (void)hipGetLastError();
+        }
+    return gpu::Event(hipEventDefault);
 }
 // KS / BR kernel times of the levels issued since the last sync (HIP events
 // on the launch stream, read once the stream has drained)
 void Device::resolve_timers() {
     for (auto& t : pending_) {
         float ks = 0, br = 0;
-        if (t.ks) HIP_CHECK(hipEventElapsedTime(&ks, (hipEvent_t)t.ev[0], (hipEvent_t)t.ev[1]));
-        HIP_CHECK(hipEventElapsedTime(&br, (hipEvent_t)t.ev[t.chain ? 1 : 2], (hipEvent_t)t.ev[3]));
+        if (t.ks) HIP_CHECK(hipEventElapsedTime(&ks, t.ev[0].get(), t.ev[1].get()));
+        HIP_CHECK(hipEventElapsedTime(&br, t.ev[t.chain ? 1 : 2].get(), t.ev[3].get()));
         timers_.ks_ms += ks;
         timers_.br_ms += br;
         timers_.br_launches += 1;
@@ -530,7 +457,7 @@ void Device::resolve_timers() {
             timers_.pair_launches += 1;
             timers_.pair_gates += t.gates;
         }
-        for (auto* e : t.ev) event_pool_.push_back(e);
+        for (auto& e : t.ev) event_pool_.push_back(std::move(e));
     }
     pending_.clear();
 }
@@ -543,7 +470,7 @@ void Device::sync() {
 // ---------------------------------------------------------------- tests
 void Device::keyswitch_host(const uint64_t* in, size_t count, uint64_t* out) {
     if (!has_keys()) throw Error(FR_ERR_NO_KEY, "server key not uploaded");
-    HIP_CHECK(hipStreamSynchronize(STREAM));  // queued matches read d_ks_ / d_gates_ (blind_rotate_host)
+    HIP_CHECK(hipStreamSynchronize(STREAM));  // queued matches read the scratch and the gate ring (blind_rotate_host)
     std::vector<int> slots(count);
     std::vector<DevGate> gates(count);
     for (size_t i = 0; i < count; ++i) slots[i] = alloc_slot();
@@ -557,13 +484,15 @@ void Device::keyswitch_host(const uint64_t* in, size_t count, uint64_t* out) {
         gates[i].direct = JOB_DIRECT;
         gates[i].out_slot[0] = slots[i];
     }
-    ensure_batch(count);
-    HIP_CHECK(hipMemcpy(d_gates_, gates.data(), sizeof(DevGate) * count, hipMemcpyHostToDevice));
-    launch_ks(d_gates_, count, d_ks_);
+    ensure_ks(count);
+    ensure_gates(count);
+    uint64_t* d_ks = cur().ks.get();
+    HIP_CHECK(hipMemcpy(gates_.device(), gates.data(), sizeof(DevGate) * count, hipMemcpyHostToDevice));
+    launch_ks(gates_.device(), count, d_ks);
     HIP_CHECK(hipStreamSynchronize(STREAM));
     const int ks = p_.ks_stride();
     for (size_t i = 0; i < count; ++i)
-        HIP_CHECK(hipMemcpy(out + i * (p_.n + 1), d_ks_ + i * ks, 8 * (size_t)(p_.n + 1), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(out + i * (p_.n + 1), d_ks + i * ks, 8 * (size_t)(p_.n + 1), hipMemcpyDeviceToHost));
     for (int s : slots) free_slot(s);
 }
 
@@ -581,22 +510,24 @@ static DevGate br_job(const uint8_t* luts, int n_out, int direct) {
 // gate i follow those of gate i - 1 in out (lwe_len words each)
 void Device::run_br_jobs(const uint64_t* ks_in, std::vector<DevGate>& gates, uint64_t* out) {
     if (!has_keys()) throw Error(FR_ERR_NO_KEY, "server key not uploaded");
-    // an asynchronous match may still read d_ks_ / d_gates_ on STREAM; the plain
+    // an asynchronous match may still read the scratch and the gate ring on STREAM; the plain
     // copies below run on the null stream, which does not wait for a non-blocking one
     HIP_CHECK(hipStreamSynchronize(STREAM));
     const size_t count = gates.size();
-    ensure_batch(count);
+    ensure_ks(count);
+    ensure_gates(count);
+    uint64_t* d_ks = cur().ks.get();
     const int ks = p_.ks_stride();
     for (size_t i = 0; i < count; ++i)
-        HIP_CHECK(hipMemcpy(d_ks_ + i * ks, ks_in + i * (p_.n + 1), 8 * (size_t)(p_.n + 1), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_ks + i * ks, ks_in + i * (p_.n + 1), 8 * (size_t)(p_.n + 1), hipMemcpyHostToDevice));
     std::vector<int> slots;
     for (auto& g : gates)
         for (int f = 0; f < g.n_out; ++f) {
             slots.push_back(alloc_slot());
             g.out_slot[f] = slots.back();
         }
-    HIP_CHECK(hipMemcpy(d_gates_, gates.data(), sizeof(DevGate) * count, hipMemcpyHostToDevice));
-    launch_br(d_gates_, d_ks_, count);
+    HIP_CHECK(hipMemcpy(gates_.device(), gates.data(), sizeof(DevGate) * count, hipMemcpyHostToDevice));
+    launch_br(gates_.device(), d_ks, count);
     HIP_CHECK(hipStreamSynchronize(STREAM));
     for (size_t i = 0; i < slots.size(); ++i) read_slot(slots[i], out + i * p_.lwe_len());
     for (int s : slots) free_slot(s);
@@ -626,26 +557,29 @@ int lut_w_norm2(const uint8_t* lut) {
 
 void Device::bench_pbs(const std::vector<DevGate>& gates, int iters, double* br_ms, double* total_ms) {
     const size_t n = gates.size();
-    ensure_batch(n);
+    ensure_ks(n);
+    ensure_gates(n);
     sync();
-    std::memcpy(stage_acquire(), gates.data(), sizeof(DevGate) * n);
-    stage_copy(n);
+    std::memcpy(gates_.acquire(), gates.data(), sizeof(DevGate) * n);
+    gates_.commit(n, STREAM);
+    const DevGate* d_gates = gates_.device();
+    uint64_t* d_ks = cur().ks.get();
     float br_sum = 0;
-    HIP_CHECK(hipEventRecord((hipEvent_t)ev_[3], STREAM));
+    HIP_CHECK(hipEventRecord(ev_[3].get(), STREAM));
     for (int it = 0; it < iters; ++it) {
-        launch_ks(d_gates_, n, d_ks_);
-        HIP_CHECK(hipEventRecord((hipEvent_t)ev_[1], STREAM));
-        launch_br(d_gates_, d_ks_, n);
-        HIP_CHECK(hipEventRecord((hipEvent_t)ev_[2], STREAM));
-        HIP_CHECK(hipEventSynchronize((hipEvent_t)ev_[2]));
+        launch_ks(d_gates, n, d_ks);
+        HIP_CHECK(hipEventRecord(ev_[1].get(), STREAM));
+        launch_br(d_gates, d_ks, n);
+        HIP_CHECK(hipEventRecord(ev_[2].get(), STREAM));
+        HIP_CHECK(hipEventSynchronize(ev_[2].get()));
         float br = 0;
-        HIP_CHECK(hipEventElapsedTime(&br, (hipEvent_t)ev_[1], (hipEvent_t)ev_[2]));
+        HIP_CHECK(hipEventElapsedTime(&br, ev_[1].get(), ev_[2].get()));
         br_sum += br;
     }
-    HIP_CHECK(hipEventRecord((hipEvent_t)ev_[0], STREAM));
-    HIP_CHECK(hipEventSynchronize((hipEvent_t)ev_[0]));
+    HIP_CHECK(hipEventRecord(ev_[0].get(), STREAM));
+    HIP_CHECK(hipEventSynchronize(ev_[0].get()));
     float tot = 0;
-    HIP_CHECK(hipEventElapsedTime(&tot, (hipEvent_t)ev_[3], (hipEvent_t)ev_[0]));
+    HIP_CHECK(hipEventElapsedTime(&tot, ev_[3].get(), ev_[0].get()));
     *br_ms = br_sum;
     *total_ms = tot;
 }

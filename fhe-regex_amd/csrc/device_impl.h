@@ -20,7 +20,7 @@ namespace fr {
     } while (0)
 
 // the stream of the current lane (inside Device methods)
-#define STREAM ((hipStream_t)cur_stream())
+#define STREAM (cur_stream())
 
 // a^-1 mod a prime p < 2^32 (Fermat)
 inline uint64_t mod_inverse(uint64_t a, uint64_t p) {

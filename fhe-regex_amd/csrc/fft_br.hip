@@ -1283,14 +1283,14 @@ void Device::init_fft() {
     });
 
     fft::Tables T(p_.N);
-    HIP_CHECK(hipMalloc(&d_ftw_, 16 * (size_t)T.M));
+    d_ftw_.alloc(2 * (size_t)T.M);  // (complex: two doubles each)
     std::vector<fft::c64> psi(2 * (size_t)p_.N);
     for (int k = 0; k < 2 * p_.N; ++k) psi[k] = fft::psi_pow(p_.N, k);
-    HIP_CHECK(hipMalloc(&d_fqt_, 16 * psi.size()));
-    HIP_CHECK(hipMalloc(&d_fleaf_, 2 * (size_t)T.M));
-    HIP_CHECK(hipMemcpy(d_ftw_, T.tw.data(), 16 * (size_t)T.M, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_fqt_, psi.data(), 16 * psi.size(), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_fleaf_, T.leaf.data(), 2 * (size_t)T.M, hipMemcpyHostToDevice));
+    d_fqt_.alloc(2 * psi.size());
+    d_fleaf_.alloc((size_t)T.M);
+    HIP_CHECK(hipMemcpy(d_ftw_.get(), T.tw.data(), 16 * (size_t)T.M, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_fqt_.get(), psi.data(), 16 * psi.size(), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_fleaf_.get(), T.leaf.data(), 2 * (size_t)T.M, hipMemcpyHostToDevice));
 }
 
 void Device::upload_fft_bsk(const std::vector<uint64_t>& bsk) {
@@ -1303,9 +1303,8 @@ void Device::upload_fft_bsk(const std::vector<uint64_t>& bsk) {
     // lane tl's element m is slot idx<LAST>(tl, m), so each load of a wave is 1 KB contiguous
     std::vector<fft::c64> lanes(four.size());
     for (int E : {16, 8, 4}) {
-        double*& dst = d_fbsk_[fbsk_index(E)];
-        (void)hipFree(dst);
-        dst = nullptr;
+        gpu::DevBuf<double>& dst = d_fbsk_[fbsk_index(E)];
+        dst.reset();
         if (!fft_supported(p_.k, N, E) || !fbsk_needed(E)) continue;
         const int T = M / E;
         int e = 0;
@@ -1317,14 +1316,13 @@ void Device::upload_fft_bsk(const std::vector<uint64_t>& bsk) {
             for (int m = 0; m < E; ++m) slot[(size_t)m * T + tl] = geo_base(tabs.LOG, e, LAST, tl, V) + (m << L);
         for (size_t pq = 0; pq < polys; ++pq)
             for (size_t q = 0; q < (size_t)M; ++q) lanes[pq * M + q] = four[pq * M + slot[q]];
-        HIP_CHECK(hipMalloc(&dst, 16 * lanes.size()));
-        HIP_CHECK(hipMemcpy(dst, lanes.data(), 16 * lanes.size(), hipMemcpyHostToDevice));
+        dst.alloc(2 * lanes.size());
+        HIP_CHECK(hipMemcpy(dst.get(), lanes.data(), 16 * lanes.size(), hipMemcpyHostToDevice));
     }
 }
 
-void Device::launch_br_fft(const DevGate* d_gates, const uint64_t* d_ks, size_t n, void* stream, void* ev_start,
-                           void* ev_stop) {
-    const hipStream_t s = (hipStream_t)stream;
+void Device::launch_br_fft(const DevGate* d_gates, const uint64_t* d_ks, size_t n, hipStream_t s, hipEvent_t ev_start,
+                           hipEvent_t ev_stop) {
     fft_dispatch(p_, [&](auto nc, auto kc) {
         constexpr int N = decltype(nc)::value, K = decltype(kc)::value;
         auto go = [&](auto ec, auto lat, auto bc) {
@@ -1334,9 +1332,10 @@ void Device::launch_br_fft(const DevGate* d_gates, const uint64_t* d_ks, size_t 
             if constexpr (fft_shape_ok<N, K, E>() && (B == 1 || K == 1))
                 hipExtLaunchKernelGGL(k_blind_rotate_fft<N, K, E, LAT, B>, dim3((unsigned)((n + B - 1) / B)),
                                       dim3(fbr_threads<N, K, E>()), (uint32_t)fbr_smem_bytes<N, K, E, LAT, B>(), s,
-                                      (hipEvent_t)ev_start, (hipEvent_t)ev_stop, 0, d_ks, p_.ks_stride(), p_.n, d_gates,
-                                      (int)n, (const double2*)d_fbsk_[fbsk_index(E)], (const double2*)d_ftw_,
-                                      (const double2*)d_fqt_, (const uint16_t*)d_fleaf_, d_arena_, p_.slot_stride());
+                                      ev_start, ev_stop, 0, d_ks, p_.ks_stride(), p_.n, d_gates, (int)n,
+                                      (const double2*)d_fbsk_[fbsk_index(E)].get(), (const double2*)d_ftw_.get(),
+                                      (const double2*)d_fqt_.get(), (const uint16_t*)d_fleaf_.get(), d_arena_.get(),
+                                      p_.slot_stride());
         };
         using I4 = std::integral_constant<int, 4>;
         using I8 = std::integral_constant<int, 8>;
@@ -1346,27 +1345,15 @@ void Device::launch_br_fft(const DevGate* d_gates, const uint64_t* d_ks, size_t 
         else if (n <= fft_pair_ && K == 1 && fft_dual_) {
             if constexpr (K == 1)
                 hipExtLaunchKernelGGL(k_blind_rotate_fft_dual<N>, dim3((unsigned)n), dim3(N / 8),
-                                      (uint32_t)fbr_dual_smem_bytes<N>(), s, (hipEvent_t)ev_start, (hipEvent_t)ev_stop, 0,
-                                      d_ks, p_.ks_stride(), p_.n, d_gates, (int)n,
-                                      (const double2*)d_fbsk_[fbsk_index(4)], (const double2*)d_ftw_,
-                                      (const double2*)d_fqt_, (const uint16_t*)d_fleaf_, d_arena_, p_.slot_stride());
+                                      (uint32_t)fbr_dual_smem_bytes<N>(), s, ev_start, ev_stop, 0, d_ks, p_.ks_stride(),
+                                      p_.n, d_gates, (int)n, (const double2*)d_fbsk_[fbsk_index(4)].get(),
+                                      (const double2*)d_ftw_.get(), (const double2*)d_fqt_.get(),
+                                      (const uint16_t*)d_fleaf_.get(), d_arena_.get(), p_.slot_stride());
         } else if (n <= fft_pair_) go(I4{}, std::true_type{}, std::integral_constant<int, 2>{});  // (k = 1)
         else if (fft_e_ == 4) go(I4{}, std::false_type{}, B1{});
         else go(I8{}, std::false_type{}, B1{});
     });
     HIP_CHECK(hipGetLastError());
-}
-
-void Device::free_fft() {
-    for (auto& b : d_fbsk_) {
-        (void)hipFree(b);
-        b = nullptr;
-    }
-    (void)hipFree(d_ftw_);
-    (void)hipFree(d_fqt_);
-    (void)hipFree(d_fleaf_);
-    d_ftw_ = d_fqt_ = nullptr;
-    d_fleaf_ = nullptr;
 }
 
 #endif  // !FR_BR_PAIR_TU

@@ -298,35 +298,19 @@ void Device::encrypt_to_slots(const ClientKey& ck, const uint8_t* msgs, size_t c
         if (slots[i] < 0 || (size_t)slots[i] >= next_slot_) throw Error(FR_ERR_INVALID, "device encryption: slot");
     std::vector<int64_t> noise;
     enc_noise(p_, key, first_block, count, noise);
-    const hipStream_t s = (hipStream_t)stream_;
-    uint64_t* d_sb = nullptr;
-    uint8_t* d_m = nullptr;
-    int64_t* d_n = nullptr;
-    int* d_sl = nullptr;
-    auto cleanup = [&] {
-        (void)hipFree(d_sb);
-        (void)hipFree(d_m);
-        (void)hipFree(d_n);
-        (void)hipFree(d_sl);
-    };
-    try {
-        HIP_CHECK(hipMalloc(&d_sb, 8 * (size_t)big));
-        HIP_CHECK(hipMalloc(&d_m, count));
-        HIP_CHECK(hipMalloc(&d_n, 8 * count));
-        HIP_CHECK(hipMalloc(&d_sl, 4 * count));
-        HIP_CHECK(hipMemcpyAsync(d_sb, ck.s_big.data(), 8 * (size_t)big, hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(d_m, msgs, count, hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(d_n, noise.data(), 8 * count, hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(d_sl, slots, 4 * count, hipMemcpyHostToDevice, s));
-        k_encrypt_blocks<<<(unsigned)count, 64, 0, s>>>(key, big, d_sb, d_m, d_n, first_block, d_sl, p_.slot_stride(),
-                                                       d_arena_);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipStreamSynchronize(s));
-    } catch (...) {
-        cleanup();
-        throw;
-    }
-    cleanup();
+    const hipStream_t s = cur().stream.get();
+    gpu::DevBuf<uint64_t> d_sb((size_t)big);
+    gpu::DevBuf<uint8_t> d_m(count);
+    gpu::DevBuf<int64_t> d_n(count);
+    gpu::DevBuf<int> d_sl(count);
+    HIP_CHECK(hipMemcpyAsync(d_sb.get(), ck.s_big.data(), 8 * (size_t)big, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_m.get(), msgs, count, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_n.get(), noise.data(), 8 * count, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_sl.get(), slots, 4 * count, hipMemcpyHostToDevice, s));
+    k_encrypt_blocks<<<(unsigned)count, 64, 0, s>>>(key, big, d_sb.get(), d_m.get(), d_n.get(), first_block, d_sl.get(),
+                                                   p_.slot_stride(), d_arena_.get());
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s));  // the temporaries go once the kernel has run
 }
 
 // Compact content (keys.h): the LWEs of `grid` blocks rebuilt in their arena slots, one
@@ -366,55 +350,32 @@ void Device::expand_to_slots(const RngKey& mask_key, uint64_t first_block, const
         for (; got < count; ++got) slots[got] = alloc_slot();
         // staging: the bodies [count] u64, then the slot list [count] int, in one H2D copy
         const size_t need = 12 * count;
-        if (need > xstage_cap_) {
-            size_t cap = xstage_cap_ ? xstage_cap_ : 12 * 4096;
-            while (cap < need) cap *= 2;
-            HIP_CHECK(hipStreamSynchronize(STREAM));  // no copy or kernel may still use the old buffers
-            (void)hipFree(d_xstage_);
-            d_xstage_ = nullptr;
-            xstage_cap_ = 0;
-            for (int i = 0; i < 2; ++i) {
-                if (h_xstage_[i]) (void)hipHostFree(h_xstage_[i]);
-                h_xstage_[i] = nullptr;
-                if (!xstage_ev_[i]) {
-                    hipEvent_t ev;
-                    HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-                    xstage_ev_[i] = ev;  // never recorded: complete
-                }
-            }
-            HIP_CHECK(hipMalloc(&d_xstage_, cap));
-            for (auto& h : h_xstage_) HIP_CHECK(hipHostMalloc(&h, cap));
-            xstage_cap_ = cap;
-        }
         const hipStream_t s = STREAM;
-        xstage_ ^= 1;
-        // the pinned buffer is rewritten only after its previous copy completed
-        HIP_CHECK(hipEventSynchronize((hipEvent_t)xstage_ev_[xstage_]));
-        uint8_t* h = h_xstage_[xstage_];
+        xstage_.reserve(need, 12 * 4096, s);
+        uint8_t* h = xstage_.acquire();
         std::memcpy(h, bodies, 8 * count);
         std::memcpy(h + 8 * count, slots, 4 * count);
-        HIP_CHECK(hipMemcpyAsync(d_xstage_, h, need, hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipEventRecord((hipEvent_t)xstage_ev_[xstage_], s));
-        // d_xstage_ is reused in stream order: the next call's copy runs after this kernel
-        hipEvent_t t0 = nullptr, t1 = nullptr;
+        xstage_.commit(need, s);
+        // the device side is reused in stream order: the next call's copy runs after this kernel
+        gpu::Event t0, t1;
         if (profiling_) {
-            t0 = (hipEvent_t)take_event();
-            t1 = (hipEvent_t)take_event();
-            HIP_CHECK(hipEventRecord(t0, s));
+            t0 = take_event();
+            t1 = take_event();
+            HIP_CHECK(hipEventRecord(t0.get(), s));
         }
-        k_expand_blocks<<<(unsigned)count, 256, 0, s>>>(mask_key, big, first_block, (const uint64_t*)d_xstage_,
-                                                       (const int*)(d_xstage_ + 8 * count), p_.slot_stride(),
-                                                       d_arena_);
+        const uint8_t* d = xstage_.device();
+        k_expand_blocks<<<(unsigned)count, 256, 0, s>>>(mask_key, big, first_block, (const uint64_t*)d,
+                                                       (const int*)(d + 8 * count), p_.slot_stride(), d_arena_.get());
         HIP_CHECK(hipGetLastError());
         if (profiling_) {
             // the probe's figure (fr_device_timers_content): a profiled call waits for its kernel
-            HIP_CHECK(hipEventRecord(t1, s));
-            HIP_CHECK(hipEventSynchronize(t1));
+            HIP_CHECK(hipEventRecord(t1.get(), s));
+            HIP_CHECK(hipEventSynchronize(t1.get()));
             float ms = 0;
-            HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
+            HIP_CHECK(hipEventElapsedTime(&ms, t0.get(), t1.get()));
             expand_ms_ = ms;
-            event_pool_.push_back(t0);
-            event_pool_.push_back(t1);
+            event_pool_.push_back(std::move(t0));
+            event_pool_.push_back(std::move(t1));
         }
     } catch (...) {
         for (size_t i = 0; i < got; ++i) free_slot(slots[i]);
@@ -431,18 +392,17 @@ static void need_device_keygen_point(const Params& p, const char* what) {
 void Device::build_fourier_bsk() {
     const int N = p_.N, M = N / 2, kp1 = p_.k + 1;
     const size_t bsk_polys = p_.bsk_ggsw() * kp1 * kp1;
-    const hipStream_t s = (hipStream_t)stream_;
+    const hipStream_t s = cur().stream.get();
     for (int E : {4, 8, 16}) {
-        double*& dst = d_fbsk_[fbsk_index(E)];
-        (void)hipFree(dst);
-        dst = nullptr;
-        if (fbsk_needed(E) && (E < 16 || p_.k == 1)) HIP_CHECK(hipMalloc(&dst, 16 * bsk_polys * M));
+        gpu::DevBuf<double>& dst = d_fbsk_[fbsk_index(E)];
+        dst.reset();
+        if (fbsk_needed(E) && (E < 16 || p_.k == 1)) dst.alloc(2 * bsk_polys * M);
     }
-    double2 *o4 = (double2*)d_fbsk_[0], *o8 = (double2*)d_fbsk_[1], *o16 = (double2*)d_fbsk_[2];
+    double2 *o4 = (double2*)d_fbsk_[0].get(), *o8 = (double2*)d_fbsk_[1].get(), *o16 = (double2*)d_fbsk_[2].get();
     if (N == 2048)
-        k_bsk_fourier<2048><<<(unsigned)bsk_polys, 256, 0, s>>>(d_tbsk_, (const double2*)d_ftw_, o4, o8, o16);
+        k_bsk_fourier<2048><<<(unsigned)bsk_polys, 256, 0, s>>>(d_tbsk_.get(), (const double2*)d_ftw_.get(), o4, o8, o16);
     else
-        k_bsk_fourier<1024><<<(unsigned)bsk_polys, 256, 0, s>>>(d_tbsk_, (const double2*)d_ftw_, o4, o8, o16);
+        k_bsk_fourier<1024><<<(unsigned)bsk_polys, 256, 0, s>>>(d_tbsk_.get(), (const double2*)d_ftw_.get(), o4, o8, o16);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -461,57 +421,39 @@ void Device::gen_server_key(const ClientKey& ck, const RngKey& key, const RngKey
     gen_bsk_noise_torus(p_, key, bsk_noise);
     const std::vector<uint8_t> msg = ggsw_messages(p_, ck);
 
-    uint64_t *d_ss = nullptr, *d_sb = nullptr;
-    int64_t* d_kn = nullptr;
-    int32_t* d_bn = nullptr;
-    uint8_t* d_msg = nullptr;
-    auto cleanup = [&] {
-        (void)hipFree(d_ss);
-        (void)hipFree(d_sb);
-        (void)hipFree(d_kn);
-        (void)hipFree(d_bn);
-        (void)hipFree(d_msg);
-    };
-    try {
-        const hipStream_t s = (hipStream_t)stream_;
-        HIP_CHECK(hipMalloc(&d_ss, 8 * ck.s_small.size()));
-        HIP_CHECK(hipMalloc(&d_sb, 8 * ck.s_big.size()));
-        HIP_CHECK(hipMalloc(&d_kn, 8 * ksk_noise.size()));
-        HIP_CHECK(hipMalloc(&d_bn, 4 * bsk_noise.size()));
-        HIP_CHECK(hipMalloc(&d_msg, msg.size()));
-        HIP_CHECK(hipMemcpyAsync(d_ss, ck.s_small.data(), 8 * ck.s_small.size(), hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(d_sb, ck.s_big.data(), 8 * ck.s_big.size(), hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(d_kn, ksk_noise.data(), 8 * ksk_noise.size(), hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(d_bn, bsk_noise.data(), 4 * bsk_noise.size(), hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(d_msg, msg.data(), msg.size(), hipMemcpyHostToDevice, s));
+    const hipStream_t s = cur().stream.get();
+    gpu::DevBuf<uint64_t> d_ss(ck.s_small.size()), d_sb(ck.s_big.size());
+    gpu::DevBuf<int64_t> d_kn(ksk_noise.size());
+    gpu::DevBuf<int32_t> d_bn(bsk_noise.size());
+    gpu::DevBuf<uint8_t> d_msg(msg.size());
+    HIP_CHECK(hipMemcpyAsync(d_ss.get(), ck.s_small.data(), 8 * ck.s_small.size(), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_sb.get(), ck.s_big.data(), 8 * ck.s_big.size(), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_kn.get(), ksk_noise.data(), 8 * ksk_noise.size(), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_bn.get(), bsk_noise.data(), 4 * bsk_noise.size(), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_msg.get(), msg.data(), msg.size(), hipMemcpyHostToDevice, s));
 
-        // KSK (torus) and its byte limbs
-        (void)hipFree(d_ksk_);
-        d_ksk_ = nullptr;
-        HIP_CHECK(hipMalloc(&d_ksk_, 8 * rows * (n + 1)));
-        k_gen_ksk<<<(unsigned)rows, 64, 0, s>>>(kkey, n, L, p_.ks_base_log, d_ss, d_sb, d_kn, d_ksk_);
-        HIP_CHECK(hipGetLastError());
-        build_ksk_limbs();
+    // KSK (torus) and its byte limbs
+    d_ksk_.alloc(rows * (n + 1));
+    k_gen_ksk<<<(unsigned)rows, 64, 0, s>>>(kkey, n, L, p_.ks_base_log, d_ss.get(), d_sb.get(), d_kn.get(), d_ksk_.get());
+    HIP_CHECK(hipGetLastError());
+    build_ksk_limbs();
 
-        // torus BSK, kept for export
-        (void)hipFree(d_tbsk_);
-        d_tbsk_ = nullptr;
-        HIP_CHECK(hipMalloc(&d_tbsk_, 8 * p_.bsk_len()));
-        const uint64_t gadget = 1ULL << (64 - p_.pbs_base_log);
-        const unsigned grid = (unsigned)(nw * kp1);
-        if (N == 2048 && !compact) k_gen_bsk<2048, false><<<grid, 256, 0, s>>>(kkey, p_.k, d_sb, d_msg, d_bn, gadget, d_tbsk_);
-        else if (N == 2048) k_gen_bsk<2048, true><<<grid, 256, 0, s>>>(kkey, p_.k, d_sb, d_msg, d_bn, gadget, d_tbsk_);
-        else if (!compact) k_gen_bsk<1024, false><<<grid, 256, 0, s>>>(kkey, p_.k, d_sb, d_msg, d_bn, gadget, d_tbsk_);
-        else k_gen_bsk<1024, true><<<grid, 256, 0, s>>>(kkey, p_.k, d_sb, d_msg, d_bn, gadget, d_tbsk_);
-        HIP_CHECK(hipGetLastError());
+    // torus BSK, kept for export
+    d_tbsk_.alloc(p_.bsk_len());
+    const uint64_t gadget = 1ULL << (64 - p_.pbs_base_log);
+    const unsigned grid = (unsigned)(nw * kp1);
+    const uint64_t* sb = d_sb.get();
+    const uint8_t* m = d_msg.get();
+    const int32_t* bn = d_bn.get();
+    uint64_t* tbsk = d_tbsk_.get();
+    if (N == 2048 && !compact) k_gen_bsk<2048, false><<<grid, 256, 0, s>>>(kkey, p_.k, sb, m, bn, gadget, tbsk);
+    else if (N == 2048) k_gen_bsk<2048, true><<<grid, 256, 0, s>>>(kkey, p_.k, sb, m, bn, gadget, tbsk);
+    else if (!compact) k_gen_bsk<1024, false><<<grid, 256, 0, s>>>(kkey, p_.k, sb, m, bn, gadget, tbsk);
+    else k_gen_bsk<1024, true><<<grid, 256, 0, s>>>(kkey, p_.k, sb, m, bn, gadget, tbsk);
+    HIP_CHECK(hipGetLastError());
 
-        build_fourier_bsk();
-        HIP_CHECK(hipStreamSynchronize(s));
-    } catch (...) {
-        cleanup();
-        throw;
-    }
-    cleanup();
+    build_fourier_bsk();
+    HIP_CHECK(hipStreamSynchronize(s));
 }
 
 void Device::load_server_key_compact(const RngKey& mask_key, const uint8_t* bodies) {
@@ -522,65 +464,49 @@ void Device::load_server_key_compact(const RngKey& mask_key, const uint8_t* bodi
     if (rows % 2 || N % 8) throw Error(FR_ERR_INVALID, "device load of a compact server key: alignment");
     // every queued launch of every lane that reads the old keys has finished before they go
     HIP_CHECK(hipDeviceSynchronize());
-    const hipStream_t s = (hipStream_t)stream_;
-    uint64_t* d_body = nullptr;
-    hipEvent_t ev[6] = {};
+    const hipStream_t s = cur().stream.get();
+    gpu::DevBuf<uint64_t> d_body(words);
+    gpu::Event ev[6];
     const bool timed = profiling_ != 0;
-    auto cleanup = [&] {
-        (void)hipFree(d_body);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    };
     auto mark = [&](int i) {
-        if (timed) HIP_CHECK(hipEventRecord(ev[i], s));
+        if (timed) HIP_CHECK(hipEventRecord(ev[i].get(), s));
     };
-    try {
-        if (timed)
-            for (hipEvent_t& e : ev) HIP_CHECK(hipEventCreate(&e));
-        (void)hipFree(d_ksk_);
-        d_ksk_ = nullptr;
-        HIP_CHECK(hipMalloc(&d_ksk_, 8 * rows * (n + 1)));
-        (void)hipFree(d_tbsk_);
-        d_tbsk_ = nullptr;
-        HIP_CHECK(hipMalloc(&d_tbsk_, 8 * p_.bsk_len()));
-        HIP_CHECK(hipMalloc(&d_body, 8 * words));
-        mark(0);
-        HIP_CHECK(hipMemcpyAsync(d_body, bodies, 8 * words, hipMemcpyHostToDevice, s));
-        mark(1);
-        k_expand_ksk<<<(unsigned)rows, 64, 0, s>>>(mask_key, n, d_body, d_ksk_);
-        HIP_CHECK(hipGetLastError());
-        mark(2);
-        if (N == 2048) k_expand_bsk<2048><<<(unsigned)brows, 256, 0, s>>>(mask_key, p_.k, d_body + rows, d_tbsk_);
-        else k_expand_bsk<1024><<<(unsigned)brows, 256, 0, s>>>(mask_key, p_.k, d_body + rows, d_tbsk_);
-        HIP_CHECK(hipGetLastError());
-        mark(3);
-        build_ksk_limbs();
-        mark(4);
-        build_fourier_bsk();
-        mark(5);
-        HIP_CHECK(hipStreamSynchronize(s));
-        if (timed)
-            for (int i = 0; i < 5; ++i) {
-                float ms = 0;
-                HIP_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-                key_load_ms_[i] = ms;
-            }
-    } catch (...) {
-        cleanup();
-        throw;
-    }
-    cleanup();
+    if (timed)
+        for (gpu::Event& e : ev) e = gpu::Event(hipEventDefault);
+    d_ksk_.alloc(rows * (n + 1));
+    d_tbsk_.alloc(p_.bsk_len());
+    mark(0);
+    HIP_CHECK(hipMemcpyAsync(d_body.get(), bodies, 8 * words, hipMemcpyHostToDevice, s));
+    mark(1);
+    k_expand_ksk<<<(unsigned)rows, 64, 0, s>>>(mask_key, n, d_body.get(), d_ksk_.get());
+    HIP_CHECK(hipGetLastError());
+    mark(2);
+    if (N == 2048) k_expand_bsk<2048><<<(unsigned)brows, 256, 0, s>>>(mask_key, p_.k, d_body.get() + rows, d_tbsk_.get());
+    else k_expand_bsk<1024><<<(unsigned)brows, 256, 0, s>>>(mask_key, p_.k, d_body.get() + rows, d_tbsk_.get());
+    HIP_CHECK(hipGetLastError());
+    mark(3);
+    build_ksk_limbs();
+    mark(4);
+    build_fourier_bsk();
+    mark(5);
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (timed)
+        for (int i = 0; i < 5; ++i) {
+            float ms = 0;
+            HIP_CHECK(hipEventElapsedTime(&ms, ev[i].get(), ev[i + 1].get()));
+            key_load_ms_[i] = ms;
+        }
 }
 
 void Device::download_server_key(uint64_t* ksk, size_t ksk_len, uint64_t* bsk, size_t bsk_len) {
     if (!d_ksk_ || !d_tbsk_) throw Error(FR_ERR_NO_KEY, "no device-generated server key");
     if (ksk) {
         if (ksk_len != (size_t)p_.big() * p_.ks_level * (p_.n + 1)) throw Error(FR_ERR_INVALID, "ksk size");
-        HIP_CHECK(hipMemcpy(ksk, d_ksk_, 8 * ksk_len, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(ksk, d_ksk_.get(), 8 * ksk_len, hipMemcpyDeviceToHost));
     }
     if (bsk) {
         if (bsk_len != p_.bsk_len()) throw Error(FR_ERR_INVALID, "bsk size");
-        HIP_CHECK(hipMemcpy(bsk, d_tbsk_, 8 * bsk_len, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(bsk, d_tbsk_.get(), 8 * bsk_len, hipMemcpyDeviceToHost));
     }
 }
 

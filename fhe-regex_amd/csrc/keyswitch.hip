@@ -532,46 +532,43 @@ void Device::init_ks() {
 }
 
 void Device::ensure_digits(size_t rows) {
-    if (rows <= dig_cap_) return;
-    size_t cap = dig_cap_ ? dig_cap_ : 1024;
-    while (cap < rows) cap *= 2;
+    const size_t row = (size_t)p_.big() * p_.ks_level;
+    if (rows * row <= cur().dig.size()) return;
     HIP_CHECK(hipStreamSynchronize(STREAM));
-    (void)hipFree(d_dig_);
-    HIP_CHECK(hipMalloc(&d_dig_, cap * (size_t)p_.big() * p_.ks_level));
-    dig_cap_ = cap;
+    cur().dig.grow(rows * row, 1024 * row);
 }
 
 // byte-limb form of the KSK for the MFMA keyswitch
 void Device::build_ksk_limbs() {
     const int KD = p_.big() * p_.ks_level, ncols = p_.n + 1;
     const int nlc = ((ncols * 8 + 127) / 128) * 128;  // whole 4-wave column groups
-    (void)hipFree(d_kl_);
-    d_kl_ = nullptr;
-    HIP_CHECK(hipMalloc(&d_kl_, (size_t)nlc * KD));
-    HIP_CHECK(hipMemsetAsync(d_kl_, 0, (size_t)nlc * KD, STREAM));
-    k_ksk_limbs<<<dim3((unsigned)((KD + 255) / 256), (unsigned)(nlc / 8)), 256, 0, STREAM>>>(d_ksk_, KD, ncols, nlc,
-                                                                                          d_kl_);
+    d_kl_.alloc((size_t)nlc * KD);
+    HIP_CHECK(hipMemsetAsync(d_kl_.get(), 0, (size_t)nlc * KD, STREAM));
+    k_ksk_limbs<<<dim3((unsigned)((KD + 255) / 256), (unsigned)(nlc / 8)), 256, 0, STREAM>>>(d_ksk_.get(), KD, ncols, nlc,
+                                                                                          d_kl_.get());
     HIP_CHECK(hipGetLastError());
     kl_cols_ = nlc;
 }
 
-void Device::launch_ks(const DevGate* d_gates, size_t n, uint64_t* d_ks, void* ev_start, void* ev_stop) {
-    const hipEvent_t e0 = (hipEvent_t)ev_start, e1 = (hipEvent_t)ev_stop;
+void Device::launch_ks(const DevGate* d_gates, size_t n, uint64_t* d_ks, hipEvent_t e0, hipEvent_t e1) {
+    const uint64_t* arena = d_arena_.get();
+    const int* d_cmap = cur().cmap.device();
     if (ks_mfma_) {
         const int KD = p_.big() * p_.ks_level;
         if (KD % 256) throw Error(FR_ERR_INVALID, "MFMA keyswitch needs kN*ks_level % 256 == 0");
         const int MR = n >= ks_mr4_min_ ? 4 : 1;  // row tiles per wave
         const size_t bp = (n + 32 * MR - 1) / (32 * MR) * (32 * MR);
         ensure_digits(bp);
+        int8_t* d_dig = cur().dig.get();
         if (KD % 16) throw Error(FR_ERR_INVALID, "MFMA keyswitch: digit rows must be whole 16-byte vectors");
         if (ks_dig16_ && p_.big() % 16 == 0)
             hipExtLaunchKernelGGL(k_ks_digits16<3, 5>, dim3((unsigned)bp), dim3(128), 0, STREAM, e0, nullptr, 0, d_gates,
-                                  (int)n, (const uint64_t*)d_arena_, p_.slot_stride(), (const int*)d_cmap_, p_.big(),
-                                  d_dig_, d_ks, p_.n, p_.ks_stride());
+                                  (int)n, arena, p_.slot_stride(), d_cmap, p_.big(),
+                                  d_dig, d_ks, p_.n, p_.ks_stride());
         else
             hipExtLaunchKernelGGL(k_ks_digits<3, 5>, dim3(8, (unsigned)bp), dim3(256), 0, STREAM, e0, nullptr, 0, d_gates,
-                                  (int)n, (const uint64_t*)d_arena_, p_.slot_stride(), (const int*)d_cmap_, p_.big(),
-                                  d_dig_, d_ks, p_.n, p_.ks_stride());
+                                  (int)n, arena, p_.slot_stride(), d_cmap, p_.big(),
+                                  d_dig, d_ks, p_.n, p_.ks_stride());
         HIP_CHECK(hipGetLastError());
         // column tiles per wave: 1 (FR_KS_MC=2 shares each digit fragment between two; with
         // fragment-ordered operands that no longer pays: 512 gates 121 -> 103 us at 1)
@@ -589,19 +586,19 @@ void Device::launch_ks(const DevGate* d_gates, size_t n, uint64_t* d_ks, void* e
         const dim3 grid((unsigned)ks_grid_blocks(GX, GY, GZ, ks_xcd_));
         if (MR == 4 && MC == 1 && ks_lds_)
             hipExtLaunchKernelGGL(k_ks_glds<FR_KS_SK, FR_KS_NB>, grid, dim3(256), 0, STREAM, nullptr, e1, 0,
-                                  (const int8_t*)d_dig_, (const int8_t*)d_kl_, (int)n, KD, p_.n + 1, kl_cols_,
+                                  (const int8_t*)d_dig, (const int8_t*)d_kl_.get(), (int)n, KD, p_.n + 1, kl_cols_,
                                   (unsigned long long*)d_ks, p_.ks_stride(), GX, GY, GZ, ks_xcd_);
         else if (MR == 4 && MC == 2)
-            hipExtLaunchKernelGGL(k_ks_mfma<4, 2>, grid, dim3(256), 0, STREAM, nullptr, e1, 0, (const int8_t*)d_dig_,
-                                  (const int8_t*)d_kl_, (int)n, KD, p_.n + 1, kl_cols_, (unsigned long long*)d_ks,
+            hipExtLaunchKernelGGL(k_ks_mfma<4, 2>, grid, dim3(256), 0, STREAM, nullptr, e1, 0, (const int8_t*)d_dig,
+                                  (const int8_t*)d_kl_.get(), (int)n, KD, p_.n + 1, kl_cols_, (unsigned long long*)d_ks,
                                   p_.ks_stride(), GX, GY, GZ, ks_xcd_);
         else if (MR == 4)
-            hipExtLaunchKernelGGL(k_ks_mfma<4, 1>, grid, dim3(256), 0, STREAM, nullptr, e1, 0, (const int8_t*)d_dig_,
-                                  (const int8_t*)d_kl_, (int)n, KD, p_.n + 1, kl_cols_, (unsigned long long*)d_ks,
+            hipExtLaunchKernelGGL(k_ks_mfma<4, 1>, grid, dim3(256), 0, STREAM, nullptr, e1, 0, (const int8_t*)d_dig,
+                                  (const int8_t*)d_kl_.get(), (int)n, KD, p_.n + 1, kl_cols_, (unsigned long long*)d_ks,
                                   p_.ks_stride(), GX, GY, GZ, ks_xcd_);
         else
-            hipExtLaunchKernelGGL(k_ks_mfma<1, 1>, grid, dim3(256), 0, STREAM, nullptr, e1, 0, (const int8_t*)d_dig_,
-                                  (const int8_t*)d_kl_, (int)n, KD, p_.n + 1, kl_cols_, (unsigned long long*)d_ks,
+            hipExtLaunchKernelGGL(k_ks_mfma<1, 1>, grid, dim3(256), 0, STREAM, nullptr, e1, 0, (const int8_t*)d_dig,
+                                  (const int8_t*)d_kl_.get(), (int)n, KD, p_.n + 1, kl_cols_, (unsigned long long*)d_ks,
                                   p_.ks_stride(), GX, GY, GZ, ks_xcd_);
         HIP_CHECK(hipGetLastError());
         return;
@@ -617,13 +614,13 @@ void Device::launch_ks(const DevGate* d_gates, size_t n, uint64_t* d_ks, void* e
     if (splits > 1) HIP_CHECK(hipMemsetAsync(d_ks, 0, (size_t)8 * p_.ks_stride() * n, STREAM));
     dim3 grid((unsigned)btiles, (unsigned)ctiles, (unsigned)splits);
     hipExtLaunchKernelGGL(k_lincomb_keyswitch<3, 5>, grid, dim3(256), 0, STREAM, e0, e1, 0, d_gates, (int)n,
-                          (const uint64_t*)d_arena_, p_.slot_stride(), (const int*)d_cmap_, (const uint64_t*)d_ksk_, p_.n,
+                          arena, p_.slot_stride(), d_cmap, (const uint64_t*)d_ksk_.get(), p_.n,
                           p_.big(), per, (unsigned long long*)d_ks, p_.ks_stride());
     HIP_CHECK(hipGetLastError());
 }
 
 void Device::run_linear(const DevGate& g) {
-    k_linear<<<(p_.lwe_len() + 255) / 256, 256, 0, STREAM>>>(g, d_arena_, p_.slot_stride(), p_.lwe_len());
+    k_linear<<<(p_.lwe_len() + 255) / 256, 256, 0, STREAM>>>(g, d_arena_.get(), p_.slot_stride(), p_.lwe_len());
     HIP_CHECK(hipGetLastError());
 }
 

@@ -710,44 +710,37 @@ void Device::init_rns() {
     std::vector<uint32_t> tw(2 * (size_t)p_.N);
     for (int q = 0; q < 2; ++q)
         for (int i = 0; i < p_.N; ++i) tw[(size_t)q * p_.N + i] = (uint32_t)(((uint64_t)T.zeta[q][i] << 32) % rns::prime(q));
-    HIP_CHECK(hipMalloc(&d_tw_, 4 * tw.size()));
-    HIP_CHECK(hipMemcpy(d_tw_, tw.data(), 4 * tw.size(), hipMemcpyHostToDevice));
-}
-
-void Device::free_rns() {
-    (void)hipFree(d_bsk_);
-    (void)hipFree(d_tw_);
+    d_tw_.alloc(tw.size());
+    HIP_CHECK(hipMemcpy(d_tw_.get(), tw.data(), 4 * tw.size(), hipMemcpyHostToDevice));
 }
 
 // BSK coefficients mod Q -> d_bsk_ (NTT domain)
 void Device::upload_rns_bsk(const std::vector<uint64_t>& bsk) {
-    uint64_t* coef = nullptr;
-    HIP_CHECK(hipMalloc(&coef, 8 * bsk.size()));
-    HIP_CHECK(hipMemcpy(coef, bsk.data(), 8 * bsk.size(), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMalloc(&d_bsk_, 4 * 2 * bsk.size()));  // two u32 residues per coefficient
+    gpu::DevBuf<uint64_t> coef(bsk.size());
+    HIP_CHECK(hipMemcpy(coef.get(), bsk.data(), 8 * bsk.size(), hipMemcpyHostToDevice));
+    d_bsk_.alloc(2 * bsk.size());  // two u32 residues per coefficient
     // 1/N in Montgomery form per prime
     uint32_t ninv_r[2];
     for (int q = 0; q < 2; ++q) ninv_r[q] = (uint32_t)((mod_inverse((uint64_t)p_.N, rns::prime(q)) << 32) % rns::prime(q));
     const int blocks = (int)p_.bsk_ggsw() * (p_.k + 1);
     dispatch(p_, e_, [&](auto n_, auto k_, auto e_c) {
         constexpr int N = decltype(n_)::value, K = decltype(k_)::value, E = decltype(e_c)::value;
-        k_bsk_to_ntt<N, K, E><<<blocks, br_threads<N, K, E>(), br_smem_bytes<N, K, E>(), STREAM>>>(coef, d_tw_, ninv_r[0],
-                                                                                                    ninv_r[1], d_bsk_);
+        k_bsk_to_ntt<N, K, E><<<blocks, br_threads<N, K, E>(), br_smem_bytes<N, K, E>(), STREAM>>>(coef.get(), d_tw_.get(), ninv_r[0],
+                                                                                                    ninv_r[1], d_bsk_.get());
     });
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(STREAM));
-    HIP_CHECK(hipFree(coef));
 }
 
-void Device::launch_br_rns(const DevGate* d_gates, const uint64_t* d_ks, size_t n, void* ev_start, void* ev_stop) {
+void Device::launch_br_rns(const DevGate* d_gates, const uint64_t* d_ks, size_t n, hipEvent_t ev_start, hipEvent_t ev_stop) {
     // small levels (at most one bootstrap per CU): more lanes per bootstrap for latency
     const int E = n <= small_batch_ ? e_small_ : e_;
     dispatch(p_, E, [&](auto n_, auto k_, auto e_c) {
         constexpr int N = decltype(n_)::value, K = decltype(k_)::value, E = decltype(e_c)::value;
         hipExtLaunchKernelGGL(k_blind_rotate<N, K, E>, dim3((unsigned)n), dim3(br_threads<N, K, E>()),
-                              (uint32_t)br_smem_bytes<N, K, E>(), STREAM, (hipEvent_t)ev_start, (hipEvent_t)ev_stop, 0,
-                              d_ks, p_.ks_stride(), p_.n, d_gates, (const uint32_t*)d_bsk_, (const uint32_t*)d_tw_,
-                              d_arena_, p_.slot_stride());
+                              (uint32_t)br_smem_bytes<N, K, E>(), STREAM, ev_start, ev_stop, 0, d_ks, p_.ks_stride(),
+                              p_.n, d_gates, (const uint32_t*)d_bsk_.get(), (const uint32_t*)d_tw_.get(), d_arena_.get(),
+                              p_.slot_stride());
     });
     HIP_CHECK(hipGetLastError());
 }
@@ -755,12 +748,9 @@ void Device::launch_br_rns(const DevGate* d_gates, const uint64_t* d_ks, size_t 
 void Device::ring_mul_host(const uint64_t* a, const uint64_t* b, size_t count, uint64_t* out) {
     if (p_.ring != FR_RING_RNS) throw Error(FR_ERR_INVALID, "ring_mul test hook: RNS ring only");
     const int N = p_.N;
-    uint64_t *da, *db, *dout;
-    HIP_CHECK(hipMalloc(&da, 8 * count * N));
-    HIP_CHECK(hipMalloc(&db, 8 * count * N));
-    HIP_CHECK(hipMalloc(&dout, 8 * count * N));
-    HIP_CHECK(hipMemcpy(da, a, 8 * count * N, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(db, b, 8 * count * N, hipMemcpyHostToDevice));
+    gpu::DevBuf<uint64_t> da(count * N), db(count * N), dout(count * N);
+    HIP_CHECK(hipMemcpy(da.get(), a, 8 * count * N, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(db.get(), b, 8 * count * N, hipMemcpyHostToDevice));
     // R^2 / N mod p (Montgomery: turns mont(a, b) = ab/R into ab/N)
     uint32_t r2n[2];
     for (int q = 0; q < 2; ++q) {
@@ -772,14 +762,11 @@ void Device::ring_mul_host(const uint64_t* a, const uint64_t* b, size_t count, u
         (void)k_;
         const size_t sm = 4 * (4 * (size_t)NttGeo<NN, E>::NP + 2 * (size_t)NN);
         HIP_CHECK(hipFuncSetAttribute((const void*)k_ring_mul<NN, E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
-        k_ring_mul<NN, E><<<(unsigned)count, 4 * (NN / E), sm, STREAM>>>(da, db, d_tw_, r2n[0], r2n[1], dout);
+        k_ring_mul<NN, E><<<(unsigned)count, 4 * (NN / E), sm, STREAM>>>(da.get(), db.get(), d_tw_.get(), r2n[0], r2n[1], dout.get());
     });
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(STREAM));
-    HIP_CHECK(hipMemcpy(out, dout, 8 * count * N, hipMemcpyDeviceToHost));
-    (void)hipFree(da);
-    (void)hipFree(db);
-    (void)hipFree(dout);
+    HIP_CHECK(hipMemcpy(out, dout.get(), 8 * count * N, hipMemcpyDeviceToHost));
 }
 
 }  // namespace fr
