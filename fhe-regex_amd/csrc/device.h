@@ -234,16 +234,16 @@ class Device {
     gpu::DevBuf<uint32_t> d_tw_;   // Montgomery zeta per prime [2][N]
     // FR_RING_FFT: Fourier BSK [w][r][c][m][lane] (complex f64, scaled by 1/M), twiddles,
     // psi quadrant table, leaf exponents (fft.h)
-    int fft_e_ = 4;           // complex points per lane in the throughput shape (4, 8 or 16)
+    int fft_e_ = 4;           // complex points per lane in the throughput shape (4 or 8)
     size_t fft_small_ = 256;  // launches of at most this many bootstraps use the latency shape
     // k = 1: larger launches up to this many use the pair shape (2 per workgroup; every size
     // by default: profiles/r03/ab_pair_shape.log)
     size_t fft_pair_ = SIZE_MAX;
     bool fft_dual_ = false;  // FR_FFT_DUAL=1: the dual shape instead of the pair (experiment)
     // Fourier BSK, one copy per lane geometry in use: [0] E = 4 (latency shape, always),
-    // [1] E = 8, [2] E = 16 (the throughput shape's when fft_e_ is that)
-    gpu::DevBuf<double> d_fbsk_[3];
-    static int fbsk_index(int E) { return E == 4 ? 0 : E == 8 ? 1 : 2; }
+    // [1] E = 8 (the throughput shape's when fft_e_ is that)
+    gpu::DevBuf<double> d_fbsk_[2];
+    static int fbsk_index(int E) { return E == 4 ? 0 : 1; }
     bool fbsk_needed(int E) const { return E == 4 || E == fft_e_; }
     gpu::DevBuf<double> d_ftw_;
     gpu::DevBuf<double> d_fqt_;   // psi^k, k < 2N

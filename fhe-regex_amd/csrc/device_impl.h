@@ -33,6 +33,24 @@ inline uint64_t mod_inverse(uint64_t a, uint64_t p) {
     return inv;
 }
 
+// FR_BR_TIMING (debug builds only, tools/build_variant.sh): wave 0 of workgroup 0 of a
+// blind-rotation kernel accumulates s_memtime deltas of the step's segments in its
+// tseg[] / tlast and prints them at the end.  The default build expands it to nothing.
+#ifdef FR_BR_TIMING
+#define BR_STAMP(k)                                             \
+    do {                                                        \
+        __builtin_amdgcn_sched_barrier(0);                      \
+        const uint64_t now_ = __builtin_amdgcn_s_memtime();     \
+        tseg[k] += now_ - tlast;                                \
+        tlast = now_;                                           \
+        __builtin_amdgcn_sched_barrier(0);                      \
+    } while (0)
+#else
+#define BR_STAMP(k) \
+    do {            \
+    } while (0)
+#endif
+
 // Multi-value w-step terms of one LUT: w_f = sum_t d_t X^pos_t with
 // d = f(m) - f(m-1) at m*box - box/2 and -(f(0) + f(15)) at N - box/2.
 // Packed as pos | (d + 128) << 16; returns the count.

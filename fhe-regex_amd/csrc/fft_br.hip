@@ -33,23 +33,6 @@ using FGeo = NttGeo<M, E, 3, fft_layout_variant(ilog2c(M), ilog2c(E))>;
 template <int M, int E>
 constexpr int FV = fft_layout_variant(ilog2c(M), ilog2c(E));
 
-// FR_BR_TIMING (debug builds only): wave 0 of workgroup 0 accumulates
-// s_memtime deltas of the step segments and prints them at the end.
-#ifdef FR_BR_TIMING
-#define FBR_STAMP(k)                                            \
-    do {                                                        \
-        __builtin_amdgcn_sched_barrier(0);                      \
-        const uint64_t now_ = __builtin_amdgcn_s_memtime();     \
-        tseg[k] += now_ - tlast;                                \
-        tlast = now_;                                           \
-        __builtin_amdgcn_sched_barrier(0);                      \
-    } while (0)
-#else
-#define FBR_STAMP(k) \
-    do {             \
-    } while (0)
-#endif
-
 __device__ __forceinline__ void cfwd(double2& x, double2& y, double2 c) { fft::fwd_bf(x.x, x.y, y.x, y.y, c.x, c.y); }
 __device__ __forceinline__ void cinv(double2& u, double2& v, double2 c) { fft::inv_bf(u.x, u.y, v.x, v.y, c.x, c.y); }
 
@@ -71,60 +54,59 @@ __device__ __forceinline__ double2 fmul_i(double2 c) { return make_double2(-c.y,
 __device__ __forceinline__ void cinv_r4(double2 (&x)[4], double2 c, double2 ca, double2 cc) {
     fft::inv_r4(x[0].x, x[0].y, x[1].x, x[1].y, x[2].x, x[2].y, x[3].x, x[3].y, c.x, c.y, ca.x, ca.y, cc.x, cc.y);
 }
+// The radix-2 butterflies of phase p: fn(s, m, dm) for each of its stages s (REV: last
+// stage first, the inverse's order) and each element m that pairs with m + dm.
+template <class G, int E, int p, bool REV, class F>
+__device__ __forceinline__ void for_butterflies(F&& fn) {
+#pragma unroll
+    for (int i = 0; i < G::s_end(p) - G::s_begin(p); ++i) {
+        const int s = REV ? G::s_end(p) - 1 - i : G::s_begin(p) + i;
+        const int dm = 1 << (G::LOG - 1 - s - G::lo(p));
+#pragma unroll
+        for (int m = 0; m < E; ++m) {
+            if (m & dm) continue;
+            fn(s, m, dm);
+        }
+    }
+}
+// stage s's entry of a twiddle table for element m of the lane whose layout-p base is b
+template <class G, int p>
+__device__ __forceinline__ double2 ftw_at(const double2* tw, int b, int s, int m) {
+    return (tw + (b >> (G::LOG - s)))[(1 << s) + (G::template moff<p>(m) >> (G::LOG - s))];
+}
 // the radix-4 twiddles (c, ca) of phase p for this lane from the LDS table
 template <int M, int E, int p>
 __device__ __forceinline__ void ftw_r4(const double2* tw, int tl, double2& c, double2& ca) {
     using G = FGeo<M, E>;
     constexpr int s0 = G::s_begin(p), s1 = s0 + 1;
     const int b = G::template base<p>(tl);
-    c = (tw + (b >> (G::LOG - s0)))[(1 << s0) + (G::template moff<p>(0) >> (G::LOG - s0))];
-    ca = (tw + (b >> (G::LOG - s1)))[(1 << s1) + (G::template moff<p>(0) >> (G::LOG - s1))];
+    c = ftw_at<G, p>(tw, b, s0, 0);
+    ca = ftw_at<G, p>(tw, b, s1, 0);
 }
 
 template <int M, int E, int p>
 __device__ __forceinline__ void ffwd_phase(double2 (&x)[E], const double2* tw, int tl) {
     using G = FGeo<M, E>;
     const int b = G::template base<p>(tl);
-#pragma unroll
-    for (int s = G::s_begin(p); s < G::s_end(p); ++s) {
-        const int dm = 1 << (G::LOG - 1 - s - G::lo(p));
-        const double2* zs = tw + (b >> (G::LOG - s));
-#pragma unroll
-        for (int m = 0; m < E; ++m) {
-            if (m & dm) continue;
-            cfwd(x[m], x[m + dm], zs[(1 << s) + (G::template moff<p>(m) >> (G::LOG - s))]);
-        }
-    }
-}
-template <int M, int E, int p>
-__device__ __forceinline__ void finv_phase(double2 (&x)[E], const double2* tw, int tl);
-// (radix-4 phases: cc = c ca from the product table twc, indexed like c)
-template <int M, int E, int p>
-__device__ __forceinline__ void finv_phase_lds(double2 (&x)[E], const double2* tw, const double2* twc, int tl) {
-    if constexpr (fradix4<M, E>()) {
-        using G = FGeo<M, E>;
-        constexpr int s0 = G::s_begin(p);
-        double2 c, ca;
-        ftw_r4<M, E, p>(tw, tl, c, ca);
-        const double2 cc = (twc + (G::template base<p>(tl) >> (G::LOG - s0)))[(1 << s0) + (G::template moff<p>(0) >> (G::LOG - s0))];
-        cinv_r4(x, c, ca, cc);
-    } else {
-        finv_phase<M, E, p>(x, tw, tl);
-    }
+    for_butterflies<G, E, p, false>([&](int s, int m, int dm) { cfwd(x[m], x[m + dm], ftw_at<G, p>(tw, b, s, m)); });
 }
 template <int M, int E, int p>
 __device__ __forceinline__ void finv_phase(double2 (&x)[E], const double2* tw, int tl) {
     using G = FGeo<M, E>;
     const int b = G::template base<p>(tl);
-#pragma unroll
-    for (int s = G::s_end(p) - 1; s >= G::s_begin(p); --s) {
-        const int dm = 1 << (G::LOG - 1 - s - G::lo(p));
-        const double2* zs = tw + (b >> (G::LOG - s));
-#pragma unroll
-        for (int m = 0; m < E; ++m) {
-            if (m & dm) continue;
-            cinv(x[m], x[m + dm], zs[(1 << s) + (G::template moff<p>(m) >> (G::LOG - s))]);
-        }
+    for_butterflies<G, E, p, true>([&](int s, int m, int dm) { cinv(x[m], x[m + dm], ftw_at<G, p>(tw, b, s, m)); });
+}
+// (radix-4 phases: cc = c ca from the product table twc, indexed like c)
+template <int M, int E, int p>
+__device__ __forceinline__ void finv_phase_lds(double2 (&x)[E], const double2* tw, const double2* twc, int tl) {
+    if constexpr (fradix4<M, E>()) {
+        using G = FGeo<M, E>;
+        double2 c, ca;
+        ftw_r4<M, E, p>(tw, tl, c, ca);
+        const double2 cc = ftw_at<G, p>(twc, G::template base<p>(tl), G::s_begin(p), 0);
+        cinv_r4(x, c, ca, cc);
+    } else {
+        finv_phase<M, E, p>(x, tw, tl);
     }
 }
 
@@ -238,16 +220,7 @@ __device__ __forceinline__ void ftw_load_phase(FTwr<M, E>& twr, const double2* t
         return;
     }
     const int b = G::template base<p>(tl);
-#pragma unroll
-    for (int s = G::s_begin(p); s < G::s_end(p); ++s) {
-        const int dm = 1 << (G::LOG - 1 - s - G::lo(p));
-        const double2* zs = tw + (b >> (G::LOG - s));
-#pragma unroll
-        for (int m = 0; m < E; ++m) {
-            if (m & dm) continue;
-            twr.v[ftw_index<M, E>(s, m)] = zs[(1 << s) + (G::template moff<p>(m) >> (G::LOG - s))];
-        }
-    }
+    for_butterflies<G, E, p, false>([&](int s, int m, int) { twr.v[ftw_index<M, E>(s, m)] = ftw_at<G, p>(tw, b, s, m); });
     if constexpr (p + 1 < G::NPH) ftw_load_phase<M, E, p + 1, UNI>(twr, tw, tl);
 }
 template <int M, int E, int p>
@@ -261,15 +234,7 @@ __device__ __forceinline__ void ffwd_phase_r(double2 (&x)[E], const FTwr<M, E>& 
         cfwd(x[2], x[3], fmul_i(ca));
         return;
     }
-#pragma unroll
-    for (int s = G::s_begin(p); s < G::s_end(p); ++s) {
-        const int dm = 1 << (G::LOG - 1 - s - G::lo(p));
-#pragma unroll
-        for (int m = 0; m < E; ++m) {
-            if (m & dm) continue;
-            cfwd(x[m], x[m + dm], twr.v[ftw_index<M, E>(s, m)]);
-        }
-    }
+    for_butterflies<G, E, p, false>([&](int s, int m, int dm) { cfwd(x[m], x[m + dm], twr.v[ftw_index<M, E>(s, m)]); });
 }
 template <int M, int E, int p>
 __device__ __forceinline__ void finv_phase_r(double2 (&x)[E], const FTwr<M, E>& twr) {
@@ -278,30 +243,9 @@ __device__ __forceinline__ void finv_phase_r(double2 (&x)[E], const FTwr<M, E>& 
         cinv_r4(x, twr.v[3 * p], twr.v[3 * p + 1], twr.v[3 * p + 2]);
         return;
     }
-#pragma unroll
-    for (int s = G::s_end(p) - 1; s >= G::s_begin(p); --s) {
-        const int dm = 1 << (G::LOG - 1 - s - G::lo(p));
-#pragma unroll
-        for (int m = 0; m < E; ++m) {
-            if (m & dm) continue;
-            cinv(x[m], x[m + dm], twr.v[ftw_index<M, E>(s, m)]);
-        }
-    }
+    for_butterflies<G, E, p, true>([&](int s, int m, int dm) { cinv(x[m], x[m + dm], twr.v[ftw_index<M, E>(s, m)]); });
 }
 
-// exchange between phase layouts stays inside each wave (see rns_br.hip)
-template <int M, int E, int PF, int PT>
-constexpr bool fwave_local() {
-    using G = FGeo<M, E>;
-    for (int b = 6; (1 << b) < G::T; ++b)
-        if (G::lane_bit(PF, b) != G::lane_bit(PT, b)) return false;
-    return true;
-}
-__device__ __forceinline__ void fwave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 // Register exchanges.  An exchange between adjacent layouts transposes the lane's
 // element bits with the lane bits that carry the arriving index bits.  When element
 // bit j leaves through the same lane bit k that brings in the next layout's element
@@ -423,23 +367,13 @@ __device__ __forceinline__ void fexchange(double2 (&x)[B][E], double2* row, int 
         for (int b = 0; b < B; ++b)
 #pragma unroll
             for (int m = 0; m < E; ++m) rf[b * BS + G::template at<X>(G::template moff<PF>(m))] = x[b][m];
-        if constexpr (fwave_local<M, E, PF, PT>() && G::wave_top(PF)) fwave_sync();
+        if constexpr (G::template wave_local<PF, PT>() && G::wave_top(PF)) wave_sync();
         else __syncthreads();
 #pragma unroll
         for (int b = 0; b < B; ++b)
 #pragma unroll
             for (int m = 0; m < E; ++m) x[b][m] = rt[b * BS + G::template at<X>(G::template moff<PT>(m))];
     }
-}
-// barrier plan as in rns_br.hip: only the first exchange of a transform and
-// exchanges writing a non-wave-top layout wait before writing
-template <int M, int E, int p>
-constexpr bool ffwd_pre() {
-    return p == 0 || !FGeo<M, E>::wave_top(p);
-}
-template <int M, int E, int p>
-constexpr bool finv_pre() {
-    return p == FGeo<M, E>::NPH - 1 || !FGeo<M, E>::wave_top(p);
 }
 // every LDS exchange conflict-free; register exchanges need no map, except that map XL
 // also serves the MAC's last-layout accesses
@@ -472,7 +406,7 @@ __device__ __forceinline__ void fforward_from(double2 (&x)[B][E], double2* row, 
     }
     hook(std::integral_constant<int, p>{});
     if constexpr (p + 1 < FGeo<M, E>::NPH) {
-        constexpr bool pre = !NOPRE && (ffwd_pre<M, E, p>() || CARRY), reg = fperm_ok<M, E, p, p + 1>();
+        constexpr bool pre = !NOPRE && (FGeo<M, E>::template fwd_pre<p>() || CARRY), reg = fperm_ok<M, E, p, p + 1>();
         fexchange<M, E, p, p + 1, reg ? false : pre, !NOPRE, B, BS>(x, row, tl);
         fforward_from<M, E, p + 1, NOPRE, TWR, B, BS, reg && pre>(x, row, twr, tw, tl, hook);
     }
@@ -496,7 +430,7 @@ __device__ __forceinline__ void finverse_from(double2 (&x)[B][E], double2* row, 
         }
     }
     if constexpr (p > 0) {
-        constexpr bool pre = !NOPRE && (finv_pre<M, E, p>() || CARRY), reg = fperm_ok<M, E, p, p - 1>();
+        constexpr bool pre = !NOPRE && (FGeo<M, E>::template inv_pre<p>() || CARRY), reg = fperm_ok<M, E, p, p - 1>();
         fexchange<M, E, p, p - 1, reg ? false : pre, !NOPRE, B, BS>(x, row, tl);
         finverse_from<M, E, p - 1, NOPRE, TWR, B, BS, reg && pre>(x, row, twr, tw, twc, tl);
     }
@@ -700,6 +634,8 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
     constexpr int M = N / 2;
     using G = FGeo<M, E>;
     static_assert(fexchanges_conflict_free<M, E>(), "LDS maps must make every exchange conflict-free");
+    static_assert(G::base_matches_geo(), "base<p> must be the index map the LDS-map proofs reason about");
+    static_assert(G::key_slot_matches_idx(), "the Fourier key's lane layout is the last-phase layout");
     static_assert(!LAT || E == 4, "the latency shape holds a step's GGSW values in registers: E = 4");
     static_assert(B == 1 || (B == 2 && LAT && K == 1 && E == 4), "pair shape: the k = 1 latency geometry");
     constexpr int NB = E >= 4 ? E / 4 : 1;  // psi bases per lane (slots m >> 2 share one)
@@ -852,7 +788,7 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
     }
     for (int t = 0; t < steps; ++t) {
         if (idle(t)) continue;  // (uniform branch)
-        FBR_STAMP(0);
+        BR_STAMP(0);
         // the step's byte offset in the key (uniform: soffset of every load)
         const uint32_t sbase = (uint32_t)__builtin_amdgcn_readfirstlane(t) * (3u * GG * 16u);
         // groups NPF.. of this step: G_TOP at the top of the step, G_L1 / G_L2 after forward
@@ -909,7 +845,7 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
 #pragma unroll
             for (int m = 0; m < E; ++m)
                 x[b][m] = make_double2(fft::acc_digit<23>(alo[b][m]), fft::acc_digit<23>(ahi[b][m]));
-        FBR_STAMP(1);
+        BR_STAMP(1);
         // 2. forward FFT (latency shape: GGSW groups 1 and 2 issued at phase boundaries)
         fforward_from<M, E, 0, LAT, TWR, B, BS>(x, row, twr, tw, tl, [&](auto ph) {
             if constexpr (LAT) {
@@ -926,7 +862,7 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
                 }
             }
         });
-        FBR_STAMP(2);
+        BR_STAMP(2);
         // 3. MAC with the three GGSWs of the pair and their monomial factors
 #pragma unroll
         for (int b = 0; b < B; ++b)
@@ -1008,10 +944,10 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
             for (int gg = 0; gg < NPF; ++gg) load_ggsw(gg, tn < steps ? tn : t);
             __builtin_amdgcn_sched_barrier(0);
         }
-        FBR_STAMP(3);
+        BR_STAMP(3);
         // 4. inverse FFT (times M; 1/M is in the key), accumulate, reduce mod 2^64
         finverse_from<M, E, LAST, LAT, TWR, B, BS>(x, irow, twr, tw, twc, tl);
-        FBR_STAMP(4);
+        BR_STAMP(4);
 #pragma unroll
         for (int b = 0; b < B; ++b)
 #pragma unroll
@@ -1019,7 +955,7 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
                 alo[b][m] = fft::acc_reduce<23>(alo[b][m] + x[b][m].x);
                 ahi[b][m] = fft::acc_reduce<23>(ahi[b][m] + x[b][m].y);
             }
-        FBR_STAMP(5);
+        BR_STAMP(5);
     }
 #ifdef FR_BR_TIMING
     if (blockIdx.x == 0 && tid == 0)
@@ -1083,6 +1019,8 @@ k_blind_rotate_fft_dual(const uint64_t* __restrict__ ks, int ks_stride, int n, c
     constexpr int K = 1, E = 4, M = N / 2, B = 2;
     using G = FGeo<M, E>;
     static_assert(fexchanges_conflict_free<M, E>(), "LDS maps must make every exchange conflict-free");
+    static_assert(G::base_matches_geo(), "base<p> must be the index map the LDS-map proofs reason about");
+    static_assert(G::key_slot_matches_idx(), "the Fourier key's lane layout is the last-phase layout");
     static_assert(fradix4<M, E>(), "dual shape: the k = 1 geometry (radix-4 inverse)");
     constexpr int T = M / E, NT = T, LAST = G::NPH - 1;
     constexpr int LOG2N2 = G::LOG + 2;
@@ -1235,12 +1173,9 @@ k_blind_rotate_fft_dual(const uint64_t* __restrict__ ks, int ks_stride, int n, c
 // ================================================================== host side
 // compiled (k, N) points: the reference's PARAM_MESSAGE_2_CARRY_2 (k = 1, N = 2048) and
 // BASELINE's "N = 1024" set (k = 2, N = 1024, the same 2048-bit flattened key)
-// k = 1: E = 4 only (its transforms are radix-4 in the inverse, fradix4)
-template <int N, int K, int E>
-constexpr bool fft_shape_ok() {
-    return (K == 1 && N == 2048 && E == 4) || (K == 2 && N == 1024 && (E == 4 || E == 8));
-}
-static bool fft_supported(int K, int N, int E) {
+// k = 1: E = 4 only (its transforms are radix-4 in the inverse, fradix4).  The one table of
+// compiled shapes, for `if constexpr` and for the runtime checks alike
+constexpr bool fft_supported(int K, int N, int E) {
     return (K == 1 && N == 2048 && E == 4) || (K == 2 && N == 1024 && (E == 4 || E == 8));
 }
 
@@ -1279,7 +1214,7 @@ void Device::init_fft() {
             HIP_CHECK(hipFuncSetAttribute((const void*)k_blind_rotate_fft_dual<N>,
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)fbr_dual_smem_bytes<N>()));
         }
-        if constexpr (fft_shape_ok<N, K, 8>()) fft_attr<N, K, 8, false>();
+        if constexpr (fft_supported(K, N, 8)) fft_attr<N, K, 8, false>();
     });
 
     fft::Tables T(p_.N);
@@ -1300,20 +1235,15 @@ void Device::upload_fft_bsk(const std::vector<uint64_t>& bsk) {
     std::vector<fft::c64> four;
     fft::bsk_to_fourier(tabs, bsk, polys, four);
     // slot order -> per-lane order [poly][m][lane] (one copy per lane geometry E):
-    // lane tl's element m is slot idx<LAST>(tl, m), so each load of a wave is 1 KB contiguous
+    // lane tl's element m is slot fft_key_slot(tl, m), so each load of a wave is 1 KB contiguous
     std::vector<fft::c64> lanes(four.size());
-    for (int E : {16, 8, 4}) {
+    for (int E : {8, 4}) {
         gpu::DevBuf<double>& dst = d_fbsk_[fbsk_index(E)];
         dst.reset();
         if (!fft_supported(p_.k, N, E) || !fbsk_needed(E)) continue;
-        const int T = M / E;
-        int e = 0;
-        while ((1 << e) < E) ++e;
-        const int LAST = (tabs.LOG + e - 1) / e - 1, L = geo_lo(tabs.LOG, e, LAST);
-        const int V = fft_layout_variant(tabs.LOG, e);
-        std::vector<int> slot((size_t)T * E);
-        for (int tl = 0; tl < T; ++tl)
-            for (int m = 0; m < E; ++m) slot[(size_t)m * T + tl] = geo_base(tabs.LOG, e, LAST, tl, V) + (m << L);
+        const int T = M / E, e = ilog2c(E);
+        std::vector<int> slot((size_t)M);
+        for (int q = 0; q < M; ++q) slot[q] = fft_key_slot(tabs.LOG, e, q % T, q / T);
         for (size_t pq = 0; pq < polys; ++pq)
             for (size_t q = 0; q < (size_t)M; ++q) lanes[pq * M + q] = four[pq * M + slot[q]];
         dst.alloc(2 * lanes.size());
@@ -1323,19 +1253,22 @@ void Device::upload_fft_bsk(const std::vector<uint64_t>& bsk) {
 
 void Device::launch_br_fft(const DevGate* d_gates, const uint64_t* d_ks, size_t n, hipStream_t s, hipEvent_t ev_start,
                            hipEvent_t ev_stop) {
+    // every blind-rotation kernel takes the same arguments; E picks the key's lane layout
+    auto launch = [&](auto kernel, size_t grid, int threads, size_t lds, int E) {
+        hipExtLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), (uint32_t)lds, s, ev_start, ev_stop, 0, d_ks,
+                              p_.ks_stride(), p_.n, d_gates, (int)n, (const double2*)d_fbsk_[fbsk_index(E)].get(),
+                              (const double2*)d_ftw_.get(), (const double2*)d_fqt_.get(),
+                              (const uint16_t*)d_fleaf_.get(), d_arena_.get(), p_.slot_stride());
+    };
     fft_dispatch(p_, [&](auto nc, auto kc) {
         constexpr int N = decltype(nc)::value, K = decltype(kc)::value;
         auto go = [&](auto ec, auto lat, auto bc) {
             constexpr int E = decltype(ec)::value;
             constexpr bool LAT = decltype(lat)::value;
             constexpr int B = decltype(bc)::value;
-            if constexpr (fft_shape_ok<N, K, E>() && (B == 1 || K == 1))
-                hipExtLaunchKernelGGL(k_blind_rotate_fft<N, K, E, LAT, B>, dim3((unsigned)((n + B - 1) / B)),
-                                      dim3(fbr_threads<N, K, E>()), (uint32_t)fbr_smem_bytes<N, K, E, LAT, B>(), s,
-                                      ev_start, ev_stop, 0, d_ks, p_.ks_stride(), p_.n, d_gates, (int)n,
-                                      (const double2*)d_fbsk_[fbsk_index(E)].get(), (const double2*)d_ftw_.get(),
-                                      (const double2*)d_fqt_.get(), (const uint16_t*)d_fleaf_.get(), d_arena_.get(),
-                                      p_.slot_stride());
+            if constexpr (fft_supported(K, N, E) && (B == 1 || K == 1))
+                launch(k_blind_rotate_fft<N, K, E, LAT, B>, (n + B - 1) / B, fbr_threads<N, K, E>(),
+                       fbr_smem_bytes<N, K, E, LAT, B>(), E);
         };
         using I4 = std::integral_constant<int, 4>;
         using I8 = std::integral_constant<int, 8>;
@@ -1343,12 +1276,7 @@ void Device::launch_br_fft(const DevGate* d_gates, const uint64_t* d_ks, size_t 
         // small launches (at most one bootstrap per CU): the latency shape
         if (n <= fft_small_) go(I4{}, std::true_type{}, B1{});
         else if (n <= fft_pair_ && K == 1 && fft_dual_) {
-            if constexpr (K == 1)
-                hipExtLaunchKernelGGL(k_blind_rotate_fft_dual<N>, dim3((unsigned)n), dim3(N / 8),
-                                      (uint32_t)fbr_dual_smem_bytes<N>(), s, ev_start, ev_stop, 0, d_ks, p_.ks_stride(),
-                                      p_.n, d_gates, (int)n, (const double2*)d_fbsk_[fbsk_index(4)].get(),
-                                      (const double2*)d_ftw_.get(), (const double2*)d_fqt_.get(),
-                                      (const uint16_t*)d_fleaf_.get(), d_arena_.get(), p_.slot_stride());
+            if constexpr (K == 1) launch(k_blind_rotate_fft_dual<N>, n, N / 8, fbr_dual_smem_bytes<N>(), 4);
         } else if (n <= fft_pair_) go(I4{}, std::true_type{}, std::integral_constant<int, 2>{});  // (k = 1)
         else if (fft_e_ == 4) go(I4{}, std::false_type{}, B1{});
         else go(I8{}, std::false_type{}, B1{});

@@ -1,5 +1,6 @@
-// Lane geometry of the register-phase NTT/FFT kernels and their bank-conflict-
-// free LDS exchange maps (shared by rns_br.hip: RNS NTT, and fft_br.hip: f64 FFT).
+// Lane geometry of the register-phase NTT/FFT kernels, their bank-conflict-free
+// LDS exchange maps and their exchange (barrier) plan (shared by rns_br.hip: RNS
+// NTT, and fft_br.hip: f64 FFT), and the Fourier key's lane layout (keygen.hip too).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -62,6 +63,14 @@ constexpr int geo_base(int LOG, int e, int p, int tl, int V = 0) {
 }
 // the layout family of the f64 FFT kernels (fft_br.hip, keygen.hip, the key upload)
 constexpr int fft_layout_variant(int LOG, int e) { return LOG == 10 && e == 2 ? 1 : 0; }
+// The Fourier key's lane layout [poly][m][lane]: the slot (index in transform order) of
+// element m of lane tl, i.e. the last-phase layout of the FFT geometry M = 2^LOG, E = 2^e.
+// One definition for the host upload, the device key build and the kernels that read it
+// (NttGeo::key_slot_matches_idx).
+__host__ __device__ constexpr int fft_key_slot(int LOG, int e, int tl, int m) {
+    const int last = (LOG + e - 1) / e - 1;
+    return geo_base(LOG, e, last, tl, fft_layout_variant(LOG, e)) + (m << geo_lo(LOG, e, last));
+}
 constexpr unsigned geo_group(int LOG, int e, int p, int GB, int V = 0) {
     unsigned g = 0;
     for (int b = 0; b < GB; ++b) g |= 1u << geo_lane_bit(LOG, e, p, b, V);
@@ -335,9 +344,10 @@ struct NttGeo {
     }
     // element m of lane tl in phase p: idx = base(tl) | moff(m), disjoint bits,
     // so at(idx) = at(base) + at(moff): every address is one per-lane register
-    // plus a compile-time immediate.
+    // plus a compile-time immediate.  base is geo_base written as the shifts the
+    // kernels run (base_matches_geo ties the two forms together).
     template <int p>
-    __device__ static __forceinline__ int base(int tl) {
+    __host__ __device__ static constexpr int base(int tl) {
         if constexpr (V == 1 && p >= 3) {  // lane bits 0..3 -> index 4, 5, 7, 6
             return ((tl & 3) << 4) | ((tl & 4) << 5) | ((tl & 8) << 3) | (((tl >> 4) & 3) << (p == 3 ? 0 : 2)) |
                    ((tl >> 6) << 8);
@@ -349,8 +359,56 @@ struct NttGeo {
     template <int p>
     static constexpr int moff(int m) { return m << lo(p); }
     template <int p>
-    __device__ static __forceinline__ int idx(int tl, int m) { return base<p>(tl) + moff<p>(m); }
+    __host__ __device__ static constexpr int idx(int tl, int m) { return base<p>(tl) + moff<p>(m); }
+    // the index map the kernels run is the one every compile-time proof above reasons
+    // about: base<p>(tl) == geo_base(.., p, tl, V) for every phase and lane (asserted by
+    // every kernel that instantiates a geometry)
+    template <int p = 0>
+    static constexpr bool base_matches_geo() {
+        for (int tl = 0; tl < T; ++tl)
+            if (base<p>(tl) != geo_base(LOG, e, p, tl, V)) return false;
+        if constexpr (p + 1 < NPH) return base_matches_geo<p + 1>();
+        else return true;
+    }
+    // the Fourier key's lane layout (fft_key_slot) is this geometry's last-phase layout
+    static constexpr bool key_slot_matches_idx() {
+        for (int tl = 0; tl < T; ++tl)
+            for (int m = 0; m < E; ++m)
+                if (fft_key_slot(LOG, e, tl, m) != idx<NPH - 1>(tl, m)) return false;
+        return true;
+    }
+
+    // Exchange plan.  Does the exchange between phase layouts PF and PT stay inside
+    // each wave?  The wave index is lane bits [6, log2 T); if those carry the same
+    // index bits in both layouts, every wave reads back only what it wrote.
+    template <int PF, int PT>
+    static constexpr bool wave_local() {
+        for (int b = 6; (1 << b) < T; ++b)
+            if (lane_bit(PF, b) != lane_bit(PT, b)) return false;
+        return true;
+    }
+    // Barrier plan (hazards between waves on the exchange rows).  After any
+    // exchange every lane reads only slots its own wave owns under the new layout;
+    // in a wave-top layout those are the wave's own address chunk under every map,
+    // so a later write of the same layout by the same wave (even under the next
+    // exchange's map) cannot race another wave.  So only the first exchange of a
+    // transform needs a barrier before writing: the forward one follows the rotation
+    // step (other waves read arbitrary slots of this row), the inverse one follows
+    // the MAC (other polynomials' waves read this row) -- plus any exchange that
+    // writes a layout that is not wave-top.
+    template <int p>
+    static constexpr bool fwd_pre() { return p == 0 || !wave_top(p); }
+    template <int p>
+    static constexpr bool inv_pre() { return p == NPH - 1 || !wave_top(p); }
 };
+
+// LDS ordering inside one wave (wave-local exchanges): no workgroup barrier, only a
+// compiler fence (LDS instructions of a wave execute in order).
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 
 }  // namespace fr

@@ -211,19 +211,12 @@ __global__ void __launch_bounds__(256) k_expand_bsk(RngKey mask_key, int k, cons
     for (int x = tid; x < N / 2; x += 256) dst[x] = src[x];
 }
 
-// element m of lane tl in the last-phase layout of lane geometry E (slot order, geo.h)
-template <int M, int E>
-__device__ __forceinline__ int lane_slot(int tl, int m) {
-    constexpr int LOG = __builtin_ctz(M), e = __builtin_ctz(E), LAST = (LOG + e - 1) / e - 1;
-    return geo_base(LOG, e, LAST, tl, fft_layout_variant(LOG, e)) + (m << geo_lo(LOG, e, LAST));
-}
 // fold + forward FFT + fourier_key_scale of one polynomial, written in the lane layouts of
-// the E = 4, 8 and 16 kernels ([poly][m][lane], slot of (lane, m) per geo.h; a null
-// output is skipped)
+// the E = 4 and E = 8 kernels ([poly][m][lane], slot of (lane, m): fft_key_slot of geo.h; a
+// null output is skipped)
 template <int N>
 __global__ void __launch_bounds__(256) k_bsk_fourier(const uint64_t* __restrict__ bsk, const double2* __restrict__ tw,
-                                                     double2* __restrict__ out4, double2* __restrict__ out8,
-                                                     double2* __restrict__ out16) {
+                                                     double2* __restrict__ out4, double2* __restrict__ out8) {
     constexpr int M = N / 2;
     constexpr int LOG = __builtin_ctz(M);
     __shared__ double2 z[M];
@@ -247,16 +240,12 @@ __global__ void __launch_bounds__(256) k_bsk_fourier(const uint64_t* __restrict_
     const double scale = fft::fourier_key_scale(LOG);  // 1/M and the accumulator unit (fft.h), exact
     for (int idx = tid; idx < M; idx += 256) {
         if (out4) {
-            const double2 v = z[lane_slot<M, 4>(idx % (M / 4), idx / (M / 4))];
+            const double2 v = z[fft_key_slot(LOG, 2, idx % (M / 4), idx / (M / 4))];
             out4[p * M + idx] = make_double2(v.x * scale, v.y * scale);
         }
         if (out8) {
-            const double2 v = z[lane_slot<M, 8>(idx % (M / 8), idx / (M / 8))];
+            const double2 v = z[fft_key_slot(LOG, 3, idx % (M / 8), idx / (M / 8))];
             out8[p * M + idx] = make_double2(v.x * scale, v.y * scale);
-        }
-        if (out16) {
-            const double2 v = z[lane_slot<M, 16>(idx % (M / 16), idx / (M / 16))];
-            out16[p * M + idx] = make_double2(v.x * scale, v.y * scale);
         }
     }
 }
@@ -393,16 +382,16 @@ void Device::build_fourier_bsk() {
     const int N = p_.N, M = N / 2, kp1 = p_.k + 1;
     const size_t bsk_polys = p_.bsk_ggsw() * kp1 * kp1;
     const hipStream_t s = cur().stream.get();
-    for (int E : {4, 8, 16}) {
+    for (int E : {4, 8}) {
         gpu::DevBuf<double>& dst = d_fbsk_[fbsk_index(E)];
         dst.reset();
-        if (fbsk_needed(E) && (E < 16 || p_.k == 1)) dst.alloc(2 * bsk_polys * M);
+        if (fbsk_needed(E)) dst.alloc(2 * bsk_polys * M);
     }
-    double2 *o4 = (double2*)d_fbsk_[0].get(), *o8 = (double2*)d_fbsk_[1].get(), *o16 = (double2*)d_fbsk_[2].get();
+    double2 *o4 = (double2*)d_fbsk_[0].get(), *o8 = (double2*)d_fbsk_[1].get();
     if (N == 2048)
-        k_bsk_fourier<2048><<<(unsigned)bsk_polys, 256, 0, s>>>(d_tbsk_.get(), (const double2*)d_ftw_.get(), o4, o8, o16);
+        k_bsk_fourier<2048><<<(unsigned)bsk_polys, 256, 0, s>>>(d_tbsk_.get(), (const double2*)d_ftw_.get(), o4, o8);
     else
-        k_bsk_fourier<1024><<<(unsigned)bsk_polys, 256, 0, s>>>(d_tbsk_.get(), (const double2*)d_ftw_.get(), o4, o8, o16);
+        k_bsk_fourier<1024><<<(unsigned)bsk_polys, 256, 0, s>>>(d_tbsk_.get(), (const double2*)d_ftw_.get(), o4, o8);
     HIP_CHECK(hipGetLastError());
 }
 

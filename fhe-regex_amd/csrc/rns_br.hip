@@ -95,29 +95,10 @@ __device__ __forceinline__ void inv_phase(uint32_t (&x)[E], const uint32_t* zt, 
         }
     }
 }
-// Does the exchange between phase layouts PF and PT stay inside each wave?
-// Lane bit b of phase p holds index bit (b < lo(p) ? b : b + e); the wave
-// index is lane bits [6, log2 T).  If those map to the same index bits in both
-// layouts, every wave reads back only what it wrote.
-template <int N, int E, int PF, int PT>
-constexpr bool wave_local() {
-    using G = NttGeo<N, E>;
-    for (int b = 6; (1 << b) < G::T; ++b) {
-        const int f = b < G::lo(PF) ? b : b + G::e, t = b < G::lo(PT) ? b : b + G::e;
-        if (f != t) return false;
-    }
-    return true;
-}
-// LDS ordering inside one wave: no workgroup barrier, only a compiler fence
-// (LDS instructions of a wave execute in order).
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 // LDS exchange between the layouts of phases PF and PT (row = this lane's
 // polynomial).  PRE: a barrier before writing (other waves may still read
-// these slots); the barrier after writing is dropped for wave-local exchanges.
+// these slots); the barrier after writing is dropped for wave-local exchanges
+// (the exchange and barrier plan: NttGeo, geo.h).
 template <int N, int E, int PF, int PT, bool PRE = true>
 __device__ __forceinline__ void exchange(uint32_t (&x)[E], uint32_t* row, int tl) {
     using G = NttGeo<N, E>;
@@ -127,28 +108,10 @@ __device__ __forceinline__ void exchange(uint32_t (&x)[E], uint32_t* row, int tl
     if constexpr (PRE) __syncthreads();
 #pragma unroll
     for (int m = 0; m < E; ++m) rf[G::template at<X>(G::template moff<PF>(m))] = x[m];
-    if constexpr (wave_local<N, E, PF, PT>() && G::wave_top(PF)) wave_sync();
+    if constexpr (G::template wave_local<PF, PT>() && G::wave_top(PF)) wave_sync();
     else __syncthreads();
 #pragma unroll
     for (int m = 0; m < E; ++m) x[m] = rt[G::template at<X>(G::template moff<PT>(m))];
-}
-
-// Barrier plan (hazards between waves on the exchange rows).  After any
-// exchange every lane reads only slots its own wave owns under the new layout;
-// in a wave-top layout those are the wave's own address chunk under every map,
-// so a later write of the same layout by the same wave (even under the next
-// exchange's map) cannot race another wave.  So only the first exchange of an
-// NTT needs a barrier before writing: the forward one follows the rotation
-// step (other waves read arbitrary slots of this row), the inverse one follows
-// the MAC (other polynomials' waves read this row) -- plus any exchange that
-// writes a layout that is not wave-top.
-template <int N, int E, int p>
-constexpr bool fwd_pre() {
-    return p == 0 || !NttGeo<N, E>::wave_top(p);
-}
-template <int N, int E, int p>
-constexpr bool inv_pre() {
-    return p == NttGeo<N, E>::NPH - 1 || !NttGeo<N, E>::wave_top(p);
 }
 
 template <int N, int E, int X = 0>
@@ -164,7 +127,7 @@ __device__ __forceinline__ void forward_from(uint32_t (&x)[E], uint32_t* row, co
                                              uint32_t pn) {
     fwd_phase<N, E, p>(x, zt, tl, pm, pn);
     if constexpr (p + 1 < NttGeo<N, E>::NPH) {
-        exchange<N, E, p, p + 1, fwd_pre<N, E, p>()>(x, row, tl);
+        exchange<N, E, p, p + 1, NttGeo<N, E>::template fwd_pre<p>()>(x, row, tl);
         forward_from<N, E, p + 1>(x, row, zt, tl, pm, pn);
     }
 }
@@ -173,7 +136,7 @@ __device__ __forceinline__ void inverse_from(uint32_t (&x)[E], uint32_t* row, co
                                              uint32_t pn) {
     inv_phase<N, E, p>(x, zt, tl, pm, pn);
     if constexpr (p > 0) {
-        exchange<N, E, p, p - 1, inv_pre<N, E, p>()>(x, row, tl);
+        exchange<N, E, p, p - 1, NttGeo<N, E>::template inv_pre<p>()>(x, row, tl);
         inverse_from<N, E, p - 1>(x, row, zt, tl, pm, pn);
     }
 }
@@ -195,23 +158,6 @@ template <int N, int K, int E>
 constexpr int br_threads() {
     return 2 * (K + 1) * (N / E);
 }
-// FR_BR_TIMING (debug builds only, tools/build_variant.sh): wave 0 of workgroup 0
-// accumulates s_memtime deltas of the pair-step segments and prints them.
-#ifdef FR_BR_TIMING
-#define BR_STAMP(k)                                             \
-    do {                                                        \
-        __builtin_amdgcn_sched_barrier(0);                      \
-        const uint64_t now_ = __builtin_amdgcn_s_memtime();     \
-        tseg[k] += now_ - tlast;                                \
-        tlast = now_;                                           \
-        __builtin_amdgcn_sched_barrier(0);                      \
-    } while (0)
-#else
-#define BR_STAMP(k) \
-    do {            \
-    } while (0)
-#endif
-
 // bootstrapping-key unrolling factor (Params::bsk_unroll): pairs for k = 1
 template <int K>
 constexpr int br_unroll() {
@@ -271,9 +217,6 @@ __device__ __forceinline__ uint32_t w_step(const uint32_t* row, const uint32_t* 
 // sibling the residues it needs, round 2 the digits it did not compute (both in
 // this lane's own row, at disjoint slots).  The caller's next write of the row
 // (the forward NTT's first exchange) is preceded by a barrier.
-#ifndef FR_SPLIT_DIGITS
-#define FR_SPLIT_DIGITS 1
-#endif
 template <int N, int E, int Q>
 __device__ __forceinline__ void split_digits(uint32_t (&x)[E], const uint32_t (&acc)[E], uint32_t* row_b0,
                                              const uint32_t* sib_b0, uint32_t pm) {
@@ -305,6 +248,7 @@ k_blind_rotate(const uint64_t* __restrict__ ks, int ks_stride, int n, const DevG
                int slot_stride) {
     using G = NttGeo<N, E>;
     static_assert(exchanges_conflict_free<N, E>(), "LDS maps must make every exchange conflict-free");
+    static_assert(G::base_matches_geo(), "base<p> must be the index map the LDS-map proofs reason about");
     constexpr int NT = br_threads<N, K, E>();
     constexpr int LAST = G::NPH - 1;
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
@@ -480,20 +424,8 @@ k_blind_rotate(const uint64_t* __restrict__ ks, int ks_stride, int n, const DevG
         // 1. signed gadget digits of acc, split between the two prime lanes of a
         //    coefficient (residues and digits swapped through LDS)
         uint32_t x[E];
-#if FR_SPLIT_DIGITS
         if (q == 0) split_digits<N, E, 0>(x, acc, row_b0, sib_b0, pm);
         else split_digits<N, E, 1>(x, acc, row_b0, sib_b0, pm);
-#else
-#pragma unroll
-        for (int m = 0; m < E; ++m) row_b0[G::template at<0>(G::template moff<0>(m))] = acc[m];
-        __syncthreads();
-#pragma unroll
-        for (int m = 0; m < E; ++m) {
-            const uint32_t o = sib_b0[G::template at<0>(G::template moff<0>(m))];
-            const int32_t dg = q ? rns::decompose(o, acc[m]) : rns::decompose(acc[m], o);
-            x[m] = dg >= 0 ? (uint32_t)dg : (uint32_t)(dg + (int32_t)pm);
-        }
-#endif
         BR_STAMP(1);
         // 2. forward NTT (its first exchange waits for the sibling reads above)
         forward_ntt<N, E>(x, row, zt, tl, pm, pn);
@@ -601,6 +533,7 @@ __global__ void __launch_bounds__(2 * (K + 1) * (N / E))
 k_bsk_to_ntt(const uint64_t* __restrict__ coef, const uint32_t* __restrict__ tw, uint32_t ninv_r0, uint32_t ninv_r1,
              uint32_t* __restrict__ out) {
     using G = NttGeo<N, E>;
+    static_assert(G::base_matches_geo(), "base<p> must be the index map the LDS-map proofs reason about");
     constexpr int NT = br_threads<N, K, E>();
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     uint32_t* xbuf = smem;
@@ -627,6 +560,7 @@ __global__ void __launch_bounds__(4 * (N / E))
 k_ring_mul(const uint64_t* __restrict__ a, const uint64_t* __restrict__ b, const uint32_t* __restrict__ tw,
            uint32_t r2n0, uint32_t r2n1, uint64_t* __restrict__ out) {
     using G = NttGeo<N, E>;
+    static_assert(G::base_matches_geo(), "base<p> must be the index map the LDS-map proofs reason about");
     constexpr int LAST = G::NPH - 1;
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     uint32_t* xbuf = smem;  // rows (operand, prime)

@@ -351,3 +351,31 @@ def test_fft_dual_shape_bit_exact(key_blob, oracle_fft, point, monkeypatch, coun
             o, _ = c.has_match(c.upload_radix(c.encrypt_str(s, seed=9)), "/abc/")
             words.append(c.download_radix(o))
         assert np.array_equal(words[0], words[1]) and dual.decrypt_radix(words[0]) == 1
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("point", [(2, 1024)], indirect=True, ids=["k2n1024"])
+@pytest.mark.parametrize("keygen", [F.KEYGEN_HOST, F.KEYGEN_DEVICE], ids=["host", "device"])
+@pytest.mark.parametrize("lane_elems", [4, 8])
+def test_fft_k2_key_layouts_bit_exact(key_blob, oracle_fft, point, monkeypatch, lane_elems, keygen):
+    """Both Fourier-key lane layouts of k = 2 (E = 4 and E = 8), laid out by the host upload
+    and by the device key build, read by the throughput kernel (FR_FFT_SMALL_BATCH=0: no
+    launch is small enough for the latency shape): every output word of three bootstraps
+    equals the oracle's, one of them with half its mask zeroed (skipped steps)."""
+    env = {"FR_FFT_SMALL_BATCH": 0, "FR_FFT_LANE_ELEMS": lane_elems}
+    for k, v in env.items():
+        monkeypatch.setenv(k, str(v))
+    ctx = F.Context(device=0, params=F.default_params(k=point[0], N=point[1], ring=F.RING_FFT))
+    for k in env:
+        monkeypatch.delenv(k)
+    ctx.load_client_key(key_blob)
+    ctx.set_keygen(keygen)
+    ctx.gen_server_key(SEED)
+    O = oracle_fft
+    rng = np.random.default_rng(1024 + lane_elems)
+    ks = rng.integers(0, 2**64 - 1, (3, O.n + 1), dtype=np.uint64, endpoint=True)
+    ks[1, 0:O.n // 2] = 0
+    luts = [[(11 * m + i) % 16 for m in range(16)] for i in range(3)]
+    got = ctx.dev_blind_rotate(ks, luts)
+    for i in range(3):
+        assert (got[i] == O.blind_rotate(ks[i], luts[i])).all(), i
