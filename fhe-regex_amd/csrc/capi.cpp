@@ -169,16 +169,9 @@ int fr_upload_radix(fr_ctx* ctx, const uint64_t* blocks, size_t n, fr_ct* out) {
     FR_TRY({
         NEED(ctx && (blocks || !n) && (out || !n));
         Device& dev = ctx->device();
-        const int L = ctx->p.lwe_len();
-        std::vector<int> slots(4 * n);
-        for (auto& s : slots) s = dev.alloc_slot();
+        Slots slots(dev, 4 * n);
         dev.write_slots(slots.data(), slots.size(), blocks);
-        for (size_t i = 0; i < n; ++i) {
-            HandleRec r;
-            for (int b = 0; b < 4; ++b) r.b[b].slot = slots[4 * i + b];
-            out[i] = ctx->new_handle(r);
-        }
-        (void)L;
+        ctx->adopt(std::move(slots), true, out);
     })
 }
 
@@ -186,10 +179,9 @@ int fr_upload_bool(fr_ctx* ctx, const uint64_t* lwe, size_t n, fr_ct* out) {
     FR_TRY({
         NEED(ctx && (lwe || !n) && (out || !n));
         Device& dev = ctx->device();
-        std::vector<int> slots(n);
-        for (auto& s : slots) s = dev.alloc_slot();
+        Slots slots(dev, n);
         dev.write_slots(slots.data(), n, lwe);
-        for (size_t i = 0; i < n; ++i) out[i] = ctx->new_bool(slots[i]);
+        ctx->adopt(std::move(slots), false, out);
     })
 }
 
@@ -260,11 +252,9 @@ static int bitop(fr_ctx* ctx, fr_ct a, fr_ct b, fr_ct* out, bool is_and) {
                 gates[blk].ins = {{cblk(0, blk), 4}, {cblk(1, blk), 1}};
                 for (int v = 0; v < 16; ++v) gates[blk].lut[v] = (uint8_t)(is_and ? ((v >> 2) & (v & 3)) : ((v >> 2) | (v & 3)));
             }
-            std::vector<int> slots = execute_gates(ctx, gates, {a, b}, nullptr);
+            Slots slots = execute_gates(ctx, gates, {a, b}, nullptr);
             ctx->device().sync();
-            HandleRec r;
-            for (int blk = 0; blk < 4; ++blk) r.b[blk].slot = slots[blk];
-            *out = ctx->new_handle(r);
+            ctx->adopt(std::move(slots), true, out);
         }
     })
 }
@@ -279,25 +269,25 @@ int fr_not(fr_ctx* ctx, fr_ct a, fr_ct* out) {
             if (ha.b[0].slot < 0) {
                 *out = ctx->new_bool(-1, ha.b[0].triv ^ 1);
             } else {  // 1 - a
-                const int s = linear_to_new_slot(ctx->device(), ha.b[0].slot, -1, 2);
+                Slots s = linear_to_new_slot(ctx->device(), ha.b[0].slot, -1, 2);
                 ctx->device().sync();
-                *out = ctx->new_bool(s);
+                ctx->adopt(std::move(s), false, out);
             }
         } else {  // general radix: block 0 through a LUT, blocks 1..3 copied
-            HandleRec r;
             std::vector<PGate> gates(1);
             gates[0].ins = {{cblk(0, 0), 1}};
             for (int v = 0; v < 16; ++v) gates[0].lut[v] = (uint8_t)((v & 3) ^ 1);
-            std::vector<int> slots = execute_gates(ctx, gates, {a}, nullptr);
-            r.b[0].slot = slots[0];
-            for (int blk = 1; blk < 4; ++blk) {
-                if (ha.b[blk].slot < 0) {
-                    r.b[blk] = ha.b[blk];
-                    continue;
-                }
-                r.b[blk].slot = linear_to_new_slot(ctx->device(), ha.b[blk].slot, 1, 0);
-            }
+            Slots part[4];  // one slot each; a trivial block has none
+            part[0] = execute_gates(ctx, gates, {a}, nullptr);
+            for (int blk = 1; blk < 4; ++blk)
+                if (ha.b[blk].slot >= 0) part[blk] = linear_to_new_slot(ctx->device(), ha.b[blk].slot, 1, 0);
             ctx->device().sync();
+            ctx->reserve_handles(1);  // new_handle cannot fail once the slots have left their owners
+            HandleRec r;
+            for (int blk = 0; blk < 4; ++blk) {
+                if (part[blk].size()) r.b[blk].slot = part[blk].take(0);
+                else r.b[blk] = ha.b[blk];
+            }
             *out = ctx->new_handle(r);
         }
     })
@@ -319,9 +309,9 @@ int fr_or_many(fr_ctx* ctx, const fr_ct* in, size_t n, fr_ct* out) {
             return FR_OK;
         }
         if (inputs.size() == 1) {  // copy
-            const int s = linear_to_new_slot(ctx->device(), ctx->get(inputs[0]).b[0].slot, 1, 0);
+            Slots s = linear_to_new_slot(ctx->device(), ctx->get(inputs[0]).b[0].slot, 1, 0);
             ctx->device().sync();
-            *out = ctx->new_bool(s);
+            ctx->adopt(std::move(s), false, out);
             return FR_OK;
         }
         // balanced tree of <= 16-input threshold ORs
@@ -384,9 +374,11 @@ int fr_run_gates(fr_ctx* ctx, fr_gate* gates, size_t n) {
                 }
             }
         }
-        std::vector<int> slots = execute_gates(ctx, pg, inputs, nullptr);
+        Slots slots = execute_gates(ctx, pg, inputs, nullptr);
         ctx->device().sync();
-        for (size_t j = 0; j < n; ++j) gates[j].out = ctx->new_bool(slots[j]);
+        std::vector<fr_ct> outs(n);
+        ctx->adopt(std::move(slots), false, outs.data());
+        for (size_t j = 0; j < n; ++j) gates[j].out = outs[j];
     })
 }
 
@@ -500,7 +492,6 @@ int fr_dev_bench_pbs(fr_ctx* ctx, const fr_ct* in, size_t count, int32_t iters, 
         Device& dev = ctx->device();
         if (!ctx->has_sk) throw Error(FR_ERR_NO_KEY, "server key not generated");
         std::vector<DevGate> gates(count);
-        std::vector<int> outs(count);
         for (size_t i = 0; i < count; ++i) {
             const HandleRec& h = ctx->get(in[i]);
             DevGate& d = gates[i];
@@ -522,11 +513,10 @@ int fr_dev_bench_pbs(fr_ctx* ctx, const fr_ct* in, size_t count, int32_t iters, 
             lut_eq(d.lut[0], 1);
             d.n_out = 1;
             d.direct = JOB_DIRECT;
-            outs[i] = dev.alloc_slot();
-            d.out_slot[0] = outs[i];
         }
+        Slots outs(dev, count);  // once every handle has been checked
+        for (size_t i = 0; i < count; ++i) gates[i].out_slot[0] = outs[i];
         dev.bench_pbs(gates, iters, br_ms, total_ms);
-        for (int s : outs) dev.free_slot(s);
     })
 }
 
@@ -545,32 +535,37 @@ uint64_t fr_debug_scalar(int32_t op, uint64_t x, uint64_t y) {
     }
 }
 
+int fr_debug_arena_stats(fr_ctx* ctx, uint64_t* slots, uint64_t* free_slots) {
+    FR_TRY({
+        NEED(ctx && slots && free_slots);
+        Device& dev = ctx->device();
+        dev.sync();  // every lane: the deferred frees return to the free list
+        *slots = dev.arena_slots();
+        *free_slots = dev.arena_free_slots();
+    })
+}
+
 // device-to-device booleans (block 0 of a handle), e.g. per-rank partial results
 // gathered over RCCL: no host round trip of the LWE
 int fr_export_bool_device(fr_ctx* ctx, const fr_ct* h, size_t n, uint64_t* dev_dst) {
     FR_TRY({
         NEED(ctx && (h || !n) && (dev_dst || !n));
         Device& dev = ctx->device();
-        std::vector<int> slots(n), tmp;
-        struct Guard {
-            Device& dev;
-            std::vector<int>& tmp;
-            ~Guard() {
-                for (int s : tmp) dev.free_slot(s);
-            }
-        } guard{dev, tmp};
+        std::vector<int> slots(n);
+        size_t n_triv = 0;
         for (size_t i = 0; i < n; ++i) {
-            const HandleRec& r = ctx->get(h[i]);
-            if (r.b[0].slot >= 0) {
-                slots[i] = r.b[0].slot;
-                continue;
-            }
-            // a trivial block 0 (e.g. a start range that cannot match): its trivial LWE
-            std::vector<uint64_t> lwe((size_t)ctx->p.lwe_len(), 0);
-            lwe.back() = (uint64_t)r.b[0].triv << DELTA_LOG;
-            tmp.push_back(dev.alloc_slot());
-            dev.write_slots(&tmp.back(), 1, lwe.data());
-            slots[i] = tmp.back();
+            slots[i] = ctx->get(h[i]).b[0].slot;
+            n_triv += slots[i] < 0;
+        }
+        // a trivial block 0 (e.g. a start range that cannot match): its trivial LWE in a slot
+        // of the call's own
+        Slots tmp(dev, n_triv);
+        std::vector<uint64_t> lwe((size_t)ctx->p.lwe_len(), 0);
+        for (size_t i = 0, t = 0; i < n; ++i) {
+            if (slots[i] >= 0) continue;
+            lwe.back() = (uint64_t)ctx->get(h[i]).b[0].triv << DELTA_LOG;
+            slots[i] = tmp[t++];
+            dev.write_slots(&slots[i], 1, lwe.data());
         }
         dev.slots_to_device(slots.data(), n, dev_dst);
     })
@@ -598,15 +593,9 @@ int fr_import_bool_device(fr_ctx* ctx, const uint64_t* dev_src, size_t n, fr_ct*
     FR_TRY({
         NEED(ctx && out && (dev_src || !n));
         Device& dev = ctx->device();
-        std::vector<int> slots;
-        try {
-            for (size_t i = 0; i < n; ++i) slots.push_back(dev.alloc_slot());
-            dev.device_to_slots(slots.data(), n, dev_src);
-        } catch (...) {
-            for (int s : slots) dev.free_slot(s);
-            throw;
-        }
-        for (size_t i = 0; i < n; ++i) out[i] = ctx->new_bool(slots[i]);
+        Slots slots(dev, n);
+        dev.device_to_slots(slots.data(), n, dev_src);
+        ctx->adopt(std::move(slots), false, out);
     })
 }
 // the accumulated timers after a synchronise: one blind-rotation triple of them, and the keyswitch's

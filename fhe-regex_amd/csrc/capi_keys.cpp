@@ -320,19 +320,9 @@ static std::vector<uint8_t> check_encrypt_upload_str(fr_ctx* ctx, const char* s,
 }
 static void encrypt_upload_with(fr_ctx* ctx, const std::vector<uint8_t>& msgs, const RngKey& key, fr_ct* out) {
     Device& dev = ctx->device();
-    std::vector<int> slots(msgs.size());
-    for (auto& x : slots) x = dev.alloc_slot();
-    try {
-        dev.encrypt_to_slots(ctx->ck, msgs.data(), msgs.size(), key, 0, slots.data());
-    } catch (...) {
-        for (int x : slots) dev.free_slot(x);
-        throw;
-    }
-    for (size_t i = 0; i < msgs.size() / 4; ++i) {
-        HandleRec r;
-        for (int b = 0; b < 4; ++b) r.b[b].slot = slots[4 * i + b];
-        out[i] = ctx->new_handle(r);
-    }
+    Slots slots(dev, msgs.size());
+    dev.encrypt_to_slots(ctx->ck, msgs.data(), msgs.size(), key, 0, slots.data());
+    ctx->adopt(std::move(slots), true, out);
 }
 
 int fr_encrypt_upload_str(fr_ctx* ctx, const char* s, size_t len, uint64_t seed, fr_ct* out) {
@@ -419,23 +409,7 @@ static void upload_compact(fr_ctx* ctx, const uint8_t* blob, size_t len, bool ra
     *n = handles;
     NEED((out || !handles) && cap >= handles);
     Device& dev = ctx->device();
-    std::vector<int> slots(c.n_blocks);
-    dev.expand_to_slots(c.mask_key, c.first_block, c.bodies, c.n_blocks, slots.data());
-    try {
-        ctx->handles.reserve(ctx->handles.size() + handles);  // new_handle cannot fail below
-    } catch (...) {
-        for (int x : slots) dev.free_slot(x);
-        throw;
-    }
-    for (size_t i = 0; i < handles; ++i) {
-        if (radix) {
-            HandleRec r;
-            for (int b = 0; b < 4; ++b) r.b[b].slot = slots[4 * i + b];
-            out[i] = ctx->new_handle(r);
-        } else {
-            out[i] = ctx->new_bool(slots[i]);
-        }
-    }
+    ctx->adopt(dev.expand_to_slots(c.mask_key, c.first_block, c.bodies, c.n_blocks), radix, out);
 }
 
 int fr_upload_compact_str(fr_ctx* ctx, const uint8_t* blob, size_t len, fr_ct* out, size_t cap, size_t* n_chars) {

@@ -81,15 +81,11 @@ struct fr_ctx {
     bool multi_value = true;  // merge same-input small-norm LUTs into one blind rotation
     bool async_match = true;  // has_match returns once its launches are enqueued (fr_set_async)
     uint64_t next_lane = 0;   // fr_set_lanes: consecutive asynchronous matches round-robin over the lanes
-    fr_plan_cache plans;
+    fr_plan_cache plans;  // after dev: the cached plans go while the device is alive (Plan, plan.h)
     // content_signature scratch: canonical id of an arena slot, valid while sig_gen[slot] == gen
     std::vector<int32_t> sig_id;
     std::vector<uint32_t> sig_gen;
     uint32_t gen = 0;
-
-    // match.cpp: the cached plans give their slots and device batches back while the
-    // device is alive (the members above outlive this body)
-    ~fr_ctx();
 
     fr::Device& device() {
         if (!dev) throw fr::Error(FR_ERR_NO_DEVICE, "host-only context: no HIP device");
@@ -121,6 +117,24 @@ struct fr_ctx {
         r.b[0].slot = slot;
         r.b[0].triv = triv;
         return new_handle(r);
+    }
+    // room for n more handles, so that new_handle cannot fail (grown geometrically)
+    void reserve_handles(size_t n) {
+        const size_t need = handles.size() + n;
+        if (need > handles.capacity()) handles.reserve(std::max(need, 2 * handles.capacity()));
+    }
+    // Handles over owned slots: a radix character per four consecutive slots, or a boolean per
+    // slot.  The table is reserved first, so the slots change hands only once nothing can fail.
+    void adopt(fr::Slots&& slots, bool radix, fr_ct* out) {
+        const size_t per = radix ? 4 : 1, n = slots.size() / per;
+        reserve_handles(n);
+        const std::vector<int> s = slots.release();
+        for (size_t i = 0; i < n; ++i) {
+            fr::HandleRec r;
+            r.is_bool = !radix;
+            for (size_t b = 0; b < per; ++b) r.b[b].slot = s[per * i + b];
+            out[i] = new_handle(r);
+        }
     }
     fr::HandleRec& get(fr_ct h) {
         if (h >= handles.size() || !handles[h].live) throw fr::Error(FR_ERR_INVALID, "invalid ciphertext handle");

@@ -49,6 +49,9 @@ struct DeviceTimers {
 
 struct ClientKey;
 struct RngKey;
+class Device;
+// arena slots owned by a call, a plan or a handle in the making (owned.h)
+using Slots = gpu::SlotsOf<Device>;
 
 class Device {
   public:
@@ -83,13 +86,13 @@ class Device {
     void encrypt_to_slots(const ClientKey& ck, const uint8_t* msgs, size_t count, const RngKey& key, uint64_t first_block,
                           const int* slots);
 
-    // compact content (keys.h): allocates `count` arena slots (returned in `slots`) and
-    // rebuilds block q's LWE in slots[q] -- the masks from mask_key on the device, the body
-    // from `bodies` (count u64, little endian, any alignment; copied before the call
-    // returns).  Lane 0; stream-ordered: returns once enqueued.  The bodies and the slot
-    // list travel in one H2D copy from a pinned staging ring owned by the device (no
-    // allocation per call).  On an error no slot stays allocated.
-    void expand_to_slots(const RngKey& mask_key, uint64_t first_block, const uint8_t* bodies, size_t count, int* slots);
+    // compact content (keys.h): allocates `count` arena slots (returned) and rebuilds block
+    // q's LWE in slot q of them -- the masks from mask_key on the device, the body from
+    // `bodies` (count u64, little endian, any alignment; copied before the call returns).
+    // Lane 0; stream-ordered: returns once enqueued.  The bodies and the slot list travel in
+    // one H2D copy from a pinned staging ring owned by the device (no staging allocation per
+    // call).
+    Slots expand_to_slots(const RngKey& mask_key, uint64_t first_block, const uint8_t* bodies, size_t count);
     // ms of the last expand_to_slots' kernel under fr_set_profiling (HIP events; a profiled
     // call waits for its kernel)
     double expand_ms() const { return expand_ms_; }
@@ -108,6 +111,10 @@ class Device {
     void slots_to_device_async(const int* slots, size_t n, uint64_t* dst);
     void* stream() const { return cur().stream.get(); }
     void zero_slot(int slot);
+    // slots ever handed out (the high-water mark) and the free list's length; a slot whose
+    // free is deferred counts as neither until the next sync()
+    size_t arena_slots() const { return next_slot_; }
+    size_t arena_free_slots() const { return free_slots_.size(); }
 
     // run one dependency level of gates (all independent), async on the stream
     void run_level(const DevGate* gates, size_t n);
@@ -116,13 +123,13 @@ class Device {
     // n_refs > 0: the batch reads content references (in_slot = -1 - r, r < n_refs)
     // through the content map bound last (bind_content, at least n_refs entries)
     void run_level_resident(const DevGate* d_gates, const DevGate* host, size_t n, size_t n_refs = 0);
-    // validated (content references r < n_refs allowed), synchronous
-    DevGate* upload_gates(const DevGate* gates, size_t n, size_t n_refs = 0);
+    // validated (content references r < n_refs allowed), synchronous; the batch is the
+    // caller's (a Plan's: plan.h says when it may go)
+    gpu::DevBuf<DevGate> upload_gates(const DevGate* gates, size_t n, size_t n_refs = 0);
     // content map of a template plan: reference r reads arena slot cmap[r] (-1: not
     // read by the plan).  Stream-ordered: launches enqueued after this call see it,
     // launches enqueued before it keep the previous map.
     void bind_content(const int* cmap, size_t n);
-    void free_gates(DevGate* d);                            // after the stream drained
     // linear combination without bootstrap (NOT of a boolean): out = offset*2^58 + sum w*in
     void run_linear(const DevGate& g);
     void sync();

@@ -377,17 +377,11 @@ void Device::run_level_resident(const DevGate* d_gates, const DevGate* host, siz
     launch_level(d_gates, host, n);
 }
 
-DevGate* Device::upload_gates(const DevGate* gates, size_t n, size_t n_refs) {
+gpu::DevBuf<DevGate> Device::upload_gates(const DevGate* gates, size_t n, size_t n_refs) {
     validate_gates(gates, n, n_refs);
     gpu::DevBuf<DevGate> d(std::max<size_t>(n, 1));
     HIP_CHECK(hipMemcpy(d.get(), gates, sizeof(DevGate) * n, hipMemcpyHostToDevice));
-    return d.release();  // the plan's, until free_gates
-}
-
-void Device::free_gates(DevGate* d) {
-    if (!d) return;
-    HIP_CHECK(hipStreamSynchronize(STREAM));
-    gpu::dev_free(d);
+    return d;
 }
 
 void Device::launch_level(const DevGate* d_gates, const DevGate* host, size_t n) {
@@ -471,9 +465,8 @@ void Device::sync() {
 void Device::keyswitch_host(const uint64_t* in, size_t count, uint64_t* out) {
     if (!has_keys()) throw Error(FR_ERR_NO_KEY, "server key not uploaded");
     HIP_CHECK(hipStreamSynchronize(STREAM));  // queued matches read the scratch and the gate ring (blind_rotate_host)
-    std::vector<int> slots(count);
+    Slots slots(*this, count);
     std::vector<DevGate> gates(count);
-    for (size_t i = 0; i < count; ++i) slots[i] = alloc_slot();
     write_slots(slots.data(), count, in);
     for (size_t i = 0; i < count; ++i) {
         std::memset(&gates[i], 0, sizeof(DevGate));
@@ -493,7 +486,6 @@ void Device::keyswitch_host(const uint64_t* in, size_t count, uint64_t* out) {
     const int ks = p_.ks_stride();
     for (size_t i = 0; i < count; ++i)
         HIP_CHECK(hipMemcpy(out + i * (p_.n + 1), d_ks + i * ks, 8 * (size_t)(p_.n + 1), hipMemcpyDeviceToHost));
-    for (int s : slots) free_slot(s);
 }
 
 // a blind-rotation job without inputs: n_out LUTs of 16 bytes, output slots filled in by run_br_jobs
@@ -520,17 +512,16 @@ void Device::run_br_jobs(const uint64_t* ks_in, std::vector<DevGate>& gates, uin
     const int ks = p_.ks_stride();
     for (size_t i = 0; i < count; ++i)
         HIP_CHECK(hipMemcpy(d_ks + i * ks, ks_in + i * (p_.n + 1), 8 * (size_t)(p_.n + 1), hipMemcpyHostToDevice));
-    std::vector<int> slots;
+    size_t n_out = 0;
+    for (auto& g : gates) n_out += (size_t)g.n_out;
+    Slots slots(*this, n_out);
+    n_out = 0;
     for (auto& g : gates)
-        for (int f = 0; f < g.n_out; ++f) {
-            slots.push_back(alloc_slot());
-            g.out_slot[f] = slots.back();
-        }
+        for (int f = 0; f < g.n_out; ++f) g.out_slot[f] = slots[n_out++];
     HIP_CHECK(hipMemcpy(gates_.device(), gates.data(), sizeof(DevGate) * count, hipMemcpyHostToDevice));
     launch_br(gates_.device(), d_ks, count);
     HIP_CHECK(hipStreamSynchronize(STREAM));
     for (size_t i = 0; i < slots.size(); ++i) read_slot(slots[i], out + i * p_.lwe_len());
-    for (int s : slots) free_slot(s);
 }
 
 void Device::blind_rotate_host(const uint64_t* ks_in, const uint8_t* luts, size_t count, uint64_t* out) {

@@ -326,50 +326,45 @@ __global__ void __launch_bounds__(256) k_expand_blocks(RngKey mask_key, int big,
     if (tid == 0) o[big] = bodies[q];
 }
 
-void Device::expand_to_slots(const RngKey& mask_key, uint64_t first_block, const uint8_t* bodies, size_t count,
-                             int* slots) {
-    if (!count) return;
+Slots Device::expand_to_slots(const RngKey& mask_key, uint64_t first_block, const uint8_t* bodies, size_t count) {
+    Slots slots(*this);
+    if (!count) return slots;
     const int big = p_.big();
     if (big % 8) throw Error(FR_ERR_INVALID, "device expansion: kN must be a multiple of 8");
     if (lane_ != 0) throw Error(FR_ERR_INVALID, "device expansion: lane 0 only");
     if (count > (size_t)1 << 30) throw Error(FR_ERR_INVALID, "device expansion: too many blocks");
     // every slot first: alloc_slot may grow the arena, which moves it (ensure_arena)
-    size_t got = 0;
-    try {
-        for (; got < count; ++got) slots[got] = alloc_slot();
-        // staging: the bodies [count] u64, then the slot list [count] int, in one H2D copy
-        const size_t need = 12 * count;
-        const hipStream_t s = STREAM;
-        xstage_.reserve(need, 12 * 4096, s);
-        uint8_t* h = xstage_.acquire();
-        std::memcpy(h, bodies, 8 * count);
-        std::memcpy(h + 8 * count, slots, 4 * count);
-        xstage_.commit(need, s);
-        // the device side is reused in stream order: the next call's copy runs after this kernel
-        gpu::Event t0, t1;
-        if (profiling_) {
-            t0 = take_event();
-            t1 = take_event();
-            HIP_CHECK(hipEventRecord(t0.get(), s));
-        }
-        const uint8_t* d = xstage_.device();
-        k_expand_blocks<<<(unsigned)count, 256, 0, s>>>(mask_key, big, first_block, (const uint64_t*)d,
-                                                       (const int*)(d + 8 * count), p_.slot_stride(), d_arena_.get());
-        HIP_CHECK(hipGetLastError());
-        if (profiling_) {
-            // the probe's figure (fr_device_timers_content): a profiled call waits for its kernel
-            HIP_CHECK(hipEventRecord(t1.get(), s));
-            HIP_CHECK(hipEventSynchronize(t1.get()));
-            float ms = 0;
-            HIP_CHECK(hipEventElapsedTime(&ms, t0.get(), t1.get()));
-            expand_ms_ = ms;
-            event_pool_.push_back(std::move(t0));
-            event_pool_.push_back(std::move(t1));
-        }
-    } catch (...) {
-        for (size_t i = 0; i < got; ++i) free_slot(slots[i]);
-        throw;
+    slots.alloc(count);
+    // staging: the bodies [count] u64, then the slot list [count] int, in one H2D copy
+    const size_t need = 12 * count;
+    const hipStream_t s = STREAM;
+    xstage_.reserve(need, 12 * 4096, s);
+    uint8_t* h = xstage_.acquire();
+    std::memcpy(h, bodies, 8 * count);
+    std::memcpy(h + 8 * count, slots.data(), 4 * count);
+    xstage_.commit(need, s);
+    // the device side is reused in stream order: the next call's copy runs after this kernel
+    gpu::Event t0, t1;
+    if (profiling_) {
+        t0 = take_event();
+        t1 = take_event();
+        HIP_CHECK(hipEventRecord(t0.get(), s));
     }
+    const uint8_t* d = xstage_.device();
+    k_expand_blocks<<<(unsigned)count, 256, 0, s>>>(mask_key, big, first_block, (const uint64_t*)d,
+                                                   (const int*)(d + 8 * count), p_.slot_stride(), d_arena_.get());
+    HIP_CHECK(hipGetLastError());
+    if (profiling_) {
+        // the probe's figure (fr_device_timers_content): a profiled call waits for its kernel
+        HIP_CHECK(hipEventRecord(t1.get(), s));
+        HIP_CHECK(hipEventSynchronize(t1.get()));
+        float ms = 0;
+        HIP_CHECK(hipEventElapsedTime(&ms, t0.get(), t1.get()));
+        expand_ms_ = ms;
+        event_pool_.push_back(std::move(t0));
+        event_pool_.push_back(std::move(t1));
+    }
+    return slots;
 }
 
 static void need_device_keygen_point(const Params& p, const char* what) {

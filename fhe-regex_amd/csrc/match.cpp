@@ -79,9 +79,10 @@ std::vector<int32_t> content_signature(fr_ctx* ctx, const fr_ct* content, size_t
     return sig;
 }
 
-void drop_cached(fr_ctx* ctx, CachedMatch& e) {
-    ctx->plans.slots_held -= std::min(ctx->plans.slots_held, e.plan.slot.size());
-    if (ctx->dev) release_plan(*ctx->dev, e.plan);
+// entry i goes: its plan waits for every lane, then gives its slots and its batch back (Plan)
+void drop_cached(fr_plan_cache& pc, size_t i) {
+    pc.slots_held -= std::min(pc.slots_held, pc.entries[i]->plan.slot.size());
+    pc.entries.erase(pc.entries.begin() + (long)i);
 }
 // drop least-recently-used plans until `entries` and `slots` more fit
 void evict_for(fr_ctx* ctx, size_t entries, size_t slots) {
@@ -91,8 +92,7 @@ void evict_for(fr_ctx* ctx, size_t entries, size_t slots) {
         size_t v = 0;
         for (size_t i = 1; i < pc.entries.size(); ++i)
             if (pc.entries[i]->last_use < pc.entries[v]->last_use) v = i;
-        drop_cached(ctx, *pc.entries[v]);
-        pc.entries.erase(pc.entries.begin() + (long)v);
+        drop_cached(pc, v);
     }
 }
 
@@ -188,7 +188,8 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
         if (keep) evict_for(ctx, 1, G * M);  // before the new plan allocates its slots
         fresh = compile_plan(ctx, gates, inputs, keep);
         if (keep) {
-            // keep the plan: its slots stay allocated, its batches go to the device once
+            // keep the plan: its slots stay allocated, its batches go to the device once; the
+            // entry is complete before the cache sees it
             auto e = std::make_unique<CachedMatch>();
             e->key = std::move(key);
             e->parts = parts;
@@ -199,10 +200,10 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
             e->rec = rec;
             e->last_use = ++pc.clock;
             e->plan = std::move(fresh);
-            pc.slots_held += e->plan.slot.size();
+            e->plan.d_gates = dev.upload_gates(e->plan.gates.data(), e->plan.gates.size(), e->plan.n_refs);
             c = e.get();
             pc.entries.push_back(std::move(e));
-            c->plan.d_gates = dev.upload_gates(c->plan.gates.data(), c->plan.gates.size(), c->plan.n_refs);
+            pc.slots_held += c->plan.slot.size();
         }
     }
     // 2. launch and emit
@@ -226,7 +227,7 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
             outs[m * nO + j] = make_output(ctx, o, plan.slot, take);
         }
     if (n_parts) *n_parts = nO;
-    if (!c) free_plan_slots(dev, plan.slot);  // later users of these slots are ordered after the launches (one stream)
+    if (!c) fresh.slot.reset();  // later users of these slots are ordered after the launches (one stream)
     if (!ctx->async_match) dev.sync();
     double t2 = now_ms();
     if (st) {
@@ -249,14 +250,6 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
 }
 
 }  // namespace
-
-// Cached plans go while the device is alive (fr_ctx's members are destroyed after this)
-fr_ctx::~fr_ctx() {
-    try {
-        for (auto& e : plans.entries) drop_cached(this, *e);
-    } catch (...) {
-    }
-}
 
 extern "C" {
 
@@ -283,10 +276,7 @@ int fr_set_lanes(fr_ctx* ctx, int32_t n) {
         // the lanes' plan copies go with the lanes (their slots are held by the cache)
         fr_plan_cache& pc = ctx->plans;
         for (size_t i = pc.entries.size(); i-- > 0;)
-            if (pc.entries[i]->lane != 0) {
-                drop_cached(ctx, *pc.entries[i]);
-                pc.entries.erase(pc.entries.begin() + (long)i);
-            }
+            if (pc.entries[i]->lane != 0) drop_cached(pc, i);
         dev.set_lanes(n);
         ctx->next_lane = 0;
     })
@@ -387,13 +377,6 @@ int fr_shard_plan(fr_ctx* ctx, const fr_ct* content, size_t n, const char* patte
         check_content(ctx, prog, content, n, 1);
         auto sh = std::make_unique<fr_shard>();
         sh->plan = compile_plan(ctx, prog.gates, std::vector<fr_ct>(content, content + n));
-        struct Guard {
-            fr_ctx* ctx;
-            fr_shard* sh;
-            ~Guard() {
-                if (sh) free_plan_slots(ctx->device(), sh->plan.slot);
-            }
-        } guard{ctx, sh.get()};
         Plan& P = sh->plan;
         P.d_gates = dev.upload_gates(P.gates.data(), P.gates.size());
         sh->out = ProgOut{prog.out_gate, prog.out_w, prog.out_const};
@@ -410,7 +393,6 @@ int fr_shard_plan(fr_ctx* ctx, const fr_ct* content, size_t n, const char* patte
         fill_stats(sh->stats, rec, P);
         sh->stats.host_ms = now_ms() - t0;
         if (st) *st = sh->stats;
-        guard.sh = nullptr;
         *out = sh.release();
     })
 }
@@ -441,7 +423,7 @@ int fr_shard_run(fr_ctx* ctx, fr_shard* sh, uint32_t level, uint32_t begin, uint
         shard_level_range(sh, level, begin, end, first, count);
         const Plan& P = sh->plan;
         const size_t a = P.level_off[level] + begin;
-        ctx->device().run_level_resident(P.d_gates + a, P.gates.data() + a, end - begin);
+        ctx->device().run_level_resident(P.d_gates.get() + a, P.gates.data() + a, end - begin);
     })
 }
 int fr_shard_export(fr_ctx* ctx, fr_shard* sh, uint32_t level, uint32_t begin, uint32_t end, uint64_t* dev_dst) {
@@ -472,9 +454,7 @@ int fr_shard_finish(fr_ctx* ctx, fr_shard* sh, fr_ct* out, fr_match_stats* st) {
 int fr_shard_free(fr_ctx* ctx, fr_shard* sh) {
     FR_TRY({
         NEED(ctx);
-        if (!sh) return FR_OK;
-        std::unique_ptr<fr_shard> own(sh);
-        if (ctx->dev) release_plan(*ctx->dev, sh->plan);
+        delete sh;  // its plan waits for every lane first (Plan)
     })
 }
 

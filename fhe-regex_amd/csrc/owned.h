@@ -2,11 +2,12 @@
 // streams, and the pinned staging ring.  No HIP header: device.h is compiled by g++ too, so the
 // calls that release and allocate are defined in device.hip.  Every destructor releases and
 // ignores the error; every allocation that fails throws Error(FR_ERR_HIP) and leaves its
-// holder empty.
+// holder empty.  SlotsOf owns arena slots the same way, for the layer above Device.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include <utility>
+#include <vector>
 
 // the runtime's handle types, as hip/hip_runtime_api.h declares them
 typedef struct ihipStream_t* hipStream_t;
@@ -76,6 +77,67 @@ template <class T>
 using DevBuf = Buf<T, dev_alloc, dev_free>;
 template <class T>
 using PinnedBuf = Buf<T, pinned_alloc, pinned_free>;
+
+// Arena slots of a call or of a plan, given back when the owner goes.  Arena is anything with
+// int alloc_slot() and void free_slot(int): Device in the library (device.h: Slots), a counting
+// fake in tests/slot_owner_check.cpp.  Slots are taken and given back in ascending index; an
+// entry of -1 is a slot handed on (take) and is skipped.
+template <class Arena>
+class SlotsOf {
+  public:
+    SlotsOf() = default;
+    explicit SlotsOf(Arena& a, size_t n = 0) : a_(&a) { alloc(n); }
+    SlotsOf(SlotsOf&& o) noexcept : a_(o.a_), s_(std::move(o.s_)) { o.s_.clear(); }
+    SlotsOf& operator=(SlotsOf&& o) noexcept {
+        if (this != &o) {
+            drop();
+            a_ = o.a_;
+            s_ = std::move(o.s_);
+            o.s_.clear();
+        }
+        return *this;
+    }
+    ~SlotsOf() { drop(); }
+    Arena* arena() const { return a_; }
+    size_t size() const { return s_.size(); }
+    const int* data() const { return s_.data(); }
+    int operator[](size_t i) const { return s_[i]; }
+    // n fresh slots in place of the previous ones, all or nothing: empty after a throw
+    void alloc(size_t n) {
+        reset();
+        try {
+            s_.reserve(n);
+            while (s_.size() < n) s_.push_back(a_->alloc_slot());
+        } catch (...) {
+            drop();
+            throw;
+        }
+    }
+    void reset() {
+        for (int& s : s_)
+            if (s >= 0) a_->free_slot(std::exchange(s, -1));
+        s_.clear();
+    }
+    // slot i becomes the caller's
+    int take(size_t i) { return std::exchange(s_[i], -1); }
+    // every slot becomes the caller's (handles)
+    std::vector<int> release() {
+        std::vector<int> v = std::move(s_);
+        s_.clear();
+        return v;
+    }
+
+  private:
+    void drop() noexcept {  // reset for destructors: an error of free_slot is ignored
+        try {
+            reset();
+        } catch (...) {
+            s_.clear();
+        }
+    }
+    Arena* a_ = nullptr;
+    std::vector<int> s_;
+};
 
 template <class H, void (*Destroy)(H) noexcept>
 class Handle {

@@ -6,18 +6,6 @@
 
 namespace fr {
 
-void free_plan_slots(Device& dev, std::vector<int>& slot) {
-    for (int& s : slot)
-        if (s >= 0) dev.free_slot(s), s = -1;
-}
-
-void release_plan(Device& dev, Plan& P) {
-    dev.sync();  // no level of this plan may still be in flight (every match ends synchronised)
-    free_plan_slots(dev, P.slot);
-    dev.free_gates(P.d_gates);
-    P.d_gates = nullptr;
-}
-
 Plan compile_plan(fr_ctx* ctx, const std::vector<PGate>& gates, const std::vector<fr_ct>& inputs, bool content_refs) {
     Device& dev = ctx->keyed_device();
     auto block_slot = [&](int cb) -> const Block& { return ctx->get(inputs[(size_t)(cb / 4)]).b[cb % 4]; };
@@ -31,16 +19,7 @@ Plan compile_plan(fr_ctx* ctx, const std::vector<PGate>& gates, const std::vecto
         return true;
     });
     Plan P;
-    P.slot.assign(gates.size(), -1);
-    struct Guard {
-        Device& dev;
-        std::vector<int>& slot;
-        bool armed = true;
-        ~Guard() {
-            if (armed) free_plan_slots(dev, slot);
-        }
-    } guard{dev, P.slot};
-    for (size_t g = 0; g < gates.size(); ++g) P.slot[g] = dev.alloc_slot();
+    P.slot = Slots(dev, gates.size());
     P.gates = std::move(S.jobs);
     for (DevGate& d : P.gates) {
         for (int q = 0; q < d.n_in; ++q)
@@ -55,14 +34,13 @@ Plan compile_plan(fr_ctx* ctx, const std::vector<PGate>& gates, const std::vecto
     P.rotations = P.gates.size();
     P.levels = S.levels;
     P.max_width = S.max_width;
-    guard.armed = false;
     return P;
 }
 
 void launch_plan(Device& dev, const Plan& P) {
     for (size_t l = 0; l + 1 < P.level_off.size(); ++l) {
         const size_t a = P.level_off[l], n = P.level_off[l + 1] - a;
-        if (P.d_gates) dev.run_level_resident(P.d_gates + a, P.gates.data() + a, n, P.n_refs);
+        if (P.d_gates) dev.run_level_resident(P.d_gates.get() + a, P.gates.data() + a, n, P.n_refs);
         else dev.run_level(P.gates.data() + a, n);
     }
 }
@@ -75,44 +53,41 @@ void add_plan_stats(const Plan& P, fr_match_stats* st) {
     st->max_level_width = std::max<uint64_t>(st->max_level_width, P.max_width);
 }
 
-std::vector<int> execute_gates(fr_ctx* ctx, const std::vector<PGate>& gates, const std::vector<fr_ct>& inputs,
-                               fr_match_stats* st) {
+Slots execute_gates(fr_ctx* ctx, const std::vector<PGate>& gates, const std::vector<fr_ct>& inputs, fr_match_stats* st) {
     Plan P = compile_plan(ctx, gates, inputs);
     launch_plan(ctx->device(), P);
     add_plan_stats(P, st);
     return std::move(P.slot);
 }
 
-int linear_to_new_slot(Device& dev, int slot, int w, int offset) {
+Slots linear_to_new_slot(Device& dev, int slot, int w, int offset) {
+    Slots out(dev, 1);
     DevGate d;
     std::memset(&d, 0, sizeof d);
     d.n_in = 1;
     d.in_slot[0] = slot;
     d.in_w[0] = w;
     d.offset = offset;
-    d.out_slot[0] = dev.alloc_slot();
+    d.out_slot[0] = out[0];
     dev.run_linear(d);
-    return d.out_slot[0];
+    return out;
 }
 
-fr_ct make_output(fr_ctx* ctx, ProgOut o, std::vector<int>& slots, bool take_slot) {
+fr_ct make_output(fr_ctx* ctx, ProgOut o, Slots& slots, bool take_slot) {
     if (o.gate < 0) return ctx->new_bool(-1, (uint8_t)o.cst);
-    if (take_slot && o.w == 1 && o.cst == 0) {
-        const int s = slots[o.gate];
-        slots[o.gate] = -1;
-        return ctx->new_bool(s);
-    }
-    return ctx->new_bool(linear_to_new_slot(ctx->device(), slots[o.gate], o.w, 2 * o.cst));
+    ctx->reserve_handles(1);  // new_bool cannot fail once a slot has left its owner
+    if (take_slot && o.w == 1 && o.cst == 0) return ctx->new_bool(slots.take(o.gate));
+    return ctx->new_bool(linear_to_new_slot(ctx->device(), slots[o.gate], o.w, 2 * o.cst).take(0));
 }
-fr_ct finish_output(fr_ctx* ctx, ProgOut o, std::vector<int>& slots, bool take_slot) {
+fr_ct finish_output(fr_ctx* ctx, ProgOut o, Slots& slots, bool take_slot) {
     const fr_ct h = make_output(ctx, o, slots, take_slot);
-    if (take_slot) free_plan_slots(ctx->device(), slots);
+    if (take_slot) slots.reset();
     ctx->device().sync();
     return h;
 }
 
 fr_ct run_program(fr_ctx* ctx, const Program& prog, const std::vector<fr_ct>& inputs, fr_match_stats* st) {
-    std::vector<int> slots = execute_gates(ctx, prog.gates, inputs, st);
+    Slots slots = execute_gates(ctx, prog.gates, inputs, st);
     return finish_output(ctx, ProgOut{prog.out_gate, prog.out_w, prog.out_const}, slots, true);
 }
 

@@ -141,17 +141,32 @@ Schedule build_schedule(const std::vector<PGate>& gates, size_t n_content, bool 
 }
 
 // A device plan: the schedule with references mapped to arena slots (one slot per
-// program gate).  The slots allocated so far are returned if compilation throws.
-// A template plan (n_refs > 0) keeps its content inputs as references
+// program gate).  A template plan (n_refs > 0) keeps its content inputs as references
 // (in_slot = -1 - (4 pos + block)) that a content map bound per call resolves
 // (Device::bind_content), so one plan serves every content of the same shape.
+// A plan owns its slots and its device batch and is move-only.  The one rule of release: a
+// resident plan (d_gates: a cached match, a shard plan) is replayed on every lane, so nothing
+// of it goes while a level of it may be in flight -- its destructor synchronises every lane
+// first.  A plan without a device batch runs once, on lane 0: its slots go back in stream
+// order, without a wait.
 struct Plan {
     std::vector<DevGate> gates;     // levels concatenated
     std::vector<size_t> level_off;  // level l (0-based): gates [level_off[l], level_off[l+1])
-    std::vector<int> slot;          // output slot per program gate
+    Slots slot;                     // output slot per program gate
     uint64_t pbs = 0, rotations = 0, levels = 0, max_width = 0;
     size_t n_refs = 0;              // template plan: content references (4 per position)
-    DevGate* d_gates = nullptr;     // device-resident copy (cached plans)
+    gpu::DevBuf<DevGate> d_gates;   // device-resident copy (cached plans)
+
+    Plan() = default;
+    Plan(Plan&&) = default;
+    Plan& operator=(Plan&&) = default;  // (onto a plan that is not resident)
+    ~Plan() {
+        if (!d_gates) return;
+        try {
+            slot.arena()->sync();
+        } catch (...) {  // (the members release all the same)
+        }
+    }
 };
 
 Plan compile_plan(fr_ctx* ctx, const std::vector<PGate>& gates, const std::vector<fr_ct>& inputs,
@@ -159,22 +174,18 @@ Plan compile_plan(fr_ctx* ctx, const std::vector<PGate>& gates, const std::vecto
 // enqueue every level of a plan (async on the device stream)
 void launch_plan(Device& dev, const Plan& P);
 void add_plan_stats(const Plan& P, fr_match_stats* st);
-void free_plan_slots(Device& dev, std::vector<int>& slot);
-// a resident plan gives back its slots and its device batches, once no level of it is in flight
-void release_plan(Device& dev, Plan& P);
 
-// Runs a program and returns one slot per gate (the caller owns those slots).
-std::vector<int> execute_gates(fr_ctx* ctx, const std::vector<PGate>& gates, const std::vector<fr_ct>& inputs,
-                               fr_match_stats* st);
+// Runs a program and returns one slot per gate.
+Slots execute_gates(fr_ctx* ctx, const std::vector<PGate>& gates, const std::vector<fr_ct>& inputs, fr_match_stats* st);
 // out = offset * Delta/2 + w * arena[slot] in a fresh slot (a linear op, no bootstrap), enqueued
-int linear_to_new_slot(Device& dev, int slot, int w, int offset);
+Slots linear_to_new_slot(Device& dev, int slot, int w, int offset);
 // result handle of a program: boolean o.cst + o.w * gate slot (a linear
 // op, no bootstrap), or trivial.  take_slot: the output gate's slot becomes the
 // result's (else the result is a fresh slot and `slots` stay untouched).  Async:
 // the caller synchronises the stream before handing the result out.
-fr_ct make_output(fr_ctx* ctx, ProgOut o, std::vector<int>& slots, bool take_slot);
+fr_ct make_output(fr_ctx* ctx, ProgOut o, Slots& slots, bool take_slot);
 // the same, synchronised; take_slot also frees the other slots
-fr_ct finish_output(fr_ctx* ctx, ProgOut o, std::vector<int>& slots, bool take_slot);
+fr_ct finish_output(fr_ctx* ctx, ProgOut o, Slots& slots, bool take_slot);
 fr_ct run_program(fr_ctx* ctx, const Program& prog, const std::vector<fr_ct>& inputs, fr_match_stats* st);
 
 }  // namespace fr

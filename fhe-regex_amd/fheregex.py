@@ -209,6 +209,7 @@ _SIGS = {
                                    C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "fr_device_info": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
     "fr_debug_scalar": (C.c_uint64, [C.c_int32, C.c_uint64, C.c_uint64]),
+    "fr_debug_arena_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "fr_export_bool_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, C.c_void_p]),
     "fr_export_bool_device_async": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, C.c_void_p]),
     "fr_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
@@ -517,6 +518,13 @@ class Context:
         v = [C.c_uint64() for _ in range(4)]
         _check(lib().fr_plan_cache_stats(self.h, *[C.byref(x) for x in v]))
         return dict(zip(("entries", "slots", "hits", "misses"), (x.value for x in v)))
+
+    def arena_stats(self):
+        """fr_debug_arena_stats, after a synchronisation of every lane: `slots` ever handed
+        out and `free_slots` on the free list (their difference is held by handles and plans)"""
+        v = [C.c_uint64() for _ in range(2)]
+        _check(lib().fr_debug_arena_stats(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("slots", "free_slots"), (x.value for x in v)))
 
     def set_profiling(self, on):
         """0/False off, 1/True blind-rotation timers, 2 also keyswitch timers (fr_set_profiling)."""

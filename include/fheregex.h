@@ -584,6 +584,11 @@ int fr_device_info(fr_ctx* ctx, char* buf, size_t buflen);
  * as u64), 2 = Z_Q -> 2^64 torus of x mod Q (from its residues),
  * 3 = modulus switch of x to 2^y, 4 = keyswitch digit y (0..4) of x (signed, as u64). */
 uint64_t fr_debug_scalar(int32_t op, uint64_t x, uint64_t y);
+/* The slot arena (test hook): synchronises every lane, so that slots whose release was
+ * deferred are recycled, then *slots = the slots ever handed out (the high-water mark) and
+ * *free_slots = the length of the free list; slots - free_slots are held by handles, cached
+ * plans and shard plans. */
+int fr_debug_arena_stats(fr_ctx* ctx, uint64_t* slots, uint64_t* free_slots);
 
 #ifdef __cplusplus
 }

@@ -489,3 +489,21 @@ def test_c_abi_consumer(tmp_path):
     res = subprocess.run([exe, os.path.join(GOLDEN, "client_key")], capture_output=True, text=True, timeout=120)
     assert res.returncode == 0, res.stderr
     assert "ok" in res.stdout
+
+
+def test_slot_owner_semantics(tmp_path):
+    """csrc/owned.h's arena-slot owner from plain C++17 against a counting fake arena that aborts
+    on a double free or a stray free (tests/slot_owner_check.cpp): all-or-nothing allocation,
+    take, release, moves, self-move and unwinding."""
+    import shutil
+    import subprocess
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    here = os.path.dirname(os.path.abspath(__file__))
+    exe = str(tmp_path / "slot_owner_check")
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I",
+                    os.path.join(os.path.dirname(here), "fhe-regex_amd", "csrc"),
+                    os.path.join(here, "slot_owner_check.cpp"), "-o", exe], check=True)
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert res.returncode == 0, res.stderr
+    assert "slot owner ok: 9 cases" in res.stdout
