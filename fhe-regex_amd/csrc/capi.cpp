@@ -46,28 +46,18 @@ void validate_params(const Params& p) {
 }  // namespace fr
 
 // eager op programs over input handles (pos 0 = a, pos 1 = b)
-static Program prog_cmp_const(int kind, uint8_t c) {
+// one output: the program's last gate
+static Program one_output(std::vector<PGate>&& gates) {
     Program p;
-    PGate lo, hi;
-    lo.ins = {{cblk(0, 0), 1}, {cblk(0, 1), 4}};
-    hi.ins = {{cblk(0, 2), 1}, {cblk(0, 3), 4}};
-    PGate fin;
-    if (kind == 0) {  // eq: [lo == c_lo] + [hi == c_hi] == 2
-        lut_eq(lo.lut, c & 15);
-        lut_eq(hi.lut, c >> 4);
-        fin.ins = {{0, 1}, {1, 1}};
-        lut_eq(fin.lut, 2);
-    } else {  // gt / le over the signs: 3*s_hi + s_lo
-        lut_sign(lo.lut, c & 15);
-        lut_sign(hi.lut, c >> 4);
-        fin.ins = {{1, 3}, {0, 1}};
-        lut_gt3(fin.lut, kind == 2);
-    }
-    p.gates = {lo, hi, fin};
-    p.out_gate = 2;
-    p.out_w = 1;
+    p.gates = std::move(gates);
+    p.outs.push_back(ProgOut{(int32_t)p.gates.size() - 1, 1, 0});
     compute_levels(p);
     return p;
+}
+// the lowering's comparison gates: the low and the high nibble test, then their combination
+static Program prog_cmp_const(VNode::Op op, uint8_t c) {
+    const bool sign = op != VNode::EQ;
+    return one_output({nibble_test_gate(sign, 0, 0, c & 15), nibble_test_gate(sign, 0, 1, c >> 4), cmp_final_gate(op, 0, 1)});
 }
 
 extern "C" {
@@ -218,17 +208,17 @@ int fr_trivial(fr_ctx* ctx, uint8_t value, fr_ct* out) {
     })
 }
 
-static int cmp_const_op(fr_ctx* ctx, fr_ct a, uint8_t c, fr_ct* out, int kind) {
+static int cmp_const_op(fr_ctx* ctx, fr_ct a, uint8_t c, fr_ct* out, VNode::Op op) {
     FR_TRY({
         NEED(ctx && out);
         if (ctx->get(a).is_bool) throw Error(FR_ERR_INVALID, "comparison operand must be a radix character");
-        Program p = prog_cmp_const(kind, c);
+        Program p = prog_cmp_const(op, c);
         *out = run_program(ctx, p, {a}, nullptr);
     })
 }
-int fr_eq_const(fr_ctx* ctx, fr_ct a, uint8_t c, fr_ct* out) { return cmp_const_op(ctx, a, c, out, 0); }
-int fr_gt_const(fr_ctx* ctx, fr_ct a, uint8_t c, fr_ct* out) { return cmp_const_op(ctx, a, c, out, 1); }
-int fr_le_const(fr_ctx* ctx, fr_ct a, uint8_t c, fr_ct* out) { return cmp_const_op(ctx, a, c, out, 2); }
+int fr_eq_const(fr_ctx* ctx, fr_ct a, uint8_t c, fr_ct* out) { return cmp_const_op(ctx, a, c, out, VNode::EQ); }
+int fr_gt_const(fr_ctx* ctx, fr_ct a, uint8_t c, fr_ct* out) { return cmp_const_op(ctx, a, c, out, VNode::GT); }
+int fr_le_const(fr_ctx* ctx, fr_ct a, uint8_t c, fr_ct* out) { return cmp_const_op(ctx, a, c, out, VNode::LE); }
 
 static int bitop(fr_ctx* ctx, fr_ct a, fr_ct b, fr_ct* out, bool is_and) {
     FR_TRY({
@@ -236,15 +226,11 @@ static int bitop(fr_ctx* ctx, fr_ct a, fr_ct b, fr_ct* out, bool is_and) {
         const HandleRec& ha = ctx->get(a);
         const HandleRec& hb = ctx->get(b);
         if (ha.is_bool && hb.is_bool) {  // booleans: one bivariate PBS on block 0
-            Program p;
             PGate g;
             g.ins = {{cblk(0, 0), 1}, {cblk(1, 0), 1}};
             if (is_and) lut_eq(g.lut, 2);
             else lut_at_least(g.lut, 1);
-            p.gates = {g};
-            p.out_gate = 0;
-            p.out_w = 1;
-            compute_levels(p);
+            const Program p = one_output({g});
             *out = run_program(ctx, p, {a, b}, nullptr);
         } else {  // general radix: per block, LUT over 4*x + y
             std::vector<PGate> gates(4);
@@ -315,32 +301,26 @@ int fr_or_many(fr_ctx* ctx, const fr_ct* in, size_t n, fr_ct* out) {
             return FR_OK;
         }
         // balanced tree of <= 16-input threshold ORs
-        Program p;
+        std::vector<PGate> gates;
         std::vector<int> cur;  // sources: negative = input q, else gate
         for (size_t q = 0; q < inputs.size(); ++q) cur.push_back(cblk((int)q, 0));
         while (cur.size() > 1) {
             std::vector<int> next;
-            size_t m = cur.size(), chunks = (m + MAX_FANIN - 1) / MAX_FANIN, start = 0;
-            for (size_t c = 0; c < chunks; ++c) {
-                size_t len = m / chunks + (c < m % chunks ? 1 : 0);
+            for_balanced_chunks(cur.size(), [&](size_t start, size_t len) {
                 if (len == 1) {
                     next.push_back(cur[start]);
-                } else {
-                    PGate g;  // OR of <= 16 booleans: sign of sum - 1/2
-                    for (size_t t = 0; t < len; ++t) g.ins.push_back({cur[start + t], 1});
-                    g.kind = GATE_SIGN;
-                    g.offset = -1;
-                    p.gates.push_back(g);
-                    next.push_back((int)p.gates.size() - 1);
+                    return;
                 }
-                start += len;
-            }
+                PGate g;  // OR of <= 16 booleans: sign of sum - 1/2
+                for (size_t t = 0; t < len; ++t) g.ins.push_back({cur[start + t], 1});
+                g.kind = GATE_SIGN;
+                g.offset = -1;
+                gates.push_back(g);
+                next.push_back((int)gates.size() - 1);
+            });
             cur = next;
         }
-        p.out_gate = cur[0];
-        p.out_w = 1;
-        compute_levels(p);
-        *out = run_program(ctx, p, inputs, nullptr);
+        *out = run_program(ctx, one_output(std::move(gates)), inputs, nullptr);
     })
 }
 
@@ -388,8 +368,7 @@ int fr_debug_enumeration_cost(const char* pattern, int32_t grammar, size_t n_cha
     FR_TRY({
         NEED(pattern && outcome && counted && enumerated && lo <= hi && cap < UINT64_MAX);
         NEED(grammar == FR_GRAMMAR_REFERENCE || grammar == FR_GRAMMAR_EXT);
-        GrammarScope scope(grammar);
-        ReP re = parse(pattern);
+        ReP re = parse(pattern, grammar);
         uint64_t c = 0;
         const CostOutcome o = enumeration_cost(n_chars, re, lo, hi, cap, &c, mem_bytes);
         *outcome = o == COST_COUNTED ? FR_COST_COUNTED : o == COST_PANIC ? FR_COST_PANIC : FR_COST_MEMORY;
@@ -402,16 +381,15 @@ int fr_debug_enumeration_cost(const char* pattern, int32_t grammar, size_t n_cha
 static void plain_match(const char* content, size_t len, const char* pattern, size_t lo, size_t hi, int32_t lowering,
                         int32_t engine, int32_t grammar, size_t max_parts, fr_plain_result* out,
                         std::vector<int>& vals) {
-    ValueDag dag;
-    GrammarScope scope(grammar);
-    Recorded rec = record_has_match_engine(dag, len, pattern, lo, hi, engine);
-    std::vector<int16_t> memo;
     std::memset(out, 0, sizeof *out);
+    const CompiledMatch cm = compile_match(MatchSpec{pattern, len, lo, hi, engine, grammar, lowering, (int)max_parts});
+    const Recorded& rec = cm.rec;
+    const Program& prog = cm.prog;
+    std::vector<int16_t> memo;
     out->ct_ops = rec.ct_ops;
     out->cache_hits = rec.cache_hits;
     out->n_branches = rec.n_branches;
-    out->result_recorded = dag.eval(rec.root, (const uint8_t*)content, memo);
-    Program prog = lower(dag, rec.root, lowering, (int)max_parts);
+    out->result_recorded = cm.dag.eval(rec.root, (const uint8_t*)content, memo);
     out->pbs = prog.gates.size();
     out->levels = (uint64_t)prog.levels;
     out->max_level_width = prog.max_width;

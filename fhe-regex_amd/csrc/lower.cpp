@@ -29,6 +29,41 @@ void lut_at_least(uint8_t* lut, int m) {
     for (int x = 0; x < 16; ++x) lut[x] = (uint8_t)(x >= m);
 }
 
+PGate nibble_test_gate(bool sign, int pos, int half, int v) {
+    PGate g;
+    g.ins = {{cblk(pos, 2 * half), 1}, {cblk(pos, 2 * half + 1), 4}};
+    if (sign) lut_sign(g.lut, v);
+    else lut_eq(g.lut, v);
+    return g;
+}
+PGate cmp_final_gate(VNode::Op op, int lo_gate, int hi_gate) {
+    PGate g;
+    if (op == VNode::EQ) {
+        g.ins = {{lo_gate, 1}, {hi_gate, 1}};
+        lut_eq(g.lut, 2);
+    } else {
+        g.ins = {{hi_gate, 3}, {lo_gate, 1}};
+        lut_gt3(g.lut, op == VNode::LE);
+    }
+    return g;
+}
+PGate pair_gate(bool is_and, const PairOperand& p, const PairOperand& q) {
+    PGate g;
+    int offset = 0;
+    for (const PairOperand* o : {&p, &q}) {
+        if (o->gate < 0) {
+            offset += o->c;  // trivial operand (e.g. or(false, x), execution.rs:154-164)
+        } else {
+            g.ins.push_back({o->gate, o->neg ? -1 : 1});
+            offset += o->neg;
+        }
+    }
+    g.offset = 2 * offset;
+    if (is_and) lut_eq(g.lut, 2);
+    else lut_at_least(g.lut, 1);
+    return g;
+}
+
 namespace {
 
 struct Lit {
@@ -46,7 +81,16 @@ struct Form {
     std::bitset<256> set;   // SET: the characters for which the form is 1
 };
 
-inline int cblock(int pos, int blk) { return -(1 + pos * 4 + blk); }
+// what leads a hash-consing key: one class of gates each
+enum KeyTag : int64_t {
+    KEY_NIBBLE = 1,         // kind, pos, half, v, tag
+    KEY_THRESHOLD = 2,      // is_and, literals
+    KEY_CMP = 3,            // op, pos, c, tag
+    KEY_EQ = 4,             // pos, c
+    KEY_FAITHFUL_PAIR = 5,  // is_and, the DAG node: one gate per reference op
+    KEY_SET_PRODUCT = 7,    // the two class gates, columns, LUT
+    KEY_TREE_PAIR = 9,      // is_and, chain root, k-th join of the chain
+};
 
 struct KeyHash {  // FNV-1a over the words of a gate key
     size_t operator()(const std::vector<int64_t>& k) const {
@@ -92,11 +136,7 @@ struct Lowerer {
     }
     // [x_{2h} + 4 x_{2h+1} ? v] over the packed nibble of char `pos`
     int nibble_gate(int kind, int pos, int half, int v, int tag) {
-        PGate g;
-        g.ins = {{cblock(pos, 2 * half), 1}, {cblock(pos, 2 * half + 1), 4}};
-        if (kind == 0) lut_eq(g.lut, v);
-        else lut_sign(g.lut, v);
-        return add_gate({1, kind, pos, half, v, tag}, std::move(g));
+        return add_gate({KEY_NIBBLE, kind, pos, half, v, tag}, nibble_test_gate(kind != 0, pos, half, v));
     }
     // arbitrary 16-entry LUT over the packed nibble (x_{2h} + 4 x_{2h+1}) of char `pos`
     // (its own index, keyed without a heap-allocated key: the lowering's most frequent lookup)
@@ -123,7 +163,7 @@ struct Lowerer {
         auto it = nib_index.find(key);
         if (it != nib_index.end()) return it->second;
         PGate g;
-        g.ins = {{cblock(pos, 2 * half), 1}, {cblock(pos, 2 * half + 1), 4}};
+        g.ins = {{cblk(pos, 2 * half), 1}, {cblk(pos, 2 * half + 1), 4}};
         std::memcpy(g.lut, lut, 16);
         prog.gates.push_back(std::move(g));
         const int id = (int)prog.gates.size() - 1;
@@ -137,6 +177,13 @@ struct Lowerer {
     //    nibble PBS, mergeable into a parent AND;
     //  * rows x cols <= 16: two class LUTs + one PBS on (cols*row + col);
     //  * otherwise OR over row classes of AND{[hi in class], [lo in L_class]}.
+    // index of signature `sig` among the classes, appended if new
+    static int class_index(std::vector<std::bitset<16>>& cls, const std::bitset<16>& sig) {
+        for (size_t i = 0; i < cls.size(); ++i)
+            if (cls[i] == sig) return (int)i;
+        cls.push_back(sig);
+        return (int)cls.size() - 1;
+    }
     Form lower_set(int pos, const std::bitset<256>& S) {
         // row h = bits 16h..16h+15 of S, read a 64-bit word at a time
         std::bitset<16> rowset[16];
@@ -150,15 +197,7 @@ struct Lowerer {
         // row classes: distinct non-empty lo-sets (class 0 = empty)
         std::vector<std::bitset<16>> rc;
         int rowcls[16];
-        for (int h = 0; h < 16; ++h) {
-            rowcls[h] = 0;
-            if (rowset[h].none()) continue;
-            int c = -1;
-            for (size_t i = 0; i < rc.size(); ++i)
-                if (rc[i] == rowset[h]) c = (int)i;
-            if (c < 0) { rc.push_back(rowset[h]); c = (int)rc.size() - 1; }
-            rowcls[h] = c + 1;
-        }
+        for (int h = 0; h < 16; ++h) rowcls[h] = rowset[h].none() ? 0 : class_index(rc, rowset[h]) + 1;
         if (rc.size() == 1) {  // product set
             uint8_t lh[16], ll[16];
             bool allh = true, alll = true;
@@ -182,11 +221,7 @@ struct Lowerer {
         for (int l = 0; l < 16; ++l) {
             std::bitset<16> sig;
             for (int h = 0; h < 16; ++h) sig[h] = rowset[h][l];
-            int c = -1;
-            for (size_t i = 0; i < cc.size(); ++i)
-                if (cc[i] == sig) c = (int)i;
-            if (c < 0) { cc.push_back(sig); c = (int)cc.size() - 1; }
-            colcls[l] = c;
+            colcls[l] = class_index(cc, sig);
         }
         const int R = (int)rc.size() + 1, Cn = (int)cc.size();
         if (R * Cn <= 16) {
@@ -207,7 +242,7 @@ struct Lowerer {
                         if (colcls[l] == c) { member = rc[r - 1][l]; break; }
                 g.lut[v] = (uint8_t)member;
             }
-            std::vector<int64_t> key{7, gh, gl, Cn};
+            std::vector<int64_t> key{KEY_SET_PRODUCT, gh, gl, Cn};
             for (int v = 0; v < 16; ++v) key.push_back(g.lut[v]);
             return lit_form(Lit{add_gate(std::move(key), std::move(g)), false});
         }
@@ -250,7 +285,7 @@ struct Lowerer {
         PGate g;
         g.kind = GATE_SIGN;
         int negs = 0;
-        std::vector<int64_t> key{2, is_and ? 1 : 0};
+        std::vector<int64_t> key{KEY_THRESHOLD, is_and ? 1 : 0};
         for (auto& l : lits) {
             g.ins.push_back({l.gate, l.neg ? -1 : 1});
             negs += l.neg;
@@ -273,16 +308,11 @@ struct Lowerer {
     // levels of threshold gates (fan-in <= 16, balanced chunks) until <= keep literals remain
     std::vector<Lit> reduce(bool is_and, std::vector<Lit> lits, size_t keep) {
         while (lits.size() > keep) {
-            size_t m = lits.size();
-            size_t chunks = (m + MAX_FANIN - 1) / MAX_FANIN;
             std::vector<Lit> next;
-            size_t start = 0;
-            for (size_t c = 0; c < chunks; ++c) {
-                size_t len = m / chunks + (c < m % chunks ? 1 : 0);
+            for_balanced_chunks(lits.size(), [&](size_t start, size_t len) {
                 std::vector<Lit> part(lits.begin() + start, lits.begin() + start + len);
-                start += len;
-                next.push_back(part.size() == 1 ? part[0] : Lit{threshold_gate(is_and, part), false});
-            }
+                next.push_back(len == 1 ? part[0] : Lit{threshold_gate(is_and, part), false});
+            });
             lits = std::move(next);
         }
         return lits;
@@ -379,6 +409,32 @@ struct Lowerer {
         return g;
     }
 
+    // ---------------------------------------------------------- the walk
+    // Post-order over the AND/OR/NOT operands below `id` (iterative: the chains of
+    // has_match are deep), memoised.  A content char and a constant are the same in every
+    // lowering; every other node's form is visit(x, node), called once its operands are done.
+    template <class Visit>
+    const Form& walk(int id, Visit&& visit) {
+        std::vector<int> st{id};
+        while (!st.empty()) {
+            int x = st.back();
+            if (done[x]) { st.pop_back(); continue; }
+            const VNode& n = dag.nodes[x];
+            bool ready = true;
+            if ((n.op == VNode::AND || n.op == VNode::OR || n.op == VNode::NOT)) {
+                if (!done[n.a]) { st.push_back(n.a); ready = false; }
+                if (n.b >= 0 && !done[n.b]) { st.push_back(n.b); ready = false; }
+            }
+            if (!ready) continue;
+            st.pop_back();
+            if (n.op == VNode::POS) throw Error(FR_ERR_INVALID, "lowering: content char used as a boolean");
+            Form f = n.op == VNode::CONST ? const_form(n.c) : visit(x, n);
+            memo[x] = std::move(f);
+            done[x] = 1;
+        }
+        return memo[id];
+    }
+
     // ---------------------------------------------------------- threshold
     std::vector<int32_t> uses;  // remaining AND/OR/NOT operand uses of each node (lower_t)
     Form take(int id) {
@@ -396,121 +452,56 @@ struct Lowerer {
                 ++uses[n.a];
             }
         ++uses[id];  // the root's form is returned
-        // iterative post-order over AND/OR/NOT chains to avoid deep recursion
-        std::vector<int> st{id};
-        while (!st.empty()) {
-            int x = st.back();
-            if (done[x]) { st.pop_back(); continue; }
-            const VNode& n = dag.nodes[x];
-            bool ready = true;
-            if ((n.op == VNode::AND || n.op == VNode::OR || n.op == VNode::NOT)) {
-                if (!done[n.a]) { st.push_back(n.a); ready = false; }
-                if (n.b >= 0 && !done[n.b]) { st.push_back(n.b); ready = false; }
+        return walk(id, [&](int, const VNode& n) {
+            if (n.op == VNode::NOT) return negate(take(n.a));
+            if (n.op == VNode::AND || n.op == VNode::OR) {
+                Form fa = take(n.a);
+                return combine(n.op == VNode::AND, std::move(fa), take(n.b));
             }
-            if (!ready) continue;
-            st.pop_back();
-            Form f;
-            switch (n.op) {
-                case VNode::POS: throw Error(FR_ERR_INVALID, "lowering: content char used as a boolean");
-                case VNode::CONST: f = const_form(n.c); break;
-                case VNode::EQ:
-                case VNode::GT:
-                case VNode::LE: {
-                    f.k = Form::SET;
-                    f.pos = n.pos;
-                    // {c}, {ch > c} or {ch <= c}, built word-wise
-                    const std::bitset<256> all = std::bitset<256>().set();
-                    if (n.op == VNode::EQ) f.set.reset().set(n.c);
-                    else if (n.op == VNode::GT) f.set = all << (n.c + 1);
-                    else f.set = all >> (255 - n.c);
-                    break;
-                }
-                case VNode::AND: {
-                    Form fa = take(n.a);
-                    f = combine(true, std::move(fa), take(n.b));
-                    break;
-                }
-                case VNode::OR: {
-                    Form fa = take(n.a);
-                    f = combine(false, std::move(fa), take(n.b));
-                    break;
-                }
-                case VNode::NOT: f = negate(take(n.a)); break;
-            }
-            memo[x] = std::move(f);
-            done[x] = 1;
-        }
-        return memo[id];
-    }
-    int cmp_gate(const VNode& n, int tag) {
-        int hi = nibble_gate(1, n.pos, 1, n.c >> 4, tag);
-        int lo = nibble_gate(1, n.pos, 0, n.c & 15, tag);
-        PGate g;
-        g.ins = {{hi, 3}, {lo, 1}};
-        lut_gt3(g.lut, n.op == VNode::LE);
-        return add_gate({3, n.op, n.pos, n.c, tag}, std::move(g));
+            Form f;  // EQ / GT / LE
+            f.k = Form::SET;
+            f.pos = n.pos;
+            // {c}, {ch > c} or {ch <= c}, built word-wise
+            const std::bitset<256> all = std::bitset<256>().set();
+            if (n.op == VNode::EQ) f.set.reset().set(n.c);
+            else if (n.op == VNode::GT) f.set = all << (n.c + 1);
+            else f.set = all >> (255 - n.c);
+            return f;
+        });
     }
 
     // ---------------------------------------------------------- faithful
+    // eq (smart_eq): both nibble tests, low first, then [lo + hi == 2]; gt / le: both sign
+    // tests, high first, then lut_gt3  (3 PBS each)
+    Form cmp_form(const VNode& n) {
+        const int tag = n.c;
+        int lo, hi;
+        if (n.op == VNode::EQ) {
+            lo = nibble_gate(0, n.pos, 0, n.c & 15, tag);
+            hi = nibble_gate(0, n.pos, 1, n.c >> 4, tag);
+        } else {
+            hi = nibble_gate(1, n.pos, 1, n.c >> 4, tag);
+            lo = nibble_gate(1, n.pos, 0, n.c & 15, tag);
+        }
+        std::vector<int64_t> key = n.op == VNode::EQ ? std::vector<int64_t>{KEY_EQ, n.pos, n.c}
+                                                     : std::vector<int64_t>{KEY_CMP, n.op, n.pos, n.c, tag};
+        return lit_form(Lit{add_gate(std::move(key), cmp_final_gate(n.op, lo, hi)), false});
+    }
+    // a faithful operand: its constant, or its literal
+    PairOperand operand(const Form& o) {
+        if (o.k == Form::CONST) return PairOperand{-1, false, o.c};
+        const Lit l = materialize(o);
+        return PairOperand{l.gate, l.neg, 0};
+    }
     // one gate group per distinct reference op
     Form lower_f(int id) {
-        std::vector<int> st{id};
-        while (!st.empty()) {
-            int x = st.back();
-            if (done[x]) { st.pop_back(); continue; }
-            const VNode& n = dag.nodes[x];
-            bool ready = true;
-            if ((n.op == VNode::AND || n.op == VNode::OR || n.op == VNode::NOT)) {
-                if (!done[n.a]) { st.push_back(n.a); ready = false; }
-                if (n.b >= 0 && !done[n.b]) { st.push_back(n.b); ready = false; }
-            }
-            if (!ready) continue;
-            st.pop_back();
-            Form f;
-            switch (n.op) {
-                case VNode::POS: throw Error(FR_ERR_INVALID, "lowering: content char used as a boolean");
-                case VNode::CONST: f = const_form(n.c); break;
-                case VNode::EQ: {
-                    // smart_eq: both nibble tests, then [lo + hi == 2]  (3 PBS)
-                    int lo = nibble_gate(0, n.pos, 0, n.c & 15, n.c);
-                    int hi = nibble_gate(0, n.pos, 1, n.c >> 4, n.c);
-                    PGate g;
-                    g.ins = {{lo, 1}, {hi, 1}};
-                    lut_eq(g.lut, 2);
-                    f = lit_form(Lit{add_gate({4, n.pos, n.c}, std::move(g)), false});
-                    break;
-                }
-                case VNode::GT:
-                case VNode::LE: f = lit_form(Lit{cmp_gate(n, n.c), false}); break;
-                case VNode::AND:
-                case VNode::OR: {
-                    bool is_and = n.op == VNode::AND;
-                    const Form& a = memo[n.a];
-                    const Form& b = memo[n.b];
-                    PGate g;
-                    int offset = 0;
-                    std::vector<int64_t> key{5, is_and, x};
-                    for (const Form* o : {&a, &b}) {
-                        if (o->k == Form::CONST) {
-                            offset += o->c;  // trivial operand (e.g. or(false, x), execution.rs:154-164)
-                        } else {
-                            Lit l = materialize(*o);
-                            g.ins.push_back({l.gate, l.neg ? -1 : 1});
-                            offset += l.neg;
-                        }
-                    }
-                    g.offset = 2 * offset;
-                    if (is_and) lut_eq(g.lut, 2);
-                    else lut_at_least(g.lut, 1);
-                    f = lit_form(Lit{add_gate(std::move(key), std::move(g)), false});
-                    break;
-                }
-                case VNode::NOT: f = negate(memo[n.a]); break;  // smart_bitxor(a, 1) on a boolean: linear
-            }
-            memo[x] = std::move(f);
-            done[x] = 1;
-        }
-        return memo[id];
+        return walk(id, [&](int x, const VNode& n) {
+            if (n.op == VNode::NOT) return negate(memo[n.a]);  // smart_bitxor(a, 1) on a boolean: linear
+            if (n.op != VNode::AND && n.op != VNode::OR) return cmp_form(n);
+            const bool is_and = n.op == VNode::AND;
+            const PairOperand a = operand(memo[n.a]), b = operand(memo[n.b]);
+            return lit_form(Lit{add_gate({KEY_FAITHFUL_PAIR, is_and, x}, pair_gate(is_and, a, b)), false});
+        });
     }
 
     // ---------------------------------------------------------- faithful tree
@@ -523,36 +514,10 @@ struct Lowerer {
     // shallowest operands are joined first (ties in operand order).  A constant operand
     // (or(false, x) is not short-circuited, execution.rs:154-164) is joined to the
     // shallowest other operand as the same trivial-offset gate lower_f makes.
-    std::vector<int32_t> glv;  // level of each gate (1 + its deepest gate input)
-    int gate_level(int g) {
-        for (int i = (int)glv.size(); i <= g; ++i) {
-            int l = 0;
-            for (const PIn& in : prog.gates[i].ins)
-                if (in.src >= 0) l = std::max(l, glv[in.src]);
-            glv.push_back(l + 1);
-        }
+    std::vector<int32_t> glv;  // level of each gate so far
+    int level_of(int g) {
+        for (int i = (int)glv.size(); i <= g; ++i) glv.push_back(gate_level(prog.gates[i], [&](int s) { return glv[s]; }));
         return glv[g];
-    }
-    struct Item {
-        bool is_const;
-        int c;
-        Lit lit;
-    };
-    int pair_gate(bool is_and, const Item& p, const Item& q, int chain, int k) {
-        PGate g;
-        int offset = 0;
-        for (const Item* o : {&p, &q}) {
-            if (o->is_const) {
-                offset += o->c;
-            } else {
-                g.ins.push_back({o->lit.gate, o->lit.neg ? -1 : 1});
-                offset += o->lit.neg;
-            }
-        }
-        g.offset = 2 * offset;
-        if (is_and) lut_eq(g.lut, 2);
-        else lut_at_least(g.lut, 1);
-        return add_gate({9, is_and, chain, k}, std::move(g));
     }
     Form lower_ft(int id) {
         const size_t nn = dag.nodes.size();
@@ -572,134 +537,75 @@ struct Lowerer {
             return (n.op == VNode::AND || n.op == VNode::OR) && nuse[x] == 1 && user[x] >= 0 &&
                    dag.nodes[user[x]].op == n.op;
         };
-        std::vector<int> st{id};
-        while (!st.empty()) {
-            int x = st.back();
-            if (done[x]) { st.pop_back(); continue; }
-            const VNode& n = dag.nodes[x];
-            bool ready = true;
-            if ((n.op == VNode::AND || n.op == VNode::OR || n.op == VNode::NOT)) {
-                if (!done[n.a]) { st.push_back(n.a); ready = false; }
-                if (n.b >= 0 && !done[n.b]) { st.push_back(n.b); ready = false; }
-            }
-            if (!ready) continue;
-            st.pop_back();
-            Form f;
-            switch (n.op) {
-                case VNode::POS: throw Error(FR_ERR_INVALID, "lowering: content char used as a boolean");
-                case VNode::CONST: f = const_form(n.c); break;
-                case VNode::EQ:
-                case VNode::GT:
-                case VNode::LE:
-                    lower_f(x);  // the comparison gates are lower_f's (it fills memo[x], done[x])
+        return walk(id, [&](int x, const VNode& n) {
+            if (n.op == VNode::NOT) return negate(memo[n.a]);
+            if (n.op != VNode::AND && n.op != VNode::OR) return cmp_form(n);  // lower_f's comparison gates
+            if (absorbed(x)) return Form{};  // an inner link: its chain root gathers its operands
+            const bool is_and = n.op == VNode::AND;
+            // the chain's operands, left to right
+            std::vector<PairOperand> leaves;
+            std::vector<int> ds{n.b, n.a};
+            while (!ds.empty()) {
+                int y = ds.back();
+                ds.pop_back();
+                if (absorbed(y) && user[y] >= 0) {
+                    ds.push_back(dag.nodes[y].b);
+                    ds.push_back(dag.nodes[y].a);
                     continue;
-                case VNode::NOT: f = negate(memo[n.a]); break;
-                case VNode::AND:
-                case VNode::OR: {
-                    if (absorbed(x)) break;  // an inner link: its chain root gathers its operands
-                    const bool is_and = n.op == VNode::AND;
-                    // the chain's operands, left to right
-                    std::vector<Item> leaves;
-                    std::vector<int> ds{n.b, n.a};
-                    while (!ds.empty()) {
-                        int y = ds.back();
-                        ds.pop_back();
-                        if (absorbed(y) && user[y] >= 0) {
-                            ds.push_back(dag.nodes[y].b);
-                            ds.push_back(dag.nodes[y].a);
-                            continue;
-                        }
-                        const Form& o = memo[y];
-                        if (o.k == Form::CONST) leaves.push_back(Item{true, o.c, Lit{-1, false}});
-                        else leaves.push_back(Item{false, 0, materialize(o)});
-                    }
-                    // least-depth binary tree: join the two shallowest operands first
-                    using QE = std::tuple<int, int, int>;  // (level, order, item index)
-                    std::priority_queue<QE, std::vector<QE>, std::greater<QE>> q;
-                    std::vector<Item> items;
-                    std::vector<Item> consts;
-                    int order = 0;
-                    for (const Item& it : leaves) {
-                        if (it.is_const) { consts.push_back(it); continue; }
-                        items.push_back(it);
-                        q.emplace(gate_level(it.lit.gate), order++, (int)items.size() - 1);
-                    }
-                    int k = 0;
-                    auto join = [&](const Item& p, const Item& r) {
-                        int g = pair_gate(is_and, p, r, x, k++);
-                        items.push_back(Item{false, 0, Lit{g, false}});
-                        q.emplace(gate_level(g), order++, (int)items.size() - 1);
-                    };
-                    size_t c0 = 0;
-                    if (q.empty()) {
-                        // every operand's value is a constant (a short-circuit returns its
-                        // operand under a new key, execution.rs:121-164, so the op above it is
-                        // real): lower_f's input-free gate, as the first join
-                        if (consts.size() < 2) throw Error(FR_ERR_INVALID, "lowering: one-operand chain");
-                        join(consts[0], consts[1]);
-                        c0 = 2;
-                    }
-                    for (size_t ci = c0; ci < consts.size(); ++ci) {
-                        const Item& c = consts[ci];
-                        auto [lv, od, ix] = q.top();
-                        q.pop();
-                        (void)lv, (void)od;
-                        join(items[ix], c);
-                    }
-                    while (q.size() > 1) {
-                        auto [l1, o1, i1] = q.top();
-                        q.pop();
-                        auto [l2, o2, i2] = q.top();
-                        q.pop();
-                        (void)l1, (void)l2;
-                        // operand order as in the chain (the earlier one first)
-                        if (o1 < o2) join(items[i1], items[i2]);
-                        else join(items[i2], items[i1]);
-                    }
-                    f = lit_form(items[std::get<2>(q.top())].lit);
-                    break;
                 }
+                leaves.push_back(operand(memo[y]));
             }
-            memo[x] = std::move(f);
-            done[x] = 1;
-        }
-        return memo[id];
+            // least-depth binary tree: join the two shallowest operands first
+            using QE = std::tuple<int, int, int>;  // (level, order, item index)
+            std::priority_queue<QE, std::vector<QE>, std::greater<QE>> q;
+            std::vector<PairOperand> items;
+            std::vector<PairOperand> consts;
+            int order = 0;
+            for (const PairOperand& it : leaves) {
+                if (it.gate < 0) { consts.push_back(it); continue; }
+                items.push_back(it);
+                q.emplace(level_of(it.gate), order++, (int)items.size() - 1);
+            }
+            int k = 0;
+            auto join = [&](const PairOperand& p, const PairOperand& r) {
+                int g = add_gate({KEY_TREE_PAIR, is_and, x, k++}, pair_gate(is_and, p, r));
+                items.push_back(PairOperand{g, false, 0});
+                q.emplace(level_of(g), order++, (int)items.size() - 1);
+            };
+            size_t c0 = 0;
+            if (q.empty()) {
+                // every operand's value is a constant (a short-circuit returns its
+                // operand under a new key, execution.rs:121-164, so the op above it is
+                // real): lower_f's input-free gate, as the first join
+                if (consts.size() < 2) throw Error(FR_ERR_INVALID, "lowering: one-operand chain");
+                join(consts[0], consts[1]);
+                c0 = 2;
+            }
+            for (size_t ci = c0; ci < consts.size(); ++ci) {
+                const PairOperand c = consts[ci];
+                const int ix = std::get<2>(q.top());
+                q.pop();
+                join(PairOperand(items[ix]), c);
+            }
+            while (q.size() > 1) {
+                auto [l1, o1, i1] = q.top();
+                q.pop();
+                auto [l2, o2, i2] = q.top();
+                q.pop();
+                (void)l1, (void)l2;
+                // operand order as in the chain (the earlier one first)
+                const PairOperand p1 = items[i1], p2 = items[i2];
+                if (o1 < o2) join(p1, p2);
+                else join(p2, p1);
+            }
+            const PairOperand& top = items[std::get<2>(q.top())];
+            return lit_form(Lit{top.gate, top.neg});
+        });
     }
 };
 
-}  // namespace
-
-void compute_levels(Program& prog) {
-    int maxl = 0;
-    std::vector<size_t> width;
-    for (auto& g : prog.gates) {
-        int l = 0;
-        for (auto& in : g.ins)
-            if (in.src >= 0) l = std::max(l, prog.gates[in.src].level);
-        g.level = l + 1;
-        maxl = std::max(maxl, g.level);
-        if ((size_t)g.level >= width.size()) width.resize(g.level + 1, 0);
-        width[g.level]++;
-    }
-    prog.levels = maxl;
-    prog.max_width = 0;
-    for (auto w : width) prog.max_width = std::max(prog.max_width, w);
-}
-
-Program lower(const ValueDag& dag, int root, int mode, int max_parts) {
-    if (max_parts < 1 || max_parts > MAX_FANIN) throw Error(FR_ERR_INVALID, "lowering: parts must be in [1, 16]");
-    Lowerer lw(dag, mode);
-    Form f = mode == FR_LOWER_FAITHFUL ? lw.lower_f(root)
-             : mode == FR_LOWER_FAITHFUL_TREE ? lw.lower_ft(root) : lw.lower_t(root);
-    Program& p = lw.prog;
-    if (f.k == Form::SET) f = lw.expand_set(f);  // (an empty or full set is a constant)
-    if (f.k == Form::CONST) {
-        p.outs.push_back(ProgOut{-1, 0, f.c});
-    } else {
-        for (const Lit& l : lw.parts(f, (size_t)max_parts))
-            p.outs.push_back(ProgOut{l.gate, l.neg ? -1 : 1, l.neg ? 1 : 0});
-    }
-    // drop gates not reachable from the outputs (e.g. materialized then merged)
+// drop the gates not reachable from the outputs (e.g. materialized then merged), renumbering the rest
+Program sweep_dead_gates(Program&& p) {
     std::vector<char> live(p.gates.size(), 0);
     for (const ProgOut& o : p.outs) {
         if (o.gate < 0) continue;
@@ -727,11 +633,49 @@ Program lower(const ValueDag& dag, int root, int mode, int max_parts) {
         if (o.gate >= 0) o.gate = remap[o.gate];
         out.outs.push_back(o);
     }
-    out.out_gate = out.outs[0].gate;
-    out.out_w = out.outs[0].w;
-    out.out_const = out.outs[0].cst;
+    return out;
+}
+
+}  // namespace
+
+void compute_levels(Program& prog) {
+    int maxl = 0;
+    std::vector<size_t> width;
+    for (auto& g : prog.gates) {
+        g.level = gate_level(g, [&](int s) { return prog.gates[s].level; });
+        maxl = std::max(maxl, g.level);
+        if ((size_t)g.level >= width.size()) width.resize(g.level + 1, 0);
+        width[g.level]++;
+    }
+    prog.levels = maxl;
+    prog.max_width = 0;
+    for (auto w : width) prog.max_width = std::max(prog.max_width, w);
+}
+
+Program lower(const ValueDag& dag, int root, int mode, int max_parts) {
+    if (max_parts < 1 || max_parts > MAX_FANIN) throw Error(FR_ERR_INVALID, "lowering: parts must be in [1, 16]");
+    Lowerer lw(dag, mode);
+    Form f = mode == FR_LOWER_FAITHFUL ? lw.lower_f(root)
+             : mode == FR_LOWER_FAITHFUL_TREE ? lw.lower_ft(root) : lw.lower_t(root);
+    Program& p = lw.prog;
+    if (f.k == Form::SET) f = lw.expand_set(f);  // (an empty or full set is a constant)
+    if (f.k == Form::CONST) {
+        p.outs.push_back(ProgOut{-1, 0, f.c});
+    } else {
+        for (const Lit& l : lw.parts(f, (size_t)max_parts))
+            p.outs.push_back(ProgOut{l.gate, l.neg ? -1 : 1, l.neg ? 1 : 0});
+    }
+    Program out = sweep_dead_gates(std::move(p));
     compute_levels(out);
     return out;
+}
+
+CompiledMatch compile_match(const MatchSpec& s) {
+    CompiledMatch m;
+    const ReP re = parse(s.pattern, s.grammar);  // engine.rs:13
+    m.rec = record_has_match_engine(m.dag, s.n_chars, re, s.lo, s.hi, s.engine);
+    m.prog = lower(m.dag, m.rec.root, s.lowering, s.parts);
+    return m;
 }
 
 int eval_program(const Program& prog, const uint8_t* content, size_t L) {
@@ -765,16 +709,12 @@ int eval_program_parts(const Program& prog, const uint8_t* content, size_t L, st
         }
     }
     parts.clear();
-    if (prog.outs.size() > 1) {
-        int any = 0;
-        for (const ProgOut& o : prog.outs) {
-            parts.push_back(o.gate < 0 ? o.cst : o.cst + o.w * val[o.gate]);
-            any |= parts.back();
-        }
-        return any;
+    int any = 0;
+    for (const ProgOut& o : prog.outs) {
+        parts.push_back(o.gate < 0 ? o.cst : o.cst + o.w * val[o.gate]);
+        any |= parts.back();
     }
-    parts.push_back(prog.out_gate < 0 ? prog.out_const : prog.out_const + prog.out_w * val[prog.out_gate]);
-    return parts[0];
+    return any;
 }
 
 }  // namespace fr

@@ -19,7 +19,9 @@
 //   equality nibble tests are shared across constants.  Same decrypted result,
 //   far fewer PBS and levels.
 #pragma once
+#include <algorithm>
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "regex.h"
@@ -44,10 +46,8 @@ struct ProgOut {
 };
 struct Program {
     std::vector<PGate> gates;
-    // result = out_const + out_w * gates[out_gate]   (out_gate == -1: constant)
-    int32_t out_gate = -1, out_const = 0, out_w = 0;
-    // the outputs: {out_*} alone, or (lower's max_parts > 1) up to max_parts booleans
-    // whose OR is the result
+    // the outputs: one boolean, or (lower's max_parts > 1) up to max_parts booleans whose
+    // OR is the result
     std::vector<ProgOut> outs;
     int32_t levels = 0;
     size_t max_width = 0;
@@ -66,11 +66,64 @@ int eval_program(const Program& prog, const uint8_t* content, size_t L);
 // the same, and each output's value in `parts`
 int eval_program_parts(const Program& prog, const uint8_t* content, size_t L, std::vector<int>& parts);
 void compute_levels(Program& prog);
+// a gate's level: one past its deepest gate input (content blocks are level 0);
+// level_of(g) gives the level of an earlier gate
+template <class LevelOf>
+int gate_level(const PGate& g, LevelOf&& level_of) {
+    int l = 0;
+    for (const PIn& in : g.ins)
+        if (in.src >= 0) l = std::max(l, (int)level_of(in.src));
+    return l + 1;
+}
+
+// The front end of every match: parse once, record under the engine, lower.  The error
+// order is the stages': a parse error first, then the recording's (FR_ERR_OOM from the
+// enumeration, the merged engine's refusals), then the lowering's.
+struct MatchSpec {
+    std::string pattern;
+    size_t n_chars = 0, lo = 0, hi = 0;  // start offsets [lo, hi)
+    int engine = FR_ENGINE_AUTO, grammar = FR_GRAMMAR_REFERENCE, lowering = FR_LOWER_THRESHOLD;
+    int parts = 1;  // lower's max_parts
+};
+struct CompiledMatch {
+    Recorded rec;
+    Program prog;
+    ValueDag dag;  // the recorded circuit (rec.root), for a plaintext evaluation
+};
+CompiledMatch compile_match(const MatchSpec& spec);
 
 // LUT builders
 void lut_eq(uint8_t* lut, int v);     // [x == v]
 void lut_sign(uint8_t* lut, int v);   // x < v -> 0, x == v -> 1, x > v -> 2
 void lut_gt3(uint8_t* lut, bool le);  // over 3*s_hi + s_lo: gt (or its negation)
 void lut_at_least(uint8_t* lut, int m);
+
+// Gate builders shared by the lowerings and the eager ops of the C ABI.
+inline int cblk(int pos, int blk) { return -(1 + pos * 4 + blk); }
+// a test of one nibble (half 0: low) of the character at pos, packed as x_{2h} + 4 x_{2h+1}:
+// [nibble == v], or (sign) its comparison with v as lut_sign
+PGate nibble_test_gate(bool sign, int pos, int half, int v);
+// the last gate of a comparison with a constant, over its two nibble tests: equality
+// [lo + hi == 2] over the eq tests, else gt (le: its negation) over 3 * sign_hi + sign_lo
+PGate cmp_final_gate(VNode::Op op, int lo_gate, int hi_gate);
+// the two-input gate of a faithful AND / OR: each operand a literal (gate, negated) or a
+// constant (gate < 0: the value c); offset = 2 * (constants' values + negated literals)
+struct PairOperand {
+    int gate;  // < 0: the constant c
+    bool neg;
+    int c;
+};
+PGate pair_gate(bool is_and, const PairOperand& p, const PairOperand& q);
+// m items cut into ceil(m / 16) contiguous chunks of near-equal length (the longer ones
+// first): f(start, len) per chunk -- one level of a balanced threshold tree
+template <class F>
+void for_balanced_chunks(size_t m, F&& f) {
+    const size_t chunks = (m + MAX_FANIN - 1) / MAX_FANIN;
+    for (size_t c = 0, start = 0; c < chunks; ++c) {
+        const size_t len = m / chunks + (c < m % chunks ? 1 : 0);
+        f(start, len);
+        start += len;
+    }
+}
 
 }  // namespace fr

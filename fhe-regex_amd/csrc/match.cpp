@@ -111,6 +111,11 @@ void check_content(fr_ctx* ctx, const Program& prog, const fr_ct* content, size_
             }
 }
 
+// the front end's input for a context's settings
+MatchSpec match_spec(const fr_ctx* ctx, const char* pattern, size_t n, size_t lo, size_t hi, size_t parts = 1) {
+    return MatchSpec{pattern, n, lo, hi, ctx->engine, ctx->grammar, ctx->lowering, (int)parts};
+}
+
 // the counters of a recording and of its plan, into zeroed stats
 void fill_stats(fr_match_stats& s, const Recorded& rec, const Plan& P) {
     s.ct_ops = rec.ct_ops;
@@ -168,10 +173,9 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
         rec = hit->rec;
     } else {
         ++pc.misses;
-        ValueDag dag;
-        GrammarScope grammar(ctx->grammar);
-        rec = record_has_match_engine(dag, n, pattern, lo, hi, ctx->engine);
-        prog = lower(dag, rec.root, ctx->lowering, (int)parts);
+        CompiledMatch cm = compile_match(match_spec(ctx, pattern, n, lo, hi, parts));
+        rec = cm.rec;
+        prog = std::move(cm.prog);
         check_content(ctx, prog, content, n, M);
         // M copies: gate g of match m is m * G + g, content block cb of match m is 4 n m + cb
         const size_t G = prog.gates.size();
@@ -370,16 +374,15 @@ int fr_shard_plan(fr_ctx* ctx, const fr_ct* content, size_t n, const char* patte
         NEED(ctx && out && pattern && (content || !n) && lo <= hi);
         Device& dev = ctx->keyed_device();
         const double t0 = now_ms();
-        ValueDag dag;
-        GrammarScope grammar(ctx->grammar);
-        Recorded rec = record_has_match_engine(dag, n, pattern, lo, hi, ctx->engine);
-        Program prog = lower(dag, rec.root, ctx->lowering);
+        const CompiledMatch cm = compile_match(match_spec(ctx, pattern, n, lo, hi));
+        const Recorded& rec = cm.rec;
+        const Program& prog = cm.prog;
         check_content(ctx, prog, content, n, 1);
         auto sh = std::make_unique<fr_shard>();
         sh->plan = compile_plan(ctx, prog.gates, std::vector<fr_ct>(content, content + n));
         Plan& P = sh->plan;
         P.d_gates = dev.upload_gates(P.gates.data(), P.gates.size());
-        sh->out = ProgOut{prog.out_gate, prog.out_w, prog.out_const};
+        sh->out = prog.outs[0];
         for (size_t l = 0; l + 1 < P.level_off.size(); ++l) {
             std::vector<int> slots;
             std::vector<uint32_t> off{0};
@@ -475,10 +478,8 @@ int fr_schedule_match_parts(size_t n_chars, const char* pattern, size_t lo, size
     FR_TRY({
         NEED(pattern && n_jobs && n_levels && outs3 && n_parts && lo <= hi);
         NEED(max_parts >= 1 && max_parts <= (size_t)MAX_FANIN);
-        ValueDag dag;
-        GrammarScope gs(grammar);
-        Recorded rec = record_has_match_engine(dag, n_chars, pattern, lo, hi, engine);
-        Program prog = lower(dag, rec.root, lowering, (int)max_parts);
+        const Program prog =
+            compile_match(MatchSpec{pattern, n_chars, lo, hi, engine, grammar, lowering, (int)max_parts}).prog;
         Schedule S = build_schedule(prog.gates, n_chars, multi_value != 0, [](int cb, int& key, int&) {
             key = cb;
             return true;

@@ -375,8 +375,7 @@ class Merged {
 
 }  // namespace
 
-Recorded record_has_match_merged(ValueDag& dag, size_t L, const std::string& pattern, size_t lo, size_t hi) {
-    ReP re = parse(pattern);  // engine.rs:13
+Recorded record_has_match_merged(ValueDag& dag, size_t L, const ReP& re, size_t lo, size_t hi) {
     if (hi > L) hi = L;
     Merged m(dag, L);
     Merged::Reach in(L + 1, ABSENT);

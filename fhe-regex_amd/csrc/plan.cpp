@@ -88,7 +88,7 @@ fr_ct finish_output(fr_ctx* ctx, ProgOut o, Slots& slots, bool take_slot) {
 
 fr_ct run_program(fr_ctx* ctx, const Program& prog, const std::vector<fr_ct>& inputs, fr_match_stats* st) {
     Slots slots = execute_gates(ctx, prog.gates, inputs, st);
-    return finish_output(ctx, ProgOut{prog.out_gate, prog.out_w, prog.out_const}, slots, true);
+    return finish_output(ctx, prog.outs[0], slots, true);
 }
 
 }  // namespace fr

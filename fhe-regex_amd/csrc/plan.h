@@ -34,8 +34,6 @@ struct Schedule {
     uint64_t levels = 0, max_width = 0;
 };
 
-inline int cblk(int pos, int blk) { return -(1 + pos * 4 + blk); }
-
 // block(cb, &key, &triv): false if content block cb is trivial (its value in triv),
 // else key identifies the block's ciphertext (the multi-value merge compares keys).
 // A template parameter, not a std::function: it is called per content reference of
@@ -47,11 +45,10 @@ Schedule build_schedule(const std::vector<PGate>& gates, size_t n_content, bool 
     int maxl = 0;
     for (size_t g = 0; g < gates.size(); ++g) {
         const PGate& G = gates[g];
-        int l = 0, nin = 0, off = G.offset;
+        int nin = 0, off = G.offset;
         for (auto& in : G.ins) {
             if (in.src >= 0) {
                 if ((size_t)in.src >= g) throw Error(FR_ERR_INVALID, "gate program is not topologically ordered");
-                l = std::max(l, level[in.src]);
                 ++nin;
                 continue;
             }
@@ -63,8 +60,8 @@ Schedule build_schedule(const std::vector<PGate>& gates, size_t n_content, bool 
         }
         if (nin > 16) throw Error(FR_ERR_INVALID, "gate fan-in > 16");
         if (G.kind != GATE_SIGN && (off & 1)) throw Error(FR_ERR_INVALID, "LUT gate with a half-integral offset");
-        level[g] = l + 1;
-        maxl = std::max(maxl, l + 1);
+        level[g] = gate_level(G, [&](int s) { return level[s]; });
+        maxl = std::max(maxl, level[g]);
     }
     std::vector<std::vector<int>> by_level(maxl + 1);
     for (size_t g = 0; g < gates.size(); ++g) by_level[level[g]].push_back((int)g);

@@ -419,13 +419,6 @@ struct Parser {
 };
 }  // namespace
 
-static thread_local int g_grammar = FR_GRAMMAR_REFERENCE;
-int current_grammar() { return g_grammar; }
-GrammarScope::GrammarScope(int grammar) : prev_(g_grammar) { g_grammar = grammar; }
-GrammarScope::~GrammarScope() { g_grammar = prev_; }
-
-ReP parse(const std::string& pattern) { return parse(pattern, g_grammar); }
-
 ReP parse(const std::string& pattern, int grammar) {
     if (grammar != FR_GRAMMAR_REFERENCE && grammar != FR_GRAMMAR_EXT) throw Error(FR_ERR_INVALID, "unknown grammar");
     Parser ps(pattern, grammar == FR_GRAMMAR_EXT);
@@ -622,14 +615,12 @@ static Lazy seq_and(const Lazy& prev, const Lazy& x) {  // engine.rs:197-205
     });
 }
 
-// variants still allowed in this enumeration (record_has_match's budget)
-static thread_local size_t g_budget = SIZE_MAX;
-static void spend(size_t n) {
-    if (n > g_budget) throw Error(FR_ERR_OOM, "variant enumeration budget exceeded");
-    g_budget -= n;
+void Enumerator::spend(size_t n) {
+    if (n > left) throw Error(FR_ERR_OOM, "variant enumeration budget exceeded");
+    left -= n;
 }
 
-std::vector<Branch> build_branches(size_t L, const ReP& re, size_t p) {
+std::vector<Branch> Enumerator::build_branches(const ReP& re, size_t p) {
     switch (re->kind) {  // engine.rs:51-67
         case Re::SOF:
             if (p == 0) return {{lazy([](Execution& ex) { return ex.ct_true(); }), p}};
@@ -650,15 +641,15 @@ std::vector<Branch> build_branches(size_t L, const ReP& re, size_t p) {
             return {{lazy([](Execution& ex) { return ex.ct_true(); }), p + 1}};
         case Re::NOT: {  // :82-93
             std::vector<Branch> out;
-            for (auto& br : build_branches(L, re->a, p)) {
+            for (auto& br : build_branches(re->a, p)) {
                 Lazy f = br.f;
                 out.push_back({lazy([f](Execution& ex) { return ex.ct_not((*f)(ex)); }), br.end});
             }
             return out;
         }
         case Re::EITHER: {  // :94-98
-            auto l = build_branches(L, re->a, p);
-            auto r = build_branches(L, re->b, p);
+            auto l = build_branches(re->a, p);
+            auto r = build_branches(re->b, p);
             l.insert(l.end(), r.begin(), r.end());
             return l;
         }
@@ -722,14 +713,14 @@ std::vector<Branch> build_branches(size_t L, const ReP& re, size_t p) {
                 uint64_t reps = at_least > 1 ? at_least : 1;
                 if (reps > (1u << 24)) throw Error(FR_ERR_REF_PANIC, "repetition count too large (reference exhausts memory)");
                 for (uint64_t r = 0; r < reps; ++r) q->xs.push_back(re->a);
-                res.push_back(build_branches(L, q, p));
+                res.push_back(build_branches(q, p));
             }
             // (at_least+1 ..= at_most): each step extends the previous list;
             // once a step yields nothing all later ones do too.
             for (uint64_t it = at_least + 1; it <= at_most; ++it) {
                 std::vector<Branch> nxt;
                 for (auto& bp : res.back())
-                    for (auto& bx : build_branches(L, re->a, bp.end)) nxt.push_back({seq_and(bp.f, bx.f), bx.end});
+                    for (auto& bx : build_branches(re->a, bp.end)) nxt.push_back({seq_and(bp.f, bx.f), bx.end});
                 spend(nxt.size());
                 bool empty = nxt.empty();
                 res.push_back(std::move(nxt));
@@ -740,17 +731,17 @@ std::vector<Branch> build_branches(size_t L, const ReP& re, size_t p) {
             return out;
         }
         case Re::OPTIONAL: {  // :184-188
-            auto out = build_branches(L, re->a, p);
+            auto out = build_branches(re->a, p);
             out.push_back({lazy([](Execution& ex) { return ex.ct_true(); }), p});
             return out;
         }
         case Re::SEQ: {  // :189-211
             if (re->xs.empty()) throw Error(FR_ERR_REF_PANIC, "Seq{[]}: index out of bounds (reference panics, engine.rs:189-190)");
-            auto conts = build_branches(L, re->xs[0], p);
+            auto conts = build_branches(re->xs[0], p);
             for (size_t i = 1; i < re->xs.size(); ++i) {
                 std::vector<Branch> nxt;
                 for (auto& bp : conts)
-                    for (auto& bx : build_branches(L, re->xs[i], bp.end)) nxt.push_back({seq_and(bp.f, bx.f), bx.end});
+                    for (auto& bx : build_branches(re->xs[i], bp.end)) nxt.push_back({seq_and(bp.f, bx.f), bx.end});
                 spend(nxt.size());
                 conts = std::move(nxt);
             }
@@ -761,19 +752,13 @@ std::vector<Branch> build_branches(size_t L, const ReP& re, size_t p) {
     throw Error(FR_ERR_REF_PANIC, "unmatched regex variant");
 }
 
-Recorded record_has_match(ValueDag& dag, size_t L, const std::string& pattern, size_t lo, size_t hi,
-                          size_t branch_budget) {
-    ReP re = parse(pattern);  // engine.rs:13
+Recorded record_has_match(ValueDag& dag, size_t L, const ReP& re, size_t lo, size_t hi, size_t branch_budget) {
     if (hi > L) hi = L;
     std::vector<Lazy> branches;
-    struct Budget {  // restored on every exit
-        explicit Budget(size_t b) : saved(g_budget) { g_budget = b; }
-        ~Budget() { g_budget = saved; }
-        size_t saved;
-    } budget(branch_budget);
+    Enumerator en{L, branch_budget};
     for (size_t i = lo; i < hi; ++i) {  // engine.rs:15-18
-        auto bs = build_branches(L, re, i);
-        spend(bs.size());
+        auto bs = en.build_branches(re, i);
+        en.spend(bs.size());
         for (auto& b : bs) branches.push_back(b.f);
     }
     Execution ex(dag);
@@ -942,19 +927,14 @@ struct Dry {
 
 uint64_t enumeration_spent(size_t L, const ReP& re, size_t lo, size_t hi, uint64_t cap) {
     if (hi > L) hi = L;
-    const size_t saved = g_budget;
-    g_budget = cap;
-    uint64_t spent;
+    Enumerator en{L, (size_t)cap};
     try {
-        for (size_t i = lo; i < hi; ++i) spend(build_branches(L, re, i).size());  // record_has_match's loop
-        spent = cap - g_budget;
+        for (size_t i = lo; i < hi; ++i) en.spend(en.build_branches(re, i).size());  // record_has_match's loop
     } catch (const Error& e) {
-        g_budget = saved;
         if (e.code != FR_ERR_OOM) throw;
         return cap + 1;
     }
-    g_budget = saved;
-    return spent;
+    return cap - en.left;
 }
 
 CostOutcome enumeration_cost(size_t L, const ReP& re, size_t lo, size_t hi, uint64_t cap, uint64_t* cost,
@@ -976,10 +956,9 @@ CostOutcome enumeration_cost(size_t L, const ReP& re, size_t lo, size_t hi, uint
     return COST_COUNTED;
 }
 
-Recorded record_has_match_engine(ValueDag& dag, size_t L, const std::string& pattern, size_t lo, size_t hi,
-                                 int engine) {
-    if (engine == FR_ENGINE_MERGED) return record_has_match_merged(dag, L, pattern, lo, hi);
-    if (engine == FR_ENGINE_ENUMERATE) return record_has_match(dag, L, pattern, lo, hi);
+Recorded record_has_match_engine(ValueDag& dag, size_t L, const ReP& re, size_t lo, size_t hi, int engine) {
+    if (engine == FR_ENGINE_MERGED) return record_has_match_merged(dag, L, re, lo, hi);
+    if (engine == FR_ENGINE_ENUMERATE) return record_has_match(dag, L, re, lo, hi);
     // AUTO: the reference's enumeration (exact counters) while it stays within
     // a few million variants, else the state-merging evaluator.  The enumeration's cost
     // is counted first (enumeration_cost, exact), so a pattern past the budget goes
@@ -988,7 +967,7 @@ Recorded record_has_match_engine(ValueDag& dag, size_t L, const std::string& pat
     // (/abc/ x 256: 763 variants) are tried directly: counting costs about as much as them.
     constexpr size_t budget = (size_t)1 << 22, small = (size_t)1 << 12;
     try {  // (the budget runs out while enumerating, before the dag is touched)
-        return record_has_match(dag, L, pattern, lo, hi, small);
+        return record_has_match(dag, L, re, lo, hi, small);
     } catch (const Error& e) {
         if (e.code != FR_ERR_OOM) throw;
     }
@@ -997,15 +976,15 @@ Recorded record_has_match_engine(ValueDag& dag, size_t L, const std::string& pat
         // tests only) -> the enumeration below decides under its budget, as without the counter
         uint64_t cost = 0, mem = 0;
         if (const char* ev = std::getenv("FR_ENUM_COST_BYTES")) mem = std::strtoull(ev, nullptr, 10);
-        if (enumeration_cost(L, parse(pattern), lo, hi, budget, &cost, mem) == COST_COUNTED && cost > budget)
-            return record_has_match_merged(dag, L, pattern, lo, hi);
+        if (enumeration_cost(L, re, lo, hi, budget, &cost, mem) == COST_COUNTED && cost > budget)
+            return record_has_match_merged(dag, L, re, lo, hi);
     }
     try {
-        return record_has_match(dag, L, pattern, lo, hi, budget);
+        return record_has_match(dag, L, re, lo, hi, budget);
     } catch (const Error& e) {
         if (e.code != FR_ERR_OOM) throw;
     }
-    return record_has_match_merged(dag, L, pattern, lo, hi);
+    return record_has_match_merged(dag, L, re, lo, hi);
 }
 
 }  // namespace fr

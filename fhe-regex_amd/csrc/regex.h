@@ -34,19 +34,8 @@ std::string to_string(const Re& r);
 // grammar FR_GRAMMAR_EXT (beyond the reference) additionally accepts bare
 // digits as characters and bracket classes mixing letters, digits, escapes and
 // ranges ([a-z0-9], [^A-Z_]) — only where the reference grammar fails, so every
-// pattern the reference accepts parses to the same AST.  The default is the
-// calling thread's grammar (GrammarScope), initially FR_GRAMMAR_REFERENCE.
+// pattern the reference accepts parses to the same AST.
 ReP parse(const std::string& pattern, int grammar);
-ReP parse(const std::string& pattern);
-int current_grammar();
-struct GrammarScope {  // sets the thread's grammar for parse(pattern)
-    explicit GrammarScope(int grammar);
-    ~GrammarScope();
-    GrammarScope(const GrammarScope&) = delete;
-    GrammarScope& operator=(const GrammarScope&) = delete;
-  private:
-    int prev_;
-};
 
 // Open-addressing index of dense ids by a 64-bit hash (linear probing, load
 // <= 1/2): hash-consing of DAG nodes and Executed keys without per-bucket
@@ -151,17 +140,23 @@ struct Branch {
     Lazy f;
     size_t end;
 };
-// build_branches, src/regex/engine.rs:45-214 (content only enters via its length)
-std::vector<Branch> build_branches(size_t L, const ReP& re, size_t pos);
+// build_branches, src/regex/engine.rs:45-214 (content only enters via its length), under a
+// budget of variants: every list of continuations it builds is spent from `left`, Error
+// FR_ERR_OOM once that runs out (the reference has no bound and exhausts memory instead)
+struct Enumerator {
+    size_t L;
+    size_t left = SIZE_MAX;
+    void spend(size_t n);
+    std::vector<Branch> build_branches(const ReP& re, size_t pos);
+};
 
 struct Recorded {
     int root = -1;  // value id of the result
     uint64_t ct_ops = 0, cache_hits = 0, n_branches = 0;
 };
-// has_match, src/regex/engine.rs:8-42 (start offsets restricted to [lo, hi)).
-// branch_budget bounds the number of enumerated variants (Error FR_ERR_OOM past
-// it); the reference itself has no bound and exhausts memory instead.
-Recorded record_has_match(ValueDag& dag, size_t L, const std::string& pattern, size_t lo, size_t hi,
+// has_match, src/regex/engine.rs:8-42, of a parsed pattern (start offsets restricted to
+// [lo, hi)).  branch_budget bounds the number of enumerated variants (Enumerator).
+Recorded record_has_match(ValueDag& dag, size_t L, const ReP& re, size_t lo, size_t hi,
                           size_t branch_budget = SIZE_MAX);
 // What record_has_match would spend of its branch budget (the variants it enumerates),
 // counted without building a branch: per (node, position) the multiset of end positions
@@ -179,9 +174,8 @@ CostOutcome enumeration_cost(size_t L, const ReP& re, size_t lo, size_t hi, uint
 uint64_t enumeration_spent(size_t L, const ReP& re, size_t lo, size_t hi, uint64_t cap);
 // State-merging evaluator (merged.cpp, beyond the reference): the same boolean,
 // polynomial in L.  Error FR_ERR_INVALID for AST shapes it does not cover.
-Recorded record_has_match_merged(ValueDag& dag, size_t L, const std::string& pattern, size_t lo, size_t hi);
+Recorded record_has_match_merged(ValueDag& dag, size_t L, const ReP& re, size_t lo, size_t hi);
 // engine: FR_ENGINE_AUTO (enumerate within a budget, else merge), _ENUMERATE, _MERGED
-Recorded record_has_match_engine(ValueDag& dag, size_t L, const std::string& pattern, size_t lo, size_t hi,
-                                 int engine);
+Recorded record_has_match_engine(ValueDag& dag, size_t L, const ReP& re, size_t lo, size_t hi, int engine);
 
 }  // namespace fr

@@ -507,3 +507,24 @@ def test_slot_owner_semantics(tmp_path):
     res = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert res.returncode == 0, res.stderr
     assert "slot owner ok: 9 cases" in res.stdout
+
+
+def test_schedule_digests():
+    """The lowered program and its schedule, gate for gate and in order: the SHA-256 of every
+    case of tests/golden/schedule_digests.json (fr_job bytes, level_off, every part's output;
+    generated by tests/golden/make_schedule_digests.py, which also defines the digest) is
+    recomputed and compared.  The corpus is the whole file, and it is the slowest CPU test by far:
+    ten of the fuzz patterns take seconds per recording (an enumeration near the AUTO budget, or
+    the merged engine's general closure over 400-500 chars), about 15 CPU-minutes in all, on the
+    generator's thread pool."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_schedule_digests",
+                                                  os.path.join(GOLDEN, "make_schedule_digests.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    stored = gen.load()
+    corpus = [c for s in gen.sources() for c in gen.cases_of(s)]
+    assert [c for c, _ in stored] == corpus  # the file holds the corpus, every case of it
+    got = gen.digests(corpus)
+    bad = [(c, g, d) for (c, d), g in zip(stored, got) if g != d]
+    assert not bad, f"{len(bad)} of {len(stored)} schedules differ, first: {bad[0]}"

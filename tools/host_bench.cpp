@@ -1,6 +1,6 @@
 // Host-side cost of one has_match before the first launch: record the
 // reference's op DAG (parse + build_branches + Execution) and lower it to the
-// PBS program.  After `make -C fhe-regex_amd` has built the host objects:
+// PBS program: compile_match's two stages, timed apart.  After `make -C fhe-regex_amd` has built the host objects:
 //   g++ -O2 -std=c++17 -Iinclude -Ifhe-regex_amd/csrc tools/host_bench.cpp
 //     fhe-regex_amd/build/{regex,merged,lower}.o -o tools/host_bench
 #include <chrono>
@@ -23,7 +23,7 @@ int main(int argc, char** argv) {
     for (int it = 0; it < iters; ++it) {
         double t0 = ms();
         ValueDag dag;
-        Recorded rec = record_has_match_engine(dag, L, pat, 0, L, FR_ENGINE_AUTO);
+        Recorded rec = record_has_match_engine(dag, L, parse(pat, FR_GRAMMAR_REFERENCE), 0, L, FR_ENGINE_AUTO);
         double t1 = ms();
         Program prog = lower(dag, rec.root, FR_LOWER_THRESHOLD);
         double t2 = ms();
