@@ -412,6 +412,36 @@ int fr_plain_match_parts(const char* content, size_t len, const char* pattern, s
     })
 }
 
+int fr_plain_match_starts(const char* content, size_t len, const char* pattern, size_t lo, size_t hi, int32_t lowering,
+                          int32_t engine, int32_t grammar, fr_plain_result* out, int32_t* lowered,
+                          int32_t* recorded, size_t cap, size_t* n_starts) {
+    FR_TRY({
+        NEED((content || !len) && pattern && out && n_starts && lo <= hi && cap >= hi - lo);
+        NEED((lowered && recorded) || lo == hi);
+        NEED(lowering >= FR_LOWER_FAITHFUL && lowering <= FR_LOWER_FAITHFUL_TREE);
+        NEED(engine >= FR_ENGINE_AUTO && engine <= FR_ENGINE_MERGED);
+        NEED(grammar == FR_GRAMMAR_REFERENCE || grammar == FR_GRAMMAR_EXT);
+        std::memset(out, 0, sizeof *out);
+        const CompiledStarts cs =
+            compile_match_starts(MatchSpec{pattern, len, lo, hi, engine, grammar, lowering, 1}, true);
+        std::vector<int> vals;
+        out->result_lowered = eval_program_parts(cs.prog, (const uint8_t*)content, len, vals);
+        out->ct_ops = cs.rec.ct_ops;
+        out->cache_hits = cs.rec.cache_hits;
+        out->n_branches = cs.rec.n_branches;
+        out->pbs = cs.prog.gates.size();
+        out->levels = (uint64_t)cs.prog.levels;
+        out->max_level_width = cs.prog.max_width;
+        for (size_t j = 0; j < vals.size(); ++j) {
+            std::vector<int16_t> memo;
+            lowered[j] = vals[j];
+            recorded[j] = cs.dags[j].eval(cs.roots[j], (const uint8_t*)content, memo);
+            out->result_recorded |= recorded[j];
+        }
+        *n_starts = vals.size();
+    })
+}
+
 int fr_parse(const char* pattern, char* buf, size_t len) {
     return fr_parse_ex(pattern, FR_GRAMMAR_REFERENCE, buf, len);
 }

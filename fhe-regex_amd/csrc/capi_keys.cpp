@@ -1,5 +1,5 @@
-// C-ABI entries of the client side and the keys (include/fheregex.h): client and server
-// keys, encryption, the radix wire format, decryption.
+// C-ABI entries of the client side and the keys (include/fheregex.h): client, server and
+// packing keys, encryption, the radix wire format, decryption.
 #include <cstring>
 #include <vector>
 
@@ -247,6 +247,105 @@ int fr_load_server_key_compact(fr_ctx* ctx, const uint8_t* blob, size_t len) {
         ctx->mask_key = mk;
         ctx->sk_compact = true;
         ctx->has_sk = true;
+    })
+}
+
+// ---- packing key (keys.h): optional, beside the server key; nothing else depends on it
+
+static void gen_packing_key_with(fr_ctx* ctx, const RngKey& key) {
+    const bool on_dev = ctx->dev && ctx->keygen != FR_KEYGEN_HOST;
+    ctx->has_pk = false;
+    if (on_dev) {
+        ctx->pksk.clear();
+        ctx->pksk.shrink_to_fit();
+        ctx->dev->gen_packing_key(ctx->ck, key);
+    } else {
+        // the whole key through the row generator: kN^2 / 2 additions per row on every host
+        // thread, a few seconds in all
+        ctx->pksk.resize(pk_len(ctx->p));
+        gen_packing_rows(ctx->p, ctx->ck, key, 0, pk_rows(ctx->p), ctx->pksk.data());
+        if (ctx->dev) {
+            ctx->dev->upload_packing_key(ctx->pksk.data());
+            ctx->pksk.clear();
+            ctx->pksk.shrink_to_fit();
+        }
+    }
+    ctx->has_pk = true;
+}
+// checked before a key is drawn
+static void check_gen_packing_key(fr_ctx* ctx) {
+    NEED(ctx);
+    if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
+    if (ctx->keygen == FR_KEYGEN_DEVICE && !ctx->dev) throw Error(FR_ERR_NO_DEVICE, "device keygen needs a device");
+}
+
+int fr_gen_packing_key(fr_ctx* ctx, uint64_t seed) {
+    FR_TRY({
+        check_gen_packing_key(ctx);
+        ScopedKey key(seed);
+        gen_packing_key_with(ctx, key.k);
+    })
+}
+
+int fr_gen_packing_key_keyed(fr_ctx* ctx, const uint8_t* key32) {
+    FR_TRY({
+        check_gen_packing_key(ctx);
+        ScopedKey key(key32);
+        gen_packing_key_with(ctx, key.k);
+    })
+}
+
+int fr_gen_packing_rows_keyed(fr_ctx* ctx, const uint8_t* key32, size_t row_lo, size_t row_hi, uint64_t* out) {
+    FR_TRY({
+        NEED(ctx && row_lo <= row_hi && row_hi <= pk_rows(ctx->p) && (out || row_lo == row_hi));
+        if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
+        ScopedKey key(key32);
+        gen_packing_rows(ctx->p, ctx->ck, key.k, row_lo, row_hi, out);
+    })
+}
+
+int fr_packing_key_size(fr_ctx* ctx, size_t* bytes) {
+    FR_TRY({
+        NEED(ctx && bytes);
+        *bytes = pk_blob_size(ctx->p);
+    })
+}
+
+int fr_export_packing_key(fr_ctx* ctx, uint8_t* buf, size_t cap, size_t* written) {
+    FR_TRY({
+        NEED(ctx && written);
+        if (!ctx->has_pk) throw Error(FR_ERR_INVALID, "no packing key (fr_gen_packing_key, fr_load_packing_key)");
+        const size_t need = pk_blob_size(ctx->p);
+        *written = need;
+        if (!buf) return FR_OK;  // size query
+        NEED(cap >= need);
+        write_pk_header(ctx->p, buf);
+        // (a little-endian host: the rows are their wire form; PK_HEADER is a multiple of 8, but
+        // buf may sit anywhere)
+        if (ctx->dev) {
+            std::vector<uint64_t> rows(pk_len(ctx->p));
+            ctx->dev->download_packing_key(rows.data());
+            std::memcpy(buf + PK_HEADER, rows.data(), 8 * rows.size());
+        } else {
+            std::memcpy(buf + PK_HEADER, ctx->pksk.data(), 8 * ctx->pksk.size());
+        }
+    })
+}
+
+int fr_load_packing_key(fr_ctx* ctx, const uint8_t* blob, size_t len) {
+    FR_TRY({
+        NEED(ctx && blob);
+        // length, magic, parameters and gadget are checked before the installed key is touched
+        check_pk_blob(ctx->p, blob, len);
+        if (ctx->dev) {
+            ctx->has_pk = false;
+            ctx->dev->upload_packing_key(blob + PK_HEADER);  // drains every lane first
+        } else {
+            std::vector<uint64_t> rows(pk_len(ctx->p));
+            std::memcpy(rows.data(), blob + PK_HEADER, 8 * rows.size());
+            ctx->pksk = std::move(rows);
+        }
+        ctx->has_pk = true;
     })
 }
 

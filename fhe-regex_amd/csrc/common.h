@@ -42,6 +42,11 @@ FR_UNROLL
     }
 }
 
+// Packing keyswitch gadget (big LWE -> one GLWE under the client's own key):
+// signed base 2^7, 3 levels.  |digit| <= 64 fits int8, and a digit-times-byte-limb sum over
+// the 3 kN rows stays below 64 * 128 * 6144 < 2^26, exact in i32.
+constexpr int PK_BASE_LOG = 7, PK_LEVELS = 3;
+
 FR_HD uint32_t mod_switch(uint64_t a, int log2N2) {
     return (uint32_t)((((a >> (64 - log2N2 - 1)) + 1) >> 1) & ((1ULL << log2N2) - 1));
 }

@@ -78,6 +78,10 @@ struct fr_ctx {
     bool sk_on_device = false;  // server key generated on the device (export downloads it)
     bool sk_compact = false;    // the server key is in compact form (keys.h): mask_key expands its masks
     fr::RngKey mask_key{};      // public by design
+    // packing key (keys.h), optional: on a device context it lives on the device (the torus rows
+    // stay there for export); a host-only context keeps the rows here
+    std::vector<uint64_t> pksk;
+    bool has_pk = false;
     bool multi_value = true;  // merge same-input small-norm LUTs into one blind rotation
     bool async_match = true;  // has_match returns once its launches are enqueued (fr_set_async)
     uint64_t next_lane = 0;   // fr_set_lanes: consecutive asynchronous matches round-robin over the lanes

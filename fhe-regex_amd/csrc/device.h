@@ -81,6 +81,26 @@ class Device {
     // H2D copy, k_expand_ksk, k_expand_bsk, KSK limbs, k_bsk_fourier
     const double* key_load_ms() const { return key_load_ms_; }
     void download_server_key(uint64_t* ksk, size_t ksk_len, uint64_t* bsk, size_t bsk_len);
+    // Packing key (keys.h: pk_rows rows of (k+1) N words).  Generated on the device word for
+    // word as gen_packing_rows does on the host, or uploaded (little-endian u64 rows, any
+    // alignment); both keep the torus rows on the device for download_packing_key and build
+    // the byte limbs pack_bools multiplies by.  All three wait for the device.
+    void gen_packing_key(const ClientKey& ck, const RngKey& key);
+    void upload_packing_key(const void* rows);
+    void download_packing_key(uint64_t* rows);
+    bool has_packing_key() const { return d_pksk_ && d_pkl_; }
+    // parity hook: column col < (k+1) N of the byte-limb operand recombined into its 3 kN torus words
+    void packing_limb_column(int col, uint64_t* out_host);
+    // Packing keyswitch (keys.h: pack_host computes the same words): boolean j < n <= N is
+    // the affine form gates[j].offset 2^58 + sum_q in_w[q] arena[in_slot[q]] (outputs unused);
+    // the (k+1) N words of the packed GLWE are copied to out_host.  Runs on the current lane's
+    // stream after whatever wrote the slots; returns after the download.  The C ABI calls it
+    // outside a lane, so it runs on lane 0's stream, which first waits for every lane's queued
+    // work (cur_stream): packs of results from different lanes serialise behind all lanes.
+    void pack_bools(const DevGate* gates, size_t n, uint64_t* out_host);
+    // HIP-event ms of the last pack_bools under fr_set_profiling: digits (with the zeroing of
+    // the scratch), GEMM, rotate-sum
+    const double* pack_ms() const { return pack_ms_; }
     // fresh encryptions of block messages (encrypt_blocks, keys.h) written into
     // allocated arena slots, bit-identical to the host encryption
     void encrypt_to_slots(const ClientKey& ck, const uint8_t* msgs, size_t count, const RngKey& key, uint64_t first_block,
@@ -166,6 +186,9 @@ class Device {
         gpu::Stream stream;
         gpu::DevBuf<uint64_t> ks;    // keyswitch outputs [gates][ks_stride]
         gpu::DevBuf<int8_t> dig;     // keyswitch digits [rows][kN*ks_level]
+        gpu::DevBuf<DevGate> pk_gates;  // pack_bools: the booleans' descriptors
+        gpu::DevBuf<int8_t> pk_dig;  // pack_bools: digits [rows][3 kN], allocated at the first pack
+        gpu::DevBuf<uint64_t> pk_g;  // pack_bools: keyswitched rows [n][(k+1) N], then the packed GLWE
         gpu::StagingRing<int> cmap;  // content map (bind_content)
         size_t cmap_n = 0;           // entries bound
         gpu::Event done_ev;          // recorded on the lane's stream when it is left
@@ -213,6 +236,7 @@ class Device {
     void launch_br_fft(const DevGate* d_gates, const uint64_t* d_ks, size_t n, hipStream_t stream,
                        hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
     void build_ksk_limbs();  // d_kl_ from d_ksk_
+    void build_pk_limbs();   // d_pkl_ from d_pksk_ (keyswitch.hip)
     void build_fourier_bsk();  // keygen.hip: d_fbsk_ (every lane layout in use) from d_tbsk_
     double key_load_ms_[5] = {0, 0, 0, 0, 0};
     // expand_to_slots: the bodies and the slot list of a call, one copy (lane 0)
@@ -230,6 +254,10 @@ class Device {
     gpu::DevBuf<uint64_t> d_tbsk_;  // torus BSK of a device-generated or device-expanded key (export)
     gpu::DevBuf<int8_t> d_kl_;      // KSK as balanced byte limbs [col*8 + limb][k] (MFMA keyswitch)
     int kl_cols_ = 0;
+    gpu::DevBuf<uint64_t> d_pksk_;  // packing key, torus rows [3 kN][(k+1) N] (export)
+    gpu::DevBuf<int8_t> d_pkl_;     // ... as balanced byte limbs [col*8 + limb][k] (pack_bools)
+    double pack_ms_[3] = {0, 0, 0};
+    int pk_split_ = 0;              // FR_PK_SPLIT: K slices of the packing GEMM (a divisor of 24; 0: auto)
     bool ks_mfma_ = true;         // FR_KS_MFMA=0: the VALU lincomb+keyswitch kernel
     size_t ks_mr4_min_ = 96;      // FR_KS_MR4_MIN: batches from this size use 4 row tiles per wave (k_ks_glds; ab_ks_glds.log: 100 gates 44 -> 37 us, 64 gates no gain)
     int ks_mc_ = 0;               // FR_KS_MC=2: two column tiles per wave in the 4-row-tile shape (else one)

@@ -77,34 +77,28 @@ __global__ void __launch_bounds__(64) k_gen_ksk(RngKey key, int n, int L, int B,
     if (lane == 0) o[n] = acc + (s_big[i] << (64 - B * (j + 1))) + (uint64_t)noise[row];
 }
 
-// one GGSW row (w, r) of the torus BSK [w][r][c][coef]; 256 threads, N / 256
-// coefficients per thread; LDS: the mask polynomial A_j (N u64).  COMPACT: `key` is the
-// public mask key, so no mask word may carry the gadget (word - ChaCha word would show
-// m_w): rows r < k subtract it from the body at every set bit of S_r instead.
-template <int N, bool COMPACT>
-__global__ void __launch_bounds__(256) k_gen_bsk(RngKey key, int k,const uint64_t* __restrict__ s_big,
-                                                 const uint8_t* __restrict__ msg, const int32_t* __restrict__ noise,
-                                                 uint64_t gadget, uint64_t* __restrict__ bsk) {
+// The masks of one GLWE row and their exact key product, shared by k_gen_bsk and k_gen_pksk:
+// mask polynomial j < k is u64 numbers base + j N + t of `stream` (N % 8 == 0: whole ChaCha
+// blocks), stored to row[j N + t] (plus `gadget` on coefficient 0 of polynomial gj, if gj >= 0,
+// after the product used the mask); acc[q] += (sum_j A_j S_j)[tid + 256 q], negacyclic, binary
+// S: one add / sub per set bit of S per coefficient.  256 threads; LDS: A (N u64), sbits.
+template <int N>
+__device__ __forceinline__ void glwe_masks_product(const RngKey& key, uint64_t stream, uint64_t base, int k,
+                                                   const uint64_t* __restrict__ s_big, int gj, uint64_t gadget,
+                                                   uint64_t* __restrict__ row, uint64_t* A, uint32_t* sbits,
+                                                   uint64_t (&acc)[N / 256]) {
     constexpr int PER = N / 256;
-    __shared__ uint64_t A[N];
-    __shared__ uint32_t sbits[N / 32];
-    const int kp1 = k + 1, tid = threadIdx.x;
-    const int w = blockIdx.x / kp1, r = blockIdx.x % kp1;
-    uint64_t* row = bsk + ((size_t)w * kp1 + r) * kp1 * N;
-    uint64_t acc[PER];
-#pragma unroll
-    for (int q = 0; q < PER; ++q) acc[q] = 0;
+    const int tid = threadIdx.x;
     for (int j = 0; j < k; ++j) {
-        const uint64_t base = (((uint64_t)w * kp1 + r) * k + j) * N;  // N % 8 == 0: whole ChaCha blocks
+        const uint64_t bj = base + (uint64_t)j * N;
         for (int b = tid; b < N / 8; b += 256) {
             uint32_t wd[16];
-            chacha_block(key, STREAM_BSK_MASK, (base >> 3) + b, wd);
+            chacha_block(key, stream, (bj >> 3) + b, wd);
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 uint64_t v = chacha_u64(wd, q);
                 A[8 * b + q] = v;
-                // the gadget lands on coefficient 0 of component r after the body used A
-                if (!COMPACT && j == r && b == 0 && q == 0 && msg[w]) v += gadget;
+                if (j == gj && b == 0 && q == 0) v += gadget;
                 row[(size_t)j * N + 8 * b + q] = v;
             }
         }
@@ -133,6 +127,28 @@ __global__ void __launch_bounds__(256) k_gen_bsk(RngKey key, int k,const uint64_
         }
         __syncthreads();
     }
+}
+
+// one GGSW row (w, r) of the torus BSK [w][r][c][coef]; 256 threads, N / 256
+// coefficients per thread; LDS: the mask polynomial A_j (N u64).  COMPACT: `key` is the
+// public mask key, so no mask word may carry the gadget (word - ChaCha word would show
+// m_w): rows r < k subtract it from the body at every set bit of S_r instead.
+template <int N, bool COMPACT>
+__global__ void __launch_bounds__(256) k_gen_bsk(RngKey key, int k,const uint64_t* __restrict__ s_big,
+                                                 const uint8_t* __restrict__ msg, const int32_t* __restrict__ noise,
+                                                 uint64_t gadget, uint64_t* __restrict__ bsk) {
+    constexpr int PER = N / 256;
+    __shared__ uint64_t A[N];
+    __shared__ uint32_t sbits[N / 32];
+    const int kp1 = k + 1, tid = threadIdx.x;
+    const int w = blockIdx.x / kp1, r = blockIdx.x % kp1;
+    uint64_t* row = bsk + ((size_t)w * kp1 + r) * kp1 * N;
+    uint64_t acc[PER];
+#pragma unroll
+    for (int q = 0; q < PER; ++q) acc[q] = 0;
+    // the gadget lands on coefficient 0 of component r (r < k: a mask polynomial)
+    glwe_masks_product<N>(key, STREAM_BSK_MASK, ((uint64_t)w * kp1 + r) * k * N, k, s_big,
+                          !COMPACT && msg[w] ? r : -1, gadget, row, A, sbits, acc);
     const int32_t* e = noise + ((size_t)w * kp1 + r) * N;
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
@@ -140,6 +156,33 @@ __global__ void __launch_bounds__(256) k_gen_bsk(RngKey key, int k,const uint64_
         uint64_t v = acc[q] + (uint64_t)(int64_t)e[t];
         if (r == k && t == 0 && msg[w]) v += gadget;
         if (COMPACT && r < k && msg[w]) v -= gadget * (s_big[(size_t)r * N + t] & 1);
+        row[(size_t)k * N + t] = v;
+    }
+}
+
+// one row 3 i + l of the packing key (keys.h): k mask polynomials from STREAM_PKSK_MASK, body =
+// sum_j A_j S_j + noise, + s_big[i] 2^(64 - PK_BASE_LOG (l + 1)) on coefficient 0.  grid = rows of
+// (k + 1) N words, so every store is inside the key
+template <int N>
+__global__ void __launch_bounds__(256) k_gen_pksk(RngKey key, int k, const uint64_t* __restrict__ s_big,
+                                                  const int32_t* __restrict__ noise, uint64_t* __restrict__ pksk) {
+    constexpr int PER = N / 256;
+    __shared__ uint64_t A[N];
+    __shared__ uint32_t sbits[N / 32];
+    const int tid = threadIdx.x;
+    const size_t r = blockIdx.x;
+    const int i = (int)(r / PK_LEVELS), l = (int)(r % PK_LEVELS);
+    uint64_t* row = pksk + r * (size_t)(k + 1) * N;
+    uint64_t acc[PER];
+#pragma unroll
+    for (int q = 0; q < PER; ++q) acc[q] = 0;
+    glwe_masks_product<N>(key, STREAM_PKSK_MASK, (uint64_t)r * k * N, k, s_big, -1, 0, row, A, sbits, acc);
+    const int32_t* e = noise + r * N;
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        const int t = tid + 256 * q;
+        uint64_t v = acc[q] + (uint64_t)(int64_t)e[t];
+        if (t == 0) v += (s_big[i] & 1) << (64 - PK_BASE_LOG * (l + 1));
         row[(size_t)k * N + t] = v;
     }
 }
@@ -480,6 +523,45 @@ void Device::load_server_key_compact(const RngKey& mask_key, const uint8_t* bodi
             HIP_CHECK(hipEventElapsedTime(&ms, ev[i].get(), ev[i + 1].get()));
             key_load_ms_[i] = ms;
         }
+}
+
+// Packing key on the device: the torus rows stay for download_packing_key (as the torus BSK
+// does), the byte limbs are the MFMA operand of pack_bools
+void Device::gen_packing_key(const ClientKey& ck, const RngKey& key) {
+    if (!((p_.N == 2048 && p_.k == 1) || (p_.N == 1024 && p_.k == 2)))
+        throw Error(FR_ERR_INVALID, "device packing keygen: (k, N) in {(1, 2048), (2, 1024)}");
+    if (ck.s_big.size() != (size_t)p_.big()) throw Error(FR_ERR_INVALID, "device packing keygen: key size");
+    const size_t rows = pk_rows(p_);
+    // every queued pack of every lane that reads the old key has finished before it goes
+    HIP_CHECK(hipDeviceSynchronize());
+    std::vector<int32_t> noise;
+    gen_pksk_noise(p_, key, noise);
+    const hipStream_t s = cur().stream.get();
+    gpu::DevBuf<uint64_t> d_sb(ck.s_big.size());
+    gpu::DevBuf<int32_t> d_n(noise.size());
+    HIP_CHECK(hipMemcpyAsync(d_sb.get(), ck.s_big.data(), 8 * ck.s_big.size(), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_n.get(), noise.data(), 4 * noise.size(), hipMemcpyHostToDevice, s));
+    d_pkl_.reset();
+    d_pksk_.alloc(pk_len(p_));
+    if (p_.N == 2048) k_gen_pksk<2048><<<(unsigned)rows, 256, 0, s>>>(key, p_.k, d_sb.get(), d_n.get(), d_pksk_.get());
+    else k_gen_pksk<1024><<<(unsigned)rows, 256, 0, s>>>(key, p_.k, d_sb.get(), d_n.get(), d_pksk_.get());
+    HIP_CHECK(hipGetLastError());
+    build_pk_limbs();
+    HIP_CHECK(hipStreamSynchronize(s));  // the temporaries go once the kernels have run
+}
+
+void Device::upload_packing_key(const void* rows) {
+    HIP_CHECK(hipDeviceSynchronize());
+    d_pkl_.reset();
+    d_pksk_.alloc(pk_len(p_));
+    HIP_CHECK(hipMemcpy(d_pksk_.get(), rows, 8 * pk_len(p_), hipMemcpyHostToDevice));
+    build_pk_limbs();
+    HIP_CHECK(hipStreamSynchronize(cur().stream.get()));
+}
+
+void Device::download_packing_key(uint64_t* rows) {
+    if (!has_packing_key()) throw Error(FR_ERR_INVALID, "no packing key on the device");
+    HIP_CHECK(hipMemcpy(rows, d_pksk_.get(), 8 * pk_len(p_), hipMemcpyDeviceToHost));
 }
 
 void Device::download_server_key(uint64_t* ksk, size_t ksk_len, uint64_t* bsk, size_t bsk_len) {

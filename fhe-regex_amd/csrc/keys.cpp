@@ -11,6 +11,7 @@
 
 #include <sys/random.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cerrno>
 #include <climits>
@@ -645,6 +646,159 @@ uint64_t lwe_phase(const Params& p, const ClientKey& ck, const uint64_t* lwe) {
     uint64_t acc = lwe[big];
     for (int t = 0; t < big; ++t) acc -= lwe[t] * ck.s_big[t];
     return acc;
+}
+
+// ---------------------------------------------------------------- packed results
+// dst += X^u src over Z_2^64[X] / (X^N + 1): coefficient t + u gets src[t], negated past the wrap
+static void add_rotated(uint64_t* dst, const uint64_t* src, int u, int N) {
+    for (int t = 0; t < N - u; ++t) dst[t + u] += src[t];
+    for (int t = N - u; t < N; ++t) dst[t + u - N] -= src[t];
+}
+
+void gen_packing_rows(const Params& p, const ClientKey& ck, const RngKey& key, size_t row_lo, size_t row_hi,
+                      uint64_t* out) {
+    const int k = p.k, N = p.N;
+    const size_t W = pk_row_words(p);
+    if (row_lo > row_hi || row_hi > pk_rows(p)) throw Error(FR_ERR_INVALID, "packing key: row range");
+    if (ck.s_big.size() != (size_t)p.big()) throw Error(FR_ERR_INVALID, "packing key: client key size");
+    parallel_for((int)(row_hi - row_lo), [&](int q) {
+        Rng rm(key, STREAM_PKSK_MASK), rn(key, STREAM_PKSK_NOISE);
+        const uint64_t r = row_lo + (uint64_t)q;
+        const size_t i = r / PK_LEVELS, l = r % PK_LEVELS;
+        uint64_t* row = out + (size_t)q * W;
+        uint64_t* Bp = row + (size_t)k * N;
+        std::fill(Bp, Bp + N, 0);
+        for (int j = 0; j < k; ++j) {
+            uint64_t* A = row + (size_t)j * N;
+            const uint64_t base = (r * k + j) * N;
+            for (int t = 0; t < N; ++t) A[t] = rm.u64(base + t);
+            const uint64_t* S = ck.s_big.data() + (size_t)j * N;
+            for (int u = 0; u < N; ++u)
+                if (S[u]) add_rotated(Bp, A, u, N);
+        }
+        for (int t = 0; t < N; ++t) Bp[t] += (uint64_t)rn.gaussian(r * N + t, p.glwe_sigma);
+        Bp[0] += ck.s_big[i] << (64 - PK_BASE_LOG * (l + 1));
+    });
+}
+
+void gen_pksk_noise(const Params& p, const RngKey& key, std::vector<int32_t>& e) {
+    const size_t rows = pk_rows(p), N = (size_t)p.N;
+    e.resize(rows * N);
+    std::atomic<bool> ok{true};
+    parallel_for((int)rows, [&](int r) {
+        Rng rn(key, STREAM_PKSK_NOISE);
+        for (size_t t = 0; t < N; ++t) {
+            const int64_t v = rn.gaussian((uint64_t)r * N + t, p.glwe_sigma);
+            if (v < INT32_MIN || v > INT32_MAX) ok = false;
+            e[(size_t)r * N + t] = (int32_t)v;
+        }
+    });
+    if (!ok) throw Error(FR_ERR_INVALID, "GLWE noise outside int32 (sigma too large for the device key generator)");
+}
+
+static const char PK_MAGIC[9] = "FRPKKEY1";
+static const char PKRES_MAGIC[9] = "FRPKRES1";
+
+void write_pk_header(const Params& p, uint8_t* out) {
+    std::memcpy(out, PK_MAGIC, 8);
+    int32_t v[8];
+    compact_params(p, v);
+    for (int i = 0; i < 8; ++i) put_le32(out + 8 + 4 * i, (uint32_t)v[i]);
+    put_le32(out + 40, (uint32_t)PK_BASE_LOG);
+    put_le32(out + 44, (uint32_t)PK_LEVELS);
+}
+
+void check_pk_blob(const Params& p, const uint8_t* blob, size_t len) {
+    if (!blob || len != pk_blob_size(p))
+        throw Error(FR_ERR_INVALID, "packing key: length does not match the context params (fr_packing_key_size)");
+    if (std::memcmp(blob, PK_MAGIC, 8)) throw Error(FR_ERR_INVALID, "packing key: bad magic");
+    int32_t want[8];
+    compact_params(p, want);
+    for (int i = 0; i < 8; ++i)
+        if (get_le32(blob + 8 + 4 * i) != (uint32_t)want[i])
+            throw Error(FR_ERR_INVALID, "packing key: parameters do not match the context params");
+    if (get_le32(blob + 40) != (uint32_t)PK_BASE_LOG || get_le32(blob + 44) != (uint32_t)PK_LEVELS)
+        throw Error(FR_ERR_INVALID, "packing key: gadget other than base 2^7, 3 levels");
+}
+
+// Rows of the key are streamed once per block of PACK_JB booleans, whose partial sums
+// (PACK_JB rows of (k+1) N words) stay in cache meanwhile.
+constexpr size_t PACK_JB = 16;
+void pack_host(const Params& p, const uint64_t* pksk, const uint64_t* lwes, const int32_t* w, const int32_t* off,
+               size_t n, uint64_t* out) {
+    const int N = p.N, big = p.big();
+    const size_t W = pk_row_words(p), KD = pk_rows(p), L = (size_t)p.lwe_len();
+    if (n < 1 || n > (size_t)N) throw Error(FR_ERR_INVALID, "pack: 1 <= n <= N booleans");
+    std::fill(out, out + W, 0);
+    const size_t blocks = (n + PACK_JB - 1) / PACK_JB;
+    std::vector<std::vector<uint64_t>> part(blocks);
+    parallel_for((int)blocks, [&](int b) {
+        const size_t j0 = (size_t)b * PACK_JB, nj = std::min(PACK_JB, n - j0);
+        std::vector<uint64_t> G(nj * W, 0);
+        std::vector<int8_t> dig(nj * KD, 0);
+        for (size_t jj = 0; jj < nj; ++jj) {
+            const size_t j = j0 + jj;
+            const uint64_t wj = (uint64_t)(int64_t)(w ? w[j] : 1);
+            uint64_t body = (uint64_t)(int64_t)(off ? off[j] : 0) << (DELTA_LOG - 1);
+            if (wj) {
+                const uint64_t* c = lwes + j * L;
+                body += wj * c[big];
+                for (int i = 0; i < big; ++i) {
+                    int32_t d[PK_LEVELS];
+                    ks_decompose<PK_BASE_LOG, PK_LEVELS>(wj * c[i], d);
+                    for (int l = 0; l < PK_LEVELS; ++l) dig[jj * KD + (size_t)i * PK_LEVELS + l] = (int8_t)d[l];
+                }
+            }
+            G[jj * W + (size_t)big] = body;  // coefficient 0 of the body polynomial
+        }
+        for (size_t r = 0; r < KD; ++r) {
+            const uint64_t* row = pksk + r * W;
+            for (size_t jj = 0; jj < nj; ++jj) {
+                const int8_t d = dig[jj * KD + r];
+                if (!d) continue;
+                const uint64_t m = (uint64_t)(int64_t)d;
+                uint64_t* g = G.data() + jj * W;
+                for (size_t t = 0; t < W; ++t) g[t] -= m * row[t];
+            }
+        }
+        std::vector<uint64_t>& acc = part[(size_t)b];
+        acc.assign(W, 0);
+        for (size_t jj = 0; jj < nj; ++jj)
+            for (int c = 0; c <= p.k; ++c)
+                add_rotated(acc.data() + (size_t)c * N, G.data() + jj * W + (size_t)c * N, (int)(j0 + jj), N);
+    });
+    for (const auto& acc : part)
+        for (size_t t = 0; t < W; ++t) out[t] += acc[t];
+}
+
+void write_packed_result(const Params& p, size_t n, const uint64_t* words, uint8_t* out) {
+    std::memcpy(out, PKRES_MAGIC, 8);
+    put_le32(out + 8, (uint32_t)p.k);
+    put_le32(out + 12, (uint32_t)p.N);
+    put_le64(out + 16, n);
+    for (size_t t = 0; t < pk_row_words(p); ++t) put_le64(out + PKRES_HEADER + 8 * t, words[t]);
+}
+
+size_t check_packed_result(const Params& p, const uint8_t* blob, size_t len) {
+    if (!blob || len != packed_result_size(p))
+        throw Error(FR_ERR_INVALID, "packed result: length is not 24 + 8 (k+1) N (fr_packed_result_size)");
+    if (std::memcmp(blob, PKRES_MAGIC, 8)) throw Error(FR_ERR_INVALID, "packed result: bad magic");
+    if (get_le32(blob + 8) != (uint32_t)p.k || get_le32(blob + 12) != (uint32_t)p.N)
+        throw Error(FR_ERR_INVALID, "packed result: k, N do not match the context params");
+    const uint64_t n = get_le64(blob + 16);
+    if (n < 1 || n > (uint64_t)p.N) throw Error(FR_ERR_INVALID, "packed result: n outside 1..N");
+    return (size_t)n;
+}
+
+void glwe_phase(const Params& p, const ClientKey& ck, const uint64_t* ct, uint64_t* phase) {
+    const int k = p.k, N = p.N;
+    std::vector<uint64_t> as((size_t)N, 0);
+    for (int j = 0; j < k; ++j) {
+        const uint64_t* S = ck.s_big.data() + (size_t)j * N;
+        for (int u = 0; u < N; ++u)
+            if (S[u]) add_rotated(as.data(), ct + (size_t)j * N, u, N);
+    }
+    for (int t = 0; t < N; ++t) phase[t] = ct[(size_t)k * N + t] - as[t];
 }
 
 uint32_t decode16(uint64_t phase) {

@@ -23,6 +23,8 @@ enum Stream : uint64_t {
     STREAM_ENC_NOISE = 6,
     STREAM_CLIENT_KEY = 7,
     STREAM_MASK_KEY = 8,  // block 0, words 0..7: the public mask key of a compact server key or content blob
+    STREAM_PKSK_MASK = 9,
+    STREAM_PKSK_NOISE = 10,
 };
 
 class Rng {
@@ -111,6 +113,44 @@ std::vector<uint8_t> pack_compact(const Params& p, const RngKey& mask_key, const
 // check_compact, then every mask from the mask key around the blob's bodies
 void expand_compact(const Params& p, const uint8_t* blob, size_t len, std::vector<uint64_t>& ksk,
                     std::vector<uint64_t>& bsk, RngKey& mask_key);
+
+// Packing key (DESIGN.md §1 "Packed results"): row 3 i + l, i < kN, l < PK_LEVELS, is a GLWE
+// encryption under the GLWE key (the big key read as k polynomials) of the constant polynomial
+// s_big[i] 2^(64 - PK_BASE_LOG (l + 1)): k mask polynomials, then the body, (k+1) N words.
+// Mask polynomial j of a row is u64 numbers (row k + j) N + t of STREAM_PKSK_MASK, the body's
+// noise numbers row N + t of STREAM_PKSK_NOISE (the BSK generator's indexing).
+inline size_t pk_rows(const Params& p) { return (size_t)p.big() * PK_LEVELS; }
+inline size_t pk_row_words(const Params& p) { return (size_t)(p.k + 1) * p.N; }
+inline size_t pk_len(const Params& p) { return pk_rows(p) * pk_row_words(p); }
+// rows row_lo <= row < row_hi into out[(row_hi - row_lo) * pk_row_words]; the whole key takes
+// a few seconds of host time (each row is k N^2 / 2 additions), hence the range
+void gen_packing_rows(const Params& p, const ClientKey& ck, const RngKey& key, size_t row_lo, size_t row_hi,
+                      uint64_t* out);
+// the body noise of every row for the device generator ([row][N], glwe sigma, torus units)
+void gen_pksk_noise(const Params& p, const RngKey& key, std::vector<int32_t>& e);
+// Wire blob: "FRPKKEY1", the eight int32 parameters of the compact server key blob,
+// PK_BASE_LOG, PK_LEVELS (int32), then the rows; little endian
+constexpr size_t PK_HEADER = 48;
+inline size_t pk_blob_size(const Params& p) { return PK_HEADER + 8 * pk_len(p); }
+void write_pk_header(const Params& p, uint8_t* out /* PK_HEADER bytes */);
+// Error(FR_ERR_INVALID) unless len, the magic, the parameters and the gadget are p's
+void check_pk_blob(const Params& p, const uint8_t* blob, size_t len);
+
+// Packing keyswitch, host restatement (plain loops; the device path is keyswitch.hip's):
+//   out = sum_j X^j ((0, .., 0, b_j) - sum_{i,l} d_{j,i,l} PKSK[3 i + l])
+// over (Z_2^64[X] / (X^N + 1))^(k+1), for the n <= N booleans c_j = off_j 2^58 + w_j lwe_j
+// (w, off NULL: 1, 0; w_j = 0: a constant, its LWE is not read), d the signed base-2^7
+// digits of the mask of c_j rounded to 21 bits.  Exact mod 2^64.
+void pack_host(const Params& p, const uint64_t* pksk, const uint64_t* lwes, const int32_t* w, const int32_t* off,
+               size_t n, uint64_t* out /* (k+1) N */);
+// Packed result blob: "FRPKRES1", int32 k, N, u64 n, then the (k+1) N words; little endian
+constexpr size_t PKRES_HEADER = 24;
+inline size_t packed_result_size(const Params& p) { return PKRES_HEADER + 8 * pk_row_words(p); }
+void write_packed_result(const Params& p, size_t n, const uint64_t* words, uint8_t* out);
+// Error(FR_ERR_INVALID) unless len, the magic, k and N are p's and 1 <= n <= N; returns n
+size_t check_packed_result(const Params& p, const uint8_t* blob, size_t len);
+// phase B - sum_c A_c S_c (negacyclic) of a GLWE ciphertext under the client key: N words
+void glwe_phase(const Params& p, const ClientKey& ck, const uint64_t* ct, uint64_t* phase);
 
 // noise of encrypt_blocks for blocks first_block .. first_block + count - 1
 void enc_noise(const Params& p, const RngKey& key, uint64_t first_block, size_t count, std::vector<int64_t>& e);

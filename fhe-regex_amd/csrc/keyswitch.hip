@@ -8,10 +8,13 @@
 //   k_ks_glds<SK,NB>    : the four-row-tile shape with both operands staged by LDS-DMA
 //   k_ksk_limbs         : one-time KSK -> balanced byte limbs in fragment order
 //   k_linear            : linear combination into a slot without a bootstrap
+//   k_pack_rotate_sum   : the packing keyswitch's sum_j X^j G[j] (its digits and GEMM are the
+//                         kernels above with the (2^7, 3) gadget and the packing key's limbs)
 #include <algorithm>
 #include <cstdlib>
 
 #include "device_impl.h"
+#include "keys.h"
 
 namespace fr {
 
@@ -529,6 +532,7 @@ void Device::init_ks() {
     if (const char* ev = std::getenv("FR_KS_XCD")) ks_xcd_ = std::atoi(ev) != 0;
     if (const char* ev = std::getenv("FR_KS_LDS")) ks_lds_ = std::atoi(ev) != 0;
     if (const char* ev = std::getenv("FR_KS_DIG16")) ks_dig16_ = std::atoi(ev) != 0;
+    if (const char* ev = std::getenv("FR_PK_SPLIT")) pk_split_ = std::atoi(ev);
 }
 
 void Device::ensure_digits(size_t rows) {
@@ -617,6 +621,140 @@ void Device::launch_ks(const DevGate* d_gates, size_t n, uint64_t* d_ks, hipEven
                           arena, p_.slot_stride(), d_cmap, (const uint64_t*)d_ksk_.get(), p_.n,
                           p_.big(), per, (unsigned long long*)d_ks, p_.ks_stride());
     HIP_CHECK(hipGetLastError());
+}
+
+// ------------------------------------------------- packing keyswitch
+// n <= N booleans into the N coefficients of one GLWE under the client's key (keys.h):
+//   G[j] = (0, .., 0, b_j) - D[j] x PKSK     the keyswitch above with the (2^7, 3) gadget, KD = 3 kN
+//                                            rows of (k+1) N columns; b_j at column kN
+//   out  = sum_j X^j G[j]                    k_pack_rotate_sum
+// The digit and MFMA kernels are the LWE keyswitch's, with this operand's KD, columns and stride.
+
+// out[c][t] += sum_{j0 <= j < j1} +-G[j][c][(t - j) mod N], negated where t < j (X^N = -1).  One
+// thread per output word and j slice (blockIdx.y); for a fixed j a wave reads 64 consecutive
+// words (two runs at the wrap).  The slices meet in 64-bit atomics, exact mod 2^64 in any
+// order, in an output zeroed before.  W = (k+1) N is a multiple of 256, N a power of two.
+__global__ void __launch_bounds__(256) k_pack_rotate_sum(const uint64_t* __restrict__ G, int n, int N, int W, int jper,
+                                                         unsigned long long* __restrict__ out) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    const int t = c & (N - 1), base = c - t;
+    const int j0 = blockIdx.y * jper, j1 = min(n, j0 + jper);
+    uint64_t acc = 0;
+    for (int j = j0; j < j1; ++j) {
+        const int d = t - j;
+        const uint64_t v = G[(size_t)j * W + base + (d >= 0 ? d : d + N)];
+        acc = d >= 0 ? acc + v : acc - v;
+    }
+    if (c < W && acc != 0) atomicAdd(&out[c], (unsigned long long)acc);
+}
+
+// test hook: column t of a limb operand put back together, out[k] = sum_l L_l[k] 256^l (mod 2^64)
+__global__ void __launch_bounds__(256) k_limb_column(const int8_t* __restrict__ kl, int KD, int t,
+                                                     uint64_t* __restrict__ out) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= KD) return;
+    uint64_t v = 0;
+#pragma unroll
+    for (int l = 0; l < 8; ++l) v += (uint64_t)(int64_t)kl[ks_frag(ks_limb_col(t, l), k, KD / 32)] << (8 * l);
+    out[k] = v;
+}
+
+void Device::packing_limb_column(int col, uint64_t* out_host) {
+    if (!has_packing_key()) throw Error(FR_ERR_INVALID, "no packing key on the device");
+    const int KD = (int)pk_rows(p_);
+    if (col < 0 || col >= (int)pk_row_words(p_)) throw Error(FR_ERR_INVALID, "packing key: column out of range");
+    gpu::DevBuf<uint64_t> d((size_t)KD);
+    k_limb_column<<<(KD + 255) / 256, 256, 0, STREAM>>>(d_pkl_.get(), KD, col, d.get());
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out_host, d.get(), 8 * (size_t)KD, hipMemcpyDeviceToHost, STREAM));
+    HIP_CHECK(hipStreamSynchronize(STREAM));
+}
+
+void Device::build_pk_limbs() {
+    const int KD = (int)pk_rows(p_), ncols = (int)pk_row_words(p_);
+    const int nlc = ((ncols * 8 + 127) / 128) * 128;  // whole 4-wave column groups
+    d_pkl_.alloc((size_t)nlc * KD);
+    HIP_CHECK(hipMemsetAsync(d_pkl_.get(), 0, (size_t)nlc * KD, STREAM));
+    k_ksk_limbs<<<dim3((unsigned)((KD + 255) / 256), (unsigned)(nlc / 8)), 256, 0, STREAM>>>(d_pksk_.get(), KD, ncols, nlc,
+                                                                                          d_pkl_.get());
+    HIP_CHECK(hipGetLastError());
+}
+
+void Device::pack_bools(const DevGate* gates, size_t n, uint64_t* out_host) {
+    if (!has_packing_key()) throw Error(FR_ERR_INVALID, "no packing key on the device");
+    const int N = p_.N, big = p_.big(), KD = (int)pk_rows(p_), W = (int)pk_row_words(p_);
+    if (n < 1 || n > (size_t)N) throw Error(FR_ERR_INVALID, "pack: 1 <= n <= N booleans");
+    if (KD % 256 || big % 16 || W % 256) throw Error(FR_ERR_INVALID, "pack: kN must be a multiple of 256");
+    for (size_t j = 0; j < n; ++j) {
+        const DevGate& g = gates[j];
+        if (g.n_in < 0 || g.n_in > 16) throw Error(FR_ERR_INVALID, "pack: bad descriptor");
+        for (int q = 0; q < g.n_in; ++q)
+            if (g.in_slot[q] < 0 || (size_t)g.in_slot[q] >= next_slot_) throw Error(FR_ERR_INVALID, "pack: bad input slot");
+    }
+    const hipStream_t s = STREAM;
+    LaneState& l = cur();
+    const int MR = n >= ks_mr4_min_ ? 4 : 1;  // row tiles per wave, as launch_ks
+    const size_t bp = (n + 32 * MR - 1) / (32 * MR) * (32 * MR);
+    // scratch: the descriptors, digits [bp][KD], G [n][W] and the packed GLWE behind it; allocated at the first
+    // pack of the lane, doubled from there
+    if (bp * KD > l.pk_dig.size() || (n + 1) * (size_t)W > l.pk_g.size() || n > l.pk_gates.size()) {
+        HIP_CHECK(hipStreamSynchronize(s));
+        l.pk_dig.grow(bp * KD, (size_t)128 * KD);
+        l.pk_g.grow((n + 1) * (size_t)W, (size_t)129 * W);
+        l.pk_gates.grow(n, 128);
+    }
+    int8_t* d_dig = l.pk_dig.get();
+    uint64_t* d_g = l.pk_g.get();
+    uint64_t* d_out = d_g + n * (size_t)W;
+    DevGate* d_gates = l.pk_gates.get();
+    HIP_CHECK(hipMemcpyAsync(d_gates, gates, sizeof(DevGate) * n, hipMemcpyHostToDevice, s));
+    gpu::Event ev[4];
+    const bool timed = profiling_ != 0;
+    auto mark = [&](int i) {
+        if (timed) HIP_CHECK(hipEventRecord(ev[i].get(), s));
+    };
+    if (timed)
+        for (gpu::Event& e : ev) e = gpu::Event(hipEventDefault);
+    // the digit pass zeroes the mask columns of G and writes column kN: the rest of the body
+    // polynomial's columns (from kN, ahead of that write) and the output row are zeroed here,
+    // inside the first stage's time
+    mark(0);
+    HIP_CHECK(hipMemset2DAsync(d_g + big, 8 * (size_t)W, 0, 8 * (size_t)N, n, s));
+    HIP_CHECK(hipMemsetAsync(d_out, 0, 8 * (size_t)W, s));
+    k_ks_digits16<PK_BASE_LOG, PK_LEVELS><<<dim3((unsigned)bp), dim3(128), 0, s>>>(
+        d_gates, (int)n, d_arena_.get(), p_.slot_stride(), l.cmap.device(), big, d_dig, d_g, big, W);
+    HIP_CHECK(hipGetLastError());
+    mark(1);
+    // Tiles for 32768 limb columns: GY = 256 column groups (the LWE keyswitch has 47) fill the
+    // 256 CUs without K slices, so the four-row-tile shape runs unsliced (tools/pack_probe.py,
+    // profiles/packed_results: 256 rows 68 us at 1 slice, 78 at 2, 117 at 8; 2048 rows 485 /
+    // 540 / 939) and one row tile per wave takes 2 (16 rows: 33 us at 2 and 4, 38 at 1)
+    const int nlc = W * 8, GX = (int)(bp / (32 * MR)), GY = nlc / 128;
+    int GZ = MR == 1 ? 2 : 1;  // a divisor of KD / 256 = 24
+    if (pk_split_ > 0 && (KD / 256) % pk_split_ == 0) GZ = pk_split_;
+    const dim3 grid((unsigned)ks_grid_blocks(GX, GY, GZ, ks_xcd_));
+    if (MR == 4)
+        k_ks_glds<FR_KS_SK, FR_KS_NB><<<grid, dim3(256), 0, s>>>((const int8_t*)d_dig, (const int8_t*)d_pkl_.get(), (int)n,
+                                                                 KD, W, nlc, (unsigned long long*)d_g, W, GX, GY, GZ,
+                                                                 ks_xcd_);
+    else
+        k_ks_mfma<1, 1><<<grid, dim3(256), 0, s>>>((const int8_t*)d_dig, (const int8_t*)d_pkl_.get(), (int)n, KD, W, nlc,
+                                                   (unsigned long long*)d_g, W, GX, GY, GZ, ks_xcd_);
+    HIP_CHECK(hipGetLastError());
+    mark(2);
+    const int jper = 32, slices = (int)((n + jper - 1) / jper);
+    k_pack_rotate_sum<<<dim3((unsigned)(W / 256), (unsigned)slices), 256, 0, s>>>(d_g, (int)n, N, W, jper,
+                                                                                   (unsigned long long*)d_out);
+    HIP_CHECK(hipGetLastError());
+    mark(3);
+    HIP_CHECK(hipMemcpyAsync(out_host, d_out, 8 * (size_t)W, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (timed)
+        for (int i = 0; i < 3; ++i) {
+            float ms = 0;
+            HIP_CHECK(hipEventElapsedTime(&ms, ev[i].get(), ev[i + 1].get()));
+            pack_ms_[i] = ms;
+        }
 }
 
 void Device::run_linear(const DevGate& g) {

@@ -678,6 +678,48 @@ CompiledMatch compile_match(const MatchSpec& s) {
     return m;
 }
 
+CompiledStarts compile_match_starts(const MatchSpec& s, bool keep_dags) {
+    CompiledStarts m;
+    const ReP re = parse(s.pattern, s.grammar);  // engine.rs:13 (an empty range lo >= hi: no start)
+    // structure of a merged gate (its inputs already remapped) -> its index
+    std::map<std::string, int32_t> seen;
+    auto structure = [](const PGate& g) {
+        std::string k((const char*)g.lut, 16);
+        auto put = [&](int32_t v) { k.append((const char*)&v, 4); };
+        put(g.offset);
+        put(g.kind);
+        for (const PIn& in : g.ins) put(in.src), put(in.w);
+        return k;
+    };
+    Program& out = m.prog;
+    for (size_t st = s.lo; st < s.hi; ++st) {
+        ValueDag dag;
+        const Recorded rec = record_has_match_engine(dag, s.n_chars, re, st, st + 1, s.engine);
+        const Program p = lower(dag, rec.root, s.lowering, 1);
+        m.rec.ct_ops += rec.ct_ops;
+        m.rec.cache_hits += rec.cache_hits;
+        m.rec.n_branches += rec.n_branches;
+        std::vector<int32_t> at(p.gates.size());  // gate of p -> merged gate
+        for (size_t g = 0; g < p.gates.size(); ++g) {
+            PGate G = p.gates[g];
+            for (PIn& in : G.ins)
+                if (in.src >= 0) in.src = at[(size_t)in.src];
+            const auto ins = seen.emplace(structure(G), (int32_t)out.gates.size());
+            if (ins.second) out.gates.push_back(std::move(G));
+            at[g] = ins.first->second;
+        }
+        ProgOut o = p.outs.at(0);
+        if (o.gate >= 0) o.gate = at[(size_t)o.gate];
+        out.outs.push_back(o);
+        if (keep_dags) {
+            m.roots.push_back(rec.root);
+            m.dags.push_back(std::move(dag));
+        }
+    }
+    compute_levels(out);
+    return m;
+}
+
 int eval_program(const Program& prog, const uint8_t* content, size_t L) {
     std::vector<int> parts;
     return eval_program_parts(prog, content, L, parts);

@@ -92,6 +92,23 @@ struct CompiledMatch {
 };
 CompiledMatch compile_match(const MatchSpec& spec);
 
+// Match starts: one boolean per start offset s of [lo, hi), the value the reference ORs away at
+// engine.rs:22-35 (compile_match of [s, s + 1) with one part).  The per-start programs are
+// merged into one with structural dedupe -- a gate with the (ins, offset, kind, lut) of an
+// earlier one is that gate -- so the nibble tests of a content position are shared by every
+// start that reads it, and everything above them transitively.  prog.outs[s - lo] is start s's
+// output (gate == -1: a constant, e.g. /^abc/ at s > 0); rec sums the recordings' counters;
+// keep_dags: dags[s - lo] / roots[s - lo] are start s's recorded circuit (a plaintext
+// evaluation's; the execution path does not hold them).  Errors in compile_match's order, of
+// the first start that has one.  spec.parts is not used; lo >= hi is no start at all.
+struct CompiledStarts {
+    Recorded rec;
+    Program prog;
+    std::vector<ValueDag> dags;
+    std::vector<int> roots;
+};
+CompiledStarts compile_match_starts(const MatchSpec& spec, bool keep_dags = false);
+
 // LUT builders
 void lut_eq(uint8_t* lut, int v);     // [x == v]
 void lut_sign(uint8_t* lut, int v);   // x < v -> 0, x == v -> 1, x > v -> 2

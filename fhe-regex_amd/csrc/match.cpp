@@ -27,10 +27,10 @@ namespace {
 // The key is a fixed number of '|'-terminated numeric fields followed by the pattern, so a
 // pattern's own text (which may contain '|' and digits) cannot make two keys collide.
 std::string match_key(fr_ctx* ctx, const char* pattern, size_t n, size_t M, size_t lo, size_t hi, size_t parts,
-                      int lane) {
+                      int lane, bool starts) {
     std::string k;
     for (size_t v : {(size_t)ctx->grammar, (size_t)ctx->engine, (size_t)ctx->lowering, (size_t)ctx->multi_value, n, M,
-                     lo, hi, parts, (size_t)lane})
+                     lo, hi, parts, (size_t)lane, (size_t)starts})
         k += std::to_string(v) + "|";
     k += pattern;
     return k;
@@ -129,8 +129,10 @@ void fill_stats(fr_match_stats& s, const Recorded& rec, const Plan& P) {
 // program, so every level of the M matches shares its launches (M = 1: has_match).
 // parts > 1 (fr_has_match_parts): each match returns up to `parts` booleans whose OR is
 // its result, outs[m * P + j] with P = *n_parts (the same for every m).
+// starts (fr_match_starts, M = 1): the program is compile_match_starts', its hi - lo outputs
+// one boolean per start offset.
 void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const char* pattern, size_t lo, size_t hi,
-                fr_ct* outs, fr_match_stats* st, size_t parts = 1, size_t* n_parts = nullptr) {
+                fr_ct* outs, fr_match_stats* st, size_t parts = 1, size_t* n_parts = nullptr, bool starts = false) {
     double t0 = now_ms();
     pattern = pattern ? pattern : "";
     Device& dev = ctx->keyed_device();
@@ -155,7 +157,7 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
         }
     } lane_scope{dev};
     if (pc.capacity) {
-        key = match_key(ctx, pattern, n, M, lo, hi, parts, lane);
+        key = match_key(ctx, pattern, n, M, lo, hi, parts, lane, starts);
         sig = content_signature(ctx, content, n * M, &cmap);
         for (auto& e : pc.entries)
             if (e->parts == parts && e->lane == lane && e->key == key && e->sig == sig) hit = e.get();
@@ -173,9 +175,15 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
         rec = hit->rec;
     } else {
         ++pc.misses;
-        CompiledMatch cm = compile_match(match_spec(ctx, pattern, n, lo, hi, parts));
-        rec = cm.rec;
-        prog = std::move(cm.prog);
+        if (starts) {
+            CompiledStarts cs = compile_match_starts(match_spec(ctx, pattern, n, lo, hi));
+            rec = cs.rec;
+            prog = std::move(cs.prog);
+        } else {
+            CompiledMatch cm = compile_match(match_spec(ctx, pattern, n, lo, hi, parts));
+            rec = cm.rec;
+            prog = std::move(cm.prog);
+        }
         check_content(ctx, prog, content, n, M);
         // M copies: gate g of match m is m * G + g, content block cb of match m is 4 n m + cb
         const size_t G = prog.gates.size();
@@ -220,16 +228,22 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
     }
     double t1 = now_ms();
     launch_plan(dev, plan);
-    if (hit && (nO < 1 || nO > parts))  // the caller's out buffer holds M * parts handles
+    if (hit && !starts && (nO < 1 || nO > parts))  // the caller's out buffer holds M * parts handles
         throw Error(FR_ERR_INVALID, "cached plan has more outputs than the caller's parts");
     // an uncached plan's one output takes its gate's slot; parts get copies (two parts may read one gate)
     const bool take = !c && nO == 1;
-    for (size_t m = 0; m < M; ++m)
-        for (size_t j = 0; j < nO; ++j) {
-            ProgOut o = po[j];
-            if (o.gate >= 0) o.gate += (int)(m * G);
-            outs[m * nO + j] = make_output(ctx, o, plan.slot, take);
-        }
+    size_t made = 0;  // handles written so far, released if a later one fails: the caller gets a code only
+    try {
+        for (size_t m = 0; m < M; ++m)
+            for (size_t j = 0; j < nO; ++j, ++made) {
+                ProgOut o = po[j];
+                if (o.gate >= 0) o.gate += (int)(m * G);
+                outs[m * nO + j] = make_output(ctx, o, plan.slot, take);
+            }
+    } catch (...) {
+        while (made) ctx->release(outs[--made]);
+        throw;
+    }
     if (n_parts) *n_parts = nO;
     if (!c) fresh.slot.reset();  // later users of these slots are ordered after the launches (one stream)
     if (!ctx->async_match) dev.sync();
@@ -328,6 +342,15 @@ int fr_has_match_range(fr_ctx* ctx, const fr_ct* content, size_t n, const char* 
     })
 }
 
+int fr_match_starts(fr_ctx* ctx, const fr_ct* content, size_t n, const char* pattern, size_t lo, size_t hi, fr_ct* out,
+                    fr_match_stats* st) {
+    FR_TRY({
+        NEED(ctx && pattern && (content || !n) && lo <= hi && (out || lo == hi));
+        // (the key's `starts` field keeps these plans apart from has_match's of the same range)
+        match_impl(ctx, content, n, 1, pattern, lo, hi, out, st, 1, nullptr, true);
+    })
+}
+
 int fr_has_match_parts(fr_ctx* ctx, const fr_ct* content, size_t n, const char* pattern, size_t lo, size_t hi,
                        size_t max_parts, fr_ct* out, size_t* n_parts, fr_match_stats* st) {
     FR_TRY({
@@ -338,6 +361,36 @@ int fr_has_match_parts(fr_ctx* ctx, const fr_ct* content, size_t n, const char* 
 }
 
 }  // extern "C"
+
+// the schedule of a lowered program over n_chars encrypted characters (each position an
+// encrypted radix character), and its outputs as (gate, w, cst) triples
+static void schedule_program(const Program& prog, size_t n_chars, int32_t multi_value, fr_job* jobs, size_t jobs_cap,
+                             size_t* n_jobs, uint32_t* level_off, size_t level_cap, size_t* n_levels, int32_t* outs3,
+                             size_t* n_parts) {
+    Schedule S = build_schedule(prog.gates, n_chars, multi_value != 0, [](int cb, int& key, int&) {
+        key = cb;
+        return true;
+    });
+    *n_jobs = S.jobs.size();
+    *n_levels = S.level_off.size() - 1;
+    *n_parts = prog.outs.size();
+    for (size_t j = 0; j < prog.outs.size(); ++j) {
+        outs3[3 * j] = prog.outs[j].gate;
+        outs3[3 * j + 1] = prog.outs[j].w;
+        outs3[3 * j + 2] = prog.outs[j].cst;
+    }
+    if (jobs) {
+        NEED(jobs_cap >= S.jobs.size());
+        static_assert(sizeof(fr_job) == sizeof(DevGate), "fr_job mirrors DevGate");
+        // (an empty schedule's vector has no storage: memcpy's source must not be null,
+        // UBSan finding of tests/test_fuzz_inputs.py)
+        if (!S.jobs.empty()) std::memcpy(jobs, S.jobs.data(), sizeof(DevGate) * S.jobs.size());
+    }
+    if (level_off) {
+        NEED(level_cap >= S.level_off.size());
+        for (size_t l = 0; l < S.level_off.size(); ++l) level_off[l] = (uint32_t)S.level_off[l];
+    }
+}
 
 // ------------------------------------------------------------ level-sharded matches
 // One match split across ranks (the reference folds ct_or over the
@@ -480,29 +533,21 @@ int fr_schedule_match_parts(size_t n_chars, const char* pattern, size_t lo, size
         NEED(max_parts >= 1 && max_parts <= (size_t)MAX_FANIN);
         const Program prog =
             compile_match(MatchSpec{pattern, n_chars, lo, hi, engine, grammar, lowering, (int)max_parts}).prog;
-        Schedule S = build_schedule(prog.gates, n_chars, multi_value != 0, [](int cb, int& key, int&) {
-            key = cb;
-            return true;
-        });
-        *n_jobs = S.jobs.size();
-        *n_levels = S.level_off.size() - 1;
-        *n_parts = prog.outs.size();
-        for (size_t j = 0; j < prog.outs.size(); ++j) {
-            outs3[3 * j] = prog.outs[j].gate;
-            outs3[3 * j + 1] = prog.outs[j].w;
-            outs3[3 * j + 2] = prog.outs[j].cst;
-        }
-        if (jobs) {
-            NEED(jobs_cap >= S.jobs.size());
-            static_assert(sizeof(fr_job) == sizeof(DevGate), "fr_job mirrors DevGate");
-            // (an empty schedule's vector has no storage: memcpy's source must not be null,
-            // UBSan finding of tests/test_fuzz_inputs.py)
-            if (!S.jobs.empty()) std::memcpy(jobs, S.jobs.data(), sizeof(DevGate) * S.jobs.size());
-        }
-        if (level_off) {
-            NEED(level_cap >= S.level_off.size());
-            for (size_t l = 0; l < S.level_off.size(); ++l) level_off[l] = (uint32_t)S.level_off[l];
-        }
+        schedule_program(prog, n_chars, multi_value, jobs, jobs_cap, n_jobs, level_off, level_cap, n_levels, outs3,
+                         n_parts);
+    })
+}
+
+int fr_schedule_match_starts(size_t n_chars, const char* pattern, size_t lo, size_t hi, int32_t lowering,
+                             int32_t engine, int32_t grammar, int32_t multi_value, fr_job* jobs, size_t jobs_cap,
+                             size_t* n_jobs, uint32_t* level_off, size_t level_cap, size_t* n_levels, int32_t* outs3,
+                             size_t outs_cap, size_t* n_starts) {
+    FR_TRY({
+        NEED(pattern && n_jobs && n_levels && n_starts && lo <= hi && (outs3 || lo == hi) && outs_cap >= hi - lo);
+        const Program prog =
+            compile_match_starts(MatchSpec{pattern, n_chars, lo, hi, engine, grammar, lowering, 1}).prog;
+        schedule_program(prog, n_chars, multi_value, jobs, jobs_cap, n_jobs, level_off, level_cap, n_levels, outs3,
+                         n_starts);
     })
 }
 

@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import struct
 from dataclasses import dataclass
 from typing import Tuple, List, Optional, Sequence
 
@@ -129,6 +130,22 @@ _SIGS = {
     "fr_export_server_key_compact": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "fr_load_server_key_compact": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
     "fr_device_timers_key_load": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "fr_gen_packing_key": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "fr_gen_packing_key_keyed": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "fr_packing_key_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
+    "fr_export_packing_key": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fr_load_packing_key": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "fr_packed_result_size": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fr_pack_bools": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, u64p]),
+    "fr_pack_bools_blob": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, C.c_char_p, C.c_size_t,
+                                     C.POINTER(C.c_size_t)]),
+    "fr_decrypt_packed": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint8),
+                                    C.POINTER(C.c_size_t)]),
+    "fr_dev_packing_limb_column": (C.c_int, [C.c_void_p, C.c_int32, u64p]),
+    "fr_device_timers_pack": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "fr_gen_packing_rows_keyed": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_size_t, u64p]),
+    "fr_pack_lwes": (C.c_int, [C.c_void_p, u64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_size_t, u64p]),
+    "fr_packed_phase": (C.c_int, [C.c_void_p, u64p, u64p]),
     "fr_compact_content_size": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "fr_encrypt_str_compact_keyed": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t,
                                                C.POINTER(C.c_size_t)]),
@@ -170,6 +187,16 @@ _SIGS = {
     "fr_has_match_parts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, C.c_char_p, C.c_size_t,
                                      C.c_size_t, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_size_t),
                                      C.POINTER(MatchStats)]),
+    "fr_match_starts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, C.c_char_p, C.c_size_t, C.c_size_t,
+                                  C.POINTER(C.c_uint32), C.POINTER(MatchStats)]),
+    "fr_plain_match_starts": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_size_t, C.c_int32,
+                                        C.c_int32, C.c_int32, C.POINTER(PlainResult), C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fr_schedule_match_starts": (C.c_int, [C.c_size_t, C.c_char_p, C.c_size_t, C.c_size_t, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32, C.POINTER(FrJob), C.c_size_t,
+                                           C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.c_size_t,
+                                           C.POINTER(C.c_size_t), C.POINTER(C.c_int32), C.c_size_t,
+                                           C.POINTER(C.c_size_t)]),
     "fr_plain_match_parts": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_size_t, C.c_int32,
                                        C.c_int32, C.c_int32, C.c_size_t, C.POINTER(PlainResult),
                                        C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]),
@@ -371,6 +398,23 @@ def plain_match_parts(content: bytes | str, pattern: str, start_lo: int, start_h
     return r, list(vals)[:n.value]
 
 
+def plain_match_starts(content: bytes | str, pattern: str, start_lo: int = 0, start_hi: Optional[int] = None,
+                       lowering: int = LOWER_THRESHOLD, engine: int = ENGINE_ENUMERATE,
+                       grammar: int = GRAMMAR_REFERENCE):
+    """Host-only run of fr_match_starts' merged program: (PlainResult, [value per start of the
+    lowered program], [value per start of the start's recorded circuit])"""
+    if isinstance(content, str):
+        content = content.encode("latin-1")
+    hi = len(content) if start_hi is None else start_hi
+    r = PlainResult()
+    cap = max(hi - start_lo, 1)
+    low, rec = (C.c_int32 * cap)(), (C.c_int32 * cap)()
+    n = C.c_size_t()
+    _check(lib().fr_plain_match_starts(content, len(content), pattern.encode("latin-1"), start_lo, hi, lowering,
+                                       engine, grammar, C.byref(r), low, rec, cap, C.byref(n)))
+    return r, list(low)[:n.value], list(rec)[:n.value]
+
+
 class Context:
     """One fr_ctx: params, keys, device arena.  device=-1: host-only."""
 
@@ -473,6 +517,104 @@ class Context:
         the bodies and expands the masks on the GPU"""
         blob = bytes(blob)
         _check(lib().fr_load_server_key_compact(self.h, blob, len(blob)))
+
+    # packed results
+    def gen_packing_key(self, seed=None):
+        """the optional packing key (fheregex.h "packed results"; 201 MB): on the GPU on a
+        device context, word for word the host generator's rows.  `seed` as in gen_client_key."""
+        keyed, v = _rng_arg(seed)
+        _check(lib().fr_gen_packing_key_keyed(self.h, v) if keyed else lib().fr_gen_packing_key(self.h, v))
+
+    def packing_key_size(self) -> int:
+        n = C.c_size_t()
+        _check(lib().fr_packing_key_size(self.h, C.byref(n)))
+        return n.value
+
+    def export_packing_key(self) -> np.ndarray:
+        """the packing key's wire blob as a uint8 array (load_packing_key takes it back)"""
+        n = C.c_size_t()
+        _check(lib().fr_export_packing_key(self.h, None, 0, C.byref(n)))
+        buf = np.empty(n.value, dtype=np.uint8)
+        _check(lib().fr_export_packing_key(self.h, buf.ctypes.data, n.value, C.byref(n)))
+        return buf
+
+    def load_packing_key(self, blob):
+        """install a packing key blob (bytes or a uint8 array): no client key needed"""
+        b = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray)) else blob,
+                                 dtype=np.uint8)
+        _check(lib().fr_load_packing_key(self.h, b.ctypes.data, len(b)))
+
+    def gen_packing_rows(self, seed, row_lo: int, row_hi: int) -> np.ndarray:
+        """rows [row_lo, row_hi) of the packing key gen_packing_key(seed) draws, on the host:
+        (rows, (k+1) N) words"""
+        keyed, v = _rng_arg(seed)
+        key = v if keyed else seed_key(v)
+        W = (self.params.k + 1) * self.params.N
+        out = np.zeros((row_hi - row_lo, W), dtype=np.uint64)
+        _check(lib().fr_gen_packing_rows_keyed(self.h, key, row_lo, row_hi, _p(out)))
+        return out
+
+    def packed_result_size(self, n: int) -> int:
+        b = C.c_size_t()
+        _check(lib().fr_packed_result_size(self.h, n, C.byref(b)))
+        return b.value
+
+    def pack_bools_words(self, handles: Sequence[int]) -> np.ndarray:
+        """the (k+1) N words of the boolean handles' packed GLWE (fr_pack_bools)"""
+        hs = (C.c_uint32 * len(handles))(*handles)
+        out = np.zeros((self.params.k + 1) * self.params.N, dtype=np.uint64)
+        _check(lib().fr_pack_bools(self.h, hs, len(handles), _p(out)))
+        return out
+
+    def pack_bools(self, handles: Sequence[int]) -> bytes:
+        """up to N boolean handles as one packed result blob (32,792 bytes), which
+        decrypt_packed opens on a context holding the client key"""
+        hs = (C.c_uint32 * len(handles))(*handles)
+        n = C.c_size_t()
+        _check(lib().fr_pack_bools_blob(self.h, hs, len(handles), None, 0, C.byref(n)))
+        buf = C.create_string_buffer(n.value)
+        _check(lib().fr_pack_bools_blob(self.h, hs, len(handles), buf, n.value, C.byref(n)))
+        return buf.raw[:n.value]
+
+    def decrypt_packed(self, blob: bytes) -> List[int]:
+        """the bits of a packed result blob (client key needed)"""
+        blob = bytes(blob)
+        n = C.c_size_t()
+        _check(lib().fr_decrypt_packed(self.h, blob, len(blob), None, C.byref(n)))
+        bits = (C.c_uint8 * n.value)()
+        _check(lib().fr_decrypt_packed(self.h, blob, len(blob), bits, C.byref(n)))
+        return list(bits)
+
+    def pack_lwes(self, lwes: Optional[np.ndarray], w=None, off=None, n: Optional[int] = None) -> np.ndarray:
+        """the packing keyswitch in plain host loops (fr_pack_lwes) of the booleans
+        off[j] 2^58 + w[j] lwes[j]: the (k+1) N words the device must give"""
+        if lwes is not None:
+            lwes = np.ascontiguousarray(lwes, dtype=np.uint64).reshape(-1, self.lwe_len)
+            n = len(lwes)
+        wa = None if w is None else (C.c_int32 * n)(*[int(x) for x in w])
+        oa = None if off is None else (C.c_int32 * n)(*[int(x) for x in off])
+        out = np.zeros((self.params.k + 1) * self.params.N, dtype=np.uint64)
+        _check(lib().fr_pack_lwes(self.h, None if lwes is None else _p(lwes), wa, oa, n, _p(out)))
+        return out
+
+    def packed_phase(self, words: np.ndarray) -> np.ndarray:
+        """the N phase words of a packed GLWE under the client key"""
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        out = np.zeros(self.params.N, dtype=np.uint64)
+        _check(lib().fr_packed_phase(self.h, _p(words), _p(out)))
+        return out
+
+    def dev_packing_limb_column(self, col: int) -> np.ndarray:
+        """column `col` of the packing key's byte-limb operand, recombined: the 3 kN torus words"""
+        out = np.zeros(3 * self.big, dtype=np.uint64)
+        _check(lib().fr_dev_packing_limb_column(self.h, col, _p(out)))
+        return out
+
+    def pack_timers(self) -> List[float]:
+        """ms of the last pack_bools' stages under set_profiling: digits, GEMM, rotate-sum"""
+        ms = (C.c_double * 3)()
+        _check(lib().fr_device_timers_pack(self.h, ms))
+        return list(ms)
 
     def key_load_timers(self) -> List[float]:
         """ms of the last load_server_key_compact's stages under set_profiling: H2D copy,
@@ -755,6 +897,21 @@ class Context:
                                         max_parts, out, C.byref(n), C.byref(st)))
         return list(out)[:n.value], st
 
+    def match_starts(self, content: Sequence[int], pattern: str, lo: Optional[int] = None,
+                     hi: Optional[int] = None, stats: bool = False):
+        """fr_match_starts: one boolean handle per start offset of [lo, hi) (default: every
+        offset of the content), the encrypted "the pattern matches starting here"; with
+        stats=True also the MatchStats"""
+        content = np.ascontiguousarray(content, dtype=np.uint32)
+        arr = content.ctypes.data_as(C.POINTER(C.c_uint32))
+        lo = 0 if lo is None else lo
+        hi = len(content) if hi is None else hi
+        out = (C.c_uint32 * max(hi - lo, 1))()
+        st = MatchStats()
+        _check(lib().fr_match_starts(self.h, arr, len(content), pattern.encode("latin-1"), lo, hi, out, C.byref(st)))
+        hs = list(out)[:max(hi - lo, 0)]
+        return (hs, st) if stats else hs
+
     def has_match_batch(self, contents: Sequence[Sequence[int]], pattern: str):
         """M independent matches of one pattern over M equal-length contents in
         shared launches (fr_has_match_batch): ([out handle per match], stats)."""
@@ -861,6 +1018,27 @@ class ClientKey:
     def decrypt(self, ct: int) -> int:
         return self.ctx.decrypt_radix(self.ctx.download_radix(ct))
 
+    def decrypt_packed(self, blob: bytes) -> List[int]:
+        """the bits of a ServerKey.pack_bools reply"""
+        return self.ctx.decrypt_packed(blob)
+
+    def decrypt_starts(self, reply: bytes) -> List[int]:
+        """the offsets at which the pattern matches, from a ServerKey.match_starts reply"""
+        if len(reply) < 4:
+            raise ValueError("not a match_starts reply")
+        (chunks,) = struct.unpack_from("<I", reply, 0)
+        if chunks == 0 and len(reply) == 4:
+            return []  # an empty content has no start
+        size = (len(reply) - 4) // chunks if chunks else 0
+        if chunks == 0 or 4 + chunks * size != len(reply):
+            raise ValueError("not a match_starts reply")
+        offs, base = [], 0
+        for c in range(chunks):
+            bits = self.ctx.decrypt_packed(reply[4 + c * size:4 + (c + 1) * size])
+            offs += [base + j for j, b in enumerate(bits) if b]
+            base += len(bits)
+        return offs
+
     def serialize(self) -> bytes:
         """bincode::serialize of the RadixClientKey (engine.rs:238-246)."""
         return self.ctx.serialize_client_key()
@@ -878,17 +1056,42 @@ class ServerKey:
         masks are rebuilt on the GPU, only the bodies cross the bus; no client key needed"""
         return self.ctx.upload_compact_str(blob)
 
-    def save(self, path: str):
-        """the server key as an .npz of its (ksk, bsk) arrays (fr_export_server_key's layout)"""
+    def pack_bools(self, handles: Sequence[int]) -> bytes:
+        """up to N boolean handles as one 32 KB reply under the client's key (needs the
+        packing key: gen_keys(packing=True) or load(..., packing_path))"""
+        return self.ctx.pack_bools(handles)
+
+    def match_starts(self, content: Sequence[int], pattern: str) -> bytes:
+        """where the pattern matches in the content, as one reply for ClientKey.decrypt_starts:
+        a u32 count of chunks, then one packed result blob per chunk of N start offsets (a
+        content of up to N characters: one 32 KB blob).  The handles are released."""
+        N = self.ctx.params.N
+        hs = self.ctx.match_starts(content, pattern)
+        try:
+            blobs = [self.ctx.pack_bools(hs[i:i + N]) for i in range(0, len(hs), N)]
+        finally:
+            for h in hs:
+                self.ctx.release(h)
+        return struct.pack("<I", len(blobs)) + b"".join(blobs)
+
+    def save(self, path: str, packing_path: Optional[str] = None):
+        """the server key as an .npz of its (ksk, bsk) arrays (fr_export_server_key's layout);
+        packing_path: the packing key's raw blob as a second file"""
         ksk, bsk = self.ctx.export_server_key()
         np.savez(path, ksk=ksk, bsk=bsk)
+        if packing_path is not None:
+            self.ctx.export_packing_key().tofile(packing_path)
 
     @staticmethod
-    def load(path: str, device: int = 0, params: Optional[Params] = None) -> "ServerKey":
-        """a server context holding only this server key (fr_load_server_key; no client key)"""
+    def load(path: str, device: int = 0, params: Optional[Params] = None,
+             packing_path: Optional[str] = None) -> "ServerKey":
+        """a server context holding only this server key (fr_load_server_key; no client key),
+        and the packing key of packing_path if given"""
         ctx = Context(device, params)
         with np.load(path, allow_pickle=False) as z:
             ctx.load_server_key(z["ksk"], z["bsk"])
+        if packing_path is not None:
+            ctx.load_packing_key(np.fromfile(packing_path, dtype=np.uint8))
         return ServerKey(ctx)
 
     def save_compact(self, path: str):
@@ -926,7 +1129,8 @@ def compact_content_mask_key(blob: bytes) -> bytes:
 
 
 def gen_keys(client_key_blob: Optional[bytes] = None, seed=None, device: int = 0,
-             params: Optional[Params] = None, client_seed=None, compact: bool = False):
+             params: Optional[Params] = None, client_seed=None, compact: bool = False, packing: bool = False,
+             packing_seed=None):
     """gen_keys (ciphertext.rs:42-45): (client key, server key).
 
     Without a blob the client key is fresh (gen_keys_radix(&PARAM_MESSAGE_2_CARRY_2, 4),
@@ -936,13 +1140,16 @@ def gen_keys(client_key_blob: Optional[bytes] = None, seed=None, device: int = 0
     bits of the OS CSPRNG each, as the reference draws.  32 bytes are a generator key, an
     int a 64-bit seed; a server key from an int seed is reproducible (tests, benchmarks,
     multi-rank keygen) and must not leave the client.  compact=True: the server key in
-    compact form (ServerKey.save_compact ships it)."""
+    compact form (ServerKey.save_compact ships it).  packing=True: also the packing key
+    (ServerKey.pack_bools), drawn under `packing_seed`."""
     ctx = Context(device, params)
     if client_key_blob is None:
         ctx.gen_client_key(client_seed)
     else:
         ctx.load_client_key(client_key_blob)
     ctx.gen_server_key(seed, compact=compact)
+    if packing:
+        ctx.gen_packing_key(packing_seed)
     return ClientKey(ctx), ServerKey(ctx)
 
 
@@ -1258,6 +1465,26 @@ def schedule_match(n_chars: int, pattern: str, start_lo: int = 0, start_hi: Opti
     n_gates = 1 + max([max(j.out_gate[f] for f in range(j.n_out)) for j in jobs[:nj.value]] or [-1])
     parts = [(outs3[3 * j], outs3[3 * j + 1], outs3[3 * j + 2]) for j in range(npart.value)]
     return Schedule(list(jobs[:nj.value]), list(off), parts[0][0], parts[0][1], parts[0][2], n_gates, parts)
+
+
+def schedule_match_starts(n_chars: int, pattern: str, start_lo: int = 0, start_hi: Optional[int] = None,
+                          lowering: int = LOWER_THRESHOLD, engine: int = ENGINE_AUTO,
+                          grammar: int = GRAMMAR_REFERENCE, multi_value: bool = True) -> Schedule:
+    """fr_match_starts' schedule: Schedule.parts holds (out_gate, out_w, out_const) per start"""
+    hi = n_chars if start_hi is None else start_hi
+    nj, nl, ns = C.c_size_t(), C.c_size_t(), C.c_size_t()
+    cap = max(hi - start_lo, 1)
+    outs3 = (C.c_int32 * (3 * cap))()
+    args = (n_chars, pattern.encode("latin-1"), start_lo, hi, lowering, engine, grammar, int(multi_value))
+    _check(lib().fr_schedule_match_starts(*args, None, 0, C.byref(nj), None, 0, C.byref(nl), outs3, cap, C.byref(ns)))
+    jobs = (FrJob * max(nj.value, 1))()
+    off = (C.c_uint32 * (nl.value + 1))()
+    _check(lib().fr_schedule_match_starts(*args, jobs, len(jobs), C.byref(nj), off, len(off), C.byref(nl), outs3, cap,
+                                          C.byref(ns)))
+    n_gates = 1 + max([max(j.out_gate[f] for f in range(j.n_out)) for j in jobs[:nj.value]] or [-1])
+    parts = [(outs3[3 * j], outs3[3 * j + 1], outs3[3 * j + 2]) for j in range(ns.value)]
+    first = parts[0] if parts else (-1, 0, 0)
+    return Schedule(list(jobs[:nj.value]), list(off), first[0], first[1], first[2], n_gates, parts)
 
 
 def content_window(n_chars: int, pattern: str, start_lo: int, start_hi: int, lowering: int = LOWER_THRESHOLD,

@@ -217,6 +217,60 @@ int fr_export_server_key_compact(fr_ctx* ctx, uint8_t* buf, size_t cap, size_t* 
  * then export both forms. */
 int fr_load_server_key_compact(fr_ctx* ctx, const uint8_t* blob, size_t len);
 
+/* ----- packed results (DESIGN.md §1 "Packed results") -----
+ * A packing key is an optional key beside the server key: with it the server puts up to N
+ * result booleans into the N coefficients of ONE GLWE ciphertext under the client's own
+ * key, (k+1)*N words (32,768 bytes at (k, N) = (1, 2048), 24,576 at (2, 1024)) whether it
+ * carries one boolean or N, where every boolean alone is a (kN+1)-word LWE of 16,392 bytes.
+ * Nothing else depends on the key's presence.
+ * Gadget: signed base 2^7, 3 levels.  Row 3*i + l (i < kN, l < 3) is a GLWE encryption,
+ * under the GLWE key (the big key read as k polynomials) with the GLWE noise, of the
+ * constant polynomial s_big[i] * 2^(64 - 7*(l+1)): k mask polynomials, then the body;
+ * 3*kN = 6,144 rows of (k+1)*N words: 201,326,592 bytes at (1, 2048), 150,994,944 at
+ * (2, 1024).  The key encrypts bits of the big key under the big key, a key cycle of the kind the KSK/BSK pair
+ * already assumes.  Masks are ChaCha20 words of stream 9, the noise of stream 10, of the
+ * generator key.  A device context generates the key on the GPU (fr_set_keygen rules), word
+ * for word the host generator's rows; FR_ERR_NO_KEY without a client key.
+ * The wire blob, little endian, exactly fr_packing_key_size bytes:
+ *     0  "FRPKKEY1"
+ *     8  int32 k, N, n, ks_base_log, ks_level, pbs_base_log, pbs_level, ring
+ *    40  int32 7, 3 (the packing gadget)
+ *    48  the rows
+ * fr_export_packing_key: buf == NULL is a size query.  fr_load_packing_key checks the
+ * length, the magic, the parameters and the gadget before the installed key is touched
+ * (anything else -> FR_ERR_INVALID, the context keeps the key it had), needs no client
+ * key, and on a device context first waits for every queued launch. */
+int fr_gen_packing_key(fr_ctx* ctx, uint64_t seed);
+int fr_gen_packing_key_keyed(fr_ctx* ctx, const uint8_t* key /* NULL: OS CSPRNG */);
+int fr_packing_key_size(fr_ctx* ctx, size_t* bytes);
+int fr_export_packing_key(fr_ctx* ctx, uint8_t* buf, size_t cap, size_t* written);
+int fr_load_packing_key(fr_ctx* ctx, const uint8_t* blob, size_t len);
+/* The packing keyswitch of n boolean handles (1 <= n <= N): out_words receives the (k+1)*N
+ * words of
+ *     sum_j X^j * ((0, .., 0, b_j) - sum_{i,l} d_{j,i,l} * row[3*i + l])
+ * over (Z_2^64[X]/(X^N+1))^(k+1), d the signed base-2^7 digits of boolean j's mask rounded
+ * to 21 bits: coefficient j of its phase is boolean j's phase plus the keyswitch error,
+ * coefficients j >= n are that error alone.  Exact integer arithmetic: the device (int8
+ * MFMA) and the host compute the same words.  A handle that is no boolean, n outside
+ * 1..N or a context without a packing key -> FR_ERR_INVALID.  A host-only context packs
+ * trivial booleans only (it has no others).  The call runs after whatever produced the
+ * handles and returns after the download.  With fr_set_lanes it runs on lane 0's stream,
+ * which first waits for every lane's queued work: packs of results from different lanes
+ * are correct but run one after the other, behind all lanes.
+ * fr_pack_bools_blob writes the wire blob, exactly fr_packed_result_size bytes:
+ *     0  "FRPKRES1"
+ *     8  int32 k, N
+ *    16  u64 n
+ *    24  the (k+1)*N words
+ * (buf == NULL: size query).  fr_decrypt_packed (client key needed) refuses a blob of another
+ * length, magic, k, N or n outside 1..N with FR_ERR_INVALID before anything is allocated;
+ * bits[j] = round(phase_j / 2^59) & 1 for j < n (bits == NULL: *n only); FR_ERR_INVALID if a
+ * coefficient j >= n does not round to 0. */
+int fr_packed_result_size(fr_ctx* ctx, size_t n, size_t* bytes);
+int fr_pack_bools(fr_ctx* ctx, const fr_ct* bools, size_t n, uint64_t* out_words);
+int fr_pack_bools_blob(fr_ctx* ctx, const fr_ct* bools, size_t n, uint8_t* buf, size_t cap, size_t* written);
+int fr_decrypt_packed(fr_ctx* ctx, const uint8_t* blob, size_t len, uint8_t* bits, size_t* n);
+
 /* ----- client side (not on the timed path) ----- */
 /* Seeded encryption, for tests and benchmarks only: two calls with one seed share their
  * masks and noise block by block (block q of a call draws at index first_block + q). */
@@ -422,6 +476,21 @@ int fr_device_timers_key_load(fr_ctx* ctx, double* ms /* 5 */);
 /* The expansion kernel of the last fr_upload_compact_* made under fr_set_profiling, by HIP
  * events, ms.  A profiled upload waits for its kernel; an unprofiled one does not. */
 int fr_device_timers_content(fr_ctx* ctx, double* ms);
+/* The stages of the last fr_pack_bools made under fr_set_profiling, by HIP events:
+ * ms[0..2] = digits (with the zeroing of the scratch), int8 GEMM, rotate-and-sum. */
+int fr_device_timers_pack(fr_ctx* ctx, double* ms /* 3 */);
+
+/* Match starts: where the pattern matches, not only whether.  out[s - start_lo] is a boolean
+ * handle that decrypts to whether the pattern matches starting at offset s, for every s of
+ * [start_lo, start_hi): the value the reference ORs away at engine.rs:22-35, i.e.
+ * has_match restricted to the starts [s, s + 1).  One program for all starts: the per-start
+ * programs merged, a gate with the inputs, offset, kind and table of an earlier one being
+ * that gate, so the nibble tests of a character are shared by every start that reads it.  A
+ * start whose value is a constant (/^abc/ at s > 0) gives a trivial boolean.  Errors, the
+ * plan cache, lanes and fr_set_async as fr_has_match_range.  fr_pack_bools puts the handles
+ * into one reply. */
+int fr_match_starts(fr_ctx* ctx, const fr_ct* content, size_t n_chars, const char* pattern, size_t start_lo,
+                    size_t start_hi, fr_ct* out /* start_hi - start_lo */, fr_match_stats* stats);
 
 /* ----- one match split across ranks ----- */
 /* The reference folds ct_or over the branches of every start offset
@@ -483,6 +552,14 @@ int fr_schedule_match_parts(size_t n_chars, const char* pattern, size_t start_lo
                             size_t jobs_cap, size_t* n_jobs, uint32_t* level_off, size_t level_cap, size_t* n_levels,
                             int32_t* outs3, size_t* n_parts);
 
+/* fr_schedule_match_parts for the merged program of fr_match_starts: outs3[3*j .. 3*j+2] =
+ * (out_gate, out_w, out_const) of start start_lo + j, j < *n_starts = start_hi - start_lo
+ * <= outs_cap. */
+int fr_schedule_match_starts(size_t n_chars, const char* pattern, size_t start_lo, size_t start_hi, int32_t lowering,
+                             int32_t engine, int32_t grammar, int32_t multi_value, fr_job* jobs, size_t jobs_cap,
+                             size_t* n_jobs, uint32_t* level_off, size_t level_cap, size_t* n_levels, int32_t* outs3,
+                             size_t outs_cap, size_t* n_starts);
+
 /* ----- host-only introspection (tests; no device needed) ----- */
 /* Canonical AST string of parse(pattern) (parser.rs:146-185). */
 int fr_parse(const char* pattern, char* buf, size_t buflen);
@@ -536,6 +613,13 @@ int fr_debug_enumeration_cost(const char* pattern, int32_t grammar, size_t n_cha
 int fr_plain_match_parts(const char* content, size_t len, const char* pattern, size_t start_lo, size_t start_hi,
                          int32_t lowering, int32_t engine, int32_t grammar, size_t max_parts, fr_plain_result* out,
                          int32_t* parts, size_t* n_parts);
+/* ... of fr_match_starts' merged program: lowered[j] / recorded[j] are the plaintext values of
+ * start start_lo + j in the lowered program and in that start's recorded circuit, j <
+ * *n_starts = start_hi - start_lo <= cap; out's counters are summed over the starts, its
+ * results the OR over them, pbs / levels / max_level_width the merged program's. */
+int fr_plain_match_starts(const char* content, size_t len, const char* pattern, size_t start_lo, size_t start_hi,
+                          int32_t lowering, int32_t engine, int32_t grammar, fr_plain_result* out, int32_t* lowered,
+                          int32_t* recorded, size_t cap, size_t* n_starts);
 int fr_set_engine(fr_ctx* ctx, int32_t engine);
 int fr_plain_match_ex(const char* content, size_t len, const char* pattern, size_t start_lo, size_t start_hi,
                       int32_t lowering, int32_t engine, fr_plain_result* out);
@@ -561,9 +645,28 @@ int fr_set_multi_value(fr_ctx* ctx, int32_t on);
  * resolve at the next synchronisation.  Any other value is FR_ERR_INVALID. */
 int fr_set_profiling(fr_ctx* ctx, int32_t on);
 
+/* ----- packed results: the host restatement (tests; the device path's reference) ----- */
+/* Rows row_lo <= row < row_hi <= 3*kN of the packing key that fr_gen_packing_key_keyed draws
+ * under the same key, (row_hi - row_lo)*(k+1)*N words (client key needed).  The whole key
+ * takes a few seconds of host time, hence the range. */
+int fr_gen_packing_rows_keyed(fr_ctx* ctx, const uint8_t* key /* NULL: OS CSPRNG */, size_t row_lo, size_t row_hi,
+                              uint64_t* out);
+/* fr_pack_bools in plain host loops, on LWEs given as words: boolean j is
+ * off[j]*2^58 + w[j]*lwes[j] (w, off NULL: 1, 0; w[j] == 0: a constant, lwes[j] is not read,
+ * and lwes may be NULL if every w[j] is 0).  Needs the packing key; on a device context the
+ * rows are downloaded for the call. */
+int fr_pack_lwes(fr_ctx* ctx, const uint64_t* lwes /* n*(kN+1) */, const int32_t* w, const int32_t* off, size_t n,
+                 uint64_t* out_words /* (k+1)*N */);
+/* phase[t] = coefficient t of B - sum_c A_c*S_c (negacyclic) of a packed result's words under
+ * the client key: N words. */
+int fr_packed_phase(fr_ctx* ctx, const uint64_t* words, uint64_t* phase);
+
 /* ----- single-stage device entry points (parity tests of each kernel) ----- */
 /* in: count*(kN+1) torus LWEs -> out: count*(n+1) keyswitched LWEs */
 int fr_dev_keyswitch(fr_ctx* ctx, const uint64_t* in, size_t count, uint64_t* out);
+/* Column col < (k+1)*N of the packing key's byte-limb operand (what the packing GEMM reads),
+ * its 8 limbs recombined on the device: out[r] must be word col of row r, r < 3*kN. */
+int fr_dev_packing_limb_column(fr_ctx* ctx, int32_t col, uint64_t* out /* 3*kN */);
 /* in: count*(n+1) keyswitched LWEs, luts: count*16 -> out: count*(kN+1) */
 int fr_dev_blind_rotate(fr_ctx* ctx, const uint64_t* in, const uint8_t* luts, size_t count, uint64_t* out);
 /* one blind rotation with n_out LUTs (direct: n_out == 1, LUT polynomial
