@@ -65,7 +65,7 @@ class Device {
 
     // keys: KSK torus 2^64 [i][j][t]; BSK coefficient domain mod Q [i][r][c][coef]
     void upload_keys(const std::vector<uint64_t>& ksk, const std::vector<uint64_t>& bsk);
-    bool has_keys() const { return d_ksk_ && (d_bsk_ || d_fbsk_[0]); }
+    bool has_keys() const { return ksk_ && (p_.ring == FR_RING_FFT ? bool(d_fbsk_[0]) : bool(d_bsk_)); }
     // server-key generation on the device (keygen.hip; FFT ring): the same keys
     // as gen_ksk + gen_bsk on the host, bit for bit; the torus keys stay on the
     // device for download_server_key
@@ -88,7 +88,7 @@ class Device {
     void gen_packing_key(const ClientKey& ck, const RngKey& key);
     void upload_packing_key(const void* rows);
     void download_packing_key(uint64_t* rows);
-    bool has_packing_key() const { return d_pksk_ && d_pkl_; }
+    bool has_packing_key() const { return bool(pksk_); }
     // parity hook: column col < (k+1) N of the byte-limb operand recombined into its 3 kN torus words
     void packing_limb_column(int col, uint64_t* out_host);
     // Packing keyswitch (keys.h: pack_host computes the same words): boolean j < n <= N is
@@ -217,9 +217,46 @@ class Device {
     gpu::Event take_event();
     void resolve_timers();
     void ensure_digits(size_t rows);
+    // A keyswitching key (LWE: ksk_, packing: pksk_): the torus rows [KD][ncols] (export, VALU
+    // keyswitch) and their balanced byte limbs in fragment order, the MFMA GEMM's column operand
+    struct LimbKey {
+        gpu::DevBuf<uint64_t> rows;
+        gpu::DevBuf<int8_t> limbs;       // [col*8 + limb][k], nlc limb columns (build_limbs, keyswitch.hip)
+        int KD = 0, ncols = 0, nlc = 0;  // nlc: ncols * 8 padded to whole 4-wave column groups
+        explicit operator bool() const { return rows && limbs; }
+        void alloc_rows(int kd, int nc) {  // the shape and fresh rows; no limbs until build_limbs
+            limbs.reset();
+            KD = kd, ncols = nc, nlc = ((nc * 8 + 127) / 128) * 128;
+            rows.alloc((size_t)kd * nc);
+        }
+        void reset() { rows.reset(), limbs.reset(); }
+    };
+    void build_limbs(LimbKey& key);
+    // every buffer of an installed key; the installs drop under a Replacing guard (device_impl.h)
+    void drop_server_key() { ksk_.reset(), d_tbsk_.reset(), d_bsk_.reset(), d_fbsk_[0].reset(), d_fbsk_[1].reset(); }
+    void drop_packing_key() { pksk_.reset(); }
+    // MFMA keyswitch of n rows: row tiles per wave and n padded to whole tiles of them (ks_shape);
+    // column tiles per wave, the LDS-DMA ring (k_ks_glds: MR 4, MC 1 only) and K slices: the caller's
+    struct KsShape {
+        int MR;
+        size_t padded;
+        int MC = 1, GZ = 1;
+        bool lds = true;
+    };
+    KsShape ks_shape(size_t n) const {
+        const int MR = n >= ks_mr4_min_ ? 4 : 1;
+        return {MR, (n + 32 * MR - 1) / (32 * MR) * (32 * MR)};
+    }
+    // its two launches (keyswitch.hip): digits of the gadget (2^KSB, KSL) into dig, out's columns
+    // < out_n zeroed and the body in column out_n; then out -= dig x key.limbs.
     // ev_start / ev_stop (profiling): HIP events stamped by the kernels' own dispatch
     // (hipExtLaunchKernel) -- the first kernel's start and the last one's end -- so timing
     // adds no marker packets between dependent launches (each cost ~5 us of gap)
+    template <int KSB, int KSL>
+    void launch_ks_digits(const DevGate* d_gates, size_t n, size_t padded, int8_t* dig, uint64_t* out, int out_n,
+                          int out_stride, hipEvent_t ev_start);
+    void launch_limb_gemm(const int8_t* dig, const LimbKey& key, size_t n, const KsShape& sh, uint64_t* out,
+                          int out_stride, hipEvent_t ev_stop);
     void launch_ks(const DevGate* d_gates, size_t n, uint64_t* d_ks, hipEvent_t ev_start = nullptr,
                    hipEvent_t ev_stop = nullptr);
     void launch_br(const DevGate* d_gates, const uint64_t* d_ks, size_t n, hipEvent_t ev_start = nullptr,
@@ -235,8 +272,6 @@ class Device {
     void upload_fft_bsk(const std::vector<uint64_t>& bsk);
     void launch_br_fft(const DevGate* d_gates, const uint64_t* d_ks, size_t n, hipStream_t stream,
                        hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
-    void build_ksk_limbs();  // d_kl_ from d_ksk_
-    void build_pk_limbs();   // d_pkl_ from d_pksk_ (keyswitch.hip)
     void build_fourier_bsk();  // keygen.hip: d_fbsk_ (every lane layout in use) from d_tbsk_
     double key_load_ms_[5] = {0, 0, 0, 0, 0};
     // expand_to_slots: the bodies and the slot list of a call, one copy (lane 0)
@@ -250,12 +285,9 @@ class Device {
     int e_ = 8;        // residues per lane in the NTT kernels (8 or 16; measured: 8 wins for k=1 and k=2)
     int e_small_ = 8;  // ... for launches of at most small_batch_ bootstraps
     size_t small_batch_ = 256;
-    gpu::DevBuf<uint64_t> d_ksk_;
+    LimbKey ksk_;                   // LWE keyswitch key: kN ks_level rows of n + 1 words
     gpu::DevBuf<uint64_t> d_tbsk_;  // torus BSK of a device-generated or device-expanded key (export)
-    gpu::DevBuf<int8_t> d_kl_;      // KSK as balanced byte limbs [col*8 + limb][k] (MFMA keyswitch)
-    int kl_cols_ = 0;
-    gpu::DevBuf<uint64_t> d_pksk_;  // packing key, torus rows [3 kN][(k+1) N] (export)
-    gpu::DevBuf<int8_t> d_pkl_;     // ... as balanced byte limbs [col*8 + limb][k] (pack_bools)
+    LimbKey pksk_;                  // packing key: 3 kN rows of (k+1) N words (pack_bools)
     double pack_ms_[3] = {0, 0, 0};
     int pk_split_ = 0;              // FR_PK_SPLIT: K slices of the packing GEMM (a divisor of 24; 0: auto)
     bool ks_mfma_ = true;         // FR_KS_MFMA=0: the VALU lincomb+keyswitch kernel

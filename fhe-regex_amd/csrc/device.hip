@@ -301,16 +301,13 @@ void Device::zero_slot(int slot) {
 void Device::upload_keys(const std::vector<uint64_t>& ksk, const std::vector<uint64_t>& bsk) {
     if (ksk.size() != (size_t)p_.big() * p_.ks_level * (p_.n + 1)) throw Error(FR_ERR_INVALID, "ksk size");
     if (bsk.size() != p_.bsk_len()) throw Error(FR_ERR_INVALID, "bsk size");
-    // every queued launch of every lane that reads the old keys has finished before they go
-    HIP_CHECK(hipDeviceSynchronize());
-    d_ksk_.reset();
-    d_bsk_.reset();
-    d_tbsk_.reset();  // host-generated keys: export reads the host copy
-    d_ksk_.alloc(ksk.size());
-    HIP_CHECK(hipMemcpy(d_ksk_.get(), ksk.data(), 8 * ksk.size(), hipMemcpyHostToDevice));
-    build_ksk_limbs();
+    Replacing key_guard([this] { drop_server_key(); });  // (no torus BSK here: export reads the host copy)
+    ksk_.alloc_rows(p_.big() * p_.ks_level, p_.n + 1);
+    HIP_CHECK(hipMemcpy(ksk_.rows.get(), ksk.data(), 8 * ksk.size(), hipMemcpyHostToDevice));
+    build_limbs(ksk_);
     if (p_.ring == FR_RING_FFT) upload_fft_bsk(bsk);
     else upload_rns_bsk(bsk);
+    key_guard.dismiss();
 }
 
 bool Device::latency_shape(size_t n) const { return n <= (p_.ring == FR_RING_FFT ? fft_small_ : small_batch_); }

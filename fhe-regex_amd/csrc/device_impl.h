@@ -1,5 +1,5 @@
 // What the .hip translation units of the Device class share (private: device.h is the
-// class's interface): the HIP error check, the current lane's stream, a modular inverse,
+// class's interface): the HIP error check, the stage timer, the current lane's stream, a modular inverse,
 // and the device-side pieces common to the blind rotation of both rings.
 #pragma once
 #include <hip/hip_ext.h>
@@ -18,6 +18,46 @@ namespace fr {
             throw Error(FR_ERR_HIP, std::string("HIP error: ") + hipGetErrorString(_e) +     \
                                         " at " __FILE__ ":" + std::to_string(__LINE__));     \
     } while (0)
+
+// HIP-event times of K consecutive stages of one call on one stream: mark(i) opens stage i
+// (and closes stage i - 1); read() follows the call's synchronisation of the stream.  Off
+// (no profiling): no event is created or recorded, and read() leaves ms alone.
+template <int K>
+struct StageTimer {
+    gpu::Event ev[K + 1];
+    hipStream_t s;  // null: off
+    StageTimer(bool on, hipStream_t stream) : s(on ? stream : nullptr) {
+        for (int i = 0; s && i <= K; ++i) ev[i] = gpu::Event(hipEventDefault);
+    }
+    void mark(int i) {
+        if (s) HIP_CHECK(hipEventRecord(ev[i].get(), s));
+    }
+    void read(double* ms) {
+        for (int i = 0; s && i < K; ++i) {
+            float t = 0;
+            HIP_CHECK(hipEventElapsedTime(&t, ev[i].get(), ev[i + 1].get()));
+            ms[i] = t;
+        }
+    }
+};
+
+// An install leaves a whole key or none.  Once every queued launch of every lane that reads the
+// old key has finished, the guard drops it (release, then allocate: never two keys side by
+// side); unless dismissed, it drops what the install has built when it goes.
+template <class Drop>
+struct Replacing {
+    Drop drop;
+    bool armed = true;
+    explicit Replacing(Drop d) : drop(d) {
+        HIP_CHECK(hipDeviceSynchronize());
+        drop();
+    }
+    Replacing(const Replacing&) = delete;
+    ~Replacing() {
+        if (armed) drop();
+    }
+    void dismiss() { armed = false; }
+};
 
 // the stream of the current lane (inside Device methods)
 #define STREAM (cur_stream())

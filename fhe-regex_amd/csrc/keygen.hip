@@ -439,8 +439,7 @@ void Device::gen_server_key(const ClientKey& ck, const RngKey& key, const RngKey
     const size_t rows = (size_t)p_.big() * L, nw = p_.bsk_ggsw();
     const bool compact = mask_key != nullptr;
     const RngKey& kkey = compact ? *mask_key : key;  // the key the kernels see
-    // every queued launch of every lane that reads the old keys has finished before they go
-    HIP_CHECK(hipDeviceSynchronize());
+    Replacing key_guard([this] { drop_server_key(); });
     // host: the noise draws and per-GGSW messages
     std::vector<int64_t> ksk_noise;
     std::vector<int32_t> bsk_noise;
@@ -460,10 +459,10 @@ void Device::gen_server_key(const ClientKey& ck, const RngKey& key, const RngKey
     HIP_CHECK(hipMemcpyAsync(d_msg.get(), msg.data(), msg.size(), hipMemcpyHostToDevice, s));
 
     // KSK (torus) and its byte limbs
-    d_ksk_.alloc(rows * (n + 1));
-    k_gen_ksk<<<(unsigned)rows, 64, 0, s>>>(kkey, n, L, p_.ks_base_log, d_ss.get(), d_sb.get(), d_kn.get(), d_ksk_.get());
+    ksk_.alloc_rows((int)rows, n + 1);
+    k_gen_ksk<<<(unsigned)rows, 64, 0, s>>>(kkey, n, L, p_.ks_base_log, d_ss.get(), d_sb.get(), d_kn.get(), ksk_.rows.get());
     HIP_CHECK(hipGetLastError());
-    build_ksk_limbs();
+    build_limbs(ksk_);
 
     // torus BSK, kept for export
     d_tbsk_.alloc(p_.bsk_len());
@@ -481,6 +480,7 @@ void Device::gen_server_key(const ClientKey& ck, const RngKey& key, const RngKey
 
     build_fourier_bsk();
     HIP_CHECK(hipStreamSynchronize(s));
+    key_guard.dismiss();
 }
 
 void Device::load_server_key_compact(const RngKey& mask_key, const uint8_t* bodies) {
@@ -489,40 +489,29 @@ void Device::load_server_key_compact(const RngKey& mask_key, const uint8_t* bodi
     const size_t rows = compact_ksk_bodies(p_), brows = p_.bsk_ggsw() * kp1, words = rows + compact_bsk_bodies(p_);
     // the BSK bodies follow the KSK bodies in one staging buffer and are read 16 bytes a lane
     if (rows % 2 || N % 8) throw Error(FR_ERR_INVALID, "device load of a compact server key: alignment");
-    // every queued launch of every lane that reads the old keys has finished before they go
-    HIP_CHECK(hipDeviceSynchronize());
+    Replacing key_guard([this] { drop_server_key(); });
     const hipStream_t s = cur().stream.get();
     gpu::DevBuf<uint64_t> d_body(words);
-    gpu::Event ev[6];
-    const bool timed = profiling_ != 0;
-    auto mark = [&](int i) {
-        if (timed) HIP_CHECK(hipEventRecord(ev[i].get(), s));
-    };
-    if (timed)
-        for (gpu::Event& e : ev) e = gpu::Event(hipEventDefault);
-    d_ksk_.alloc(rows * (n + 1));
+    StageTimer<5> timer(profiling_ != 0, s);
+    ksk_.alloc_rows((int)rows, n + 1);
     d_tbsk_.alloc(p_.bsk_len());
-    mark(0);
+    timer.mark(0);
     HIP_CHECK(hipMemcpyAsync(d_body.get(), bodies, 8 * words, hipMemcpyHostToDevice, s));
-    mark(1);
-    k_expand_ksk<<<(unsigned)rows, 64, 0, s>>>(mask_key, n, d_body.get(), d_ksk_.get());
+    timer.mark(1);
+    k_expand_ksk<<<(unsigned)rows, 64, 0, s>>>(mask_key, n, d_body.get(), ksk_.rows.get());
     HIP_CHECK(hipGetLastError());
-    mark(2);
+    timer.mark(2);
     if (N == 2048) k_expand_bsk<2048><<<(unsigned)brows, 256, 0, s>>>(mask_key, p_.k, d_body.get() + rows, d_tbsk_.get());
     else k_expand_bsk<1024><<<(unsigned)brows, 256, 0, s>>>(mask_key, p_.k, d_body.get() + rows, d_tbsk_.get());
     HIP_CHECK(hipGetLastError());
-    mark(3);
-    build_ksk_limbs();
-    mark(4);
+    timer.mark(3);
+    build_limbs(ksk_);
+    timer.mark(4);
     build_fourier_bsk();
-    mark(5);
+    timer.mark(5);
     HIP_CHECK(hipStreamSynchronize(s));
-    if (timed)
-        for (int i = 0; i < 5; ++i) {
-            float ms = 0;
-            HIP_CHECK(hipEventElapsedTime(&ms, ev[i].get(), ev[i + 1].get()));
-            key_load_ms_[i] = ms;
-        }
+    timer.read(key_load_ms_);
+    key_guard.dismiss();
 }
 
 // Packing key on the device: the torus rows stay for download_packing_key (as the torus BSK
@@ -532,8 +521,7 @@ void Device::gen_packing_key(const ClientKey& ck, const RngKey& key) {
         throw Error(FR_ERR_INVALID, "device packing keygen: (k, N) in {(1, 2048), (2, 1024)}");
     if (ck.s_big.size() != (size_t)p_.big()) throw Error(FR_ERR_INVALID, "device packing keygen: key size");
     const size_t rows = pk_rows(p_);
-    // every queued pack of every lane that reads the old key has finished before it goes
-    HIP_CHECK(hipDeviceSynchronize());
+    Replacing key_guard([this] { drop_packing_key(); });
     std::vector<int32_t> noise;
     gen_pksk_noise(p_, key, noise);
     const hipStream_t s = cur().stream.get();
@@ -541,34 +529,34 @@ void Device::gen_packing_key(const ClientKey& ck, const RngKey& key) {
     gpu::DevBuf<int32_t> d_n(noise.size());
     HIP_CHECK(hipMemcpyAsync(d_sb.get(), ck.s_big.data(), 8 * ck.s_big.size(), hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(d_n.get(), noise.data(), 4 * noise.size(), hipMemcpyHostToDevice, s));
-    d_pkl_.reset();
-    d_pksk_.alloc(pk_len(p_));
-    if (p_.N == 2048) k_gen_pksk<2048><<<(unsigned)rows, 256, 0, s>>>(key, p_.k, d_sb.get(), d_n.get(), d_pksk_.get());
-    else k_gen_pksk<1024><<<(unsigned)rows, 256, 0, s>>>(key, p_.k, d_sb.get(), d_n.get(), d_pksk_.get());
+    pksk_.alloc_rows((int)rows, (int)pk_row_words(p_));
+    if (p_.N == 2048) k_gen_pksk<2048><<<(unsigned)rows, 256, 0, s>>>(key, p_.k, d_sb.get(), d_n.get(), pksk_.rows.get());
+    else k_gen_pksk<1024><<<(unsigned)rows, 256, 0, s>>>(key, p_.k, d_sb.get(), d_n.get(), pksk_.rows.get());
     HIP_CHECK(hipGetLastError());
-    build_pk_limbs();
+    build_limbs(pksk_);
     HIP_CHECK(hipStreamSynchronize(s));  // the temporaries go once the kernels have run
+    key_guard.dismiss();
 }
 
 void Device::upload_packing_key(const void* rows) {
-    HIP_CHECK(hipDeviceSynchronize());
-    d_pkl_.reset();
-    d_pksk_.alloc(pk_len(p_));
-    HIP_CHECK(hipMemcpy(d_pksk_.get(), rows, 8 * pk_len(p_), hipMemcpyHostToDevice));
-    build_pk_limbs();
+    Replacing key_guard([this] { drop_packing_key(); });
+    pksk_.alloc_rows((int)pk_rows(p_), (int)pk_row_words(p_));
+    HIP_CHECK(hipMemcpy(pksk_.rows.get(), rows, 8 * pk_len(p_), hipMemcpyHostToDevice));
+    build_limbs(pksk_);
     HIP_CHECK(hipStreamSynchronize(cur().stream.get()));
+    key_guard.dismiss();
 }
 
 void Device::download_packing_key(uint64_t* rows) {
     if (!has_packing_key()) throw Error(FR_ERR_INVALID, "no packing key on the device");
-    HIP_CHECK(hipMemcpy(rows, d_pksk_.get(), 8 * pk_len(p_), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(rows, pksk_.rows.get(), 8 * pksk_.rows.size(), hipMemcpyDeviceToHost));
 }
 
 void Device::download_server_key(uint64_t* ksk, size_t ksk_len, uint64_t* bsk, size_t bsk_len) {
-    if (!d_ksk_ || !d_tbsk_) throw Error(FR_ERR_NO_KEY, "no device-generated server key");
+    if (!ksk_ || !d_tbsk_) throw Error(FR_ERR_NO_KEY, "no device-generated server key");
     if (ksk) {
-        if (ksk_len != (size_t)p_.big() * p_.ks_level * (p_.n + 1)) throw Error(FR_ERR_INVALID, "ksk size");
-        HIP_CHECK(hipMemcpy(ksk, d_ksk_.get(), 8 * ksk_len, hipMemcpyDeviceToHost));
+        if (ksk_len != ksk_.rows.size()) throw Error(FR_ERR_INVALID, "ksk size");
+        HIP_CHECK(hipMemcpy(ksk, ksk_.rows.get(), 8 * ksk_len, hipMemcpyDeviceToHost));
     }
     if (bsk) {
         if (bsk_len != p_.bsk_len()) throw Error(FR_ERR_INVALID, "bsk size");

@@ -542,71 +542,74 @@ void Device::ensure_digits(size_t rows) {
     cur().dig.grow(rows * row, 1024 * row);
 }
 
-// byte-limb form of the KSK for the MFMA keyswitch
-void Device::build_ksk_limbs() {
-    const int KD = p_.big() * p_.ks_level, ncols = p_.n + 1;
-    const int nlc = ((ncols * 8 + 127) / 128) * 128;  // whole 4-wave column groups
-    d_kl_.alloc((size_t)nlc * KD);
-    HIP_CHECK(hipMemsetAsync(d_kl_.get(), 0, (size_t)nlc * KD, STREAM));
-    k_ksk_limbs<<<dim3((unsigned)((KD + 255) / 256), (unsigned)(nlc / 8)), 256, 0, STREAM>>>(d_ksk_.get(), KD, ncols, nlc,
-                                                                                          d_kl_.get());
+// byte-limb form of a key's torus rows, the MFMA keyswitch's column operand
+void Device::build_limbs(LimbKey& key) {
+    const size_t bytes = (size_t)key.nlc * key.KD;
+    key.limbs.alloc(bytes);
+    HIP_CHECK(hipMemsetAsync(key.limbs.get(), 0, bytes, STREAM));
+    k_ksk_limbs<<<dim3((unsigned)((key.KD + 255) / 256), (unsigned)(key.nlc / 8)), 256, 0, STREAM>>>(
+        key.rows.get(), key.KD, key.ncols, key.nlc, key.limbs.get());
     HIP_CHECK(hipGetLastError());
-    kl_cols_ = nlc;
+}
+
+// lincomb + digits of `padded` rows.  The byte-store pass (FR_KS_DIG16=0, or kN no multiple of
+// 16) is compiled for the LWE gadget only; the packing keyswitch always takes k_ks_digits16.
+template <int KSB, int KSL>
+void Device::launch_ks_digits(const DevGate* d_gates, size_t n, size_t padded, int8_t* dig, uint64_t* out, int out_n,
+                              int out_stride, hipEvent_t ev_start) {
+    auto launch = [&](auto kernel, dim3 grid, int threads) {
+        hipExtLaunchKernelGGL(kernel, grid, dim3(threads), 0, STREAM, ev_start, nullptr, 0, d_gates, (int)n,
+                              (const uint64_t*)d_arena_.get(), p_.slot_stride(), (const int*)cur().cmap.device(), p_.big(),
+                              dig, out, out_n, out_stride);
+        HIP_CHECK(hipGetLastError());
+    };
+    if constexpr (KSB == 3 && KSL == 5)
+        if (!ks_dig16_ || p_.big() % 16) return launch(k_ks_digits<KSB, KSL>, dim3(8, (unsigned)padded), 256);
+    launch(k_ks_digits16<KSB, KSL>, dim3((unsigned)padded), 128);
+}
+
+// out -= dig x key.limbs: every MFMA kernel takes the same arguments, the shape picks one
+void Device::launch_limb_gemm(const int8_t* dig, const LimbKey& key, size_t n, const KsShape& sh, uint64_t* out,
+                              int out_stride, hipEvent_t ev_stop) {
+    const int GX = (int)(sh.padded / (32 * sh.MR)), GY = (key.nlc + 128 * sh.MC - 1) / (128 * sh.MC);
+    auto launch = [&](auto kernel) {
+        hipExtLaunchKernelGGL(kernel, dim3((unsigned)ks_grid_blocks(GX, GY, sh.GZ, ks_xcd_)), dim3(256), 0, STREAM, nullptr,
+                              ev_stop, 0, dig, (const int8_t*)key.limbs.get(), (int)n, key.KD, key.ncols, key.nlc,
+                              (unsigned long long*)out, out_stride, GX, GY, sh.GZ, ks_xcd_);
+        HIP_CHECK(hipGetLastError());
+    };
+    if (sh.MR == 4 && sh.MC == 1 && sh.lds) launch(k_ks_glds<FR_KS_SK, FR_KS_NB>);
+    else if (sh.MR == 4 && sh.MC == 2) launch(k_ks_mfma<4, 2>);
+    else if (sh.MR == 4) launch(k_ks_mfma<4, 1>);
+    else launch(k_ks_mfma<1, 1>);
 }
 
 void Device::launch_ks(const DevGate* d_gates, size_t n, uint64_t* d_ks, hipEvent_t e0, hipEvent_t e1) {
-    const uint64_t* arena = d_arena_.get();
-    const int* d_cmap = cur().cmap.device();
     if (ks_mfma_) {
         const int KD = p_.big() * p_.ks_level;
         if (KD % 256) throw Error(FR_ERR_INVALID, "MFMA keyswitch needs kN*ks_level % 256 == 0");
-        const int MR = n >= ks_mr4_min_ ? 4 : 1;  // row tiles per wave
-        const size_t bp = (n + 32 * MR - 1) / (32 * MR) * (32 * MR);
-        ensure_digits(bp);
+        KsShape sh = ks_shape(n);
+        ensure_digits(sh.padded);
         int8_t* d_dig = cur().dig.get();
-        if (KD % 16) throw Error(FR_ERR_INVALID, "MFMA keyswitch: digit rows must be whole 16-byte vectors");
-        if (ks_dig16_ && p_.big() % 16 == 0)
-            hipExtLaunchKernelGGL(k_ks_digits16<3, 5>, dim3((unsigned)bp), dim3(128), 0, STREAM, e0, nullptr, 0, d_gates,
-                                  (int)n, arena, p_.slot_stride(), d_cmap, p_.big(),
-                                  d_dig, d_ks, p_.n, p_.ks_stride());
-        else
-            hipExtLaunchKernelGGL(k_ks_digits<3, 5>, dim3(8, (unsigned)bp), dim3(256), 0, STREAM, e0, nullptr, 0, d_gates,
-                                  (int)n, arena, p_.slot_stride(), d_cmap, p_.big(),
-                                  d_dig, d_ks, p_.n, p_.ks_stride());
-        HIP_CHECK(hipGetLastError());
+        launch_ks_digits<3, 5>(d_gates, n, sh.padded, d_dig, d_ks, p_.n, p_.ks_stride(), e0);
         // column tiles per wave: 1 (FR_KS_MC=2 shares each digit fragment between two; with
         // fragment-ordered operands that no longer pays: 512 gates 121 -> 103 us at 1)
-        const int MC = MR == 4 && ks_mc_ == 2 ? 2 : 1;
+        sh.MC = sh.MR == 4 && ks_mc_ == 2 ? 2 : 1;
+        sh.lds = ks_lds_;
         // K slices (partial sums meet in 64-bit atomics, so more slices cost atomic traffic, and
         // every slice its epilogue): 8 for one row tile per wave (1-17 gates ~30 us); four row
         // tiles (k_ks_glds): 5 up to 256 gates, 2 up to 512, then 1 (profiles/r03/ab_ks_glds.log:
         // 254 gates 55 us at 4-5 against 60 at 2; 512: 77 at 2 against 86-89 at 4-5; 1024 /
         // 2048: 125 / 231 at 1 against 130 / 234 at 2); a divisor of KD / 256
-        const int gx = (int)(bp / (32 * MR));
-        int split = MR == 1 ? 8 : gx <= 2 ? 5 : gx <= 4 ? 2 : 1;
-        while ((KD / 256) % split) --split;
-        if (ks_split_ > 0 && (KD / 256) % ks_split_ == 0) split = ks_split_;
-        const int GX = gx, GY = (kl_cols_ + 128 * MC - 1) / (128 * MC), GZ = split;
-        const dim3 grid((unsigned)ks_grid_blocks(GX, GY, GZ, ks_xcd_));
-        if (MR == 4 && MC == 1 && ks_lds_)
-            hipExtLaunchKernelGGL(k_ks_glds<FR_KS_SK, FR_KS_NB>, grid, dim3(256), 0, STREAM, nullptr, e1, 0,
-                                  (const int8_t*)d_dig, (const int8_t*)d_kl_.get(), (int)n, KD, p_.n + 1, kl_cols_,
-                                  (unsigned long long*)d_ks, p_.ks_stride(), GX, GY, GZ, ks_xcd_);
-        else if (MR == 4 && MC == 2)
-            hipExtLaunchKernelGGL(k_ks_mfma<4, 2>, grid, dim3(256), 0, STREAM, nullptr, e1, 0, (const int8_t*)d_dig,
-                                  (const int8_t*)d_kl_.get(), (int)n, KD, p_.n + 1, kl_cols_, (unsigned long long*)d_ks,
-                                  p_.ks_stride(), GX, GY, GZ, ks_xcd_);
-        else if (MR == 4)
-            hipExtLaunchKernelGGL(k_ks_mfma<4, 1>, grid, dim3(256), 0, STREAM, nullptr, e1, 0, (const int8_t*)d_dig,
-                                  (const int8_t*)d_kl_.get(), (int)n, KD, p_.n + 1, kl_cols_, (unsigned long long*)d_ks,
-                                  p_.ks_stride(), GX, GY, GZ, ks_xcd_);
-        else
-            hipExtLaunchKernelGGL(k_ks_mfma<1, 1>, grid, dim3(256), 0, STREAM, nullptr, e1, 0, (const int8_t*)d_dig,
-                                  (const int8_t*)d_kl_.get(), (int)n, KD, p_.n + 1, kl_cols_, (unsigned long long*)d_ks,
-                                  p_.ks_stride(), GX, GY, GZ, ks_xcd_);
-        HIP_CHECK(hipGetLastError());
+        const int gx = (int)(sh.padded / (32 * sh.MR));
+        sh.GZ = sh.MR == 1 ? 8 : gx <= 2 ? 5 : gx <= 4 ? 2 : 1;
+        while ((KD / 256) % sh.GZ) --sh.GZ;
+        if (ks_split_ > 0 && (KD / 256) % ks_split_ == 0) sh.GZ = ks_split_;
+        launch_limb_gemm(d_dig, ksk_, n, sh, d_ks, p_.ks_stride(), e1);
         return;
     }
+    const uint64_t* arena = d_arena_.get();
+    const int* d_cmap = cur().cmap.device();
     const int btiles = (int)((n + KS_BT - 1) / KS_BT);
     const int ctiles = (p_.n + 1 + KS_CT - 1) / KS_CT;
     const int chunks = (p_.big() + KS_CH - 1) / KS_CH;
@@ -618,7 +621,7 @@ void Device::launch_ks(const DevGate* d_gates, size_t n, uint64_t* d_ks, hipEven
     if (splits > 1) HIP_CHECK(hipMemsetAsync(d_ks, 0, (size_t)8 * p_.ks_stride() * n, STREAM));
     dim3 grid((unsigned)btiles, (unsigned)ctiles, (unsigned)splits);
     hipExtLaunchKernelGGL(k_lincomb_keyswitch<3, 5>, grid, dim3(256), 0, STREAM, e0, e1, 0, d_gates, (int)n,
-                          arena, p_.slot_stride(), d_cmap, (const uint64_t*)d_ksk_.get(), p_.n,
+                          arena, p_.slot_stride(), d_cmap, (const uint64_t*)ksk_.rows.get(), p_.n,
                           p_.big(), per, (unsigned long long*)d_ks, p_.ks_stride());
     HIP_CHECK(hipGetLastError());
 }
@@ -661,28 +664,18 @@ __global__ void __launch_bounds__(256) k_limb_column(const int8_t* __restrict__ 
 
 void Device::packing_limb_column(int col, uint64_t* out_host) {
     if (!has_packing_key()) throw Error(FR_ERR_INVALID, "no packing key on the device");
-    const int KD = (int)pk_rows(p_);
-    if (col < 0 || col >= (int)pk_row_words(p_)) throw Error(FR_ERR_INVALID, "packing key: column out of range");
+    const int KD = pksk_.KD;
+    if (col < 0 || col >= pksk_.ncols) throw Error(FR_ERR_INVALID, "packing key: column out of range");
     gpu::DevBuf<uint64_t> d((size_t)KD);
-    k_limb_column<<<(KD + 255) / 256, 256, 0, STREAM>>>(d_pkl_.get(), KD, col, d.get());
+    k_limb_column<<<(KD + 255) / 256, 256, 0, STREAM>>>(pksk_.limbs.get(), KD, col, d.get());
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(out_host, d.get(), 8 * (size_t)KD, hipMemcpyDeviceToHost, STREAM));
     HIP_CHECK(hipStreamSynchronize(STREAM));
 }
 
-void Device::build_pk_limbs() {
-    const int KD = (int)pk_rows(p_), ncols = (int)pk_row_words(p_);
-    const int nlc = ((ncols * 8 + 127) / 128) * 128;  // whole 4-wave column groups
-    d_pkl_.alloc((size_t)nlc * KD);
-    HIP_CHECK(hipMemsetAsync(d_pkl_.get(), 0, (size_t)nlc * KD, STREAM));
-    k_ksk_limbs<<<dim3((unsigned)((KD + 255) / 256), (unsigned)(nlc / 8)), 256, 0, STREAM>>>(d_pksk_.get(), KD, ncols, nlc,
-                                                                                          d_pkl_.get());
-    HIP_CHECK(hipGetLastError());
-}
-
 void Device::pack_bools(const DevGate* gates, size_t n, uint64_t* out_host) {
     if (!has_packing_key()) throw Error(FR_ERR_INVALID, "no packing key on the device");
-    const int N = p_.N, big = p_.big(), KD = (int)pk_rows(p_), W = (int)pk_row_words(p_);
+    const int N = p_.N, big = p_.big(), KD = pksk_.KD, W = pksk_.ncols;
     if (n < 1 || n > (size_t)N) throw Error(FR_ERR_INVALID, "pack: 1 <= n <= N booleans");
     if (KD % 256 || big % 16 || W % 256) throw Error(FR_ERR_INVALID, "pack: kN must be a multiple of 256");
     for (size_t j = 0; j < n; ++j) {
@@ -693,8 +686,8 @@ void Device::pack_bools(const DevGate* gates, size_t n, uint64_t* out_host) {
     }
     const hipStream_t s = STREAM;
     LaneState& l = cur();
-    const int MR = n >= ks_mr4_min_ ? 4 : 1;  // row tiles per wave, as launch_ks
-    const size_t bp = (n + 32 * MR - 1) / (32 * MR) * (32 * MR);
+    KsShape sh = ks_shape(n);  // (one column tile and the LDS-DMA ring, whatever FR_KS_MC / FR_KS_LDS say)
+    const size_t bp = sh.padded;  // rows of whole tiles, as launch_ks
     // scratch: the descriptors, digits [bp][KD], G [n][W] and the packed GLWE behind it; allocated at the first
     // pack of the lane, doubled from there
     if (bp * KD > l.pk_dig.size() || (n + 1) * (size_t)W > l.pk_g.size() || n > l.pk_gates.size()) {
@@ -708,53 +701,31 @@ void Device::pack_bools(const DevGate* gates, size_t n, uint64_t* out_host) {
     uint64_t* d_out = d_g + n * (size_t)W;
     DevGate* d_gates = l.pk_gates.get();
     HIP_CHECK(hipMemcpyAsync(d_gates, gates, sizeof(DevGate) * n, hipMemcpyHostToDevice, s));
-    gpu::Event ev[4];
-    const bool timed = profiling_ != 0;
-    auto mark = [&](int i) {
-        if (timed) HIP_CHECK(hipEventRecord(ev[i].get(), s));
-    };
-    if (timed)
-        for (gpu::Event& e : ev) e = gpu::Event(hipEventDefault);
+    StageTimer<3> timer(profiling_ != 0, s);
     // the digit pass zeroes the mask columns of G and writes column kN: the rest of the body
     // polynomial's columns (from kN, ahead of that write) and the output row are zeroed here,
     // inside the first stage's time
-    mark(0);
+    timer.mark(0);
     HIP_CHECK(hipMemset2DAsync(d_g + big, 8 * (size_t)W, 0, 8 * (size_t)N, n, s));
     HIP_CHECK(hipMemsetAsync(d_out, 0, 8 * (size_t)W, s));
-    k_ks_digits16<PK_BASE_LOG, PK_LEVELS><<<dim3((unsigned)bp), dim3(128), 0, s>>>(
-        d_gates, (int)n, d_arena_.get(), p_.slot_stride(), l.cmap.device(), big, d_dig, d_g, big, W);
-    HIP_CHECK(hipGetLastError());
-    mark(1);
+    launch_ks_digits<PK_BASE_LOG, PK_LEVELS>(d_gates, n, bp, d_dig, d_g, big, W, nullptr);
+    timer.mark(1);
     // Tiles for 32768 limb columns: GY = 256 column groups (the LWE keyswitch has 47) fill the
     // 256 CUs without K slices, so the four-row-tile shape runs unsliced (tools/pack_probe.py,
     // profiles/packed_results: 256 rows 68 us at 1 slice, 78 at 2, 117 at 8; 2048 rows 485 /
     // 540 / 939) and one row tile per wave takes 2 (16 rows: 33 us at 2 and 4, 38 at 1)
-    const int nlc = W * 8, GX = (int)(bp / (32 * MR)), GY = nlc / 128;
-    int GZ = MR == 1 ? 2 : 1;  // a divisor of KD / 256 = 24
-    if (pk_split_ > 0 && (KD / 256) % pk_split_ == 0) GZ = pk_split_;
-    const dim3 grid((unsigned)ks_grid_blocks(GX, GY, GZ, ks_xcd_));
-    if (MR == 4)
-        k_ks_glds<FR_KS_SK, FR_KS_NB><<<grid, dim3(256), 0, s>>>((const int8_t*)d_dig, (const int8_t*)d_pkl_.get(), (int)n,
-                                                                 KD, W, nlc, (unsigned long long*)d_g, W, GX, GY, GZ,
-                                                                 ks_xcd_);
-    else
-        k_ks_mfma<1, 1><<<grid, dim3(256), 0, s>>>((const int8_t*)d_dig, (const int8_t*)d_pkl_.get(), (int)n, KD, W, nlc,
-                                                   (unsigned long long*)d_g, W, GX, GY, GZ, ks_xcd_);
-    HIP_CHECK(hipGetLastError());
-    mark(2);
+    sh.GZ = sh.MR == 1 ? 2 : 1;  // a divisor of KD / 256 = 24
+    if (pk_split_ > 0 && (KD / 256) % pk_split_ == 0) sh.GZ = pk_split_;
+    launch_limb_gemm(d_dig, pksk_, n, sh, d_g, W, nullptr);
+    timer.mark(2);
     const int jper = 32, slices = (int)((n + jper - 1) / jper);
     k_pack_rotate_sum<<<dim3((unsigned)(W / 256), (unsigned)slices), 256, 0, s>>>(d_g, (int)n, N, W, jper,
                                                                                    (unsigned long long*)d_out);
     HIP_CHECK(hipGetLastError());
-    mark(3);
+    timer.mark(3);
     HIP_CHECK(hipMemcpyAsync(out_host, d_out, 8 * (size_t)W, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    if (timed)
-        for (int i = 0; i < 3; ++i) {
-            float ms = 0;
-            HIP_CHECK(hipEventElapsedTime(&ms, ev[i].get(), ev[i + 1].get()));
-            pack_ms_[i] = ms;
-        }
+    timer.read(pack_ms_);
 }
 
 void Device::run_linear(const DevGate& g) {
