@@ -189,6 +189,9 @@ class Device {
         gpu::DevBuf<DevGate> pk_gates;  // pack_bools: the booleans' descriptors
         gpu::DevBuf<int8_t> pk_dig;  // pack_bools: digits [rows][3 kN], allocated at the first pack
         gpu::DevBuf<uint64_t> pk_g;  // pack_bools: keyswitched rows [n][(k+1) N], then the packed GLWE
+        // key products of the lane's smallest launches [bootstrap][step][P][own, other][m][lane]
+        // (fft_br.hip: k_key_products), allocated at the first such launch, grown to the largest
+        gpu::DevBuf<double> kpre;
         gpu::StagingRing<int> cmap;  // content map (bind_content)
         size_t cmap_n = 0;           // entries bound
         gpu::Event done_ev;          // recorded on the lane's stream when it is left
@@ -233,7 +236,11 @@ class Device {
     };
     void build_limbs(LimbKey& key);
     // every buffer of an installed key; the installs drop under a Replacing guard (device_impl.h)
-    void drop_server_key() { ksk_.reset(), d_tbsk_.reset(), d_bsk_.reset(), d_fbsk_[0].reset(), d_fbsk_[1].reset(); }
+    void drop_server_key() {
+        ksk_.reset(), d_tbsk_.reset(), d_bsk_.reset(), d_fbsk_[0].reset(), d_fbsk_[1].reset();
+        lane0_.kpre.reset();
+        for (auto& l : lanes_) l.kpre.reset();
+    }
     void drop_packing_key() { pksk_.reset(); }
     // MFMA keyswitch of n rows: row tiles per wave and n padded to whole tiles of them (ks_shape);
     // column tiles per wave, the LDS-DMA ring (k_ks_glds: MR 4, MC 1 only) and K slices: the caller's
@@ -307,6 +314,12 @@ class Device {
     // by default: profiles/r03/ab_pair_shape.log)
     size_t fft_pair_ = SIZE_MAX;
     bool fft_dual_ = false;  // FR_FFT_DUAL=1: the dual shape instead of the pair (experiment)
+    // k = 1: latency-shape launches of at most this many bootstraps precompute their key
+    // products on the idle CUs (k_key_products, then k_blind_rotate_fft_kp); FR_FFT_KPRE_BATCH,
+    // 0: off.  24.3 MB of scratch per bootstrap and lane.  32: the largest of 1, 2, 4, ..., 64 at
+    // which every run of the pair of kernels beats the plain latency shape (1.19 against 1.34 ms;
+    // at 64 1.5-2% at the median for 1.6 GB of scratch: profiles/key_products/)
+    size_t fft_kpre_ = 32;
     // Fourier BSK, one copy per lane geometry in use: [0] E = 4 (latency shape, always),
     // [1] E = 8 (the throughput shape's when fft_e_ is that)
     gpu::DevBuf<double> d_fbsk_[2];

@@ -450,6 +450,10 @@ constexpr int fbr_threads() {
 //    inverse: 3 barriers per step instead of 5) in LDS.  k = 1 keeps the lane's
 //    twiddles in registers (TWR); k = 2 reads them from LDS (the 36 GGSW values
 //    take the registers).
+//  * latency with key products (k = 1, KP; launches of at most fft_kpre_): k_key_products forms
+//    every step's K_own, K_oth on the idle CUs first; the rotation loads the 2 E products of
+//    the next unskipped step right after the MAC and nothing inside a step: no key, no psi
+//    table, no slot factors; 491 instructions per wave-step against 722, 148 VGPRs.
 //  * pair (k = 1, B = 2; launches between the latency shape's limit and fft_pair_): the
 //    latency geometry with two bootstraps per workgroup.  One set of key loads, twiddle
 //    registers and barriers serves both (the two workgroups a CU would run side by side
@@ -484,6 +488,51 @@ __device__ __forceinline__ void slot_factor(double br, double bi, uint32_t e, ui
     cr = __longlong_as_double(__double_as_longlong(ar) ^ sg);
     ci = __longlong_as_double(__double_as_longlong(ai) ^ sg);
 }
+// The key-only half of the MAC, defined once: everything a step's MAC forms from the Fourier
+// key and the mod-switched pair (e_i, e_j) before it touches the digits.  The MAC of every
+// launch shape and k_key_products call these two functions and nothing else forms these
+// values, so a product is the same operations in the same order wherever it is computed.
+// (a) the slot base's factor psi^(e Lb) from the LDS table psi (filled through psi_slot):
+// the whole circle (k < 2N) or the quadrant table (k < N/2) and a quarter turn
+template <int N, bool PSIQ>
+__device__ __forceinline__ void key_psi_base(const double2* psi, uint32_t e, uint32_t Lb, double& br, double& bi) {
+    const uint32_t k = __umul24(e, Lb) & (2 * N - 1);
+    if constexpr (!PSIQ) {  // psi^k, k < 2N, straight from the table
+        const double2 c = psi[psi_slot((int)k)];
+        br = c.x;
+        bi = c.y;
+    } else {
+        const double2 q = psi[psi_slot((int)(k & (N / 2 - 1)))];
+        fft::psi_quadrant(q.x, q.y, k >> (ilog2c(N) - 1), br, bi);
+    }
+}
+// (b) slot sm's products from its base's factors (bre, bim)[e_i, e_j][mb] and the slot's key values
+// key(g, r) (r = 0: the own row B_g[P][P], r = 1 + q: the q-th other row): c_1, c_2 by
+// slot_factor, c_0 = c_1 c_2, then per row K_r = sum_g B_g[r][P] (c_g - 1), g ascending, own
+// row first.  16 (K + 1) VALU per slot (k = 1: 32, against 36 for sum_g (c_g - 1) y_g)
+template <int K, int NB, class KeyAt>
+__device__ __forceinline__ void key_products(const double (&bre)[2][NB], const double (&bim)[2][NB], int mb, uint32_t ei,
+                                             uint32_t ej, uint32_t sm, KeyAt&& key, double& kor, double& koi,
+                                             double (&kxr)[K], double (&kxi)[K]) {
+    double cr[3], ci[3];
+#pragma unroll
+    for (int h = 1; h < 3; ++h)  // uniform quarter turn
+        slot_factor(bre[h - 1][mb], bim[h - 1][mb], h == 1 ? ei : ej, sm, cr[h], ci[h]);
+    fft::cmul(cr[1], ci[1], cr[2], ci[2], cr[0], ci[0]);
+#pragma unroll
+    for (int gg = 0; gg < 3; ++gg) {
+        const double c1r = cr[gg] - 1.0, c1i = ci[gg];
+        const double2 Bo = key(gg, 0);
+        if (gg == 0) fft::cmul(Bo.x, Bo.y, c1r, c1i, kor, koi);
+        else fft::cmac(Bo.x, Bo.y, c1r, c1i, kor, koi);
+#pragma unroll
+        for (int q = 0; q < K; ++q) {
+            const double2 Bx = key(gg, 1 + q);
+            if (gg == 0) fft::cmul(Bx.x, Bx.y, c1r, c1i, kxr[q], kxi[q]);
+            else fft::cmac(Bx.x, Bx.y, c1r, c1i, kxr[q], kxi[q]);
+        }
+    }
+}
 // twiddles in registers (latency shape, k = 1)
 template <int K, bool LAT>
 constexpr bool fbr_twr() {
@@ -498,10 +547,11 @@ constexpr int fbr_twc_entries() {
 // latency shape's two row sets per bootstrap (139 KB at k = 1) by dropping the forward
 // twiddle table (its registers load from global memory once) and using the quadrant
 // psi table; its multi-value terms live in the inverse rows after the loop.
-template <int N, int K, int E, bool LAT, int B = 1>
+// (KP, the key-products variant of the latency shape: no psi table)
+template <int N, int K, int E, bool LAT, int B = 1, bool KP = false>
 constexpr size_t fbr_smem_bytes() {
     return 16 * ((LAT ? 2 : 1) * B * (K + 1) * (size_t)FGeo<N / 2, E>::NP + (B == 1 ? (size_t)N / 2 : 0) +
-                 (LAT && B == 1 ? 2 * (size_t)N : (size_t)N / 2) + (size_t)fbr_twc_entries<N, K, E, LAT>()) +
+                 (KP ? 0 : LAT && B == 1 ? 2 * (size_t)N : (size_t)N / 2) + (size_t)fbr_twc_entries<N, K, E, LAT>()) +
            B * (16 * MAX_OUT + 2 * 1026) + (B == 1 ? 4 * 17 * MAX_OUT : 0) + 2 * 514;
 }
 // workgroups per CU of the throughput shapes (LDS: fbr_smem_bytes * this <= 160 KB)
@@ -625,13 +675,22 @@ __device__ __forceinline__ void fbr_outputs(int tid, const uint64_t* ab, const D
     }
 }
 
-template <int N, int K, int E, bool LAT, int B = 1>
-__global__ void __launch_bounds__((fbr_threads<N, K, E>()), (fbr_min_waves<N, K, E, LAT>()))
-k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const DevGate* __restrict__ gates,
-                   int n_gates, const double2* __restrict__ bsk, const double2* __restrict__ tw_g,
-                   const double2* __restrict__ psi_g, const uint16_t* __restrict__ leaf_g, uint64_t* __restrict__ arena,
-                   int slot_stride) {
+// Byte sizes of the precomputed key products (k_key_products): one step's K_r values
+// [P][own, other rows][m][lane] and one bootstrap's [t] of them
+template <int N, int K>
+constexpr uint32_t kpre_step_bytes() {
+    return 16u * (uint32_t)((K + 1) * (K + 1) * (N / 2));
+}
+
+// The blind rotation of every launch shape.  KP (the latency shape, k = 1): the step's key
+// products K_own, K_oth come from kpre, where k_key_products put them before this launch
+// (kpre + bootstrap x steps x kpre_step_bytes), instead of the key, the psi table and the pair.
+template <int N, int K, int E, bool LAT, int B, bool KP>
+__device__ __forceinline__ void fbr_rotate(const uint64_t* ks, int ks_stride, int n, const DevGate* gates, int n_gates,
+                                           const double2* bsk, const double2* tw_g, const double2* psi_g,
+                                           const uint16_t* leaf_g, uint64_t* arena, int slot_stride, const double2* kpre) {
     constexpr int M = N / 2;
+    static_assert(!KP || (LAT && B == 1 && K == 1 && E == 4), "key products: the k = 1 latency shape");
     using G = FGeo<M, E>;
     static_assert(fexchanges_conflict_free<M, E>(), "LDS maps must make every exchange conflict-free");
     static_assert(G::base_matches_geo(), "base<p> must be the index map the LDS-map proofs reason about");
@@ -648,7 +707,7 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
     double2* xbuf = fsm;                  // B x (K+1) rows of NP complex: bootstrap b, row P at b BS + P NP
     double2* ibuf = LAT ? xbuf + B * BS : xbuf;  // inverse-transform rows (latency shapes: separate)
     double2* tw = xbuf + (LAT ? 2 : 1) * B * BS;  // M forward twiddles (B = 1)
-    constexpr int NPSI = PSIQ ? N / 2 : 2 * N;  // (latency shape: the whole circle, no sign flips)
+    constexpr int NPSI = KP ? 0 : PSIQ ? N / 2 : 2 * N;  // (latency shape: the whole circle, no sign flips)
     double2* psi = tw + (B == 1 ? M : 0);  // psi^k, k < NPSI
     double2* twc = psi + NPSI;            // radix-4 products c ca (fbr_twc_entries)
     constexpr int NTWC = fbr_twc_entries<N, K, E, LAT>();
@@ -737,7 +796,9 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
     const int steps = (n + 1) / 2;
     // latency shape: Fourier GGSW slots of a step for this lane, [g][own, other rows][m],
     // and (k = 1) the lane's twiddles
-    double2 gv[3][K + 1][LAT ? E : 1];
+    // (KP: kv, the step's key products [own, other rows][m], in their place)
+    double2 gv[3][K + 1][LAT && !KP ? E : 1];
+    double2 kv[K + 1][KP ? E : 1];
     FTwr<M, TWR ? E : 2> twr;
     if constexpr (TWR) ftw_load_phase<M, E, 0, B == 1 ? false : FR_TW_SGPR_PAIR>(twr, B == 1 ? tw : tw_g, tl);
 #ifdef FR_BR_TIMING
@@ -747,16 +808,31 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
 #endif
     // latency shape: GGSW g's slots of step tt for this lane ([g][own, other rows][m])
     auto load_ggsw = [&](int gg, int tt) {
-        const uint32_t sb = (uint32_t)__builtin_amdgcn_readfirstlane(tt) * (3u * GG * 16u);
+        if constexpr (!KP) {
+            const uint32_t sb = (uint32_t)__builtin_amdgcn_readfirstlane(tt) * (3u * GG * 16u);
 #pragma unroll
-        for (int m = 0; m < E; ++m) {
-            gv[gg][0][m] =
-                bsk_load(rs, lane_off, sb + 16u * (gg * GG + (uint32_t)(P * (K + 1) + P) * M + (uint32_t)m * T));
+            for (int m = 0; m < E; ++m) {
+                gv[gg][0][m] =
+                    bsk_load(rs, lane_off, sb + 16u * (gg * GG + (uint32_t)(P * (K + 1) + P) * M + (uint32_t)m * T));
 #pragma unroll
-            for (int q = 0; q < K; ++q)
-                gv[gg][1 + q][m] = bsk_load(
-                    rs, lane_off,
-                    sb + 16u * (gg * GG + (uint32_t)(other_row<K>(P, q) * (K + 1) + P) * M + (uint32_t)m * T));
+                for (int q = 0; q < K; ++q)
+                    gv[gg][1 + q][m] = bsk_load(
+                        rs, lane_off,
+                        sb + 16u * (gg * GG + (uint32_t)(other_row<K>(P, q) * (K + 1) + P) * M + (uint32_t)m * T));
+            }
+        }
+    };
+    // KP: all of step tt's key products for this lane, 2 E loads of 1 KB per wave
+    const __amdgpu_buffer_rsrc_t rk =
+        bsk_rsrc(KP ? kpre + (size_t)blockIdx.x * ((size_t)((n + 1) / 2) * (kpre_step_bytes<N, K>() / 16)) : bsk);
+    auto load_kp = [&](int tt) {
+        if constexpr (KP) {
+            const uint32_t sb = (uint32_t)__builtin_amdgcn_readfirstlane(tt) * kpre_step_bytes<N, K>();
+#pragma unroll
+            for (int r = 0; r <= K; ++r)
+#pragma unroll
+                for (int m = 0; m < E; ++m)
+                    kv[r][m] = bsk_load(rk, lane_off, sb + 16u * (uint32_t)(((P * (K + 1) + r) * E + m) * T));
         }
     };
     // latency shape, LATPF: groups 0 .. NPF-1 of a step's key values are loaded one
@@ -765,7 +841,9 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
     // single CU streams ~50 GB/s of key at 3.9 us per step); the others across the
     // step's own forward FFT.  The next unskipped step comes from the table nxt (no
     // control flow around the prefetch, which keeps it after the MAC's last use).
-    constexpr int NPF = LAT ? (B > 1 ? FR_PAIR_PF : K == 1 ? FR_LAT_PF : FR_LAT_PF2) : 0;
+    // KP: the whole of the next unskipped step's products in that place, nothing loaded inside
+    // a step.
+    constexpr int NPF = KP ? 0 : LAT ? (B > 1 ? FR_PAIR_PF : K == 1 ? FR_LAT_PF : FR_LAT_PF2) : 0;
     constexpr bool LATPF = NPF > 0;
     // step t is skipped when every bootstrap's pair is (0, 0): X^0 acc - acc = 0.  The pair
     // shape runs a step that is zero for one bootstrap only: its factors c - 1 are exact
@@ -776,7 +854,7 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
         for (int b = 0; b < B; ++b) z |= abar[b * 1026 + 2 * t] | abar[b * 1026 + 2 * t + 1];
         return z == 0;
     };
-    if constexpr (LATPF) {
+    if constexpr (LATPF || KP) {
         for (int t = tid; t <= steps; t += NT) {
             int tt = t;
             while (tt < steps && idle(tt)) ++tt;
@@ -785,6 +863,7 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
         __syncthreads();
         const int t0 = __builtin_amdgcn_readfirstlane((int)nxt[0]);
         for (int gg = 0; gg < NPF; ++gg) load_ggsw(gg, t0 < steps ? t0 : 0);
+        load_kp(t0 < steps ? t0 : 0);
     }
     for (int t = 0; t < steps; ++t) {
         if (idle(t)) continue;  // (uniform branch)
@@ -798,9 +877,9 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
         // The pair shape (NPF = 1) loads its second group after forward phase FR_PAIR_LOAD and
         // its third after FR_PAIR_LOAD2 = 4, right before the MAC barrier (the pair's 64 live
         // transform values leave no room for a group across the whole transform).
-        constexpr int G_TOP = !LAT || B > 1 ? 3 : (NPF < 2 || K == 1) ? NPF : 3;
-        constexpr int G_L1 = !LAT ? 3 : B > 1 ? NPF : G_TOP + 1 < 3 ? G_TOP + 1 : 3;
-        constexpr int G_L2 = !LAT ? 3 : B > 1 ? (NPF + 1 < 3 ? NPF + 1 : 3) : G_TOP == 3 ? NPF : G_TOP + 2 < 3 ? G_TOP + 2 : 3;
+        constexpr int G_TOP = !LAT || KP || B > 1 ? 3 : (NPF < 2 || K == 1) ? NPF : 3;
+        constexpr int G_L1 = !LAT || KP ? 3 : B > 1 ? NPF : G_TOP + 1 < 3 ? G_TOP + 1 : 3;
+        constexpr int G_L2 = !LAT || KP ? 3 : B > 1 ? (NPF + 1 < 3 ? NPF + 1 : 3) : G_TOP == 3 ? NPF : G_TOP + 2 < 3 ? G_TOP + 2 : 3;
         constexpr int PH_L1 = B > 1 ? FR_PAIR_LOAD : FR_LAT_LOAD1;
         constexpr int PH_L2 = B > 1 ? FR_PAIR_LOAD2 : FR_LAT_LOAD2;
         // a group loaded after a forward phase needs that phase to exist: an out-of-range
@@ -825,19 +904,10 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
 #pragma unroll
                 for (int h = 0; h < 2; ++h)
 #pragma unroll
-                    for (int bb = 0; bb < NB; ++bb) {
-                        const uint32_t k = __umul24(h == 0 ? ei[b] : ej[b], Lb[bb]) & (2 * N - 1);
-                        if constexpr (!PSIQ) {  // psi^k, k < 2N, straight from the table
-                            const double2 c = psi[psi_slot((int)k)];
-                            bre[b][h][bb] = c.x;
-                            bim[b][h][bb] = c.y;
-                        } else {
-                            const double2 q = psi[psi_slot((int)(k & (N / 2 - 1)))];
-                            fft::psi_quadrant(q.x, q.y, k >> (LOG2N2 - 2), bre[b][h][bb], bim[b][h][bb]);
-                        }
-                    }
+                    for (int bb = 0; bb < NB; ++bb)
+                        key_psi_base<N, PSIQ>(psi, h == 0 ? ei[b] : ej[b], Lb[bb], bre[b][h][bb], bim[b][h][bb]);
         };
-        if constexpr (LAT && B == 1) psi_factors();
+        if constexpr (LAT && B == 1 && !KP) psi_factors();
         // 1. signed gadget digits, folded: x = d_j + i d_(j+M)
         double2 x[B][E];
 #pragma unroll
@@ -898,28 +968,19 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
                 double2 oth[K];
 #pragma unroll
                 for (int q = 0; q < K; ++q) oth[q] = orow_bl[q][b * BS + G::template at<XL>(G::template moff<LAST>(m))];
-                const uint32_t sm = ((m & 1) << 1) | ((m >> 1) & 1);  // brv2(m & 3)
-                double cr[3], ci[3];
-#pragma unroll
-                for (int h = 1; h < 3; ++h)  // uniform quarter turn
-                    slot_factor(bre[b][h - 1][m >> 2], bim[b][h - 1][m >> 2], h == 1 ? ei[b] : ej[b], sm, cr[h], ci[h]);
-                fft::cmul(cr[1], ci[1], cr[2], ci[2], cr[0], ci[0]);
-                // per row r: K_r = sum_g B_g[r][P] (c_g - 1), g ascending; then
-                // z = D_P K_P + sum_(r != P, ascending) D_r K_r  (own row first).
-                // 16 (K + 1) VALU per slot (k = 1: 32, against 36 for sum_g (c_g - 1) y_g)
+                // per row r: K_r = sum_g B_g[r][P] (c_g - 1) (key_products, or loaded: KP); then
+                // z = D_P K_P + sum_(r != P, ascending) D_r K_r  (own row first)
                 double kor, koi, kxr[K], kxi[K];
+                if constexpr (KP) {
+                    kor = kv[0][m].x, koi = kv[0][m].y;
 #pragma unroll
-                for (int gg = 0; gg < 3; ++gg) {
-                    const double c1r = cr[gg] - 1.0, c1i = ci[gg];
-                    const double2 Bo = LAT ? gv[gg][0][LAT ? m : 0] : Bc[gg][0];
-                    if (gg == 0) fft::cmul(Bo.x, Bo.y, c1r, c1i, kor, koi);
-                    else fft::cmac(Bo.x, Bo.y, c1r, c1i, kor, koi);
-#pragma unroll
-                    for (int q = 0; q < K; ++q) {
-                        const double2 Bx = LAT ? gv[gg][1 + q][LAT ? m : 0] : Bc[gg][1 + q];
-                        if (gg == 0) fft::cmul(Bx.x, Bx.y, c1r, c1i, kxr[q], kxi[q]);
-                        else fft::cmac(Bx.x, Bx.y, c1r, c1i, kxr[q], kxi[q]);
-                    }
+                    for (int q = 0; q < K; ++q) kxr[q] = kv[1 + q][m].x, kxi[q] = kv[1 + q][m].y;
+                } else {
+                    const uint32_t sm = ((m & 1) << 1) | ((m >> 1) & 1);  // brv2(m & 3)
+                    auto key_at = [&](int gg, int r) __attribute__((always_inline)) {
+                        return LAT ? gv[gg][r][LAT ? m : 0] : Bc[gg][r];
+                    };
+                    key_products<K>(bre[b], bim[b], m >> 2, ei[b], ej[b], sm, key_at, kor, koi, kxr, kxi);
                 }
                 double zr, zi;
                 fft::cmul(own.x, own.y, kor, koi, zr, zi);
@@ -938,10 +999,11 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
                     for (int r = 0; r <= K; ++r) Bc[gg][r] = Bn[gg][r];
             }
         }
-        if constexpr (LATPF) {  // the next step's key, into the registers the MAC just freed
+        if constexpr (LATPF || KP) {  // the next step's key, into the registers the MAC just freed
             const int tn = __builtin_amdgcn_readfirstlane((int)nxt[t + 1]);
             __builtin_amdgcn_sched_barrier(0);
             for (int gg = 0; gg < NPF; ++gg) load_ggsw(gg, tn < steps ? tn : t);
+            load_kp(tn < steps ? tn : t);
             __builtin_amdgcn_sched_barrier(0);
         }
         BR_STAMP(3);
@@ -982,6 +1044,81 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
         if (has[b])
             fbr_outputs<N, K, NT>(tid, accs + b * (K + 1) * N, gates[gb[b]], n_out[b], kind[b], wterms + b * 16 * MAX_OUT,
                                   wcnt + b * MAX_OUT, arena, slot_stride);
+}
+
+template <int N, int K, int E, bool LAT, int B = 1>
+__global__ void __launch_bounds__((fbr_threads<N, K, E>()), (fbr_min_waves<N, K, E, LAT>()))
+k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const DevGate* __restrict__ gates,
+                   int n_gates, const double2* __restrict__ bsk, const double2* __restrict__ tw_g,
+                   const double2* __restrict__ psi_g, const uint16_t* __restrict__ leaf_g, uint64_t* __restrict__ arena,
+                   int slot_stride) {
+    fbr_rotate<N, K, E, LAT, B, false>(ks, ks_stride, n, gates, n_gates, bsk, tw_g, psi_g, leaf_g, arena, slot_stride,
+                                       nullptr);
+}
+// The key-products variant of the latency shape, after k_key_products on the same stream.  A
+// kernel of its own name with the same <N, K, E, LAT, B>, so tools that read the shape off a
+// kernel's template arguments (tools/pmc_summary.py) read it as a latency-shape launch.
+template <int N, int K, int E, bool LAT, int B = 1>
+__global__ void __launch_bounds__((fbr_threads<N, K, E>()), (fbr_min_waves<N, K, E, LAT>()))
+k_blind_rotate_fft_kp(const uint64_t* __restrict__ ks, int ks_stride, int n, const DevGate* __restrict__ gates,
+                      int n_gates, const double2* __restrict__ tw_g, uint64_t* __restrict__ arena, int slot_stride,
+                      const double2* __restrict__ kpre) {
+    fbr_rotate<N, K, E, LAT, B, true>(ks, ks_stride, n, gates, n_gates, nullptr, tw_g, nullptr, nullptr, arena,
+                                      slot_stride, kpre);
+}
+
+// Producer of the key products (k = 1, E = 4): workgroup (t, P) holds step t's three GGSW
+// groups of polynomial P in registers (the lanes and loads of load_ggsw) and forms, for each
+// bootstrap b of the launch with a non-idle pair, the 2 E products of every lane by
+// key_psi_base and key_products -- the operations of the MAC, in its order -- and stores them
+// as kpre[b][t][P][own, other][m][lane]: each store of a wave, and each later load, 1 KB
+// contiguous.  The key is read once per launch whatever the batch; the steps are independent,
+// so the grid fills the CUs the latency shape leaves idle.
+template <int N>
+__global__ void __launch_bounds__(N / 8)
+k_key_products(const uint64_t* __restrict__ ks, int ks_stride, int n, int n_gates, const double2* __restrict__ bsk,
+               const double2* __restrict__ psi_g, double2* __restrict__ kpre) {
+    constexpr int K = 1, E = 4, M = N / 2, T = M / E;
+    using G = FGeo<M, E>;
+    static_assert(G::key_slot_matches_idx(), "the Fourier key's lane layout is the last-phase layout");
+    constexpr int LAST = G::NPH - 1, LOG2N2 = G::LOG + 2;
+    constexpr uint32_t GG = (uint32_t)(K + 1) * (K + 1) * M;
+    __shared__ __attribute__((aligned(16))) double2 psi[N / 2];  // quadrant table psi^k, k < N/2
+    const int tl = threadIdx.x, t = (int)blockIdx.x, P = (int)blockIdx.y;
+    const int steps = (n + 1) / 2;
+    for (int i = tl; i < N / 2; i += T) psi[psi_slot(i)] = psi_g[i];
+    const __amdgpu_buffer_rsrc_t rs = bsk_rsrc(bsk);
+    const uint32_t lane_off = 16u * (uint32_t)tl, sb = (uint32_t)t * (3u * GG * 16u);
+    double2 gv[3][K + 1][E];
+#pragma unroll
+    for (int gg = 0; gg < 3; ++gg)
+#pragma unroll
+        for (int m = 0; m < E; ++m) {
+            gv[gg][0][m] = bsk_load(rs, lane_off, sb + 16u * (gg * GG + (uint32_t)(P * (K + 1) + P) * M + (uint32_t)m * T));
+            gv[gg][1][m] = bsk_load(
+                rs, lane_off, sb + 16u * (gg * GG + (uint32_t)(other_row<K>(P, 0) * (K + 1) + P) * M + (uint32_t)m * T));
+        }
+    const uint32_t Lb = (1u + 4u * (__brev((uint32_t)G::template idx<LAST>(tl, 0)) >> (32 - G::LOG))) & (uint32_t)(M - 1);
+    __syncthreads();
+    for (int b = 0; b < n_gates; ++b) {
+        const uint64_t* in = ks + (size_t)b * ks_stride;
+        const uint32_t ei = (uint16_t)mod_switch(in[2 * t], LOG2N2);
+        const uint32_t ej = 2 * t + 1 < n ? (uint16_t)mod_switch(in[2 * t + 1], LOG2N2) : 0u;  // (an odd n: padded)
+        if ((ei | ej) == 0) continue;  // an idle pair: the rotation skips the step
+        double br[2][1], bi[2][1];
+        key_psi_base<N, true>(psi, ei, Lb, br[0][0], bi[0][0]);
+        key_psi_base<N, true>(psi, ej, Lb, br[1][0], bi[1][0]);
+        double2* out = kpre + (((size_t)b * steps + t) * (K + 1) + P) * ((K + 1) * M) + tl;
+#pragma unroll
+        for (int m = 0; m < E; ++m) {
+            const uint32_t sm = ((m & 1) << 1) | ((m >> 1) & 1);  // brv2(m & 3)
+            double kor, koi, kxr[K], kxi[K];
+            key_products<K>(br, bi, 0, ei, ej, sm, [&](int gg, int r) __attribute__((always_inline)) { return gv[gg][r][m]; },
+                            kor, koi, kxr, kxi);
+            out[m * T] = make_double2(kor, koi);
+            out[(E + m) * T] = make_double2(kxr[0], kxi[0]);
+        }
+    }
 }
 
 // The pair shape's one instantiation is compiled in its own translation unit,
@@ -1201,7 +1338,8 @@ void Device::init_fft() {
     if (const char* ev = std::getenv("FR_FFT_SMALL_BATCH")) fft_small_ = (size_t)std::atol(ev);
     if (const char* ev = std::getenv("FR_FFT_PAIR_BATCH")) fft_pair_ = (size_t)std::atol(ev);
     if (const char* ev = std::getenv("FR_FFT_DUAL")) fft_dual_ = std::atoi(ev) != 0;
-    if (p_.k != 1) fft_pair_ = 0;
+    if (const char* ev = std::getenv("FR_FFT_KPRE_BATCH")) fft_kpre_ = (size_t)std::atol(ev);
+    if (p_.k != 1) fft_pair_ = 0, fft_kpre_ = 0;
     if (!fft_supported(p_.k, p_.N, fft_e_))
         throw Error(FR_ERR_INVALID, "device: FFT ring needs (k, N, E) in {(1, 2048, 4), (2, 1024, 4 or 8)}");
     fft_dispatch(p_, [&](auto nc, auto kc) {
@@ -1210,6 +1348,10 @@ void Device::init_fft() {
         fft_attr<N, K, 4, false>();
         if constexpr (K == 1) {
             fft_attr<N, K, 4, true, 2>();
+            static_assert(fbr_smem_bytes<N, K, 4, true, 1, true>() <= 160 * 1024, "LDS per workgroup of the shape");
+            HIP_CHECK(hipFuncSetAttribute((const void*)k_blind_rotate_fft_kp<N, K, 4, true, 1>,
+                                          hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)fbr_smem_bytes<N, K, 4, true, 1, true>()));
             static_assert(fbr_dual_smem_bytes<N>() <= 80 * 1024, "dual shape: two workgroups per CU");
             HIP_CHECK(hipFuncSetAttribute((const void*)k_blind_rotate_fft_dual<N>,
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)fbr_dual_smem_bytes<N>()));
@@ -1273,8 +1415,30 @@ void Device::launch_br_fft(const DevGate* d_gates, const uint64_t* d_ks, size_t 
         using I4 = std::integral_constant<int, 4>;
         using I8 = std::integral_constant<int, 8>;
         using B1 = std::integral_constant<int, 1>;
-        // small launches (at most one bootstrap per CU): the latency shape
-        if (n <= fft_small_) go(I4{}, std::true_type{}, B1{});
+        // small launches (at most one bootstrap per CU): the latency shape; the smallest
+        // (k = 1, at most fft_kpre_) as the producer of their key products, then the variant that
+        // loads them, in stream order: the pair of kernels lies between ev_start and ev_stop, so
+        // the producer's time counts as blind rotation
+        if (n <= fft_small_ && n <= fft_kpre_ && K == 1) {
+            if constexpr (K == 1) {
+                const int steps = (p_.n + 1) / 2;
+                const size_t per = (size_t)steps * (kpre_step_bytes<N, K>() / 8);  // doubles per bootstrap
+                gpu::DevBuf<double>& kpre = cur().kpre;
+                if (kpre.size() < n * per) {
+                    HIP_CHECK(hipStreamSynchronize(s));  // the lane's queued rotations read the old scratch
+                    kpre.alloc(n * per);
+                }
+                hipExtLaunchKernelGGL(k_key_products<N>, dim3((unsigned)steps, K + 1), dim3(N / 8), 0, s, ev_start,
+                                      nullptr, 0, d_ks, p_.ks_stride(), p_.n, (int)n,
+                                      (const double2*)d_fbsk_[fbsk_index(4)].get(), (const double2*)d_fqt_.get(),
+                                      (double2*)kpre.get());
+                hipExtLaunchKernelGGL((k_blind_rotate_fft_kp<N, K, 4, true, 1>), dim3((unsigned)n),
+                                      dim3(fbr_threads<N, K, 4>()), (uint32_t)fbr_smem_bytes<N, K, 4, true, 1, true>(), s,
+                                      nullptr, ev_stop, 0, d_ks, p_.ks_stride(), p_.n, d_gates, (int)n,
+                                      (const double2*)d_ftw_.get(), d_arena_.get(), p_.slot_stride(),
+                                      (const double2*)kpre.get());
+            }
+        } else if (n <= fft_small_) go(I4{}, std::true_type{}, B1{});
         else if (n <= fft_pair_ && K == 1 && fft_dual_) {
             if constexpr (K == 1) launch(k_blind_rotate_fft_dual<N>, n, N / 8, fbr_dual_smem_bytes<N>(), 4);
         } else if (n <= fft_pair_) go(I4{}, std::true_type{}, std::integral_constant<int, 2>{});  // (k = 1)

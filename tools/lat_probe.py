@@ -1,5 +1,7 @@
 """Blind-rotation launch times for A/B runs of library variants (FHEREGEX_LIB=...):
-median over R repetitions of dev_bench_pbs at the given batch sizes.
+median over R repetitions of dev_bench_pbs at the given batch sizes: the blind rotation's
+launch time (between the keyswitch's end and its own, the key-products producer included), and
+under "total" the keyswitch and the rotation together.
 Usage: python3 tools/lat_probe.py [reps] [sizes...]"""
 import os
 import statistics
@@ -20,9 +22,11 @@ if os.environ.get("FR_LAT_PROBE_HOSTKEY"):  # keys through the host upload path 
     ctx.set_keygen(F.KEYGEN_HOST)
 ctx.gen_server_key(42)
 hs = ctx.upload_bool(ctx.encrypt_blocks([i % 16 for i in range(64)], seed=3))
-out = {}
+out, total = {}, {}
 for cnt in sizes:
     batch = [hs[i % len(hs)] for i in range(cnt)]
     ctx.dev_bench_pbs(batch, 1)  # warm-up
-    out[cnt] = round(statistics.median(ctx.dev_bench_pbs(batch, 1)[0] for _ in range(reps)), 4)
-print(os.path.basename(os.environ.get("FHEREGEX_LIB", "libfheregex.so")), out, flush=True)
+    runs = [ctx.dev_bench_pbs(batch, 1) for _ in range(reps)]
+    out[cnt] = round(statistics.median(r[0] for r in runs), 4)
+    total[cnt] = round(statistics.median(r[1] for r in runs), 4)
+print(os.path.basename(os.environ.get("FHEREGEX_LIB", "libfheregex.so")), out, "total", total, flush=True)
