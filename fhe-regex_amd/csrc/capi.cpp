@@ -635,6 +635,12 @@ int fr_device_timers_key_load(fr_ctx* ctx, double* ms) {
         std::memcpy(ms, ctx->device().key_load_ms(), 5 * sizeof(double));
     })
 }
+int fr_device_timers_packing_key_load(fr_ctx* ctx, double* ms) {
+    FR_TRY({
+        NEED(ctx && ms);
+        std::memcpy(ms, ctx->device().pk_load_ms(), 3 * sizeof(double));
+    })
+}
 int fr_device_timers_content(fr_ctx* ctx, double* ms) {
     FR_TRY({
         NEED(ctx && ms);

@@ -252,24 +252,32 @@ int fr_load_server_key_compact(fr_ctx* ctx, const uint8_t* blob, size_t len) {
 
 // ---- packing key (keys.h): optional, beside the server key; nothing else depends on it
 
-static void gen_packing_key_with(fr_ctx* ctx, const RngKey& key) {
+// compact: the compact form (keys.h) -- the masks under the public mask key, which is all a
+// kernel sees; the noise under `key` on the host either way
+static void gen_packing_key_with(fr_ctx* ctx, const RngKey& key, bool compact = false) {
     const bool on_dev = ctx->dev && ctx->keygen != FR_KEYGEN_HOST;
+    RngKey mk{};  // public; the secret key is never copied
+    if (compact) mk = derive_mask_key(key);
+    const RngKey& mask = compact ? mk : key;
     ctx->has_pk = false;
+    ctx->pk_compact = false;
     if (on_dev) {
         ctx->pksk.clear();
         ctx->pksk.shrink_to_fit();
-        ctx->dev->gen_packing_key(ctx->ck, key);
+        ctx->dev->gen_packing_key(ctx->ck, mask, key, compact);
     } else {
         // the whole key through the row generator: kN^2 / 2 additions per row on every host
         // thread, a few seconds in all
         ctx->pksk.resize(pk_len(ctx->p));
-        gen_packing_rows(ctx->p, ctx->ck, key, 0, pk_rows(ctx->p), ctx->pksk.data());
+        gen_packing_rows(ctx->p, ctx->ck, mask, key, compact, 0, pk_rows(ctx->p), ctx->pksk.data());
         if (ctx->dev) {
             ctx->dev->upload_packing_key(ctx->pksk.data());
             ctx->pksk.clear();
             ctx->pksk.shrink_to_fit();
         }
     }
+    if (compact) ctx->pk_mask_key = mask;
+    ctx->pk_compact = compact;
     ctx->has_pk = true;
 }
 // checked before a key is drawn
@@ -295,13 +303,39 @@ int fr_gen_packing_key_keyed(fr_ctx* ctx, const uint8_t* key32) {
     })
 }
 
-int fr_gen_packing_rows_keyed(fr_ctx* ctx, const uint8_t* key32, size_t row_lo, size_t row_hi, uint64_t* out) {
+int fr_gen_packing_key_compact(fr_ctx* ctx, uint64_t seed) {
     FR_TRY({
-        NEED(ctx && row_lo <= row_hi && row_hi <= pk_rows(ctx->p) && (out || row_lo == row_hi));
-        if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
-        ScopedKey key(key32);
-        gen_packing_rows(ctx->p, ctx->ck, key.k, row_lo, row_hi, out);
+        check_gen_packing_key(ctx);
+        ScopedKey key(seed);
+        gen_packing_key_with(ctx, key.k, true);
     })
+}
+
+int fr_gen_packing_key_compact_keyed(fr_ctx* ctx, const uint8_t* key32) {
+    FR_TRY({
+        check_gen_packing_key(ctx);
+        ScopedKey key(key32);
+        gen_packing_key_with(ctx, key.k, true);
+    })
+}
+
+static void gen_packing_rows_with(fr_ctx* ctx, const uint8_t* key32, bool compact, size_t row_lo, size_t row_hi,
+                                  uint64_t* out) {
+    NEED(ctx && row_lo <= row_hi && row_hi <= pk_rows(ctx->p) && (out || row_lo == row_hi));
+    if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
+    ScopedKey key(key32);
+    RngKey mk{};
+    if (compact) mk = derive_mask_key(key.k);
+    const RngKey& mask = compact ? mk : key.k;
+    gen_packing_rows(ctx->p, ctx->ck, mask, key.k, compact, row_lo, row_hi, out);
+}
+
+int fr_gen_packing_rows_keyed(fr_ctx* ctx, const uint8_t* key32, size_t row_lo, size_t row_hi, uint64_t* out) {
+    FR_TRY(gen_packing_rows_with(ctx, key32, false, row_lo, row_hi, out))
+}
+
+int fr_gen_packing_rows_compact_keyed(fr_ctx* ctx, const uint8_t* key32, size_t row_lo, size_t row_hi, uint64_t* out) {
+    FR_TRY(gen_packing_rows_with(ctx, key32, true, row_lo, row_hi, out))
 }
 
 int fr_packing_key_size(fr_ctx* ctx, size_t* bytes) {
@@ -339,12 +373,62 @@ int fr_load_packing_key(fr_ctx* ctx, const uint8_t* blob, size_t len) {
         check_pk_blob(ctx->p, blob, len);
         if (ctx->dev) {
             ctx->has_pk = false;
+            ctx->pk_compact = false;
             ctx->dev->upload_packing_key(blob + PK_HEADER);  // drains every lane first
         } else {
             std::vector<uint64_t> rows(pk_len(ctx->p));
             std::memcpy(rows.data(), blob + PK_HEADER, 8 * rows.size());
             ctx->pksk = std::move(rows);
         }
+        ctx->pk_compact = false;
+        ctx->has_pk = true;
+    })
+}
+
+// ---- compact packing key (keys.h): the mask key and the 40-bit bodies travel
+
+int fr_packing_key_compact_size(fr_ctx* ctx, size_t* bytes) {
+    FR_TRY({
+        NEED(ctx && bytes);
+        *bytes = pk_compact_size(ctx->p);
+    })
+}
+
+int fr_export_packing_key_compact(fr_ctx* ctx, uint8_t* buf, size_t cap, size_t* written) {
+    FR_TRY({
+        NEED(ctx && written);
+        if (!ctx->has_pk) throw Error(FR_ERR_INVALID, "no packing key (fr_gen_packing_key, fr_load_packing_key)");
+        if (!ctx->pk_compact)
+            throw Error(FR_ERR_INVALID, "the installed packing key was not generated in compact form: its masks are "
+                                        "not expandable from a mask key (fr_gen_packing_key_compact)");
+        const size_t need = pk_compact_size(ctx->p);
+        *written = need;
+        if (!buf) return FR_OK;  // size query
+        NEED(cap >= need);
+        write_pk_compact_header(ctx->p, ctx->pk_mask_key, buf);
+        // the device gathers the planes from its resident rows: 5 of every 8 (k+1) bytes come back
+        if (ctx->dev) ctx->dev->download_packing_key_compact(buf + PKC_HEADER);
+        else pack_pk_compact(ctx->p, ctx->pksk.data(), buf + PKC_HEADER);
+    })
+}
+
+int fr_load_packing_key_compact(fr_ctx* ctx, const uint8_t* blob, size_t len) {
+    FR_TRY({
+        NEED(ctx && blob);
+        // the whole header is checked before the installed key is touched or anything is allocated
+        const RngKey mk = check_pk_compact(ctx->p, blob, len);
+        if (ctx->dev) {
+            ctx->has_pk = false;
+            ctx->pk_compact = false;
+            ctx->dev->load_packing_key_compact(mk, blob + PKC_HEADER);  // drains every lane first
+        } else {
+            std::vector<uint64_t> rows;
+            RngKey m;
+            expand_pk_compact(ctx->p, blob, len, rows, m);
+            ctx->pksk = std::move(rows);
+        }
+        ctx->pk_mask_key = mk;
+        ctx->pk_compact = true;
         ctx->has_pk = true;
     })
 }

@@ -82,6 +82,8 @@ struct fr_ctx {
     // stay there for export); a host-only context keeps the rows here
     std::vector<uint64_t> pksk;
     bool has_pk = false;
+    bool pk_compact = false;   // the packing key is in compact form (keys.h): pk_mask_key expands its masks
+    fr::RngKey pk_mask_key{};  // public by design
     bool multi_value = true;  // merge same-input small-norm LUTs into one blind rotation
     bool async_match = true;  // has_match returns once its launches are enqueued (fr_set_async)
     uint64_t next_lane = 0;   // fr_set_lanes: consecutive asynchronous matches round-robin over the lanes

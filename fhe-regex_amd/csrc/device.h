@@ -78,16 +78,28 @@ class Device {
     // gen_server_key.  The torus keys stay on the device for download_server_key.
     void load_server_key_compact(const RngKey& mask_key, const uint8_t* bodies);
     // stages of the last load_server_key_compact under fr_set_profiling, HIP events, ms:
-    // H2D copy, k_expand_ksk, k_expand_bsk, KSK limbs, k_bsk_fourier
+    // H2D copy, k_expand_ksk, k_expand_rows (the BSK), KSK limbs, k_bsk_fourier
     const double* key_load_ms() const { return key_load_ms_; }
     void download_server_key(uint64_t* ksk, size_t ksk_len, uint64_t* bsk, size_t bsk_len);
     // Packing key (keys.h: pk_rows rows of (k+1) N words).  Generated on the device word for
     // word as gen_packing_rows does on the host, or uploaded (little-endian u64 rows, any
     // alignment); both keep the torus rows on the device for download_packing_key and build
     // the byte limbs pack_bools multiplies by.  All three wait for the device.
-    void gen_packing_key(const ClientKey& ck, const RngKey& key);
+    // gen_packing_key: the masks under mask_key, which is the kernel's argument, the noise
+    // drawn on the host under noise_key (the standard form: one key for both); compact: the
+    // compact form (keys.h), mask_key the public mask key and the bodies rounded to 40 bits
+    void gen_packing_key(const ClientKey& ck, const RngKey& mask_key, const RngKey& noise_key, bool compact = false);
     void upload_packing_key(const void* rows);
     void download_packing_key(uint64_t* rows);
+    // install a compact packing key: `planes` are the blob's high plane u32[3kN][N] then low
+    // plane u8[3kN][N] (little endian, any alignment); one H2D copy, one kernel that expands
+    // the masks from mask_key and rebuilds the bodies, then the byte limbs
+    void load_packing_key_compact(const RngKey& mask_key, const uint8_t* planes);
+    // the two planes gathered on the device from the resident rows (pk_compact_planes bytes)
+    void download_packing_key_compact(uint8_t* planes);
+    // stages of the last load_packing_key_compact under fr_set_profiling, HIP events, ms:
+    // H2D copy, expansion, byte limbs
+    const double* pk_load_ms() const { return pk_load_ms_; }
     bool has_packing_key() const { return bool(pksk_); }
     // parity hook: column col < (k+1) N of the byte-limb operand recombined into its 3 kN torus words
     void packing_limb_column(int col, uint64_t* out_host);
@@ -281,6 +293,7 @@ class Device {
                        hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
     void build_fourier_bsk();  // keygen.hip: d_fbsk_ (every lane layout in use) from d_tbsk_
     double key_load_ms_[5] = {0, 0, 0, 0, 0};
+    double pk_load_ms_[3] = {0, 0, 0};
     // expand_to_slots: the bodies and the slot list of a call, one copy (lane 0)
     gpu::StagingRing<uint8_t> xstage_;
     double expand_ms_ = 0;

@@ -17,8 +17,11 @@
 //                  (keys.h): rows r < k carry the gadget in the body, -m_w g S_r
 //   k_expand_ksk   compact key load, one wave per KSK row: the mask words from ChaCha
 //                  blocks of the public mask key, the body from the uploaded blob
-//   k_expand_bsk   the same for one GGSW row (w, r) per workgroup: k mask polynomials
-//                  and the body row.  Both are pure store streams, 16 bytes a store
+//   k_expand_rows  the same for one GLWE row per workgroup: k mask polynomials and the body
+//                  -- a GGSW row (w, r) of the BSK with the blob's u64 body, or a row of a
+//                  compact packing key with its 40-bit body from the two planes.  Both are
+//                  pure store streams, 16 bytes a store
+//   k_gather_planes40  the planes of a compact packing key back from its resident rows
 //   k_expand_blocks  compact content, one workgroup per LWE block: the mask words from
 //                  ChaCha blocks of the blob's mask key straight into the block's arena
 //                  slot, the body from the staged bodies; the same 16-byte store stream
@@ -162,8 +165,10 @@ __global__ void __launch_bounds__(256) k_gen_bsk(RngKey key, int k,const uint64_
 
 // one row 3 i + l of the packing key (keys.h): k mask polynomials from STREAM_PKSK_MASK, body =
 // sum_j A_j S_j + noise, + s_big[i] 2^(64 - PK_BASE_LOG (l + 1)) on coefficient 0.  grid = rows of
-// (k + 1) N words, so every store is inside the key
-template <int N>
+// (k + 1) N words, so every store is inside the key.  COMPACT (keys.h): `key` is the public mask
+// key (the message sits in the body, so no mask word carries a secret) and the epilogue rounds
+// the body to its top 40 bits, pk_round40(v) << 24
+template <int N, bool COMPACT>
 __global__ void __launch_bounds__(256) k_gen_pksk(RngKey key, int k, const uint64_t* __restrict__ s_big,
                                                   const int32_t* __restrict__ noise, uint64_t* __restrict__ pksk) {
     constexpr int PER = N / 256;
@@ -183,6 +188,7 @@ __global__ void __launch_bounds__(256) k_gen_pksk(RngKey key, int k, const uint6
         const int t = tid + 256 * q;
         uint64_t v = acc[q] + (uint64_t)(int64_t)e[t];
         if (t == 0) v += (s_big[i] & 1) << (64 - PK_BASE_LOG * (l + 1));
+        if (COMPACT) v = ((v + ((uint64_t)1 << (PKC_DROP_BITS - 1))) >> PKC_DROP_BITS) << PKC_DROP_BITS;  // pk_round40
         row[(size_t)k * N + t] = v;
     }
 }
@@ -232,26 +238,75 @@ __global__ void __launch_bounds__(64) k_expand_ksk(RngKey mask_key, int n, const
     if (lane == 0) o[n] = body[row];
 }
 
-// one GGSW row (w, r) of the torus BSK: k mask polynomials (kN / 8 whole ChaCha blocks,
-// 64 aligned bytes each) and the body polynomial from the blob; grid = W (k + 1) rows of
-// (k + 1) N words, so every store is inside bsk_len()
+// Where the body polynomial of an expanded row comes from: row(gr, dst) writes the N words of
+// row gr's body to dst (16-byte aligned) with 16-byte stores, 256 threads.
+// the compact server key's blob: the u64 bodies as they are
 template <int N>
-__global__ void __launch_bounds__(256) k_expand_bsk(RngKey mask_key, int k, const uint64_t* __restrict__ body,
-                                                    uint64_t* __restrict__ bsk) {
+struct BodyWords {
+    const uint64_t* body;  // [rows][N], 16-byte aligned
+    __device__ __forceinline__ void row(size_t gr, uint64_t* __restrict__ dst) const {
+        const ulonglong2* src = reinterpret_cast<const ulonglong2*>(body + gr * N);
+        ulonglong2* d = reinterpret_cast<ulonglong2*>(dst);
+        for (int x = threadIdx.x; x < N / 2; x += 256) d[x] = src[x];
+    }
+};
+// the compact packing key's planes (keys.h): word t = b40 << 24, b40 = hi[t] << 8 | lo[t]; four
+// coefficients per thread step, 16 bytes of the high plane and 4 of the low into two stores
+template <int N>
+struct BodyPlanes40 {
+    const uint32_t* hi;  // [rows][N], 16-byte aligned
+    const uint8_t* lo;   // [rows][N], 4-byte aligned
+    __device__ __forceinline__ void row(size_t gr, uint64_t* __restrict__ dst) const {
+        const uint4* h4 = reinterpret_cast<const uint4*>(hi + gr * N);
+        const uint32_t* l4 = reinterpret_cast<const uint32_t*>(lo + gr * N);
+        ulonglong2* d = reinterpret_cast<ulonglong2*>(dst);
+        for (int x = threadIdx.x; x < N / 4; x += 256) {
+            const uint4 h = h4[x];
+            const uint32_t l = l4[x];
+            auto word = [](uint32_t hw, uint32_t lb) { return ((uint64_t)hw << 32) | ((uint64_t)lb << PKC_DROP_BITS); };
+            d[2 * x] = make_ulonglong2(word(h.x, l & 0xFF), word(h.y, (l >> 8) & 0xFF));
+            d[2 * x + 1] = make_ulonglong2(word(h.z, (l >> 16) & 0xFF), word(h.w, l >> 24));
+        }
+    }
+};
+
+// one GLWE row of a key of rows [k mask polynomials][body] -- a GGSW row (w, r) of the torus
+// BSK (STREAM_BSK_MASK, BodyWords) or a row of the packing key (STREAM_PKSK_MASK,
+// BodyPlanes40): the masks are the kN / 8 whole ChaCha blocks from u64 number gr k N of
+// MASK_STREAM under the mask key, 64 aligned bytes each, the body comes from `body`; grid = rows of
+// (k + 1) N words, so every store is inside the key
+template <int N, uint64_t MASK_STREAM, class Body>
+__global__ void __launch_bounds__(256) k_expand_rows(RngKey mask_key, int k, Body body, uint64_t* __restrict__ key) {
     const int tid = threadIdx.x;
-    const size_t gr = blockIdx.x;  // w * (k + 1) + r
-    uint64_t* row = bsk + gr * (size_t)(k + 1) * N;
+    const size_t gr = blockIdx.x;  // BSK: w * (k + 1) + r
+    uint64_t* row = key + gr * (size_t)(k + 1) * N;
     const uint64_t base = gr * (uint64_t)k * N;  // mask polynomial j starts at base + j N
     for (int b = tid; b < k * (N / 8); b += 256) {
         uint32_t wd[16];
-        chacha_block(mask_key, STREAM_BSK_MASK, (base >> 3) + b, wd);
+        chacha_block(mask_key, MASK_STREAM, (base >> 3) + b, wd);
         ulonglong2* o = reinterpret_cast<ulonglong2*>(row + 8 * (size_t)b);
 #pragma unroll
         for (int q = 0; q < 4; ++q) o[q] = make_ulonglong2(chacha_u64(wd, 2 * q), chacha_u64(wd, 2 * q + 1));
     }
-    const ulonglong2* src = reinterpret_cast<const ulonglong2*>(body + gr * N);
-    ulonglong2* dst = reinterpret_cast<ulonglong2*>(row + (size_t)k * N);
-    for (int x = tid; x < N / 2; x += 256) dst[x] = src[x];
+    body.row(gr, row + (size_t)k * N);
+}
+
+// the two planes of a compact packing key from its resident rows (export): one workgroup per
+// row, four body words per thread step into 16 bytes of the high plane and 4 of the low; grid
+// = rows, so every store is inside the planes' 5 rows N bytes
+template <int N>
+__global__ void __launch_bounds__(256) k_gather_planes40(int k, const uint64_t* __restrict__ key,
+                                                         uint32_t* __restrict__ hi, uint8_t* __restrict__ lo) {
+    const size_t gr = blockIdx.x;
+    const ulonglong2* src = reinterpret_cast<const ulonglong2*>(key + (gr * (size_t)(k + 1) + k) * N);
+    uint4* h4 = reinterpret_cast<uint4*>(hi + gr * N);
+    uint32_t* l4 = reinterpret_cast<uint32_t*>(lo + gr * N);
+    for (int x = threadIdx.x; x < N / 4; x += 256) {
+        const ulonglong2 a = src[2 * x], b = src[2 * x + 1];
+        auto low = [](uint64_t v) { return (uint32_t)(v >> PKC_DROP_BITS) & 0xFF; };
+        h4[x] = make_uint4((uint32_t)(a.x >> 32), (uint32_t)(a.y >> 32), (uint32_t)(b.x >> 32), (uint32_t)(b.y >> 32));
+        l4[x] = low(a.x) | (low(a.y) << 8) | (low(b.x) << 16) | (low(b.y) << 24);
+    }
 }
 
 // fold + forward FFT + fourier_key_scale of one polynomial, written in the lane layouts of
@@ -349,7 +404,7 @@ void Device::encrypt_to_slots(const ClientKey& ck, const uint8_t* msgs, size_t c
 // workgroup per LWE.  Mask word t of block q is u64 number (first_block + q) kN + t of
 // STREAM_ENC_MASK under the public mask key (k_encrypt_blocks's indices; kN % 8 == 0: whole
 // ChaCha blocks); thread t owns ChaCha block (first_block + q) kN / 8 + t, 64 aligned bytes
-// of the slot (slot stride: a multiple of 64 B), stored 16 bytes at a time as k_expand_bsk
+// of the slot (slot stride: a multiple of 64 B), stored 16 bytes at a time as k_expand_rows
 // does.  The body word comes from the staged bodies.  Every store is inside the slot's
 // big + 1 words; the host checked slots[q] < next_slot_.
 __global__ void __launch_bounds__(256) k_expand_blocks(RngKey mask_key, int big, uint64_t first_block,
@@ -501,8 +556,12 @@ void Device::load_server_key_compact(const RngKey& mask_key, const uint8_t* bodi
     k_expand_ksk<<<(unsigned)rows, 64, 0, s>>>(mask_key, n, d_body.get(), ksk_.rows.get());
     HIP_CHECK(hipGetLastError());
     timer.mark(2);
-    if (N == 2048) k_expand_bsk<2048><<<(unsigned)brows, 256, 0, s>>>(mask_key, p_.k, d_body.get() + rows, d_tbsk_.get());
-    else k_expand_bsk<1024><<<(unsigned)brows, 256, 0, s>>>(mask_key, p_.k, d_body.get() + rows, d_tbsk_.get());
+    if (N == 2048)
+        k_expand_rows<2048, STREAM_BSK_MASK><<<(unsigned)brows, 256, 0, s>>>(
+            mask_key, p_.k, BodyWords<2048>{d_body.get() + rows}, d_tbsk_.get());
+    else
+        k_expand_rows<1024, STREAM_BSK_MASK><<<(unsigned)brows, 256, 0, s>>>(
+            mask_key, p_.k, BodyWords<1024>{d_body.get() + rows}, d_tbsk_.get());
     HIP_CHECK(hipGetLastError());
     timer.mark(3);
     build_limbs(ksk_);
@@ -516,26 +575,81 @@ void Device::load_server_key_compact(const RngKey& mask_key, const uint8_t* bodi
 
 // Packing key on the device: the torus rows stay for download_packing_key (as the torus BSK
 // does), the byte limbs are the MFMA operand of pack_bools
-void Device::gen_packing_key(const ClientKey& ck, const RngKey& key) {
+void Device::gen_packing_key(const ClientKey& ck, const RngKey& mask_key, const RngKey& noise_key, bool compact) {
     if (!((p_.N == 2048 && p_.k == 1) || (p_.N == 1024 && p_.k == 2)))
         throw Error(FR_ERR_INVALID, "device packing keygen: (k, N) in {(1, 2048), (2, 1024)}");
     if (ck.s_big.size() != (size_t)p_.big()) throw Error(FR_ERR_INVALID, "device packing keygen: key size");
     const size_t rows = pk_rows(p_);
     Replacing key_guard([this] { drop_packing_key(); });
+    // host: the noise under the secret key; the kernel sees the mask key alone
     std::vector<int32_t> noise;
-    gen_pksk_noise(p_, key, noise);
+    gen_pksk_noise(p_, noise_key, noise);
     const hipStream_t s = cur().stream.get();
     gpu::DevBuf<uint64_t> d_sb(ck.s_big.size());
     gpu::DevBuf<int32_t> d_n(noise.size());
     HIP_CHECK(hipMemcpyAsync(d_sb.get(), ck.s_big.data(), 8 * ck.s_big.size(), hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(d_n.get(), noise.data(), 4 * noise.size(), hipMemcpyHostToDevice, s));
     pksk_.alloc_rows((int)rows, (int)pk_row_words(p_));
-    if (p_.N == 2048) k_gen_pksk<2048><<<(unsigned)rows, 256, 0, s>>>(key, p_.k, d_sb.get(), d_n.get(), pksk_.rows.get());
-    else k_gen_pksk<1024><<<(unsigned)rows, 256, 0, s>>>(key, p_.k, d_sb.get(), d_n.get(), pksk_.rows.get());
+    const unsigned grid = (unsigned)rows;
+    const uint64_t* sb = d_sb.get();
+    const int32_t* e = d_n.get();
+    uint64_t* out = pksk_.rows.get();
+    if (p_.N == 2048 && !compact) k_gen_pksk<2048, false><<<grid, 256, 0, s>>>(mask_key, p_.k, sb, e, out);
+    else if (p_.N == 2048) k_gen_pksk<2048, true><<<grid, 256, 0, s>>>(mask_key, p_.k, sb, e, out);
+    else if (!compact) k_gen_pksk<1024, false><<<grid, 256, 0, s>>>(mask_key, p_.k, sb, e, out);
+    else k_gen_pksk<1024, true><<<grid, 256, 0, s>>>(mask_key, p_.k, sb, e, out);
     HIP_CHECK(hipGetLastError());
     build_limbs(pksk_);
     HIP_CHECK(hipStreamSynchronize(s));  // the temporaries go once the kernels have run
     key_guard.dismiss();
+}
+
+static void need_pk_compact_point(const Params& p, const char* what) {
+    if (p.N != 2048 && p.N != 1024) throw Error(FR_ERR_INVALID, std::string(what) + ": N in {1024, 2048}");
+}
+
+void Device::load_packing_key_compact(const RngKey& mask_key, const uint8_t* planes) {
+    need_pk_compact_point(p_, "device load of a compact packing key");
+    const size_t rows = pk_rows(p_), N = (size_t)p_.N, bytes = pk_compact_planes(p_);
+    Replacing key_guard([this] { drop_packing_key(); });
+    const hipStream_t s = cur().stream.get();
+    // hipMalloc's alignment; the low plane follows 4 rows N bytes of the high one: 16-byte aligned
+    gpu::DevBuf<uint8_t> d_planes(bytes);
+    StageTimer<3> timer(profiling_ != 0, s);
+    pksk_.alloc_rows((int)rows, (int)pk_row_words(p_));
+    timer.mark(0);
+    HIP_CHECK(hipMemcpyAsync(d_planes.get(), planes, bytes, hipMemcpyHostToDevice, s));
+    timer.mark(1);
+    const uint32_t* hi = reinterpret_cast<const uint32_t*>(d_planes.get());
+    const uint8_t* lo = d_planes.get() + 4 * rows * N;
+    if (N == 2048)
+        k_expand_rows<2048, STREAM_PKSK_MASK><<<(unsigned)rows, 256, 0, s>>>(mask_key, p_.k, BodyPlanes40<2048>{hi, lo},
+                                                                            pksk_.rows.get());
+    else
+        k_expand_rows<1024, STREAM_PKSK_MASK><<<(unsigned)rows, 256, 0, s>>>(mask_key, p_.k, BodyPlanes40<1024>{hi, lo},
+                                                                            pksk_.rows.get());
+    HIP_CHECK(hipGetLastError());
+    timer.mark(2);
+    build_limbs(pksk_);
+    timer.mark(3);
+    HIP_CHECK(hipStreamSynchronize(s));
+    timer.read(pk_load_ms_);
+    key_guard.dismiss();
+}
+
+void Device::download_packing_key_compact(uint8_t* planes) {
+    if (!has_packing_key()) throw Error(FR_ERR_INVALID, "no packing key on the device");
+    need_pk_compact_point(p_, "device export of a compact packing key");
+    const size_t rows = pk_rows(p_), N = (size_t)p_.N, bytes = pk_compact_planes(p_);
+    const hipStream_t s = STREAM;
+    gpu::DevBuf<uint8_t> d_planes(bytes);
+    uint32_t* hi = reinterpret_cast<uint32_t*>(d_planes.get());
+    uint8_t* lo = d_planes.get() + 4 * rows * N;
+    if (N == 2048) k_gather_planes40<2048><<<(unsigned)rows, 256, 0, s>>>(p_.k, pksk_.rows.get(), hi, lo);
+    else k_gather_planes40<1024><<<(unsigned)rows, 256, 0, s>>>(p_.k, pksk_.rows.get(), hi, lo);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(planes, d_planes.get(), bytes, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));  // the staging buffer goes once the copy has run
 }
 
 void Device::upload_packing_key(const void* rows) {

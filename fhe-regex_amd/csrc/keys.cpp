@@ -657,12 +657,17 @@ static void add_rotated(uint64_t* dst, const uint64_t* src, int u, int N) {
 
 void gen_packing_rows(const Params& p, const ClientKey& ck, const RngKey& key, size_t row_lo, size_t row_hi,
                       uint64_t* out) {
+    gen_packing_rows(p, ck, key, key, false, row_lo, row_hi, out);
+}
+
+void gen_packing_rows(const Params& p, const ClientKey& ck, const RngKey& mask_key, const RngKey& noise_key,
+                      bool round40, size_t row_lo, size_t row_hi, uint64_t* out) {
     const int k = p.k, N = p.N;
     const size_t W = pk_row_words(p);
     if (row_lo > row_hi || row_hi > pk_rows(p)) throw Error(FR_ERR_INVALID, "packing key: row range");
     if (ck.s_big.size() != (size_t)p.big()) throw Error(FR_ERR_INVALID, "packing key: client key size");
     parallel_for((int)(row_hi - row_lo), [&](int q) {
-        Rng rm(key, STREAM_PKSK_MASK), rn(key, STREAM_PKSK_NOISE);
+        Rng rm(mask_key, STREAM_PKSK_MASK), rn(noise_key, STREAM_PKSK_NOISE);
         const uint64_t r = row_lo + (uint64_t)q;
         const size_t i = r / PK_LEVELS, l = r % PK_LEVELS;
         uint64_t* row = out + (size_t)q * W;
@@ -678,6 +683,8 @@ void gen_packing_rows(const Params& p, const ClientKey& ck, const RngKey& key, s
         }
         for (int t = 0; t < N; ++t) Bp[t] += (uint64_t)rn.gaussian(r * N + t, p.glwe_sigma);
         Bp[0] += ck.s_big[i] << (64 - PK_BASE_LOG * (l + 1));
+        if (round40)
+            for (int t = 0; t < N; ++t) Bp[t] = pk_round40(Bp[t]) << PKC_DROP_BITS;
     });
 }
 
@@ -719,6 +726,73 @@ void check_pk_blob(const Params& p, const uint8_t* blob, size_t len) {
             throw Error(FR_ERR_INVALID, "packing key: parameters do not match the context params");
     if (get_le32(blob + 40) != (uint32_t)PK_BASE_LOG || get_le32(blob + 44) != (uint32_t)PK_LEVELS)
         throw Error(FR_ERR_INVALID, "packing key: gadget other than base 2^7, 3 levels");
+}
+
+// ---------------------------------------------------------------- compact packing key
+static const char PKC_MAGIC[9] = "FRCPKEY1";
+
+void write_pk_compact_header(const Params& p, const RngKey& mask_key, uint8_t* out) {
+    std::memcpy(out, PKC_MAGIC, 8);
+    int32_t v[8];
+    compact_params(p, v);
+    for (int i = 0; i < 8; ++i) put_le32(out + 8 + 4 * i, (uint32_t)v[i]);
+    put_le32(out + 40, (uint32_t)PK_BASE_LOG);
+    put_le32(out + 44, (uint32_t)PK_LEVELS);
+    put_le32(out + 48, (uint32_t)PKC_BODY_BITS);
+    put_le32(out + 52, 0);
+    for (int i = 0; i < 8; ++i) put_le32(out + 56 + 4 * i, mask_key.w[i]);
+    std::memset(out + 88, 0, 8);
+}
+
+RngKey check_pk_compact(const Params& p, const uint8_t* blob, size_t len) {
+    if (!blob || len != pk_compact_size(p))
+        throw Error(FR_ERR_INVALID, "compact packing key: length does not match the context params "
+                                    "(fr_packing_key_compact_size)");
+    if (std::memcmp(blob, PKC_MAGIC, 8)) throw Error(FR_ERR_INVALID, "compact packing key: bad magic");
+    int32_t want[8];
+    compact_params(p, want);
+    for (int i = 0; i < 8; ++i)
+        if (get_le32(blob + 8 + 4 * i) != (uint32_t)want[i])
+            throw Error(FR_ERR_INVALID, "compact packing key: parameters do not match the context params");
+    if (get_le32(blob + 40) != (uint32_t)PK_BASE_LOG || get_le32(blob + 44) != (uint32_t)PK_LEVELS)
+        throw Error(FR_ERR_INVALID, "compact packing key: gadget other than base 2^7, 3 levels");
+    if (get_le32(blob + 48) != (uint32_t)PKC_BODY_BITS)
+        throw Error(FR_ERR_INVALID, "compact packing key: body bits other than 40");
+    if (get_le32(blob + 52) != 0) throw Error(FR_ERR_INVALID, "compact packing key: reserved word is not zero");
+    for (int i = 88; i < 96; ++i)
+        if (blob[i]) throw Error(FR_ERR_INVALID, "compact packing key: pad bytes are not zero");
+    return RngKey::from_bytes(blob + 56);
+}
+
+void pack_pk_compact(const Params& p, const uint64_t* rows, uint8_t* planes) {
+    const size_t R = pk_rows(p), N = (size_t)p.N, W = pk_row_words(p), kN = (size_t)p.k * N;
+    uint8_t* lo = planes + 4 * R * N;
+    parallel_for((int)R, [&](int r) {
+        const uint64_t* body = rows + (size_t)r * W + kN;
+        for (size_t t = 0; t < N; ++t) {
+            const uint64_t b40 = body[t] >> PKC_DROP_BITS;
+            put_le32(planes + 4 * ((size_t)r * N + t), (uint32_t)(b40 >> 8));
+            lo[(size_t)r * N + t] = (uint8_t)b40;
+        }
+    });
+}
+
+void expand_pk_compact(const Params& p, const uint8_t* blob, size_t len, std::vector<uint64_t>& rows,
+                       RngKey& mask_key) {
+    mask_key = check_pk_compact(p, blob, len);
+    const size_t R = pk_rows(p), N = (size_t)p.N, W = pk_row_words(p), kN = (size_t)p.k * N;
+    const uint8_t* hi = blob + PKC_HEADER;
+    const uint8_t* lo = hi + 4 * R * N;
+    rows.resize(pk_len(p));
+    parallel_for((int)R, [&](int r) {
+        Rng rm(mask_key, STREAM_PKSK_MASK);
+        uint64_t* o = rows.data() + (size_t)r * W;
+        for (size_t t = 0; t < kN; ++t) o[t] = rm.u64((uint64_t)r * kN + t);
+        for (size_t t = 0; t < N; ++t) {
+            const uint64_t b40 = ((uint64_t)get_le32(hi + 4 * ((size_t)r * N + t)) << 8) | lo[(size_t)r * N + t];
+            o[kN + t] = b40 << PKC_DROP_BITS;
+        }
+    });
 }
 
 // Rows of the key are streamed once per block of PACK_JB booleans, whose partial sums

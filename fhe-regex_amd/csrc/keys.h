@@ -126,6 +126,10 @@ inline size_t pk_len(const Params& p) { return pk_rows(p) * pk_row_words(p); }
 // a few seconds of host time (each row is k N^2 / 2 additions), hence the range
 void gen_packing_rows(const Params& p, const ClientKey& ck, const RngKey& key, size_t row_lo, size_t row_hi,
                       uint64_t* out);
+// the same rows with the masks drawn under mask_key and the noise under noise_key; round40:
+// every body word rounded to its top PKC_BODY_BITS bits (the compact form below)
+void gen_packing_rows(const Params& p, const ClientKey& ck, const RngKey& mask_key, const RngKey& noise_key,
+                      bool round40, size_t row_lo, size_t row_hi, uint64_t* out);
 // the body noise of every row for the device generator ([row][N], glwe sigma, torus units)
 void gen_pksk_noise(const Params& p, const RngKey& key, std::vector<int32_t>& e);
 // Wire blob: "FRPKKEY1", the eight int32 parameters of the compact server key blob,
@@ -135,6 +139,31 @@ inline size_t pk_blob_size(const Params& p) { return PK_HEADER + 8 * pk_len(p); 
 void write_pk_header(const Params& p, uint8_t* out /* PK_HEADER bytes */);
 // Error(FR_ERR_INVALID) unless len, the magic, the parameters and the gadget are p's
 void check_pk_blob(const Params& p, const uint8_t* blob, size_t len);
+
+// Compact (seeded) packing key, every ring.  The masks are ChaCha20 words of
+// the public mask key M = derive_mask_key(K) at the standard generator's indices, the noise is
+// the standard generator's under the call's secret key K, and the message sits on the body's
+// coefficient 0, so no mask word carries a secret.  The body B travels rounded to 40 bits,
+// b40 = ((B + 2^23) >> 24) mod 2^40, and is installed as b40 << 24 on both sides: installed - B
+// lies in (-2^23, 2^23] (a 2^-16 share of the gadget's own rounding variance).
+// The installed key is an ordinary packing key.
+constexpr int PKC_BODY_BITS = 40, PKC_DROP_BITS = 64 - PKC_BODY_BITS;
+inline uint64_t pk_round40(uint64_t body) { return (body + ((uint64_t)1 << (PKC_DROP_BITS - 1))) >> PKC_DROP_BITS; }
+// Wire blob (include/fheregex.h): "FRCPKEY1", the eight int32 parameters, the gadget, the body
+// bits, a reserved zero, the mask key, 8 zero bytes, then the high plane u32[3kN][N] (b40 >> 8)
+// and the low plane u8[3kN][N] (b40 & 0xFF); little endian
+constexpr size_t PKC_HEADER = 96;
+inline size_t pk_compact_planes(const Params& p) { return 5 * pk_rows(p) * (size_t)p.N; }  // bytes
+inline size_t pk_compact_size(const Params& p) { return PKC_HEADER + pk_compact_planes(p); }
+void write_pk_compact_header(const Params& p, const RngKey& mask_key, uint8_t* out /* PKC_HEADER bytes */);
+// Error(FR_ERR_INVALID) unless len, the magic, the parameters, the gadget and the body bits are
+// p's and the reserved word and the pad are zero; the mask key
+RngKey check_pk_compact(const Params& p, const uint8_t* blob, size_t len);
+// the bodies of full rows [pk_rows][(k+1) N] into the two planes (pk_compact_planes bytes)
+void pack_pk_compact(const Params& p, const uint64_t* rows, uint8_t* planes);
+// check_pk_compact, then the full rows: every mask from the mask key, every body b40 << 24
+void expand_pk_compact(const Params& p, const uint8_t* blob, size_t len, std::vector<uint64_t>& rows,
+                       RngKey& mask_key);
 
 // Packing keyswitch, host restatement (plain loops; the device path is keyswitch.hip's):
 //   out = sum_j X^j ((0, .., 0, b_j) - sum_{i,l} d_{j,i,l} PKSK[3 i + l])

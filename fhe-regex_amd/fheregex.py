@@ -135,6 +135,12 @@ _SIGS = {
     "fr_packing_key_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
     "fr_export_packing_key": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "fr_load_packing_key": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "fr_gen_packing_key_compact": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "fr_gen_packing_key_compact_keyed": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "fr_packing_key_compact_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
+    "fr_export_packing_key_compact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fr_load_packing_key_compact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "fr_device_timers_packing_key_load": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "fr_packed_result_size": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "fr_pack_bools": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, u64p]),
     "fr_pack_bools_blob": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, C.c_char_p, C.c_size_t,
@@ -144,6 +150,7 @@ _SIGS = {
     "fr_dev_packing_limb_column": (C.c_int, [C.c_void_p, C.c_int32, u64p]),
     "fr_device_timers_pack": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "fr_gen_packing_rows_keyed": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_size_t, u64p]),
+    "fr_gen_packing_rows_compact_keyed": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_size_t, u64p]),
     "fr_pack_lwes": (C.c_int, [C.c_void_p, u64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_size_t, u64p]),
     "fr_packed_phase": (C.c_int, [C.c_void_p, u64p, u64p]),
     "fr_compact_content_size": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -519,11 +526,19 @@ class Context:
         _check(lib().fr_load_server_key_compact(self.h, blob, len(blob)))
 
     # packed results
-    def gen_packing_key(self, seed=None):
+    def gen_packing_key(self, seed=None, compact=False):
         """the optional packing key (fheregex.h "packed results"; 201 MB): on the GPU on a
-        device context, word for word the host generator's rows.  `seed` as in gen_client_key."""
+        device context, word for word the host generator's rows.  `seed` as in gen_client_key.
+        compact=True: the compact form, whose masks are ChaCha20 words of a public mask key
+        and whose bodies are rounded to 40 bits, so that export_packing_key_compact ships
+        63 MB; a compact key from an int seed must not leave the client."""
         keyed, v = _rng_arg(seed)
-        _check(lib().fr_gen_packing_key_keyed(self.h, v) if keyed else lib().fr_gen_packing_key(self.h, v))
+        L = lib()
+        if compact:
+            f = L.fr_gen_packing_key_compact_keyed if keyed else L.fr_gen_packing_key_compact
+        else:
+            f = L.fr_gen_packing_key_keyed if keyed else L.fr_gen_packing_key
+        _check(f(self.h, v))
 
     def packing_key_size(self) -> int:
         n = C.c_size_t()
@@ -544,14 +559,36 @@ class Context:
                                  dtype=np.uint8)
         _check(lib().fr_load_packing_key(self.h, b.ctypes.data, len(b)))
 
-    def gen_packing_rows(self, seed, row_lo: int, row_hi: int) -> np.ndarray:
-        """rows [row_lo, row_hi) of the packing key gen_packing_key(seed) draws, on the host:
-        (rows, (k+1) N) words"""
+    def packing_key_compact_size(self) -> int:
+        n = C.c_size_t()
+        _check(lib().fr_packing_key_compact_size(self.h, C.byref(n)))
+        return n.value
+
+    def export_packing_key_compact(self) -> np.ndarray:
+        """the compact wire blob (fheregex.h: header, mask key, two planes of 40-bit bodies)
+        as a uint8 array, of a key generated with compact=True or loaded from such a blob"""
+        n = C.c_size_t()
+        _check(lib().fr_export_packing_key_compact(self.h, None, 0, C.byref(n)))
+        buf = np.empty(n.value, dtype=np.uint8)
+        _check(lib().fr_export_packing_key_compact(self.h, buf.ctypes.data, n.value, C.byref(n)))
+        return buf
+
+    def load_packing_key_compact(self, blob):
+        """install a compact packing key blob (bytes or a uint8 array): no client key needed;
+        a device context uploads the planes and rebuilds masks and bodies on the GPU"""
+        b = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray)) else blob,
+                                 dtype=np.uint8)
+        _check(lib().fr_load_packing_key_compact(self.h, b.ctypes.data, len(b)))
+
+    def gen_packing_rows(self, seed, row_lo: int, row_hi: int, compact=False) -> np.ndarray:
+        """rows [row_lo, row_hi) of the packing key gen_packing_key(seed, compact) draws, on
+        the host: (rows, (k+1) N) words"""
         keyed, v = _rng_arg(seed)
         key = v if keyed else seed_key(v)
         W = (self.params.k + 1) * self.params.N
         out = np.zeros((row_hi - row_lo, W), dtype=np.uint64)
-        _check(lib().fr_gen_packing_rows_keyed(self.h, key, row_lo, row_hi, _p(out)))
+        f = lib().fr_gen_packing_rows_compact_keyed if compact else lib().fr_gen_packing_rows_keyed
+        _check(f(self.h, key, row_lo, row_hi, _p(out)))
         return out
 
     def packed_result_size(self, n: int) -> int:
@@ -621,6 +658,13 @@ class Context:
         KSK expansion, BSK expansion, KSK limbs, BSK Fourier transform"""
         ms = (C.c_double * 5)()
         _check(lib().fr_device_timers_key_load(self.h, ms))
+        return list(ms)
+
+    def packing_key_load_timers(self) -> List[float]:
+        """ms of the last load_packing_key_compact's stages under set_profiling: H2D copy,
+        expansion, byte limbs"""
+        ms = (C.c_double * 3)()
+        _check(lib().fr_device_timers_packing_key_load(self.h, ms))
         return list(ms)
 
     def set_lowering(self, mode: int):
@@ -1094,17 +1138,24 @@ class ServerKey:
             ctx.load_packing_key(np.fromfile(packing_path, dtype=np.uint8))
         return ServerKey(ctx)
 
-    def save_compact(self, path: str):
-        """the raw compact blob (fr_export_server_key_compact) of a compact-form key"""
+    def save_compact(self, path: str, packing_path: Optional[str] = None):
+        """the raw compact blob (fr_export_server_key_compact) of a compact-form key;
+        packing_path: the compact blob of a compact-form packing key as a second file"""
         with open(path, "wb") as f:
             f.write(self.ctx.export_server_key_compact())
+        if packing_path is not None:
+            self.ctx.export_packing_key_compact().tofile(packing_path)
 
     @staticmethod
-    def load_compact(path: str, device: int = 0, params: Optional[Params] = None) -> "ServerKey":
-        """a server context holding only the server key of a compact blob"""
+    def load_compact(path: str, device: int = 0, params: Optional[Params] = None,
+                     packing_path: Optional[str] = None) -> "ServerKey":
+        """a server context holding only the server key of a compact blob, and the packing
+        key of the compact blob at packing_path if given"""
         ctx = Context(device, params)
         with open(path, "rb") as f:
             ctx.load_server_key_compact(f.read())
+        if packing_path is not None:
+            ctx.load_packing_key_compact(np.fromfile(packing_path, dtype=np.uint8))
         return ServerKey(ctx)
 
 
@@ -1128,9 +1179,19 @@ def compact_content_mask_key(blob: bytes) -> bytes:
     return bytes(blob[32:64])
 
 
+COMPACT_PACKING_MAGIC = b"FRCPKEY1"
+
+
+def compact_packing_mask_key(blob) -> bytes:
+    """the public 32-byte mask key of a compact packing-key blob (bytes 56..87)"""
+    if len(blob) < 96 or bytes(blob[:8]) != COMPACT_PACKING_MAGIC:
+        raise ValueError("not a compact packing key blob")
+    return bytes(blob[56:88])
+
+
 def gen_keys(client_key_blob: Optional[bytes] = None, seed=None, device: int = 0,
              params: Optional[Params] = None, client_seed=None, compact: bool = False, packing: bool = False,
-             packing_seed=None):
+             packing_seed=None, packing_compact: bool = False):
     """gen_keys (ciphertext.rs:42-45): (client key, server key).
 
     Without a blob the client key is fresh (gen_keys_radix(&PARAM_MESSAGE_2_CARRY_2, 4),
@@ -1141,7 +1202,8 @@ def gen_keys(client_key_blob: Optional[bytes] = None, seed=None, device: int = 0
     int a 64-bit seed; a server key from an int seed is reproducible (tests, benchmarks,
     multi-rank keygen) and must not leave the client.  compact=True: the server key in
     compact form (ServerKey.save_compact ships it).  packing=True: also the packing key
-    (ServerKey.pack_bools), drawn under `packing_seed`."""
+    (ServerKey.pack_bools), drawn under `packing_seed`; packing_compact=True: that key in
+    its compact form (ServerKey.save_compact(path, packing_path) ships it)."""
     ctx = Context(device, params)
     if client_key_blob is None:
         ctx.gen_client_key(client_seed)
@@ -1149,7 +1211,7 @@ def gen_keys(client_key_blob: Optional[bytes] = None, seed=None, device: int = 0
         ctx.load_client_key(client_key_blob)
     ctx.gen_server_key(seed, compact=compact)
     if packing:
-        ctx.gen_packing_key(packing_seed)
+        ctx.gen_packing_key(packing_seed, compact=packing_compact)
     return ClientKey(ctx), ServerKey(ctx)
 
 

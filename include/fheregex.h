@@ -245,6 +245,45 @@ int fr_gen_packing_key_keyed(fr_ctx* ctx, const uint8_t* key /* NULL: OS CSPRNG 
 int fr_packing_key_size(fr_ctx* ctx, size_t* bytes);
 int fr_export_packing_key(fr_ctx* ctx, uint8_t* buf, size_t cap, size_t* written);
 int fr_load_packing_key(fr_ctx* ctx, const uint8_t* blob, size_t len);
+/* Compact (seeded) packing key, every ring: 3.2x (k = 1, N = 2048) and 4.8x (k = 2, N = 1024)
+ * fewer bytes than the blob above.  K is the call's secret generator key and M the public
+ * mask key of "Randomness" (words 0..7 of block 0 of K's stream 8, as for a compact server
+ * key).  Mask word t of polynomial j of row r is u64 number (r*k + j)*N + t of stream 9 under
+ * M: the standard generator's index under another key.  The message sits on the body's
+ * coefficient 0, so no mask word carries a secret.  The noise is the standard generator's
+ * under K (stream 10).  The body B = sum_j A_j S_j + e + s_big[i] * 2^(64 - 7*(l+1)) on
+ * coefficient 0 travels rounded to 40 bits, b40 = ((B + 2^23) >> 24) mod 2^40, and is
+ * installed as b40 << 24 on the client as on the server: installed - B lies in
+ * (-2^23, 2^23], a 2^-16 share of the variance of the gadget's own rounding.
+ * The rounding is a public function of a public ciphertext.  What is installed is an ordinary
+ * packing key: every entry above and every packing kernel runs on it unchanged.  Same
+ * preconditions and fr_set_keygen placement as fr_gen_packing_key[_keyed]; host and device
+ * give the same words.  A compact key from a guessable seed must never leave the client
+ * (see "Randomness").
+ * The wire blob, little endian, exactly fr_packing_key_compact_size bytes = 96 + 5*3kN*N
+ * (62,914,656 at (1, 2048), 31,457,376 at (2, 1024)):
+ *     0  "FRCPKEY1"
+ *     8  int32 k, N, n, ks_base_log, ks_level, pbs_base_log, pbs_level, ring
+ *    40  int32 7, 3 (the packing gadget), int32 40 (body bits), int32 0 (reserved)
+ *    56  the mask key M (8 words)
+ *    88  8 zero bytes (both planes start 16-byte aligned)
+ *    96  high plane u32[3kN][N]: b40 >> 8
+ *    96 + 4*3kN*N  low plane u8[3kN][N]: b40 & 0xFF
+ * fr_export_packing_key_compact: buf == NULL is a size query; FR_ERR_INVALID without a
+ * packing key, or if the installed one was not generated compact or loaded from a compact
+ * blob (a standard key's masks are not expandable from a mask key).  A device context
+ * gathers the planes on the GPU and downloads them alone.  fr_load_packing_key_compact
+ * refuses a wrong length or magic, any of the eight parameters differing from the context's,
+ * another gadget, body bits other than 40 and a non-zero reserved word or pad with
+ * FR_ERR_INVALID, before the installed key is touched and before anything is allocated; it
+ * needs no client key.  A device context uploads the planes in one copy and rebuilds masks
+ * and bodies in one kernel; a host-only context expands on the host.  Every other install of
+ * a packing key makes the compact export refuse again. */
+int fr_gen_packing_key_compact(fr_ctx* ctx, uint64_t seed);
+int fr_gen_packing_key_compact_keyed(fr_ctx* ctx, const uint8_t* key /* NULL: OS CSPRNG */);
+int fr_packing_key_compact_size(fr_ctx* ctx, size_t* bytes);
+int fr_export_packing_key_compact(fr_ctx* ctx, uint8_t* buf, size_t cap, size_t* written);
+int fr_load_packing_key_compact(fr_ctx* ctx, const uint8_t* blob, size_t len);
 /* The packing keyswitch of n boolean handles (1 <= n <= N): out_words receives the (k+1)*N
  * words of
  *     sum_j X^j * ((0, .., 0, b_j) - sum_{i,l} d_{j,i,l} * row[3*i + l])
@@ -473,6 +512,9 @@ int fr_device_timers_pair(fr_ctx* ctx, double* br_ms, uint64_t* br_launches, uin
  * events: ms[0..4] = H2D copy of the bodies, KSK mask expansion, BSK mask expansion, KSK
  * byte limbs, Fourier transform of the BSK. */
 int fr_device_timers_key_load(fr_ctx* ctx, double* ms /* 5 */);
+/* The same for the last fr_load_packing_key_compact: ms[0..2] = H2D copy of the planes, the
+ * expansion kernel (masks and bodies), the byte limbs. */
+int fr_device_timers_packing_key_load(fr_ctx* ctx, double* ms /* 3 */);
 /* The expansion kernel of the last fr_upload_compact_* made under fr_set_profiling, by HIP
  * events, ms.  A profiled upload waits for its kernel; an unprofiled one does not. */
 int fr_device_timers_content(fr_ctx* ctx, double* ms);
@@ -651,6 +693,10 @@ int fr_set_profiling(fr_ctx* ctx, int32_t on);
  * takes a few seconds of host time, hence the range. */
 int fr_gen_packing_rows_keyed(fr_ctx* ctx, const uint8_t* key /* NULL: OS CSPRNG */, size_t row_lo, size_t row_hi,
                               uint64_t* out);
+/* The same rows of the key that fr_gen_packing_key_compact_keyed draws: masks under the mask
+ * key, bodies rounded to 40 bits. */
+int fr_gen_packing_rows_compact_keyed(fr_ctx* ctx, const uint8_t* key /* NULL: OS CSPRNG */, size_t row_lo,
+                                      size_t row_hi, uint64_t* out);
 /* fr_pack_bools in plain host loops, on LWEs given as words: boolean j is
  * off[j]*2^58 + w[j]*lwes[j] (w, off NULL: 1, 0; w[j] == 0: a constant, lwes[j] is not read,
  * and lwes may be NULL if every w[j] is 0).  Needs the packing key; on a device context the
