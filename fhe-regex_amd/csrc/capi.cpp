@@ -553,6 +553,13 @@ int fr_debug_arena_stats(fr_ctx* ctx, uint64_t* slots, uint64_t* free_slots) {
     })
 }
 
+int fr_debug_handle_count(fr_ctx* ctx, uint64_t* live) {
+    FR_TRY({
+        NEED(ctx && live);
+        *live = ctx->handles.size() - ctx->free_handles.size();
+    })
+}
+
 // device-to-device booleans (block 0 of a handle), e.g. per-rank partial results
 // gathered over RCCL: no host round trip of the LWE
 int fr_export_bool_device(fr_ctx* ctx, const fr_ct* h, size_t n, uint64_t* dev_dst) {

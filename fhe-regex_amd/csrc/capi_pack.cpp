@@ -13,9 +13,9 @@ static void need_packing_key(fr_ctx* ctx) {
         throw Error(FR_ERR_INVALID, "packing needs a packing key (fr_gen_packing_key, fr_load_packing_key)");
 }
 
-// the (k+1) N words of the handles' packed GLWE
-static void pack_handles(fr_ctx* ctx, const fr_ct* bools, size_t n, uint64_t* out) {
-    NEED(ctx && bools && out);
+// the (k+1) N words of the handles' packed GLWE, or (compact) its blob's k N + n rounded values
+static void pack_handles(fr_ctx* ctx, const fr_ct* bools, size_t n, uint64_t* out, uint16_t* compact = nullptr) {
+    NEED(ctx && bools && (out || compact));
     NEED(n >= 1 && n <= (size_t)ctx->p.N);
     need_packing_key(ctx);
     // every handle is checked before anything runs; a boolean is one slot or a trivial value
@@ -35,8 +35,16 @@ static void pack_handles(fr_ctx* ctx, const fr_ct* bools, size_t n, uint64_t* ou
         }
         off[j] = g.offset;
     }
-    if (ctx->dev) ctx->dev->pack_bools(gates.data(), n, out);
-    else pack_host(ctx->p, ctx->pksk.data(), nullptr, w.data(), off.data(), n, out);  // trivial handles only
+    if (ctx->dev && compact) return ctx->dev->pack_bools_compact(gates.data(), n, compact);
+    if (ctx->dev) return ctx->dev->pack_bools(gates.data(), n, out);
+    std::vector<uint64_t> words(compact ? pk_row_words(ctx->p) : 0);
+    if (compact) out = words.data();
+    pack_host(ctx->p, ctx->pksk.data(), nullptr, w.data(), off.data(), n, out);  // trivial handles only
+    for (size_t t = 0; compact && t < packed_compact_values(ctx->p, n); ++t) compact[t] = packed_round16(out[t]);
+}
+
+static void put_values16(const std::vector<uint16_t>& v, uint8_t* out) {
+    for (size_t t = 0; t < v.size(); ++t) out[2 * t] = (uint8_t)v[t], out[2 * t + 1] = (uint8_t)(v[t] >> 8);
 }
 
 extern "C" {
@@ -64,6 +72,66 @@ int fr_pack_bools_blob(fr_ctx* ctx, const fr_ct* bools, size_t n, uint8_t* buf, 
         std::vector<uint64_t> words(pk_row_words(ctx->p));
         pack_handles(ctx, bools, n, words.data());
         write_packed_result(ctx->p, n, words.data(), buf);
+    })
+}
+
+int fr_packed_compact_size(fr_ctx* ctx, size_t n, size_t* bytes) {
+    FR_TRY({
+        NEED(ctx && bytes);
+        NEED(n >= 1 && n <= (size_t)ctx->p.N);
+        *bytes = packed_compact_size(ctx->p, n);
+    })
+}
+
+int fr_pack_bools_compact(fr_ctx* ctx, const fr_ct* bools, size_t n, uint8_t* buf, size_t cap, size_t* written) {
+    FR_TRY({
+        NEED(ctx && written);
+        NEED(n >= 1 && n <= (size_t)ctx->p.N);
+        const size_t need = packed_compact_size(ctx->p, n);
+        *written = need;
+        if (!buf) return FR_OK;  // size query
+        NEED(cap >= need);
+        std::vector<uint16_t> v(packed_compact_values(ctx->p, n));
+        pack_handles(ctx, bools, n, nullptr, v.data());
+        write_packed_compact_header(ctx->p, n, buf);
+        put_values16(v, buf + PKCRES_HEADER);
+    })
+}
+
+int fr_compress_packed(fr_ctx* ctx, const uint64_t* words, size_t n, uint8_t* buf, size_t cap, size_t* written) {
+    FR_TRY({
+        NEED(ctx && written);
+        NEED(n >= 1 && n <= (size_t)ctx->p.N);
+        const size_t need = packed_compact_size(ctx->p, n);
+        *written = need;
+        if (!buf) return FR_OK;  // size query
+        NEED(words && cap >= need);
+        compress_packed(ctx->p, n, words, buf);
+    })
+}
+
+int fr_expand_packed_compact(fr_ctx* ctx, const uint8_t* blob, size_t len, uint64_t* words, size_t* n) {
+    FR_TRY({
+        NEED(ctx && blob && n);
+        *n = check_packed_compact(ctx->p, blob, len);  // before anything is written
+        if (words) expand_packed_compact(ctx->p, blob, words);
+    })
+}
+
+int fr_decrypt_packed_compact(fr_ctx* ctx, const uint8_t* blob, size_t len, uint8_t* bits, size_t* n) {
+    FR_TRY({
+        NEED(ctx && blob && n);
+        // the blob is checked before anything is allocated
+        const size_t nb = check_packed_compact(ctx->p, blob, len);
+        *n = nb;
+        if (!bits) return FR_OK;  // size query
+        if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
+        std::vector<uint64_t> ct(pk_row_words(ctx->p)), phase((size_t)ctx->p.N);
+        expand_packed_compact(ctx->p, blob, ct.data());
+        glwe_phase(ctx->p, ctx->ck, ct.data(), phase.data());
+        const uint64_t half = 1ULL << (DELTA_LOG - 1);
+        // (the coefficients past n were not sent: nothing to check there)
+        for (size_t j = 0; j < nb; ++j) bits[j] = (uint8_t)(((phase[j] + half) >> DELTA_LOG) & 1);
     })
 }
 
@@ -126,6 +194,13 @@ int fr_device_timers_pack(fr_ctx* ctx, double* ms) {
     FR_TRY({
         NEED(ctx && ms);
         std::memcpy(ms, ctx->device().pack_ms(), 3 * sizeof(double));
+    })
+}
+
+int fr_device_timers_pack_compact(fr_ctx* ctx, double* ms) {
+    FR_TRY({
+        NEED(ctx && ms);
+        std::memcpy(ms, ctx->device().pack_ms(), 4 * sizeof(double));
     })
 }
 

@@ -106,12 +106,18 @@ class Device {
     // Packing keyswitch (keys.h: pack_host computes the same words): boolean j < n <= N is
     // the affine form gates[j].offset 2^58 + sum_q in_w[q] arena[in_slot[q]] (outputs unused);
     // the (k+1) N words of the packed GLWE are copied to out_host.  Runs on the current lane's
-    // stream after whatever wrote the slots; returns after the download.  The C ABI calls it
+    // stream after whatever wrote the slots; returns after the download.  fr_pack_bools* call it
     // outside a lane, so it runs on lane 0's stream, which first waits for every lane's queued
     // work (cur_stream): packs of results from different lanes serialise behind all lanes.
+    // Inside a lane (fr_match_starts_packed) it runs on that lane's stream after the lane's
+    // launches, on the lane's own scratch, and waits for that stream only.
     void pack_bools(const DevGate* gates, size_t n, uint64_t* out_host);
-    // HIP-event ms of the last pack_bools under fr_set_profiling: digits (with the zeroing of
-    // the scratch), GEMM, rotate-sum
+    // The same pack in its compact form (keys.h: compress_packed computes the same values): the
+    // packed GLWE's k N mask coefficients and its first n body coefficients, each rounded to its
+    // top 16 bits by k_pack_compress; only these k N + n u16 values are downloaded.
+    void pack_bools_compact(const DevGate* gates, size_t n, uint16_t* out_host /* kN + n */);
+    // HIP-event ms of the last pack under fr_set_profiling: digits (with the zeroing of the
+    // scratch), GEMM, rotate-sum, and the compact form's rounding (0 for pack_bools)
     const double* pack_ms() const { return pack_ms_; }
     // fresh encryptions of block messages (encrypt_blocks, keys.h) written into
     // allocated arena slots, bit-identical to the host encryption
@@ -201,6 +207,7 @@ class Device {
         gpu::DevBuf<DevGate> pk_gates;  // pack_bools: the booleans' descriptors
         gpu::DevBuf<int8_t> pk_dig;  // pack_bools: digits [rows][3 kN], allocated at the first pack
         gpu::DevBuf<uint64_t> pk_g;  // pack_bools: keyswitched rows [n][(k+1) N], then the packed GLWE
+        gpu::DevBuf<uint16_t> pk_c16;  // pack_bools_compact: the k N + N rounded coefficients
         // key products of the lane's smallest launches [bootstrap][step][P][own, other][m][lane]
         // (fft_br.hip: k_key_products), allocated at the first such launch, grown to the largest
         gpu::DevBuf<double> kpre;
@@ -308,7 +315,9 @@ class Device {
     LimbKey ksk_;                   // LWE keyswitch key: kN ks_level rows of n + 1 words
     gpu::DevBuf<uint64_t> d_tbsk_;  // torus BSK of a device-generated or device-expanded key (export)
     LimbKey pksk_;                  // packing key: 3 kN rows of (k+1) N words (pack_bools)
-    double pack_ms_[3] = {0, 0, 0};
+    double pack_ms_[4] = {0, 0, 0, 0};
+    // both forms of the pack: the words to out_words, or (out_c16) the rounded values alone
+    void pack_launch(const DevGate* gates, size_t n, uint64_t* out_words, uint16_t* out_c16);
     int pk_split_ = 0;              // FR_PK_SPLIT: K slices of the packing GEMM (a divisor of 24; 0: auto)
     bool ks_mfma_ = true;         // FR_KS_MFMA=0: the VALU lincomb+keyswitch kernel
     size_t ks_mr4_min_ = 96;      // FR_KS_MR4_MIN: batches from this size use 4 row tiles per wave (k_ks_glds; ab_ks_glds.log: 100 gates 44 -> 37 us, 64 gates no gain)

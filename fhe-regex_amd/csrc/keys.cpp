@@ -864,6 +864,52 @@ size_t check_packed_result(const Params& p, const uint8_t* blob, size_t len) {
     return (size_t)n;
 }
 
+static const char PKCRES_MAGIC[9] = "FRCPRES1";
+
+void write_packed_compact_header(const Params& p, size_t n, uint8_t* out) {
+    std::memcpy(out, PKCRES_MAGIC, 8);
+    put_le32(out + 8, (uint32_t)p.k);
+    put_le32(out + 12, (uint32_t)p.N);
+    put_le64(out + 16, n);
+    put_le32(out + 24, (uint32_t)PKCRES_BITS);
+    put_le32(out + 28, 0);
+}
+
+void compress_packed(const Params& p, size_t n, const uint64_t* words, uint8_t* out) {
+    if (n < 1 || n > (size_t)p.N) throw Error(FR_ERR_INVALID, "compact packed result: n outside 1..N");
+    write_packed_compact_header(p, n, out);
+    // the body's first n coefficients follow the masks in the words as they do in the blob
+    for (size_t t = 0; t < packed_compact_values(p, n); ++t) {
+        const uint16_t v = packed_round16(words[t]);
+        out[PKCRES_HEADER + 2 * t] = (uint8_t)v;
+        out[PKCRES_HEADER + 2 * t + 1] = (uint8_t)(v >> 8);
+    }
+}
+
+size_t check_packed_compact(const Params& p, const uint8_t* blob, size_t len) {
+    if (!blob || len < PKCRES_HEADER)
+        throw Error(FR_ERR_INVALID, "compact packed result: length is not 32 + 2 (kN + n) (fr_packed_compact_size)");
+    if (std::memcmp(blob, PKCRES_MAGIC, 8)) throw Error(FR_ERR_INVALID, "compact packed result: bad magic");
+    if (get_le32(blob + 8) != (uint32_t)p.k || get_le32(blob + 12) != (uint32_t)p.N)
+        throw Error(FR_ERR_INVALID, "compact packed result: k, N do not match the context params");
+    const uint64_t n = get_le64(blob + 16);
+    if (n < 1 || n > (uint64_t)p.N) throw Error(FR_ERR_INVALID, "compact packed result: n outside 1..N");
+    if (get_le32(blob + 24) != (uint32_t)PKCRES_BITS)
+        throw Error(FR_ERR_INVALID, "compact packed result: coefficient bits other than 16");
+    if (get_le32(blob + 28) != 0) throw Error(FR_ERR_INVALID, "compact packed result: reserved word not zero");
+    if (len != packed_compact_size(p, (size_t)n))
+        throw Error(FR_ERR_INVALID, "compact packed result: length is not 32 + 2 (kN + n) (fr_packed_compact_size)");
+    return (size_t)n;
+}
+
+void expand_packed_compact(const Params& p, const uint8_t* blob, uint64_t* words) {
+    const size_t n = (size_t)get_le64(blob + 16), sent = packed_compact_values(p, n);
+    for (size_t t = 0; t < pk_row_words(p); ++t) {
+        const uint8_t* v = blob + PKCRES_HEADER + 2 * t;
+        words[t] = t < sent ? ((uint64_t)v[0] | ((uint64_t)v[1] << 8)) << PKCRES_DROP : 0;
+    }
+}
+
 void glwe_phase(const Params& p, const ClientKey& ck, const uint64_t* ct, uint64_t* phase) {
     const int k = p.k, N = p.N;
     std::vector<uint64_t> as((size_t)N, 0);

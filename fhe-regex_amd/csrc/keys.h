@@ -178,6 +178,31 @@ inline size_t packed_result_size(const Params& p) { return PKRES_HEADER + 8 * pk
 void write_packed_result(const Params& p, size_t n, const uint64_t* words, uint8_t* out);
 // Error(FR_ERR_INVALID) unless len, the magic, k and N are p's and 1 <= n <= N; returns n
 size_t check_packed_result(const Params& p, const uint8_t* blob, size_t len);
+// Compact packed result.  A packed boolean is never bootstrapped again, so
+// only the client's rounding at Delta / 2 = 2^58 sees its error: every coefficient travels
+// rounded to its top 16 bits, v = ((x + 2^47) >> 48) mod 2^16, and is installed as v << 48, the
+// mask and the body alike; the body coefficients past n carry no boolean and are not sent.
+// The rounding adds std sqrt((h + 1) / 12) 2^48 to the phase, h the key's weight: 2^51.2 at
+// h = 1024 against the 2^58 threshold.
+// Wire blob: "FRCPRES1", int32 k, N, u64 n, u32 16 (coefficient bits), u32 0 (reserved), then
+// u16 mask[kN], u16 body[n]; little endian, exactly 32 + 2 (kN + n) bytes.
+// Decryption is glwe_phase of the expanded words and round(phase / 2^59) & 1 for j < n; the
+// coefficients past n were not sent (they expand to a zero body), so there is nothing to check
+// there, unlike check_packed_result's blob.
+constexpr int PKCRES_BITS = 16, PKCRES_DROP = 64 - PKCRES_BITS;
+constexpr size_t PKCRES_HEADER = 32;
+inline uint16_t packed_round16(uint64_t x) { return (uint16_t)((x + ((uint64_t)1 << (PKCRES_DROP - 1))) >> PKCRES_DROP); }
+inline size_t packed_compact_values(const Params& p, size_t n) { return (size_t)p.big() + n; }  // u16 values
+inline size_t packed_compact_size(const Params& p, size_t n) { return PKCRES_HEADER + 2 * packed_compact_values(p, n); }
+void write_packed_compact_header(const Params& p, size_t n, uint8_t* out /* PKCRES_HEADER bytes */);
+// the blob of a packed GLWE's (k+1) N words carrying n booleans: plain loops, the word-for-word
+// reference of the device's k_pack_compress
+void compress_packed(const Params& p, size_t n, const uint64_t* words, uint8_t* out);
+// Error(FR_ERR_INVALID) unless len, the magic, k and N are p's, 1 <= n <= N, the bit count is 16
+// and the reserved word is 0; returns n
+size_t check_packed_compact(const Params& p, const uint8_t* blob, size_t len);
+// a checked blob's (k+1) N words: v << 48, the body past n zero
+void expand_packed_compact(const Params& p, const uint8_t* blob, uint64_t* words);
 // phase B - sum_c A_c S_c (negacyclic) of a GLWE ciphertext under the client key: N words
 void glwe_phase(const Params& p, const ClientKey& ck, const uint64_t* ct, uint64_t* phase);
 

@@ -10,6 +10,7 @@
 //   k_linear            : linear combination into a slot without a bootstrap
 //   k_pack_rotate_sum   : the packing keyswitch's sum_j X^j G[j] (its digits and GEMM are the
 //                         kernels above with the (2^7, 3) gadget and the packing key's limbs)
+//   k_pack_compress     : the compact reply, every sent coefficient rounded to its top 16 bits
 #include <algorithm>
 #include <cstdlib>
 
@@ -651,6 +652,28 @@ __global__ void __launch_bounds__(256) k_pack_rotate_sum(const uint64_t* __restr
     if (c < W && acc != 0) atomicAdd(&out[c], (unsigned long long)acc);
 }
 
+// The compact reply (keys.h: packed_round16): out[c] = ((in[c] + 2^47) >> 48) mod 2^16 for the
+// total = kN + n coefficients the blob carries; the body's first n follow the masks in the words
+// as they do in the blob, so input and output share the index.  A separate launch: the
+// rotate-sum's slices meet in atomics, so no thread of it sees a finished word.  Thread i rounds
+// the eight coefficients from min(8 i, total - 8) and issues one 16-byte store.  The last thread's
+// eight end at `total`, so nothing is written past it; where total is no multiple of 8 they
+// overlap the thread before's, which stores the same values, and that one store is only 2-byte
+// aligned (a global store need not be aligned).  total >= kN >= 8.
+typedef unsigned short v8u16_t __attribute__((ext_vector_type(8)));
+typedef v8u16_t v8u16_unaligned_t __attribute__((aligned(2)));
+__global__ void __launch_bounds__(256) k_pack_compress(const uint64_t* __restrict__ in, int total,
+                                                       uint16_t* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (8 * i >= total) return;
+    const int s = min(8 * i, total - 8);
+    v8u16_t v;
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+        v[u] = (unsigned short)((in[s + u] + ((uint64_t)1 << (PKCRES_DROP - 1))) >> PKCRES_DROP);  // packed_round16
+    *(v8u16_unaligned_t*)(out + s) = v;
+}
+
 // test hook: column t of a limb operand put back together, out[k] = sum_l L_l[k] 256^l (mod 2^64)
 __global__ void __launch_bounds__(256) k_limb_column(const int8_t* __restrict__ kl, int KD, int t,
                                                      uint64_t* __restrict__ out) {
@@ -673,7 +696,12 @@ void Device::packing_limb_column(int col, uint64_t* out_host) {
     HIP_CHECK(hipStreamSynchronize(STREAM));
 }
 
-void Device::pack_bools(const DevGate* gates, size_t n, uint64_t* out_host) {
+void Device::pack_bools(const DevGate* gates, size_t n, uint64_t* out_host) { pack_launch(gates, n, out_host, nullptr); }
+void Device::pack_bools_compact(const DevGate* gates, size_t n, uint16_t* out_host) {
+    pack_launch(gates, n, nullptr, out_host);
+}
+
+void Device::pack_launch(const DevGate* gates, size_t n, uint64_t* out_words, uint16_t* out_c16) {
     if (!has_packing_key()) throw Error(FR_ERR_INVALID, "no packing key on the device");
     const int N = p_.N, big = p_.big(), KD = pksk_.KD, W = pksk_.ncols;
     if (n < 1 || n > (size_t)N) throw Error(FR_ERR_INVALID, "pack: 1 <= n <= N booleans");
@@ -688,20 +716,21 @@ void Device::pack_bools(const DevGate* gates, size_t n, uint64_t* out_host) {
     LaneState& l = cur();
     KsShape sh = ks_shape(n);  // (one column tile and the LDS-DMA ring, whatever FR_KS_MC / FR_KS_LDS say)
     const size_t bp = sh.padded;  // rows of whole tiles, as launch_ks
-    // scratch: the descriptors, digits [bp][KD], G [n][W] and the packed GLWE behind it; allocated at the first
-    // pack of the lane, doubled from there
-    if (bp * KD > l.pk_dig.size() || (n + 1) * (size_t)W > l.pk_g.size() || n > l.pk_gates.size()) {
+    // scratch: the descriptors, digits [bp][KD], G [n][W] and the packed GLWE behind it, and the compact form's
+    // W rounded values (kN + n <= W of them used); allocated at the first pack of the lane, doubled from there
+    if (bp * KD > l.pk_dig.size() || (n + 1) * (size_t)W > l.pk_g.size() || n > l.pk_gates.size() || !l.pk_c16) {
         HIP_CHECK(hipStreamSynchronize(s));
         l.pk_dig.grow(bp * KD, (size_t)128 * KD);
         l.pk_g.grow((n + 1) * (size_t)W, (size_t)129 * W);
         l.pk_gates.grow(n, 128);
+        l.pk_c16.grow((size_t)W, (size_t)W);
     }
     int8_t* d_dig = l.pk_dig.get();
     uint64_t* d_g = l.pk_g.get();
     uint64_t* d_out = d_g + n * (size_t)W;
     DevGate* d_gates = l.pk_gates.get();
     HIP_CHECK(hipMemcpyAsync(d_gates, gates, sizeof(DevGate) * n, hipMemcpyHostToDevice, s));
-    StageTimer<3> timer(profiling_ != 0, s);
+    StageTimer<4> timer(profiling_ != 0, s);
     // the digit pass zeroes the mask columns of G and writes column kN: the rest of the body
     // polynomial's columns (from kN, ahead of that write) and the output row are zeroed here,
     // inside the first stage's time
@@ -723,7 +752,16 @@ void Device::pack_bools(const DevGate* gates, size_t n, uint64_t* out_host) {
                                                                                    (unsigned long long*)d_out);
     HIP_CHECK(hipGetLastError());
     timer.mark(3);
-    HIP_CHECK(hipMemcpyAsync(out_host, d_out, 8 * (size_t)W, hipMemcpyDeviceToHost, s));
+    if (out_c16) {
+        const int total = big + (int)n;  // <= W, the size of pk_c16
+        k_pack_compress<<<(unsigned)((total + 2047) / 2048), 256, 0, s>>>(d_out, total, l.pk_c16.get());
+        HIP_CHECK(hipGetLastError());
+        timer.mark(4);
+        HIP_CHECK(hipMemcpyAsync(out_c16, l.pk_c16.get(), 2 * (size_t)total, hipMemcpyDeviceToHost, s));
+    } else {
+        timer.mark(4);
+        HIP_CHECK(hipMemcpyAsync(out_words, d_out, 8 * (size_t)W, hipMemcpyDeviceToHost, s));
+    }
     HIP_CHECK(hipStreamSynchronize(s));
     timer.read(pack_ms_);
 }

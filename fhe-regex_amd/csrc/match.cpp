@@ -131,8 +131,15 @@ void fill_stats(fr_match_stats& s, const Recorded& rec, const Plan& P) {
 // its result, outs[m * P + j] with P = *n_parts (the same for every m).
 // starts (fr_match_starts, M = 1): the program is compile_match_starts', its hi - lo outputs
 // one boolean per start offset.
+// reply (fr_match_starts_packed; starts, M = 1): no handles -- the outputs go straight into one
+// packing keyswitch on the match's own lane, and reply->buf receives the blob (`outs` unused).
+struct PackedReply {
+    bool compact;  // FRCPRES1, else FRPKRES1
+    uint8_t* buf;  // packed_compact_size / packed_result_size bytes
+};
 void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const char* pattern, size_t lo, size_t hi,
-                fr_ct* outs, fr_match_stats* st, size_t parts = 1, size_t* n_parts = nullptr, bool starts = false) {
+                fr_ct* outs, fr_match_stats* st, size_t parts = 1, size_t* n_parts = nullptr, bool starts = false,
+                const PackedReply* reply = nullptr) {
     double t0 = now_ms();
     pattern = pattern ? pattern : "";
     Device& dev = ctx->keyed_device();
@@ -230,19 +237,52 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
     launch_plan(dev, plan);
     if (hit && !starts && (nO < 1 || nO > parts))  // the caller's out buffer holds M * parts handles
         throw Error(FR_ERR_INVALID, "cached plan has more outputs than the caller's parts");
-    // an uncached plan's one output takes its gate's slot; parts get copies (two parts may read one gate)
-    const bool take = !c && nO == 1;
-    size_t made = 0;  // handles written so far, released if a later one fails: the caller gets a code only
-    try {
-        for (size_t m = 0; m < M; ++m)
-            for (size_t j = 0; j < nO; ++j, ++made) {
-                ProgOut o = po[j];
-                if (o.gate >= 0) o.gate += (int)(m * G);
-                outs[m * nO + j] = make_output(ctx, o, plan.slot, take);
+    if (reply) {
+        // Each output o.cst + o.w * gate is an affine descriptor over the plan's own gate slot (a
+        // constant start: no input), so no handle, no arena slot and no k_linear launch stands
+        // between the plan and the pack.  Still inside the lane scope: the pack follows the plan's
+        // launches on this lane's stream, uses this lane's scratch and waits for this stream only.
+        if (nO != hi - lo) throw Error(FR_ERR_INVALID, "cached plan's outputs are not the call's starts");
+        std::vector<DevGate> desc(nO);
+        for (size_t j = 0; j < nO; ++j) {
+            const ProgOut& o = po[j];
+            DevGate& g = desc[j];
+            std::memset(&g, 0, sizeof g);
+            g.offset = 2 * o.cst;  // units of Delta / 2
+            if (o.gate >= 0) {
+                g.n_in = 1;
+                g.in_slot[0] = plan.slot[o.gate];
+                g.in_w[0] = o.w;
             }
-    } catch (...) {
-        while (made) ctx->release(outs[--made]);
-        throw;
+        }
+        if (reply->compact) {
+            std::vector<uint16_t> v(packed_compact_values(ctx->p, nO));
+            dev.pack_bools_compact(desc.data(), nO, v.data());
+            write_packed_compact_header(ctx->p, nO, reply->buf);
+            for (size_t t = 0; t < v.size(); ++t) {
+                reply->buf[PKCRES_HEADER + 2 * t] = (uint8_t)v[t];
+                reply->buf[PKCRES_HEADER + 2 * t + 1] = (uint8_t)(v[t] >> 8);
+            }
+        } else {
+            std::vector<uint64_t> words(pk_row_words(ctx->p));
+            dev.pack_bools(desc.data(), nO, words.data());
+            write_packed_result(ctx->p, nO, words.data(), reply->buf);
+        }
+    } else {
+        // an uncached plan's one output takes its gate's slot; parts get copies (two parts may read one gate)
+        const bool take = !c && nO == 1;
+        size_t made = 0;  // handles written so far, released if a later one fails: the caller gets a code only
+        try {
+            for (size_t m = 0; m < M; ++m)
+                for (size_t j = 0; j < nO; ++j, ++made) {
+                    ProgOut o = po[j];
+                    if (o.gate >= 0) o.gate += (int)(m * G);
+                    outs[m * nO + j] = make_output(ctx, o, plan.slot, take);
+                }
+        } catch (...) {
+            while (made) ctx->release(outs[--made]);
+            throw;
+        }
     }
     if (n_parts) *n_parts = nO;
     if (!c) fresh.slot.reset();  // later users of these slots are ordered after the launches (one stream)
@@ -348,6 +388,24 @@ int fr_match_starts(fr_ctx* ctx, const fr_ct* content, size_t n, const char* pat
         NEED(ctx && pattern && (content || !n) && lo <= hi && (out || lo == hi));
         // (the key's `starts` field keeps these plans apart from has_match's of the same range)
         match_impl(ctx, content, n, 1, pattern, lo, hi, out, st, 1, nullptr, true);
+    })
+}
+
+int fr_match_starts_packed(fr_ctx* ctx, const fr_ct* content, size_t n, const char* pattern, size_t lo, size_t hi,
+                           int32_t compact, uint8_t* buf, size_t cap, size_t* written, fr_match_stats* st) {
+    FR_TRY({
+        NEED(ctx && pattern && written && (content || !n) && lo < hi && hi - lo <= (size_t)ctx->p.N);
+        NEED(compact == 0 || compact == 1);
+        ctx->keyed_device();  // a host-only or keyless context refuses as fr_match_starts does
+        if (!ctx->has_pk)     // ... and nothing is launched without a packing key
+            throw Error(FR_ERR_INVALID, "packing needs a packing key (fr_gen_packing_key, fr_load_packing_key)");
+        const size_t need = compact ? packed_compact_size(ctx->p, hi - lo) : packed_result_size(ctx->p);
+        *written = need;
+        if (!buf) return FR_OK;  // size query
+        NEED(cap >= need);
+        const PackedReply reply{compact != 0, buf};
+        // the plans are fr_match_starts' own (same key): one compiled by either call serves the other
+        match_impl(ctx, content, n, 1, pattern, lo, hi, nullptr, st, 1, nullptr, true, &reply);
     })
 }
 

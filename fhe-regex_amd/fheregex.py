@@ -147,8 +147,19 @@ _SIGS = {
                                      C.POINTER(C.c_size_t)]),
     "fr_decrypt_packed": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint8),
                                     C.POINTER(C.c_size_t)]),
+    "fr_packed_compact_size": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fr_pack_bools_compact": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, C.c_char_p, C.c_size_t,
+                                        C.POINTER(C.c_size_t)]),
+    "fr_compress_packed": (C.c_int, [C.c_void_p, u64p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fr_expand_packed_compact": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, u64p, C.POINTER(C.c_size_t)]),
+    "fr_decrypt_packed_compact": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint8),
+                                            C.POINTER(C.c_size_t)]),
+    "fr_match_starts_packed": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, C.c_char_p, C.c_size_t,
+                                         C.c_size_t, C.c_int32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                         C.POINTER(MatchStats)]),
     "fr_dev_packing_limb_column": (C.c_int, [C.c_void_p, C.c_int32, u64p]),
     "fr_device_timers_pack": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "fr_device_timers_pack_compact": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "fr_gen_packing_rows_keyed": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_size_t, u64p]),
     "fr_gen_packing_rows_compact_keyed": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_size_t, u64p]),
     "fr_pack_lwes": (C.c_int, [C.c_void_p, u64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_size_t, u64p]),
@@ -244,6 +255,7 @@ _SIGS = {
     "fr_device_info": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
     "fr_debug_scalar": (C.c_uint64, [C.c_int32, C.c_uint64, C.c_uint64]),
     "fr_debug_arena_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fr_debug_handle_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "fr_export_bool_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, C.c_void_p]),
     "fr_export_bool_device_async": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, C.c_void_p]),
     "fr_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
@@ -622,6 +634,49 @@ class Context:
         _check(lib().fr_decrypt_packed(self.h, blob, len(blob), bits, C.byref(n)))
         return list(bits)
 
+    # compact reply: every sent coefficient rounded to 16 bits, 32 + 2 (kN + n) bytes
+    def packed_compact_size(self, n: int) -> int:
+        b = C.c_size_t()
+        _check(lib().fr_packed_compact_size(self.h, n, C.byref(b)))
+        return b.value
+
+    def pack_bools_compact(self, handles: Sequence[int]) -> bytes:
+        """pack_bools in the compact form (fr_pack_bools_compact): the blob decrypt_packed_compact opens"""
+        hs = (C.c_uint32 * len(handles))(*handles)
+        n = C.c_size_t()
+        _check(lib().fr_pack_bools_compact(self.h, hs, len(handles), None, 0, C.byref(n)))
+        buf = C.create_string_buffer(n.value)
+        _check(lib().fr_pack_bools_compact(self.h, hs, len(handles), buf, n.value, C.byref(n)))
+        return buf.raw[:n.value]
+
+    def compress_packed(self, words: np.ndarray, n: int) -> bytes:
+        """the compact blob of a packed GLWE's (k+1) N words carrying n booleans, on the host"""
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        if len(words) != (self.params.k + 1) * self.params.N:
+            raise ValueError("compress_packed: (k+1) N words")
+        sz = C.c_size_t()
+        _check(lib().fr_compress_packed(self.h, None, n, None, 0, C.byref(sz)))
+        buf = C.create_string_buffer(sz.value)
+        _check(lib().fr_compress_packed(self.h, _p(words), n, buf, sz.value, C.byref(sz)))
+        return buf.raw[:sz.value]
+
+    def expand_packed_compact(self, blob: bytes) -> Tuple[np.ndarray, int]:
+        """(the (k+1) N words a compact blob installs, its n)"""
+        blob = bytes(blob)
+        n = C.c_size_t()
+        out = np.zeros((self.params.k + 1) * self.params.N, dtype=np.uint64)
+        _check(lib().fr_expand_packed_compact(self.h, blob, len(blob), _p(out), C.byref(n)))
+        return out, n.value
+
+    def decrypt_packed_compact(self, blob: bytes) -> List[int]:
+        """the bits of a compact packed result blob (client key needed)"""
+        blob = bytes(blob)
+        n = C.c_size_t()
+        _check(lib().fr_decrypt_packed_compact(self.h, blob, len(blob), None, C.byref(n)))
+        bits = (C.c_uint8 * n.value)()
+        _check(lib().fr_decrypt_packed_compact(self.h, blob, len(blob), bits, C.byref(n)))
+        return list(bits)
+
     def pack_lwes(self, lwes: Optional[np.ndarray], w=None, off=None, n: Optional[int] = None) -> np.ndarray:
         """the packing keyswitch in plain host loops (fr_pack_lwes) of the booleans
         off[j] 2^58 + w[j] lwes[j]: the (k+1) N words the device must give"""
@@ -651,6 +706,13 @@ class Context:
         """ms of the last pack_bools' stages under set_profiling: digits, GEMM, rotate-sum"""
         ms = (C.c_double * 3)()
         _check(lib().fr_device_timers_pack(self.h, ms))
+        return list(ms)
+
+    def pack_timers_compact(self) -> List[float]:
+        """pack_timers and, fourth, the compact form's rounding kernel, of the last pack of
+        either form (match_starts_packed's included)"""
+        ms = (C.c_double * 4)()
+        _check(lib().fr_device_timers_pack_compact(self.h, ms))
         return list(ms)
 
     def key_load_timers(self) -> List[float]:
@@ -711,6 +773,12 @@ class Context:
         v = [C.c_uint64() for _ in range(2)]
         _check(lib().fr_debug_arena_stats(self.h, *[C.byref(x) for x in v]))
         return dict(zip(("slots", "free_slots"), (x.value for x in v)))
+
+    def handle_count(self) -> int:
+        """fr_debug_handle_count: the handles not yet released"""
+        v = C.c_uint64()
+        _check(lib().fr_debug_handle_count(self.h, C.byref(v)))
+        return v.value
 
     def set_profiling(self, on):
         """0/False off, 1/True blind-rotation timers, 2 also keyswitch timers (fr_set_profiling)."""
@@ -956,6 +1024,27 @@ class Context:
         hs = list(out)[:max(hi - lo, 0)]
         return (hs, st) if stats else hs
 
+    def match_starts_packed(self, content: Sequence[int], pattern: str, lo: Optional[int] = None,
+                            hi: Optional[int] = None, compact: bool = True, stats: bool = False):
+        """fr_match_starts_packed: the booleans of match_starts over [lo, hi) (at most N starts)
+        as one reply blob -- compact: the FRCPRES1 form decrypt_packed_compact opens, else the
+        FRPKRES1 form of pack_bools -- with no handle in between; with stats=True also the
+        MatchStats"""
+        content = np.ascontiguousarray(content, dtype=np.uint32)
+        arr = content.ctypes.data_as(C.POINTER(C.c_uint32))
+        lo = 0 if lo is None else lo
+        hi = len(content) if hi is None else hi
+        pat = pattern.encode("latin-1")
+        n = C.c_size_t()
+        st = MatchStats()
+        _check(lib().fr_match_starts_packed(self.h, arr, len(content), pat, lo, hi, int(compact), None, 0, C.byref(n),
+                                            None))
+        buf = C.create_string_buffer(n.value)
+        _check(lib().fr_match_starts_packed(self.h, arr, len(content), pat, lo, hi, int(compact), buf, n.value,
+                                            C.byref(n), C.byref(st)))
+        blob = buf.raw[:n.value]
+        return (blob, st) if stats else blob
+
     def has_match_batch(self, contents: Sequence[Sequence[int]], pattern: str):
         """M independent matches of one pattern over M equal-length contents in
         shared launches (fr_has_match_batch): ([out handle per match], stats)."""
@@ -1040,6 +1129,10 @@ class Context:
 
 
 # ------------------------------------------------------------- reference API
+# first word of a compact match_starts reply; never a chunk count of the full form's framing
+COMPACT_REPLY = 0xFFFFFFFF
+
+
 @dataclass
 class ClientKey:
     ctx: Context
@@ -1071,6 +1164,8 @@ class ClientKey:
         if len(reply) < 4:
             raise ValueError("not a match_starts reply")
         (chunks,) = struct.unpack_from("<I", reply, 0)
+        if chunks == COMPACT_REPLY:
+            return self._decrypt_starts_compact(reply)
         if chunks == 0 and len(reply) == 4:
             return []  # an empty content has no start
         size = (len(reply) - 4) // chunks if chunks else 0
@@ -1081,6 +1176,29 @@ class ClientKey:
             bits = self.ctx.decrypt_packed(reply[4 + c * size:4 + (c + 1) * size])
             offs += [base + j for j, b in enumerate(bits) if b]
             base += len(bits)
+        return offs
+
+    def _decrypt_starts_compact(self, reply: bytes) -> List[int]:
+        """the compact reply: u32 0xFFFFFFFF, u32 chunks, then the chunks' FRCPRES1 blobs, each
+        delimited by its own header (32 + 2 (kN + n) bytes, n at byte 16)"""
+        if len(reply) < 8:
+            raise ValueError("not a match_starts reply")
+        (chunks,) = struct.unpack_from("<I", reply, 4)
+        kN = self.ctx.params.k * self.ctx.params.N
+        offs, base, at = [], 0, 8
+        for _ in range(chunks):
+            if at + 32 > len(reply):
+                raise ValueError("not a match_starts reply: a chunk's header overruns the reply")
+            (n,) = struct.unpack_from("<Q", reply, at + 16)
+            size = 32 + 2 * (kN + n)
+            if n > self.ctx.params.N or at + size > len(reply):
+                raise ValueError("not a match_starts reply: a chunk overruns the reply")
+            bits = self.ctx.decrypt_packed_compact(reply[at:at + size])
+            offs += [base + j for j, b in enumerate(bits) if b]
+            base += len(bits)
+            at += size
+        if at != len(reply):
+            raise ValueError("not a match_starts reply: bytes after the last chunk")
         return offs
 
     def serialize(self) -> bytes:
@@ -1105,11 +1223,18 @@ class ServerKey:
         packing key: gen_keys(packing=True) or load(..., packing_path))"""
         return self.ctx.pack_bools(handles)
 
-    def match_starts(self, content: Sequence[int], pattern: str) -> bytes:
+    def match_starts(self, content: Sequence[int], pattern: str, compact: bool = False) -> bytes:
         """where the pattern matches in the content, as one reply for ClientKey.decrypt_starts:
         a u32 count of chunks, then one packed result blob per chunk of N start offsets (a
-        content of up to N characters: one 32 KB blob).  The handles are released."""
+        content of up to N characters: one 32 KB blob).  The handles are released.
+        compact=True: u32 0xFFFFFFFF (no chunk count of the form above), a u32 count of chunks,
+        then one compact blob of 32 + 2 (kN + n) bytes per chunk of n <= N starts, each from one
+        fr_match_starts_packed call: no handles, 4,640 bytes for 256 characters at (1, 2048)."""
         N = self.ctx.params.N
+        if compact:
+            blobs = [self.ctx.match_starts_packed(content, pattern, lo, min(lo + N, len(content)))
+                     for lo in range(0, len(content), N)]
+            return struct.pack("<II", COMPACT_REPLY, len(blobs)) + b"".join(blobs)
         hs = self.ctx.match_starts(content, pattern)
         try:
             blobs = [self.ctx.pack_bools(hs[i:i + N]) for i in range(0, len(hs), N)]

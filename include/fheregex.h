@@ -309,6 +309,34 @@ int fr_packed_result_size(fr_ctx* ctx, size_t n, size_t* bytes);
 int fr_pack_bools(fr_ctx* ctx, const fr_ct* bools, size_t n, uint64_t* out_words);
 int fr_pack_bools_blob(fr_ctx* ctx, const fr_ct* bools, size_t n, uint8_t* buf, size_t cap, size_t* written);
 int fr_decrypt_packed(fr_ctx* ctx, const uint8_t* blob, size_t len, uint8_t* bits, size_t* n);
+/* Compact packed result (DESIGN.md §1 "Compact reply", §7).  A packed boolean is never
+ * bootstrapped again, so only the client's rounding at Delta/2 = 2^58 sees its error.  Every
+ * coefficient travels rounded to its top 16 bits, v = ((x + 2^47) >> 48) mod 2^16, and is
+ * installed as v << 48, mask and body alike; the body coefficients past n carry no boolean and
+ * are not sent.  The rounding adds std sqrt((h+1)/12) * 2^48 to the phase (h the key's weight:
+ * 2^51.2 at h = 1024).  The wire blob, little endian, exactly fr_packed_compact_size bytes =
+ * 32 + 2*(kN + n) (4,640 at n = 256, 8,224 at n = N, 4,130 at n = 1, all at (1, 2048)):
+ *     0  "FRCPRES1"
+ *     8  int32 k, N
+ *    16  u64 n                      (1 <= n <= N)
+ *    24  u32 16 (coefficient bits), u32 0 (reserved)
+ *    32  u16 mask[k*N]              (the k mask polynomials, rounded)
+ *    ..  u16 body[n]                (body coefficients 0..n-1, rounded)
+ * fr_pack_bools_compact is fr_pack_bools_blob in this form: a device context rounds on the GPU
+ * and downloads the 2*(kN + n) bytes alone; a host-only context packs trivial booleans.
+ * fr_compress_packed is the same rounding of (k+1)*N given words on the host, word for word
+ * what the device gives (buf == NULL: size query).  fr_expand_packed_compact checks a blob and
+ * writes its (k+1)*N words, v << 48 and a zero body past n (words == NULL: *n only).
+ * fr_decrypt_packed_compact (client key needed): bits[j] = round(phase_j / 2^59) & 1 of the
+ * expanded words for j < n (bits == NULL: *n only); the coefficients past n were not sent, so
+ * unlike fr_decrypt_packed there is nothing to check there.  The last two refuse a wrong
+ * length, a wrong magic (FRPKRES1 included), another k or N, n outside 1..N, a bit count other
+ * than 16 and a non-zero reserved word with FR_ERR_INVALID before anything is allocated. */
+int fr_packed_compact_size(fr_ctx* ctx, size_t n, size_t* bytes);
+int fr_pack_bools_compact(fr_ctx* ctx, const fr_ct* bools, size_t n, uint8_t* buf, size_t cap, size_t* written);
+int fr_compress_packed(fr_ctx* ctx, const uint64_t* words, size_t n, uint8_t* buf, size_t cap, size_t* written);
+int fr_expand_packed_compact(fr_ctx* ctx, const uint8_t* blob, size_t len, uint64_t* words, size_t* n);
+int fr_decrypt_packed_compact(fr_ctx* ctx, const uint8_t* blob, size_t len, uint8_t* bits, size_t* n);
 
 /* ----- client side (not on the timed path) ----- */
 /* Seeded encryption, for tests and benchmarks only: two calls with one seed share their
@@ -521,6 +549,9 @@ int fr_device_timers_content(fr_ctx* ctx, double* ms);
 /* The stages of the last fr_pack_bools made under fr_set_profiling, by HIP events:
  * ms[0..2] = digits (with the zeroing of the scratch), int8 GEMM, rotate-and-sum. */
 int fr_device_timers_pack(fr_ctx* ctx, double* ms /* 3 */);
+/* The same three stages and ms[3], the compact form's rounding kernel (0 after a pack in the
+ * full form), of the last pack of either form, fr_match_starts_packed's included. */
+int fr_device_timers_pack_compact(fr_ctx* ctx, double* ms /* 4 */);
 
 /* Match starts: where the pattern matches, not only whether.  out[s - start_lo] is a boolean
  * handle that decrypts to whether the pattern matches starting at offset s, for every s of
@@ -533,6 +564,20 @@ int fr_device_timers_pack(fr_ctx* ctx, double* ms /* 3 */);
  * into one reply. */
 int fr_match_starts(fr_ctx* ctx, const fr_ct* content, size_t n_chars, const char* pattern, size_t start_lo,
                     size_t start_hi, fr_ct* out /* start_hi - start_lo */, fr_match_stats* stats);
+/* From match to reply in one call: fr_match_starts' booleans of [start_lo, start_hi),
+ * 1 <= start_hi - start_lo <= N, packed into one blob, compact = 0 the FRPKRES1 form and 1 the
+ * FRCPRES1 form, byte for byte what fr_match_starts + fr_pack_bools_blob (then
+ * fr_compress_packed) give.  The plan is fr_match_starts' own: one compiled by either call
+ * serves the other.  Each start's affine output is read by the packing keyswitch straight
+ * from the plan's gate slot: no handle, no arena slot and no launch per start.  With
+ * fr_set_lanes the pack runs on the match's own lane after the plan's launches, on that lane's
+ * scratch; the call returns after its own download and waits for no other lane, so replies of
+ * matches on different lanes overlap (after fr_set_async(0) it then waits for every lane, as
+ * every blocking match does).  buf == NULL: size query.  FR_ERR_INVALID without a
+ * packing key, before anything is launched; other errors as fr_match_starts. */
+int fr_match_starts_packed(fr_ctx* ctx, const fr_ct* content, size_t n_chars, const char* pattern, size_t start_lo,
+                           size_t start_hi, int32_t compact, uint8_t* buf, size_t cap, size_t* written,
+                           fr_match_stats* stats);
 
 /* ----- one match split across ranks ----- */
 /* The reference folds ct_or over the branches of every start offset
@@ -738,6 +783,8 @@ uint64_t fr_debug_scalar(int32_t op, uint64_t x, uint64_t y);
  * *free_slots = the length of the free list; slots - free_slots are held by handles, cached
  * plans and shard plans. */
 int fr_debug_arena_stats(fr_ctx* ctx, uint64_t* slots, uint64_t* free_slots);
+/* The handle table (test hook): *live = the handles not yet released. */
+int fr_debug_handle_count(fr_ctx* ctx, uint64_t* live);
 
 #ifdef __cplusplus
 }
