@@ -488,6 +488,26 @@ int fr_dev_blind_rotate(fr_ctx* ctx, const uint64_t* in, const uint8_t* luts, si
         ctx->device().blind_rotate_host(in, luts, count, out);
     })
 }
+int fr_dev_blind_rotate_acc(fr_ctx* ctx, const uint64_t* in, const uint64_t* accs, size_t count, uint64_t* out) {
+    FR_TRY({
+        NEED(ctx && in && accs && out);
+        ctx->device().blind_rotate_acc_host(in, accs, count, out);
+    })
+}
+int fr_plain_find(const char* content, size_t len, const uint16_t* masks, size_t m, size_t start_lo, size_t start_hi,
+                  uint8_t* starts_out, int32_t* any) {
+    FR_TRY({
+        NEED((content || !len) && masks && any && start_lo <= start_hi && (starts_out || start_lo == start_hi));
+        NEED(m >= 1 && m <= NEEDLE_MAX_CHARS);
+        // both lowered programs, evaluated gate by gate: the per-start outputs and the OR tree's root
+        std::vector<int> vals;
+        eval_program_parts(compile_needle(len, m, start_lo, start_hi, true), (const uint8_t*)content, len, vals, masks,
+                           2 * m);
+        for (size_t j = 0; j < vals.size(); ++j) starts_out[j] = (uint8_t)vals[j];
+        *any = eval_program_parts(compile_needle(len, m, start_lo, start_hi, false), (const uint8_t*)content, len, vals,
+                                  masks, 2 * m);
+    })
+}
 int fr_dev_ring_mul(fr_ctx* ctx, const uint64_t* a, const uint64_t* b, size_t count, uint64_t* out) {
     FR_TRY({
         NEED(ctx && a && b && out);

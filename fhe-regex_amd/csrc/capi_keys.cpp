@@ -603,6 +603,72 @@ int fr_upload_compact_blocks(fr_ctx* ctx, const uint8_t* blob, size_t len, fr_ct
     FR_TRY(upload_compact(ctx, blob, len, false, out, cap, n))
 }
 
+// ---- private search (keys.h): the client encrypts the needle's 2 m nibble tables as GLWE
+// selectors (bodies + mask key), the server expands them on the host and uploads them once
+
+int fr_needle_size(fr_ctx* ctx, size_t m, size_t* bytes) {
+    FR_TRY({
+        NEED(ctx && bytes);
+        *bytes = needle_blob_size(ctx->p, m);
+    })
+}
+
+int fr_encrypt_needle_keyed(fr_ctx* ctx, const uint16_t* masks, size_t m, const uint8_t* key32, uint8_t* buf,
+                            size_t cap, size_t* written) {
+    FR_TRY({
+        NEED(ctx && masks && written);
+        if (ctx->p.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "private search: FFT ring only");
+        if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
+        const size_t need = needle_blob_size(ctx->p, m);
+        *written = need;
+        if (!buf) return FR_OK;  // size query
+        NEED(cap >= need);
+        ScopedKey key(key32);
+        const std::vector<uint8_t> blob = encrypt_needle_blob(ctx->p, ctx->ck, masks, m, key.k);
+        std::memcpy(buf, blob.data(), need);
+    })
+}
+
+int fr_expand_needle(fr_ctx* ctx, const uint8_t* blob, size_t len, uint64_t* words, size_t cap_words, size_t* m) {
+    FR_TRY({
+        NEED(ctx && blob && m);
+        const NeedleBlob nb = check_needle_blob(ctx->p, blob, len);
+        *m = nb.m;
+        if (!words) return FR_OK;  // size query
+        NEED(cap_words >= needle_words(ctx->p, nb.m));
+        expand_needle(ctx->p, blob, len, words);
+    })
+}
+
+int fr_upload_needle(fr_ctx* ctx, const uint8_t* blob, size_t len, fr_needle** out) {
+    FR_TRY({
+        NEED(ctx && blob && out);
+        // the blob is checked before the device is asked for and before anything is allocated
+        const NeedleBlob nb = check_needle_blob(ctx->p, blob, len);
+        Device& dev = ctx->device();
+        std::vector<uint64_t> words(needle_words(ctx->p, nb.m));  // at most 4 MB
+        expand_needle(ctx->p, blob, len, words.data());
+        auto nd = std::unique_ptr<fr_needle>(new fr_needle{dev.upload_needle(words.data(), nb.m), ctx->p.k, ctx->p.N});
+        *out = nd.release();
+    })
+}
+
+int fr_needle_len(const fr_needle* needle, size_t* m) {
+    FR_TRY({
+        NEED(needle && m);
+        *m = needle->dev.m;
+    })
+}
+
+int fr_needle_free(fr_ctx* ctx, fr_needle* needle) {
+    FR_TRY({
+        NEED(ctx);
+        if (needle && needle->dev.dev != ctx->dev.get())
+            throw Error(FR_ERR_INVALID, "needle: uploaded to another context");
+        delete needle;  // waits for every lane first (DevNeedle)
+    })
+}
+
 // bincode (fixint, little endian) of tfhe-rs 0.2 RadixCiphertext:
 //   u64 n_blocks, then per block: u64 len, len x u64 LWE words, u64 degree,
 //   u64 message_modulus, u64 carry_modulus

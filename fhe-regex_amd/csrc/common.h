@@ -46,6 +46,9 @@ FR_UNROLL
 // signed base 2^7, 3 levels.  |digit| <= 64 fits int8, and a digit-times-byte-limb sum over
 // the 3 kN rows stays below 64 * 128 * 6144 < 2^26, exact in i32.
 constexpr int PK_BASE_LOG = 7, PK_LEVELS = 3;
+// Private search: the longest needle, in characters (two selectors each).  The one bound of
+// the blob (keys.h), the lowering (lower.h) and the device's selector table (device.h).
+constexpr size_t NEEDLE_MAX_CHARS = 64;
 
 FR_HD uint32_t mod_switch(uint64_t a, int log2N2) {
     return (uint32_t)((((a >> (64 - log2N2 - 1)) + 1) >> 1) & ((1ULL << log2N2) - 1));

@@ -155,6 +155,12 @@ struct fr_ctx {
     }
 };
 
+// a needle uploaded to a device context (private search): its selectors and the (k, N) they are for
+struct fr_needle {
+    fr::DevNeedle dev;
+    int k = 0, N = 0;
+};
+
 #define FR_TRY(...)                                   \
     try {                                             \
         __VA_ARGS__;                                       \

@@ -21,7 +21,10 @@ constexpr int MAX_OUT = 8;
 // sparse small-integer product w_f per output (see k_blind_rotate).
 // direct = 2: sign gate, test polynomial (Delta/2)*sum_j X^j, one output
 // [c > 0] obtained as +-Delta/2 + Delta/2.
-enum : int32_t { JOB_MULTI = 0, JOB_DIRECT = 1, JOB_SIGN = 2 };
+// direct = 3: selector job (private search), one output.  The rotation starts from a GLWE
+// ciphertext of a direct test polynomial, selector acc_selector(gate) of the table bound last
+// (bind_selectors), instead of from a LUT's own; sample extract as direct = 1.  FFT ring only.
+enum : int32_t { JOB_MULTI = 0, JOB_DIRECT = 1, JOB_SIGN = 2, JOB_ACC = 3 };
 struct DevGate {
     int32_t n_in;
     int32_t offset;  // units of Delta/2 = 2^58
@@ -33,6 +36,15 @@ struct DevGate {
     uint8_t lut[MAX_OUT][16];
 };
 static_assert(sizeof(DevGate) == 304, "DevGate layout");
+// a selector job's index: the first four bytes of lut[0], little endian
+constexpr int MAX_SELECTORS = 2 * (int)NEEDLE_MAX_CHARS;
+FR_HD uint32_t acc_selector(const DevGate& g) {
+    return (uint32_t)g.lut[0][0] | ((uint32_t)g.lut[0][1] << 8) | ((uint32_t)g.lut[0][2] << 16) |
+           ((uint32_t)g.lut[0][3] << 24);
+}
+inline void set_acc_selector(DevGate& g, uint32_t q) {
+    for (int i = 0; i < 4; ++i) g.lut[0][i] = (uint8_t)(q >> (8 * i));
+}
 // sum of squared w_f coefficients of a LUT (noise growth of its factored output)
 int lut_w_norm2(const uint8_t* lut);
 
@@ -52,6 +64,19 @@ struct RngKey;
 class Device;
 // arena slots owned by a call, a plan or a handle in the making (owned.h)
 using Slots = gpu::SlotsOf<Device>;
+
+// A needle on the device (private search): its 2 m selectors, [selector][polynomial][N] u64.
+// Move-only.  Finds on any lane may read it, so, by Plan's rule (plan.h), it waits for every
+// lane before its memory goes.
+struct DevNeedle {
+    gpu::DevBuf<uint64_t> words;
+    size_t m = 0;  // characters: 2 m selectors
+    Device* dev = nullptr;
+    DevNeedle() = default;
+    DevNeedle(DevNeedle&&) = default;
+    DevNeedle& operator=(DevNeedle&&) = delete;
+    ~DevNeedle();
+};
 
 class Device {
   public:
@@ -168,6 +193,13 @@ class Device {
     // read by the plan).  Stream-ordered: launches enqueued after this call see it,
     // launches enqueued before it keep the previous map.
     void bind_content(const int* cmap, size_t n);
+    // Private search (FFT ring).  upload_needle: the 2 m expanded selectors (2 m (k+1) N words),
+    // one H2D copy, synchronous.  bind_selectors is to a selector launch what bind_content is to
+    // a template plan: JOB_ACC jobs enqueued on the current lane after it read selector q < count
+    // at table + q (k+1) N (the pointer is a launch argument: launches enqueued before keep
+    // theirs).  nullptr: none bound.
+    DevNeedle upload_needle(const uint64_t* words, size_t m);
+    void bind_selectors(const uint64_t* table, size_t count);
     // linear combination without bootstrap (NOT of a boolean): out = offset*2^58 + sum w*in
     void run_linear(const DevGate& g);
     void sync();
@@ -191,6 +223,8 @@ class Device {
     void blind_rotate_host(const uint64_t* ks_in, const uint8_t* luts, size_t count, uint64_t* out);
     // one job with n_out LUTs on one keyswitched input (multi-value or direct)
     void blind_rotate_multi_host(const uint64_t* ks_in, const uint8_t* luts, int n_out, int direct, uint64_t* out);
+    // one selector launch: job i starts from the GLWE ciphertext accs + i (k+1) N
+    void blind_rotate_acc_host(const uint64_t* ks_in, const uint64_t* accs, size_t count, uint64_t* out);
     void ring_mul_host(const uint64_t* a, const uint64_t* b, size_t count, uint64_t* out);
     // repeated full-PBS batches on resident inputs (bench / roofline)
     void bench_pbs(const std::vector<DevGate>& gates, int iters, double* br_ms, double* total_ms);
@@ -213,6 +247,8 @@ class Device {
         gpu::DevBuf<double> kpre;
         gpu::StagingRing<int> cmap;  // content map (bind_content)
         size_t cmap_n = 0;           // entries bound
+        const uint64_t* sel = nullptr;  // selector table (bind_selectors)
+        size_t sel_n = 0;               // selectors bound
         gpu::Event done_ev;          // recorded on the lane's stream when it is left
         bool pending = false;        // work enqueued since lane 0 last waited for it
     };
@@ -285,8 +321,12 @@ class Device {
                           int out_stride, hipEvent_t ev_stop);
     void launch_ks(const DevGate* d_gates, size_t n, uint64_t* d_ks, hipEvent_t ev_start = nullptr,
                    hipEvent_t ev_stop = nullptr);
+    // acc: a launch of selector jobs (JOB_ACC) only; else none of them
     void launch_br(const DevGate* d_gates, const uint64_t* d_ks, size_t n, hipEvent_t ev_start = nullptr,
-                   hipEvent_t ev_stop = nullptr);
+                   hipEvent_t ev_stop = nullptr, bool acc = false);
+    // selector jobs come first in a batch: their count, checked against the table bound
+    size_t leading_selector_jobs(const DevGate* host, size_t n) const;
+    void launch_jobs(const DevGate* d_gates, const DevGate* host, size_t n, bool acc);  // one keyswitch + rotation
     void run_br_jobs(const uint64_t* ks_in, std::vector<DevGate>& gates, uint64_t* out);  // the blind_rotate_*_host hooks
     // FR_RING_RNS (rns_br.hip)
     void init_rns();
@@ -297,7 +337,7 @@ class Device {
     void init_fft();
     void upload_fft_bsk(const std::vector<uint64_t>& bsk);
     void launch_br_fft(const DevGate* d_gates, const uint64_t* d_ks, size_t n, hipStream_t stream,
-                       hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+                       hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, bool acc = false);
     void build_fourier_bsk();  // keygen.hip: d_fbsk_ (every lane layout in use) from d_tbsk_
     double key_load_ms_[5] = {0, 0, 0, 0, 0};
     double pk_load_ms_[3] = {0, 0, 0};

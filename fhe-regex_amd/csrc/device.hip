@@ -313,17 +313,23 @@ void Device::upload_keys(const std::vector<uint64_t>& ksk, const std::vector<uin
 bool Device::latency_shape(size_t n) const { return n <= (p_.ring == FR_RING_FFT ? fft_small_ : small_batch_); }
 bool Device::pair_shape(size_t n) const { return p_.ring == FR_RING_FFT && !latency_shape(n) && n <= fft_pair_; }
 
-void Device::launch_br(const DevGate* d_gates, const uint64_t* d_ks, size_t n, hipEvent_t ev_start, hipEvent_t ev_stop) {
-    if (p_.ring == FR_RING_FFT) launch_br_fft(d_gates, d_ks, n, cur().stream.get(), ev_start, ev_stop);
+void Device::launch_br(const DevGate* d_gates, const uint64_t* d_ks, size_t n, hipEvent_t ev_start, hipEvent_t ev_stop,
+                       bool acc) {
+    if (acc && p_.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "private search: FFT ring only");
+    if (p_.ring == FR_RING_FFT) launch_br_fft(d_gates, d_ks, n, cur().stream.get(), ev_start, ev_stop, acc);
     else launch_br_rns(d_gates, d_ks, n, ev_start, ev_stop);
 }
 
 void Device::validate_gates(const DevGate* gates, size_t n, size_t n_refs) const {
     for (size_t i = 0; i < n; ++i) {
         const DevGate& g = gates[i];
-        if (g.n_in < 0 || g.n_in > 16 || g.n_out < 1 || g.n_out > MAX_OUT || g.direct < 0 || g.direct > 2 ||
+        if (g.n_in < 0 || g.n_in > 16 || g.n_out < 1 || g.n_out > MAX_OUT || g.direct < 0 || g.direct > JOB_ACC ||
             (g.direct && g.n_out != 1))
             throw Error(FR_ERR_INVALID, "device gate: bad descriptor");
+        if (g.direct == JOB_ACC) {
+            if (p_.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "private search: FFT ring only");
+            if (acc_selector(g) >= (uint32_t)MAX_SELECTORS) throw Error(FR_ERR_INVALID, "device gate: bad selector index");
+        }
         for (int f = 0; f < g.n_out; ++f)
             if (g.out_slot[f] < 0 || (size_t)g.out_slot[f] >= next_slot_) throw Error(FR_ERR_INVALID, "device gate: bad output slot");
         for (int q = 0; q < g.n_in; ++q) {
@@ -350,6 +356,46 @@ void Device::bind_content(const int* cmap, size_t n) {
         l.cmap.commit(n, s);
     }
     l.cmap_n = n;
+}
+
+DevNeedle::~DevNeedle() {
+    if (!words || !dev) return;
+    try {
+        dev->sync();
+    } catch (...) {  // (the buffer goes all the same)
+    }
+}
+
+DevNeedle Device::upload_needle(const uint64_t* words, size_t m) {
+    if (p_.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "private search: FFT ring only");
+    if (!words || m < 1 || 2 * m > (size_t)MAX_SELECTORS) throw Error(FR_ERR_INVALID, "needle: 1 <= m <= 64");
+    DevNeedle nd;
+    nd.dev = this;
+    nd.m = m;
+    nd.words.alloc(2 * m * (size_t)(p_.k + 1) * p_.N);
+    HIP_CHECK(hipMemcpy(nd.words.get(), words, 8 * nd.words.size(), hipMemcpyHostToDevice));
+    return nd;
+}
+
+void Device::bind_selectors(const uint64_t* table, size_t count) {
+    if (table && p_.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "private search: FFT ring only");
+    cur().sel = table;
+    cur().sel_n = table ? count : 0;
+}
+
+size_t Device::leading_selector_jobs(const DevGate* host, size_t n) const {
+    // build_schedule puts a level's selector jobs first: a batch that does not begin with one
+    // has none, and every match without a needle leaves here
+    if (!n || host[0].direct != JOB_ACC) return 0;
+    size_t a = 0;
+    while (a < n && host[a].direct == JOB_ACC) ++a;
+    for (size_t i = 0; i < n; ++i) {
+        if (host[i].direct != JOB_ACC) continue;
+        if (i >= a) throw Error(FR_ERR_INVALID, "selector jobs must lead their level");
+        if ((size_t)acc_selector(host[i]) >= cur().sel_n)
+            throw Error(FR_ERR_INVALID, "selector job: index past the selector table bound");
+    }
+    return a;
 }
 
 void Device::run_level(const DevGate* gates, size_t n) {
@@ -381,7 +427,14 @@ gpu::DevBuf<DevGate> Device::upload_gates(const DevGate* gates, size_t n, size_t
     return d;
 }
 
+// a level's selector jobs (they lead it) are launched apart from its other jobs
 void Device::launch_level(const DevGate* d_gates, const DevGate* host, size_t n) {
+    const size_t a = leading_selector_jobs(host, n);
+    if (a) launch_jobs(d_gates, host, a, true);
+    if (n > a) launch_jobs(d_gates + a, host + a, n - a, false);
+}
+
+void Device::launch_jobs(const DevGate* d_gates, const DevGate* host, size_t n, bool acc) {
     PendingTimer t{};
     if (profiling_)
         for (auto& e : t.ev) e = take_event();
@@ -395,12 +448,12 @@ void Device::launch_level(const DevGate* d_gates, const DevGate* host, size_t n)
     uint64_t* d_ks = cur().ks.get();
     if (profiling_ >= 2) launch_ks(d_gates, n, d_ks, t.ev[0].get(), t.ev[1].get());
     else launch_ks(d_gates, n, d_ks, nullptr, t.chain ? t.ev[1].get() : nullptr);
-    launch_br(d_gates, d_ks, n, t.chain ? nullptr : t.ev[2].get(), t.ev[3].get());
+    launch_br(d_gates, d_ks, n, t.chain ? nullptr : t.ev[2].get(), t.ev[3].get(), acc);
     HIP_CHECK(hipGetLastError());
     if (profiling_) {
         t.gates = n;
         t.lat = latency_shape(n);
-        t.pair = pair_shape(n) && !fft_dual_;  // FR_FFT_DUAL launches: one bootstrap per workgroup
+        t.pair = pair_shape(n) && (!fft_dual_ || acc);  // FR_FFT_DUAL launches: one bootstrap per workgroup
         t.ks = profiling_ >= 2;
         t.outs = 0;
         for (size_t i = 0; i < n; ++i) t.outs += host[i].n_out;
@@ -448,7 +501,8 @@ void Device::resolve_timers() {
             timers_.pair_launches += 1;
             timers_.pair_gates += t.gates;
         }
-        for (auto& e : t.ev) event_pool_.push_back(std::move(e));
+        for (auto& e : t.ev)  // (a timer that stamped fewer than four holds empty ones)
+            if (e) event_pool_.push_back(std::move(e));
     }
     pending_.clear();
 }
@@ -516,9 +570,54 @@ void Device::run_br_jobs(const uint64_t* ks_in, std::vector<DevGate>& gates, uin
     for (auto& g : gates)
         for (int f = 0; f < g.n_out; ++f) g.out_slot[f] = slots[n_out++];
     HIP_CHECK(hipMemcpy(gates_.device(), gates.data(), sizeof(DevGate) * count, hipMemcpyHostToDevice));
-    launch_br(gates_.device(), d_ks, count);
-    HIP_CHECK(hipStreamSynchronize(STREAM));
+    const size_t a = leading_selector_jobs(gates.data(), count);
+    if (a && a != count) throw Error(FR_ERR_INVALID, "a launch is all selector jobs or none");
+    // under fr_set_profiling the launch is stamped by its own dispatch, as a level's is, and
+    // counts in the timers (tools/needle_probe.py compares the two kinds of launch by them)
+    PendingTimer t{};
+    if (profiling_) {
+        t.ev[2] = take_event(), t.ev[3] = take_event();
+        t.gates = count, t.outs = n_out;
+        t.lat = latency_shape(count);
+        t.pair = pair_shape(count) && (!fft_dual_ || a != 0);
+    }
+    launch_br(gates_.device(), d_ks, count, t.ev[2].get(), t.ev[3].get(), a != 0);
+    if (profiling_) {
+        pending_.push_back(std::move(t));
+        sync();  // every lane: the pending timers of queued matches are resolved with this one
+    } else {
+        HIP_CHECK(hipStreamSynchronize(STREAM));
+    }
     for (size_t i = 0; i < slots.size(); ++i) read_slot(slots[i], out + i * p_.lwe_len());
+}
+
+void Device::blind_rotate_acc_host(const uint64_t* ks_in, const uint64_t* accs, size_t count, uint64_t* out) {
+    if (p_.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "private search: FFT ring only");
+    if (!has_keys()) throw Error(FR_ERR_NO_KEY, "server key not uploaded");
+    if (lane_ != 0) throw Error(FR_ERR_INVALID, "parity hooks run on lane 0 only");
+    if (!count) return;
+    // each job its own accumulator: the table of this call alone, indices past MAX_SELECTORS allowed
+    const size_t W = (size_t)(p_.k + 1) * p_.N;
+    gpu::DevBuf<uint64_t> table(count * W);
+    HIP_CHECK(hipMemcpy(table.get(), accs, 8 * count * W, hipMemcpyHostToDevice));
+    std::vector<DevGate> gates(count);
+    for (size_t i = 0; i < count; ++i) {
+        std::memset(&gates[i], 0, sizeof(DevGate));
+        gates[i].n_out = 1;
+        gates[i].direct = JOB_ACC;
+        set_acc_selector(gates[i], (uint32_t)i);
+    }
+    const uint64_t* prev = cur().sel;
+    const size_t prev_n = cur().sel_n;
+    bind_selectors(table.get(), count);
+    try {
+        run_br_jobs(ks_in, gates, out);  // (synchronises before it returns: the table may go)
+    } catch (...) {
+        (void)hipStreamSynchronize(cur().stream.get());
+        bind_selectors(prev, prev_n);
+        throw;
+    }
+    bind_selectors(prev, prev_n);
 }
 
 void Device::blind_rotate_host(const uint64_t* ks_in, const uint8_t* luts, size_t count, uint64_t* out) {

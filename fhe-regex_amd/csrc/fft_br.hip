@@ -685,12 +685,18 @@ constexpr uint32_t kpre_step_bytes() {
 // The blind rotation of every launch shape.  KP (the latency shape, k = 1): the step's key
 // products K_own, K_oth come from kpre, where k_key_products put them before this launch
 // (kpre + bootstrap x steps x kpre_step_bytes), instead of the key, the psi table and the pair.
-template <int N, int K, int E, bool LAT, int B, bool KP>
+// ACC (a launch of JOB_ACC jobs only): the accumulator starts from the job's selector, a GLWE
+// ciphertext [polynomial][N] of the table sel ([selector][polynomial][N] u64), every polynomial
+// rotated by X^-bbar, instead of the trivial (0, .., 0, X^-bbar V(lut)).  Only the prologue
+// differs: the step loop and the tail are the other variants'.
+template <int N, int K, int E, bool LAT, int B, bool KP, bool ACC = false>
 __device__ __forceinline__ void fbr_rotate(const uint64_t* ks, int ks_stride, int n, const DevGate* gates, int n_gates,
                                            const double2* bsk, const double2* tw_g, const double2* psi_g,
-                                           const uint16_t* leaf_g, uint64_t* arena, int slot_stride, const double2* kpre) {
+                                           const uint16_t* leaf_g, uint64_t* arena, int slot_stride, const double2* kpre,
+                                           const uint64_t* sel = nullptr) {
     constexpr int M = N / 2;
     static_assert(!KP || (LAT && B == 1 && K == 1 && E == 4), "key products: the k = 1 latency shape");
+    static_assert(!(ACC && KP), "selector launches never take the key-products path");
     using G = FGeo<M, E>;
     static_assert(fexchanges_conflict_free<M, E>(), "LDS maps must make every exchange conflict-free");
     static_assert(G::base_matches_geo(), "base<p> must be the index map the LDS-map proofs reason about");
@@ -767,6 +773,25 @@ __device__ __forceinline__ void fbr_rotate(const uint64_t* ks, int ks_stride, in
     double alo[B][E], ahi[B][E];
 #pragma unroll
     for (int b = 0; b < B; ++b) {
+        if constexpr (ACC) {
+            // polynomial P of the job's selector (acc_selector: the index in the first LUT's
+            // bytes), straight from global memory: 16 KB per polynomial, read once
+            const uint64_t* A = sel + ((size_t)acc_selector(gates[gb[b]]) * (K + 1) + P) * N;
+#pragma unroll
+            for (int m = 0; m < E; ++m) {
+                const int j = G::template idx<0>(tl, m);
+                uint64_t v[2];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int s = (j + h * M + (int)bbar[b]) & (2 * N - 1);
+                    const uint64_t tv = A[s & (N - 1)];
+                    v[h] = s < N ? tv : (uint64_t)0 - tv;
+                }
+                alo[b][m] = fft::acc_of_torus(v[0]);
+                ahi[b][m] = fft::acc_of_torus(v[1]);
+            }
+            continue;
+        }
         const bool direct = kind[b] == JOB_DIRECT;
 #pragma unroll
         for (int m = 0; m < E; ++m) {
@@ -1067,6 +1092,18 @@ k_blind_rotate_fft_kp(const uint64_t* __restrict__ ks, int ks_stride, int n, con
                                       slot_stride, kpre);
 }
 
+// The selector variant of every shape (ACC), after the same pattern: kernels of their own name
+// with the shape's <N, K, E, LAT, B>, and the selector table as one more argument.
+template <int N, int K, int E, bool LAT, int B = 1>
+__global__ void __launch_bounds__((fbr_threads<N, K, E>()), (fbr_min_waves<N, K, E, LAT>()))
+k_blind_rotate_fft_acc(const uint64_t* __restrict__ ks, int ks_stride, int n, const DevGate* __restrict__ gates,
+                       int n_gates, const double2* __restrict__ bsk, const double2* __restrict__ tw_g,
+                       const double2* __restrict__ psi_g, const uint16_t* __restrict__ leaf_g,
+                       uint64_t* __restrict__ arena, int slot_stride, const uint64_t* __restrict__ sel) {
+    fbr_rotate<N, K, E, LAT, B, false, true>(ks, ks_stride, n, gates, n_gates, bsk, tw_g, psi_g, leaf_g, arena,
+                                             slot_stride, nullptr, sel);
+}
+
 // Producer of the key products (k = 1, E = 4): workgroup (t, P) holds step t's three GGSW
 // groups of polynomial P in registers (the lanes and loads of load_ggsw) and forms, for each
 // bootstrap b of the launch with a non-idle pair, the 2 E products of every lane by
@@ -1130,6 +1167,10 @@ k_key_products(const uint64_t* __restrict__ ks, int ks_stride, int n, int n_gate
 extern template __global__ void k_blind_rotate_fft<2048, 1, 4, true, 2>(const uint64_t*, int, int, const DevGate*, int,
                                                                          const double2*, const double2*, const double2*,
                                                                          const uint16_t*, uint64_t*, int);
+extern template __global__ void k_blind_rotate_fft_acc<2048, 1, 4, true, 2>(const uint64_t*, int, int, const DevGate*,
+                                                                             int, const double2*, const double2*,
+                                                                             const double2*, const uint16_t*, uint64_t*,
+                                                                             int, const uint64_t*);
 #endif
 
 // Dual shape (round 4 experiment, k = 1, FR_FFT_DUAL=1): one bootstrap per workgroup on
@@ -1322,6 +1363,8 @@ static void fft_attr() {
                   "LDS per workgroup of the shape");
     HIP_CHECK(hipFuncSetAttribute((const void*)k_blind_rotate_fft<N, K, E, LAT, B>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)fbr_smem_bytes<N, K, E, LAT, B>()));
+    HIP_CHECK(hipFuncSetAttribute((const void*)k_blind_rotate_fft_acc<N, K, E, LAT, B>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)fbr_smem_bytes<N, K, E, LAT, B>()));
 }
 
 // run body(N, K) with the compile-time ring dimensions of the parameters
@@ -1394,13 +1437,16 @@ void Device::upload_fft_bsk(const std::vector<uint64_t>& bsk) {
 }
 
 void Device::launch_br_fft(const DevGate* d_gates, const uint64_t* d_ks, size_t n, hipStream_t s, hipEvent_t ev_start,
-                           hipEvent_t ev_stop) {
+                           hipEvent_t ev_stop, bool acc) {
     // every blind-rotation kernel takes the same arguments; E picks the key's lane layout
-    auto launch = [&](auto kernel, size_t grid, int threads, size_t lds, int E) {
+    // (a selector launch: the table bound to the lane as one more)
+    const uint64_t* sel = cur().sel;
+    if (acc && !sel) throw Error(FR_ERR_INVALID, "selector jobs: no selector table bound");
+    auto launch = [&](auto kernel, size_t grid, int threads, size_t lds, int E, auto... more) {
         hipExtLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), (uint32_t)lds, s, ev_start, ev_stop, 0, d_ks,
                               p_.ks_stride(), p_.n, d_gates, (int)n, (const double2*)d_fbsk_[fbsk_index(E)].get(),
                               (const double2*)d_ftw_.get(), (const double2*)d_fqt_.get(),
-                              (const uint16_t*)d_fleaf_.get(), d_arena_.get(), p_.slot_stride());
+                              (const uint16_t*)d_fleaf_.get(), d_arena_.get(), p_.slot_stride(), more...);
     };
     fft_dispatch(p_, [&](auto nc, auto kc) {
         constexpr int N = decltype(nc)::value, K = decltype(kc)::value;
@@ -1408,9 +1454,14 @@ void Device::launch_br_fft(const DevGate* d_gates, const uint64_t* d_ks, size_t 
             constexpr int E = decltype(ec)::value;
             constexpr bool LAT = decltype(lat)::value;
             constexpr int B = decltype(bc)::value;
-            if constexpr (fft_supported(K, N, E) && (B == 1 || K == 1))
-                launch(k_blind_rotate_fft<N, K, E, LAT, B>, (n + B - 1) / B, fbr_threads<N, K, E>(),
-                       fbr_smem_bytes<N, K, E, LAT, B>(), E);
+            if constexpr (fft_supported(K, N, E) && (B == 1 || K == 1)) {
+                if (acc)
+                    launch(k_blind_rotate_fft_acc<N, K, E, LAT, B>, (n + B - 1) / B, fbr_threads<N, K, E>(),
+                           fbr_smem_bytes<N, K, E, LAT, B>(), E, sel);
+                else
+                    launch(k_blind_rotate_fft<N, K, E, LAT, B>, (n + B - 1) / B, fbr_threads<N, K, E>(),
+                           fbr_smem_bytes<N, K, E, LAT, B>(), E);
+            }
         };
         using I4 = std::integral_constant<int, 4>;
         using I8 = std::integral_constant<int, 8>;
@@ -1419,7 +1470,8 @@ void Device::launch_br_fft(const DevGate* d_gates, const uint64_t* d_ks, size_t 
         // (k = 1, at most fft_kpre_) as the producer of their key products, then the variant that
         // loads them, in stream order: the pair of kernels lies between ev_start and ev_stop, so
         // the producer's time counts as blind rotation
-        if (n <= fft_small_ && n <= fft_kpre_ && K == 1) {
+        // (selector launches: the shape by count alone -- never the key products, never the dual)
+        if (n <= fft_small_ && n <= fft_kpre_ && K == 1 && !acc) {
             if constexpr (K == 1) {
                 const int steps = (p_.n + 1) / 2;
                 const size_t per = (size_t)steps * (kpre_step_bytes<N, K>() / 8);  // doubles per bootstrap
@@ -1439,7 +1491,7 @@ void Device::launch_br_fft(const DevGate* d_gates, const uint64_t* d_ks, size_t 
                                       (const double2*)kpre.get());
             }
         } else if (n <= fft_small_) go(I4{}, std::true_type{}, B1{});
-        else if (n <= fft_pair_ && K == 1 && fft_dual_) {
+        else if (n <= fft_pair_ && K == 1 && fft_dual_ && !acc) {
             if constexpr (K == 1) launch(k_blind_rotate_fft_dual<N>, n, N / 8, fbr_dual_smem_bytes<N>(), 4);
         } else if (n <= fft_pair_) go(I4{}, std::true_type{}, std::integral_constant<int, 2>{});  // (k = 1)
         else if (fft_e_ == 4) go(I4{}, std::false_type{}, B1{});

@@ -921,6 +921,83 @@ void glwe_phase(const Params& p, const ClientKey& ck, const uint64_t* ct, uint64
     for (int t = 0; t < N; ++t) phase[t] = ct[(size_t)k * N + t] - as[t];
 }
 
+// ---------------------------------------------------------------- private search: the needle
+static const char NEEDLE_MAGIC[9] = "FRNEEDL1";
+
+size_t needle_blob_size(const Params& p, size_t m) {
+    if (m < 1 || m > NEEDLE_MAX_CHARS) throw Error(FR_ERR_INVALID, "needle: 1 <= m <= 64");
+    return NEEDLE_HEADER + 16 * m * (size_t)p.N;
+}
+
+uint64_t needle_test_poly(int N, int t, uint16_t table) {
+    const int box = N / 16, half = box / 2, mm = (t + half) / box;
+    const uint64_t v = (uint64_t)((table >> (mm < 16 ? mm : 0)) & 1) << DELTA_LOG;
+    return mm < 16 ? v : (uint64_t)0 - v;
+}
+
+NeedleBlob check_needle_blob(const Params& p, const uint8_t* blob, size_t len) {
+    if (p.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "private search: FFT ring only");
+    if (!blob || len < NEEDLE_HEADER) throw Error(FR_ERR_INVALID, "needle: length is not 64 + 16 m N (fr_needle_size)");
+    if (std::memcmp(blob, NEEDLE_MAGIC, 8)) throw Error(FR_ERR_INVALID, "needle: bad magic");
+    if (get_le32(blob + 8) != (uint32_t)p.k || get_le32(blob + 12) != (uint32_t)p.N)
+        throw Error(FR_ERR_INVALID, "needle: k, N do not match the context params");
+    const uint64_t m = get_le64(blob + 16);
+    if (m < 1 || m > NEEDLE_MAX_CHARS) throw Error(FR_ERR_INVALID, "needle: 1 <= m <= 64");
+    if (len != needle_blob_size(p, (size_t)m))
+        throw Error(FR_ERR_INVALID, "needle: length is not 64 + 16 m N (fr_needle_size)");
+    if (get_le64(blob + 56) != 0) throw Error(FR_ERR_INVALID, "needle: reserved bytes are not zero");
+    NeedleBlob nb;
+    nb.m = (size_t)m;
+    nb.mask_key = RngKey::from_bytes(blob + 24);
+    nb.bodies = blob + NEEDLE_HEADER;
+    return nb;
+}
+
+std::vector<uint8_t> encrypt_needle_blob(const Params& p, const ClientKey& ck, const uint16_t* masks, size_t m,
+                                         const RngKey& key) {
+    if (p.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "private search: FFT ring only");
+    if (ck.s_big.size() != (size_t)p.big()) throw Error(FR_ERR_INVALID, "needle: client key size");
+    const int k = p.k, N = p.N;
+    std::vector<uint8_t> out(needle_blob_size(p, m));
+    const RngKey mk = derive_mask_key(key);  // public
+    std::memcpy(out.data(), NEEDLE_MAGIC, 8);
+    put_le32(out.data() + 8, (uint32_t)k);
+    put_le32(out.data() + 12, (uint32_t)N);
+    put_le64(out.data() + 16, m);
+    for (int i = 0; i < 8; ++i) put_le32(out.data() + 24 + 4 * i, mk.w[i]);
+    put_le64(out.data() + 56, 0);
+    parallel_for((int)(2 * m), [&](int q) {
+        Rng rm(mk, STREAM_NEEDLE_MASK), rn(key, STREAM_NEEDLE_NOISE);
+        std::vector<uint64_t> A((size_t)N), B((size_t)N, 0);
+        for (int c = 0; c < k; ++c) {
+            const uint64_t base = ((uint64_t)q * k + c) * N;
+            for (int t = 0; t < N; ++t) A[t] = rm.u64(base + t);
+            const uint64_t* S = ck.s_big.data() + (size_t)c * N;
+            for (int u = 0; u < N; ++u)
+                if (S[u]) add_rotated(B.data(), A.data(), u, N);
+        }
+        uint8_t* o = out.data() + NEEDLE_HEADER + 8 * (size_t)q * N;
+        for (int t = 0; t < N; ++t) {
+            B[t] += needle_test_poly(N, t, masks[q]) + (uint64_t)rn.gaussian((uint64_t)q * N + t, p.glwe_sigma);
+            put_le64(o + 8 * (size_t)t, B[t]);
+        }
+        explicit_bzero(A.data(), 8 * A.size());  // (public) and the noisy body's scratch
+        explicit_bzero(B.data(), 8 * B.size());
+    });
+    return out;
+}
+
+void expand_needle(const Params& p, const uint8_t* blob, size_t len, uint64_t* out) {
+    const NeedleBlob nb = check_needle_blob(p, blob, len);
+    const size_t k = (size_t)p.k, N = (size_t)p.N;
+    parallel_for((int)(2 * nb.m), [&](int q) {
+        Rng rm(nb.mask_key, STREAM_NEEDLE_MASK);
+        uint64_t* o = out + (size_t)q * (k + 1) * N;
+        for (size_t t = 0; t < k * N; ++t) o[t] = rm.u64((uint64_t)q * k * N + t);
+        for (size_t t = 0; t < N; ++t) o[k * N + t] = get_le64(nb.bodies + 8 * ((size_t)q * N + t));
+    });
+}
+
 uint32_t decode16(uint64_t phase) {
     const uint64_t delta = 1ULL << DELTA_LOG;
     uint64_t rounding = (phase & (delta >> 1)) << 1;

@@ -25,6 +25,8 @@ enum Stream : uint64_t {
     STREAM_MASK_KEY = 8,  // block 0, words 0..7: the public mask key of a compact server key or content blob
     STREAM_PKSK_MASK = 9,
     STREAM_PKSK_NOISE = 10,
+    STREAM_NEEDLE_MASK = 11,
+    STREAM_NEEDLE_NOISE = 12,
 };
 
 class Rng {
@@ -241,6 +243,36 @@ std::vector<uint8_t> encrypt_content_blob(const Params& p, const ClientKey& ck, 
 // check_content_blob (radix = false), then every mask from the mask key around the blob's
 // bodies; out has n_blocks * (kN+1) words.  Needs no client key.
 void expand_content(const Params& p, const uint8_t* blob, size_t len, uint64_t* out);
+// Private search: an encrypted needle, FFT ring.  A selector is a GLWE
+// ciphertext, k mask polynomials then the body, (k+1) N words, under the GLWE key (the big key
+// read as k polynomials) whose phase is the direct test polynomial V(T) of a 0/1 table T of
+// the 16 nibble values: boxes of N/16 recentred by half a box, -T[0] in the last half box,
+// T[s] 2^59 (needle_test_poly: the device's test_poly).  A needle of m characters is 2 m
+// selectors, selector 2 i + h the table of nibble h (0: low) of character i, a table the
+// 16-bit mask of its accepted values.  Mask word t of mask polynomial c of selector q is u64
+// number (q k + c) N + t of STREAM_NEEDLE_MASK under the public mask key M = derive_mask_key(K);
+// the noise is the gaussian (glwe sigma) of STREAM_NEEDLE_NOISE under the call's secret key K
+// at q N + t; body = sum_c A_c S_c + V(T_q) + e, negacyclic.  No secret touches a mask word.
+// Wire blob (include/fheregex.h): "FRNEEDL1", int32 k, N, u64 m, the mask key, 8 zero bytes,
+// then the 2 m body polynomials of N u64; little endian, exactly 64 + 16 m N bytes.
+constexpr size_t NEEDLE_HEADER = 64;
+inline size_t needle_words(const Params& p, size_t m) { return 2 * m * (size_t)(p.k + 1) * p.N; }
+size_t needle_blob_size(const Params& p, size_t m);  // Error(FR_ERR_INVALID) unless 1 <= m <= 64
+uint64_t needle_test_poly(int N, int t, uint16_t table);
+struct NeedleBlob {
+    RngKey mask_key;
+    size_t m = 0;
+    const uint8_t* bodies = nullptr;  // 2 m N u64, little endian, any alignment
+};
+// Error(FR_ERR_INVALID) unless the ring is the FFT ring, len is exact, the magic matches, k and N
+// are p's, 1 <= m <= 64 and the pad is zero; nothing is allocated
+NeedleBlob check_needle_blob(const Params& p, const uint8_t* blob, size_t len);
+// masks: lo, hi per character (2 m tables); `key` is the caller's to wipe
+std::vector<uint8_t> encrypt_needle_blob(const Params& p, const ClientKey& ck, const uint16_t* masks, size_t m,
+                                         const RngKey& key);
+// check_needle_blob, then every mask from the mask key around the blob's bodies: out has
+// needle_words(p, m) words, [selector][polynomial][N].  Needs no client key.
+void expand_needle(const Params& p, const uint8_t* blob, size_t len, uint64_t* out);
 uint64_t lwe_phase(const Params& p, const ClientKey& ck, const uint64_t* lwe);
 // tfhe-rs shortint decrypt_message_and_carry: round(phase / Delta) mod 16
 uint32_t decode16(uint64_t phase);

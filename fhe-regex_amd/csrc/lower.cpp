@@ -720,12 +720,73 @@ CompiledStarts compile_match_starts(const MatchSpec& s, bool keep_dags) {
     return m;
 }
 
+// AND / OR of the gates `lits` as a balanced tree of threshold gates (threshold_gate's offsets,
+// no negations), appended to prog; the root's index (one literal: itself)
+static int threshold_tree(Program& prog, bool is_and, std::vector<int> lits) {
+    while (lits.size() > 1) {
+        std::vector<int> next;
+        for_balanced_chunks(lits.size(), [&](size_t start, size_t len) {
+            if (len == 1) {
+                next.push_back(lits[start]);
+                return;
+            }
+            PGate g;
+            g.kind = GATE_SIGN;
+            for (size_t i = 0; i < len; ++i) g.ins.push_back({lits[start + i], 1});
+            g.offset = is_and ? 1 - 2 * (int)len : -1;
+            next.push_back((int)prog.gates.size());
+            prog.gates.push_back(std::move(g));
+        });
+        lits = std::move(next);
+    }
+    return lits[0];
+}
+
+Program compile_needle(size_t n_chars, size_t m, size_t lo, size_t hi, bool starts) {
+    if (m < 1 || m > NEEDLE_MAX_CHARS) throw Error(FR_ERR_INVALID, "needle: 1 <= m <= 64");
+    if (lo > hi) throw Error(FR_ERR_INVALID, "needle: start range");
+    if (n_chars > (size_t)1 << 24) throw Error(FR_ERR_INVALID, "needle: content too long");
+    if (starts && hi - lo > (size_t)1 << 24) throw Error(FR_ERR_INVALID, "needle: more than 2^24 starts");
+    // (the OR reads only starts that fit: no walk over a range far past the content)
+    const size_t end = starts ? hi : std::min(hi, n_chars);
+    Program prog;
+    std::vector<int> found;  // the AND of each start that fits
+    for (size_t p = lo; p < end; ++p) {
+        if (p + m > n_chars || p + m < p) {
+            if (starts) prog.outs.push_back(ProgOut{-1, 0, 0});
+            continue;
+        }
+        std::vector<int> tests;
+        for (size_t i = 0; i < m; ++i)
+            for (int h = 0; h < 2; ++h) {
+                PGate g;
+                g.kind = GATE_SELECT;
+                g.sel = (int32_t)(2 * i + h);
+                g.ins = {{cblk((int)(p + i), 2 * h + 1), 4}, {cblk((int)(p + i), 2 * h), 1}};
+                tests.push_back((int)prog.gates.size());
+                prog.gates.push_back(std::move(g));
+            }
+        const int a = threshold_tree(prog, true, std::move(tests));
+        if (starts) prog.outs.push_back(ProgOut{a, 1, 0});
+        else found.push_back(a);
+    }
+    if (!starts) {
+        if (found.empty()) prog.outs.push_back(ProgOut{-1, 0, 0});
+        else prog.outs.push_back(ProgOut{threshold_tree(prog, false, std::move(found)), 1, 0});
+    }
+    // topological order by construction, but a tree's gates follow their start's tests: the
+    // scheduler orders by level, and level 1 is the selector gates alone
+    compute_levels(prog);
+    return prog;
+}
+
 int eval_program(const Program& prog, const uint8_t* content, size_t L) {
     std::vector<int> parts;
     return eval_program_parts(prog, content, L, parts);
 }
 
-int eval_program_parts(const Program& prog, const uint8_t* content, size_t L, std::vector<int>& parts) {
+int eval_program_parts(const Program& prog, const uint8_t* content, size_t L, std::vector<int>& parts,
+                       const uint16_t* tables, size_t n_tables) {
     std::vector<int> val(prog.gates.size(), 0);
     for (size_t g = 0; g < prog.gates.size(); ++g) {
         const PGate& G = prog.gates[g];
@@ -747,6 +808,11 @@ int eval_program_parts(const Program& prog, const uint8_t* content, size_t L, st
             val[g] = s > 0 ? 1 : 0;
         } else {
             if ((s & 1) || s < 0 || s >= 32) throw Error(FR_ERR_INVALID, "program lincomb out of the 16-value message space");
+            if (G.kind == GATE_SELECT) {
+                if (G.sel < 0 || (size_t)G.sel >= n_tables) throw Error(FR_ERR_INVALID, "selector gate without its table");
+                val[g] = (tables[G.sel] >> (s / 2)) & 1;
+                continue;
+            }
             val[g] = G.lut[s / 2];
         }
     }

@@ -10,6 +10,9 @@
 //  * SIGN : s half-integral in (-16, 16), out = [s > 0] (constant test
 //           polynomial: the negacyclic rotation yields +-Delta/2, then +Delta/2).
 //           Threshold AND/OR of up to 16 literals in one bootstrap.
+//  * SELECT : a LUT gate whose table the server does not know (private search): out =
+//           T_sel[s] for the 0/1 table T_sel that selector `sel` of the call's needle encrypts.
+//           Inputs, offsets and level rule are a LUT gate's; the lut field is unused.
 //
 // FR_LOWER_FAITHFUL: one gate group per reference op (eq/gt/le = 3 PBS, and/or
 //   = 1 PBS, not = linear), the decomposition of SURVEY App. D.3.
@@ -32,13 +35,14 @@ struct PIn {
     int32_t src;  // >= 0: gate index; < 0: content block -(1 + pos*4 + blk)
     int32_t w;
 };
-enum GateKind : int32_t { GATE_LUT = 0, GATE_SIGN = 1 };
+enum GateKind : int32_t { GATE_LUT = 0, GATE_SIGN = 1, GATE_SELECT = 2 };
 struct PGate {
     std::vector<PIn> ins;
     int32_t offset = 0;  // units of Delta/2
     int32_t kind = GATE_LUT;
     uint8_t lut[16] = {0};
     int32_t level = 0;
+    int32_t sel = 0;  // GATE_SELECT: the selector's index in the needle
 };
 // one boolean output: cst + w * gates[gate]   (gate == -1: the constant cst)
 struct ProgOut {
@@ -63,8 +67,10 @@ Program lower(const ValueDag& dag, int root, int mode, int max_parts = 1);
 // Plaintext semantics of a program (LUT semantics, with the [0,16) range
 // check); returns the result value (several parts: their OR).
 int eval_program(const Program& prog, const uint8_t* content, size_t L);
-// the same, and each output's value in `parts`
-int eval_program_parts(const Program& prog, const uint8_t* content, size_t L, std::vector<int>& parts);
+// the same, and each output's value in `parts`; tables (n_tables 16-bit masks of accepted
+// values) are what the program's selector gates look up: bit s of tables[sel]
+int eval_program_parts(const Program& prog, const uint8_t* content, size_t L, std::vector<int>& parts,
+                       const uint16_t* tables = nullptr, size_t n_tables = 0);
 void compute_levels(Program& prog);
 // a gate's level: one past its deepest gate input (content blocks are level 0);
 // level_of(g) gives the level of an earlier gate
@@ -108,6 +114,14 @@ struct CompiledStarts {
     std::vector<int> roots;
 };
 CompiledStarts compile_match_starts(const MatchSpec& spec, bool keep_dags = false);
+
+// Private search: has-match (starts = false: one output, the OR over the starts) or match starts
+// (one output per start of [lo, hi)) of a needle of m characters whose 2 m nibble tables are
+// encrypted.  For every start p of the range with p + m <= n_chars: selector gates 2 i + h over
+// nibble h (0: low) of content character p + i, then their AND.  A start that cannot fit is the
+// constant 0, and so is the OR over no start.  1 <= m <= NEEDLE_MAX_CHARS (common.h); m > n_chars is no error.
+// The program depends on (n_chars, m, lo, hi, starts) alone.  starts: at most 2^24 of them.
+Program compile_needle(size_t n_chars, size_t m, size_t lo, size_t hi, bool starts);
 
 // LUT builders
 void lut_eq(uint8_t* lut, int v);     // [x == v]

@@ -26,11 +26,13 @@ namespace {
 
 // The key is a fixed number of '|'-terminated numeric fields followed by the pattern, so a
 // pattern's own text (which may contain '|' and digits) cannot make two keys collide.
+// needle_m > 0: a private search (fr_find*) for a needle of that many characters, the pattern
+// empty -- the plan does not depend on the needle's ciphertext, so the length stands for it.
 std::string match_key(fr_ctx* ctx, const char* pattern, size_t n, size_t M, size_t lo, size_t hi, size_t parts,
-                      int lane, bool starts) {
+                      int lane, bool starts, size_t needle_m) {
     std::string k;
     for (size_t v : {(size_t)ctx->grammar, (size_t)ctx->engine, (size_t)ctx->lowering, (size_t)ctx->multi_value, n, M,
-                     lo, hi, parts, (size_t)lane, (size_t)starts})
+                     lo, hi, parts, (size_t)lane, (size_t)starts, needle_m})
         k += std::to_string(v) + "|";
     k += pattern;
     return k;
@@ -137,13 +139,22 @@ struct PackedReply {
     bool compact;  // FRCPRES1, else FRPKRES1
     uint8_t* buf;  // packed_compact_size / packed_result_size bytes
 };
+// needle (fr_find, fr_find_starts; M = 1, no pattern): the program is compile_needle's, its
+// selector jobs read the needle's table, bound to the match's lane around its launches.
 void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const char* pattern, size_t lo, size_t hi,
                 fr_ct* outs, fr_match_stats* st, size_t parts = 1, size_t* n_parts = nullptr, bool starts = false,
-                const PackedReply* reply = nullptr) {
+                const PackedReply* reply = nullptr, const fr_needle* needle = nullptr) {
     double t0 = now_ms();
     pattern = pattern ? pattern : "";
     Device& dev = ctx->keyed_device();
     if (M == 0) throw Error(FR_ERR_INVALID, "no matches");
+    if (needle) {  // refused before anything is planned or launched
+        if (ctx->p.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "private search: FFT ring only");
+        if (needle->k != ctx->p.k || needle->N != ctx->p.N)
+            throw Error(FR_ERR_INVALID, "needle: k, N do not match the context params");
+        if (needle->dev.dev != &dev || !needle->dev.words) throw Error(FR_ERR_INVALID, "needle: uploaded to another context");
+    }
+    const size_t needle_m = needle ? needle->dev.m : 0;
     fr_plan_cache& pc = ctx->plans;
     CachedMatch* hit = nullptr;
     std::string key;
@@ -164,7 +175,7 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
         }
     } lane_scope{dev};
     if (pc.capacity) {
-        key = match_key(ctx, pattern, n, M, lo, hi, parts, lane, starts);
+        key = match_key(ctx, pattern, n, M, lo, hi, parts, lane, starts, needle_m);
         sig = content_signature(ctx, content, n * M, &cmap);
         for (auto& e : pc.entries)
             if (e->parts == parts && e->lane == lane && e->key == key && e->sig == sig) hit = e.get();
@@ -182,7 +193,9 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
         rec = hit->rec;
     } else {
         ++pc.misses;
-        if (starts) {
+        if (needle) {
+            prog = compile_needle(n, needle_m, lo, hi, starts);
+        } else if (starts) {
             CompiledStarts cs = compile_match_starts(match_spec(ctx, pattern, n, lo, hi));
             rec = cs.rec;
             prog = std::move(cs.prog);
@@ -234,6 +247,14 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
         dev.bind_content(cmap.data(), cmap.size());
     }
     double t1 = now_ms();
+    struct SelectorScope {  // the needle's table, for this match's launches on this lane only
+        Device& d;
+        bool on;
+        ~SelectorScope() {
+            if (on) d.bind_selectors(nullptr, 0);
+        }
+    } selector_scope{dev, needle != nullptr};
+    if (needle) dev.bind_selectors(needle->dev.words.get(), 2 * needle_m);
     launch_plan(dev, plan);
     if (hit && !starts && (nO < 1 || nO > parts))  // the caller's out buffer holds M * parts handles
         throw Error(FR_ERR_INVALID, "cached plan has more outputs than the caller's parts");
@@ -406,6 +427,25 @@ int fr_match_starts_packed(fr_ctx* ctx, const fr_ct* content, size_t n, const ch
         const PackedReply reply{compact != 0, buf};
         // the plans are fr_match_starts' own (same key): one compiled by either call serves the other
         match_impl(ctx, content, n, 1, pattern, lo, hi, nullptr, st, 1, nullptr, true, &reply);
+    })
+}
+
+int fr_find(fr_ctx* ctx, const fr_ct* content, size_t n_chars, const fr_needle* needle, size_t start_lo,
+            size_t start_hi, fr_ct* out, fr_match_stats* st) {
+    FR_TRY({
+        NEED(ctx && needle && out && (content || !n_chars) && start_lo <= start_hi);
+        // no start past the content fits: the range is cut there (one plan for every such range)
+        const size_t hi = std::min(start_hi, n_chars), lo = std::min(start_lo, hi);
+        match_impl(ctx, content, n_chars, 1, "", lo, hi, out, st, 1, nullptr, false, nullptr, needle);
+    })
+}
+
+int fr_find_starts(fr_ctx* ctx, const fr_ct* content, size_t n_chars, const fr_needle* needle, size_t start_lo,
+                   size_t start_hi, fr_ct* out, fr_match_stats* st) {
+    FR_TRY({
+        NEED(ctx && needle && (content || !n_chars) && start_lo <= start_hi && (out || start_lo == start_hi));
+        NEED(start_hi - start_lo <= ((size_t)1 << 24));
+        match_impl(ctx, content, n_chars, 1, "", start_lo, start_hi, out, st, 1, nullptr, true, nullptr, needle);
     })
 }
 
@@ -593,6 +633,17 @@ int fr_schedule_match_parts(size_t n_chars, const char* pattern, size_t lo, size
             compile_match(MatchSpec{pattern, n_chars, lo, hi, engine, grammar, lowering, (int)max_parts}).prog;
         schedule_program(prog, n_chars, multi_value, jobs, jobs_cap, n_jobs, level_off, level_cap, n_levels, outs3,
                          n_parts);
+    })
+}
+
+int fr_schedule_find(size_t n_chars, size_t m, size_t start_lo, size_t start_hi, int32_t starts, fr_job* jobs,
+                     size_t jobs_cap, size_t* n_jobs, uint32_t* level_off, size_t level_cap, size_t* n_levels,
+                     int32_t* outs3, size_t outs_cap, size_t* n_outs) {
+    FR_TRY({
+        NEED(n_jobs && n_levels && n_outs && outs3 && start_lo <= start_hi && (starts == 0 || starts == 1));
+        NEED(outs_cap >= (starts ? start_hi - start_lo : 1));
+        const Program prog = compile_needle(n_chars, m, start_lo, start_hi, starts != 0);
+        schedule_program(prog, n_chars, 1, jobs, jobs_cap, n_jobs, level_off, level_cap, n_levels, outs3, n_outs);
     })
 }
 

@@ -60,11 +60,16 @@ Schedule build_schedule(const std::vector<PGate>& gates, size_t n_content, bool 
         }
         if (nin > 16) throw Error(FR_ERR_INVALID, "gate fan-in > 16");
         if (G.kind != GATE_SIGN && (off & 1)) throw Error(FR_ERR_INVALID, "LUT gate with a half-integral offset");
+        if (G.kind == GATE_SELECT && (G.sel < 0 || G.sel >= MAX_SELECTORS))
+            throw Error(FR_ERR_INVALID, "selector gate: index out of range");
         level[g] = gate_level(G, [&](int s) { return level[s]; });
         maxl = std::max(maxl, level[g]);
     }
     std::vector<std::vector<int>> by_level(maxl + 1);
-    for (size_t g = 0; g < gates.size(); ++g) by_level[level[g]].push_back((int)g);
+    // (a level's selector gates first: their jobs are launched apart from the others, device.h)
+    for (int sel = 1; sel >= 0; --sel)
+        for (size_t g = 0; g < gates.size(); ++g)
+            if ((gates[g].kind == GATE_SELECT) == (sel == 1)) by_level[level[g]].push_back((int)g);
     // 2. jobs, level by level
     Schedule S;
     S.n_gates = gates.size();
@@ -105,6 +110,14 @@ Schedule build_schedule(const std::vector<PGate>& gates, size_t n_content, bool 
             if (G.kind == GATE_SIGN) {
                 d.n_out = 1;
                 d.direct = JOB_SIGN;
+                d.out_slot[0] = g;
+                S.jobs.push_back(d);
+                continue;
+            }
+            if (G.kind == GATE_SELECT) {  // never merged: its table is the needle's, not the plan's
+                d.n_out = 1;
+                d.direct = JOB_ACC;
+                set_acc_selector(d, (uint32_t)G.sel);
                 d.out_slot[0] = g;
                 S.jobs.push_back(d);
                 continue;

@@ -97,7 +97,8 @@ class FrJob(C.Structure):
                 ("n_out", C.c_int32), ("kind", C.c_int32), ("out_gate", C.c_int32 * 8), ("lut", (C.c_uint8 * 16) * 8)]
 
 
-JOB_MULTI, JOB_DIRECT, JOB_SIGN = 0, 1, 2
+JOB_MULTI, JOB_DIRECT, JOB_SIGN, JOB_ACC = 0, 1, 2, 3
+NEEDLE_HEADER = 64  # bytes before a needle blob's bodies
 
 u64p = C.POINTER(C.c_uint64)
 _lib = None
@@ -176,6 +177,23 @@ _SIGS = {
     "fr_upload_compact_blocks": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t,
                                            C.POINTER(C.c_size_t)]),
     "fr_device_timers_content": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "fr_needle_size": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fr_encrypt_needle_keyed": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint16), C.c_size_t, C.c_char_p, C.c_char_p,
+                                          C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fr_expand_needle": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, u64p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fr_upload_needle": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "fr_needle_len": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
+    "fr_needle_free": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fr_find": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                          C.POINTER(C.c_uint32), C.POINTER(MatchStats)]),
+    "fr_find_starts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                 C.POINTER(C.c_uint32), C.POINTER(MatchStats)]),
+    "fr_schedule_find": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int32, C.POINTER(FrJob),
+                                   C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.c_size_t,
+                                   C.POINTER(C.c_size_t), C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fr_plain_find": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint16), C.c_size_t, C.c_size_t, C.c_size_t,
+                                C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]),
+    "fr_dev_blind_rotate_acc": (C.c_int, [C.c_void_p, u64p, u64p, C.c_size_t, u64p]),
     "fr_encrypt_str": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint64, u64p]),
     "fr_encrypt_blocks": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, C.c_uint64, C.c_uint64, u64p]),
     "fr_decrypt_radix": (C.c_int, [C.c_void_p, u64p, u64p]),
@@ -894,6 +912,70 @@ class Context:
         """a compact blob expanded on the device into boolean handles (as upload_bool)"""
         return self._upload_compact(lib().fr_upload_compact_blocks, blob, 1)
 
+    # ---- private search (fr_find*): an encrypted needle on encrypted content
+    def needle_size(self, m: int) -> int:
+        n = C.c_size_t()
+        _check(lib().fr_needle_size(self.h, m, C.byref(n)))
+        return n.value
+
+    def encrypt_needle(self, masks: Sequence[Tuple[int, int]], seed=None) -> bytes:
+        """fr_encrypt_needle_keyed: the needle blob of (lo_mask, hi_mask) per character
+        (needle_masks); seed None: the OS CSPRNG, else an int seed or a 32-byte key"""
+        flat = [v for lo_hi in masks for v in lo_hi]
+        arr = (C.c_uint16 * max(len(flat), 1))(*flat)
+        n = C.c_size_t()
+        key = self._compact_key(seed)
+        _check(lib().fr_encrypt_needle_keyed(self.h, arr, len(masks), key, None, 0, C.byref(n)))
+        buf = C.create_string_buffer(n.value)
+        _check(lib().fr_encrypt_needle_keyed(self.h, arr, len(masks), key, buf, n.value, C.byref(n)))
+        return buf.raw[:n.value]
+
+    def expand_needle(self, blob: bytes) -> np.ndarray:
+        """fr_expand_needle: the selectors [2 m][k + 1][N] of a needle blob (no key needed)"""
+        m = C.c_size_t()
+        _check(lib().fr_expand_needle(self.h, blob, len(blob), None, 0, C.byref(m)))
+        out = np.zeros((2 * m.value, self.params.k + 1, self.params.N), dtype=np.uint64)
+        _check(lib().fr_expand_needle(self.h, blob, len(blob), _p(out), out.size, C.byref(m)))
+        return out
+
+    def upload_needle(self, blob: bytes) -> "Needle":
+        h = C.c_void_p()
+        _check(lib().fr_upload_needle(self.h, blob, len(blob), C.byref(h)))
+        return Needle(self, h)
+
+    def _find(self, fn, content, needle, lo, hi, n_out):
+        if needle.h is None:
+            raise ValueError("needle is closed")
+        content = np.ascontiguousarray(content, dtype=np.uint32)
+        arr = content.ctypes.data_as(C.POINTER(C.c_uint32))
+        out = (C.c_uint32 * max(n_out, 1))()
+        st = MatchStats()
+        _check(fn(self.h, arr, len(content), needle.h, lo, hi, out, C.byref(st)))
+        return list(out)[:n_out], st
+
+    def find(self, content: Sequence[int], needle: "Needle", lo: Optional[int] = None, hi: Optional[int] = None):
+        """fr_find: (boolean handle, MatchStats): the needle matches at some start of [lo, hi)"""
+        lo = 0 if lo is None else lo
+        hi = len(content) if hi is None else hi
+        out, st = self._find(lib().fr_find, content, needle, lo, hi, 1)
+        return out[0], st
+
+    def find_starts(self, content: Sequence[int], needle: "Needle", lo: Optional[int] = None,
+                    hi: Optional[int] = None, stats: bool = False):
+        """fr_find_starts: one boolean handle per start offset of [lo, hi)"""
+        lo = 0 if lo is None else lo
+        hi = len(content) if hi is None else hi
+        hs, st = self._find(lib().fr_find_starts, content, needle, lo, hi, max(hi - lo, 0))
+        return (hs, st) if stats else hs
+
+    def dev_blind_rotate_acc(self, ks: np.ndarray, accs: np.ndarray) -> np.ndarray:
+        """fr_dev_blind_rotate_acc: one selector launch, rotation i from the GLWE accs[i]"""
+        a = np.ascontiguousarray(ks.reshape(-1, self.params.n + 1), dtype=np.uint64)
+        g = np.ascontiguousarray(accs, dtype=np.uint64).reshape(a.shape[0], (self.params.k + 1) * self.params.N)
+        out = np.zeros((a.shape[0], self.lwe_len), dtype=np.uint64)
+        _check(lib().fr_dev_blind_rotate_acc(self.h, _p(a), _p(g), a.shape[0], _p(out)))
+        return out
+
     def content_expand_timer(self) -> float:
         """ms of the last upload_compact_*'s expansion kernel under set_profiling"""
         ms = C.c_double()
@@ -1128,6 +1210,63 @@ class Context:
         return br.value, tot.value
 
 
+class Needle:
+    """An uploaded needle (fr_upload_needle): close() releases its device memory, after every
+    lane's queued finds."""
+
+    def __init__(self, ctx: "Context", h):
+        self.ctx, self.h = ctx, h
+
+    def __len__(self) -> int:
+        m = C.c_size_t()
+        _check(lib().fr_needle_len(self.h, C.byref(m)))
+        return m.value
+
+    def close(self):
+        if self.h is not None and self.ctx.h:
+            _check(lib().fr_needle_free(self.ctx.h, self.h))
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def needle_masks(s: bytes | str, ignore_case: bool = False, any_char: Optional[str] = None) -> List[Tuple[int, int]]:
+    """(lo_mask, hi_mask) per character of a needle: bit v of a mask accepts nibble value v.  A
+    literal byte is one bit in each; ignore_case gives an ASCII letter both cases (high nibble 4
+    or 6, 5 or 7); a character equal to any_char matches any byte."""
+    b = s.encode("latin-1") if isinstance(s, str) else bytes(s)
+    wild = None if any_char is None else (any_char.encode("latin-1") if isinstance(any_char, str) else bytes(any_char))
+    if wild is not None and len(wild) != 1:
+        raise ValueError("any_char is one character")
+    out = []
+    for c in b:
+        if wild is not None and c == wild[0]:
+            out.append((0xFFFF, 0xFFFF))
+            continue
+        lo, hi = 1 << (c & 15), 1 << (c >> 4)
+        if ignore_case and (0x41 <= (c & ~0x20) <= 0x5A):
+            hi = (1 << ((c >> 4) & ~2)) | (1 << ((c >> 4) | 2))
+        out.append((lo, hi))
+    return out
+
+
+def plain_find(content: bytes | str, masks: Sequence[Tuple[int, int]], start_lo: int = 0,
+               start_hi: Optional[int] = None) -> Tuple[List[int], int]:
+    """fr_plain_find: the lowered programs of find_starts and find in plaintext: (starts, any)"""
+    b = content.encode("latin-1") if isinstance(content, str) else bytes(content)
+    hi = len(b) if start_hi is None else start_hi
+    flat = [v for lo_hi in masks for v in lo_hi]
+    arr = (C.c_uint16 * max(len(flat), 1))(*flat)
+    out = (C.c_uint8 * max(hi - start_lo, 1))()
+    any_ = C.c_int32()
+    _check(lib().fr_plain_find(b, len(b), arr, len(masks), start_lo, hi, out, C.byref(any_)))
+    return list(out)[:max(hi - start_lo, 0)], any_.value
+
+
 # ------------------------------------------------------------- reference API
 # first word of a compact match_starts reply; never a chunk count of the full form's framing
 COMPACT_REPLY = 0xFFFFFFFF
@@ -1151,6 +1290,12 @@ class ClientKey:
         if any(ord(ch) > 127 for ch in s):
             raise ValueError("content contains non-ascii characters")
         return self.ctx.encrypt_str_compact(s, seed)
+
+    def encrypt_needle(self, s: str, ignore_case: bool = False, any_char: Optional[str] = None, seed=None) -> bytes:
+        """the private-search query for s as a needle blob (64 + 16 len(s) N bytes) that
+        ServerKey.upload_needle takes: the server learns len(s) and nothing else.  ignore_case
+        and any_char as in needle_masks; `seed` as in encrypt_str"""
+        return self.ctx.encrypt_needle(needle_masks(s, ignore_case, any_char), seed)
 
     def decrypt(self, ct: int) -> int:
         return self.ctx.decrypt_radix(self.ctx.download_radix(ct))
@@ -1241,6 +1386,29 @@ class ServerKey:
         finally:
             for h in hs:
                 self.ctx.release(h)
+        return struct.pack("<I", len(blobs)) + b"".join(blobs)
+
+    def upload_needle(self, blob: bytes) -> Needle:
+        """a client's needle blob (ClientKey.encrypt_needle) on the device; no client key needed"""
+        return self.ctx.upload_needle(blob)
+
+    def find(self, content: Sequence[int], needle: Needle) -> int:
+        """boolean handle: the encrypted needle occurs in the encrypted content"""
+        return self.ctx.find(content, needle)[0]
+
+    def find_starts(self, content: Sequence[int], needle: Needle, compact: bool = False) -> bytes:
+        """where the needle occurs, as match_starts' reply for ClientKey.decrypt_starts (both
+        forms): fr_find_starts, then one pack per chunk of N starts.  The handles are released."""
+        N = self.ctx.params.N
+        hs = self.ctx.find_starts(content, needle)
+        try:
+            pack = self.ctx.pack_bools_compact if compact else self.ctx.pack_bools
+            blobs = [pack(hs[i:i + N]) for i in range(0, len(hs), N)]
+        finally:
+            for h in hs:
+                self.ctx.release(h)
+        if compact:
+            return struct.pack("<II", COMPACT_REPLY, len(blobs)) + b"".join(blobs)
         return struct.pack("<I", len(blobs)) + b"".join(blobs)
 
     def save(self, path: str, packing_path: Optional[str] = None):
@@ -1668,6 +1836,26 @@ def schedule_match_starts(n_chars: int, pattern: str, start_lo: int = 0, start_h
     off = (C.c_uint32 * (nl.value + 1))()
     _check(lib().fr_schedule_match_starts(*args, jobs, len(jobs), C.byref(nj), off, len(off), C.byref(nl), outs3, cap,
                                           C.byref(ns)))
+    n_gates = 1 + max([max(j.out_gate[f] for f in range(j.n_out)) for j in jobs[:nj.value]] or [-1])
+    parts = [(outs3[3 * j], outs3[3 * j + 1], outs3[3 * j + 2]) for j in range(ns.value)]
+    first = parts[0] if parts else (-1, 0, 0)
+    return Schedule(list(jobs[:nj.value]), list(off), first[0], first[1], first[2], n_gates, parts)
+
+
+def schedule_find(n_chars: int, m: int, start_lo: int = 0, start_hi: Optional[int] = None,
+                  starts: bool = False) -> Schedule:
+    """fr_schedule_find: the schedule of find (one output) or find_starts (Schedule.parts: one
+    (out_gate, out_w, out_const) per start) for a needle of m characters"""
+    hi = n_chars if start_hi is None else start_hi
+    nj, nl, ns = C.c_size_t(), C.c_size_t(), C.c_size_t()
+    cap = max(hi - start_lo, 1)
+    outs3 = (C.c_int32 * (3 * cap))()
+    args = (n_chars, m, start_lo, hi, int(starts))
+    _check(lib().fr_schedule_find(*args, None, 0, C.byref(nj), None, 0, C.byref(nl), outs3, cap, C.byref(ns)))
+    jobs = (FrJob * max(nj.value, 1))()
+    off = (C.c_uint32 * (nl.value + 1))()
+    _check(lib().fr_schedule_find(*args, jobs, len(jobs), C.byref(nj), off, len(off), C.byref(nl), outs3, cap,
+                                  C.byref(ns)))
     n_gates = 1 + max([max(j.out_gate[f] for f in range(j.n_out)) for j in jobs[:nj.value]] or [-1])
     parts = [(outs3[3 * j], outs3[3 * j + 1], outs3[3 * j + 2]) for j in range(ns.value)]
     first = parts[0] if parts else (-1, 0, 0)

@@ -579,6 +579,55 @@ int fr_match_starts_packed(fr_ctx* ctx, const fr_ct* content, size_t n_chars, co
                            size_t start_hi, int32_t compact, uint8_t* buf, size_t cap, size_t* written,
                            fr_match_stats* stats);
 
+/* ----- private search: an encrypted needle on encrypted content (FFT ring) ----- */
+/* Every match entry above takes its pattern in the clear.  A needle is the encrypted form of a
+ * fixed-length query: character i is a product class lo_mask x hi_mask of accepted low and high
+ * nibble values (16-bit masks; a literal byte: one bit in each; a case-insensitive letter: two
+ * bits in the high mask; any byte: 0xFFFF, 0xFFFF).  The client encrypts each of the 2 m masks
+ * as a selector, a GLWE ciphertext of (k+1) N words under its GLWE key whose phase is the
+ * direct test polynomial of the mask read as a 0/1 table; selector 2 i + h tests nibble h
+ * (0: low) of character i.  The server starts one blind rotation per (content nibble, needle
+ * nibble) from the selector instead of from a table of its own, so it learns the needle's length
+ * m and the content length, and nothing else about the query.
+ * Blob: "FRNEEDL1", int32 k, N, u64 m, the 32-byte public mask key, 8 zero bytes, then the 2 m
+ * body polynomials of N u64; little endian, exactly 64 + 16 m N bytes (fr_needle_size; 32 KB per
+ * character at (1, 2048)).  Mask word t of mask polynomial c of selector q is u64 number
+ * (q k + c) N + t of ChaCha20 stream 11 under the mask key; the noise (GLWE sigma) is drawn
+ * under the call's secret key.  1 <= m <= 64.
+ * fr_encrypt_needle_keyed (client key needed): masks[2 i], masks[2 i + 1] = lo, hi of character
+ * i; key NULL: the OS CSPRNG; buf NULL: size query.  fr_expand_needle (no key needed): the
+ * 2 m (k+1) N words [selector][polynomial][N]; words NULL: *m only.  Both refuse an RNS context,
+ * and every blob whose length, magic, k, N, m or pad is off, with FR_ERR_INVALID before anything
+ * is allocated. */
+int fr_needle_size(fr_ctx* ctx, size_t m, size_t* bytes);
+int fr_encrypt_needle_keyed(fr_ctx* ctx, const uint16_t* masks /* 2*m: lo, hi per character */, size_t m,
+                            const uint8_t* key /* NULL: OS CSPRNG */, uint8_t* buf, size_t cap, size_t* written);
+int fr_expand_needle(fr_ctx* ctx, const uint8_t* blob, size_t len, uint64_t* words, size_t cap_words, size_t* m);
+/* Server side (needs no client key): the blob expanded on the host and sent in one H2D copy.  The
+ * needle belongs to the context's device; fr_needle_free first waits for every lane, as a cached
+ * plan's release does, so it may follow asynchronous finds directly.  Free every needle of a
+ * context before fr_ctx_destroy: a needle that outlives its context must not be freed or used.
+ * fr_needle_free takes the context the needle was uploaded to (another: FR_ERR_INVALID, nothing
+ * freed); a NULL needle is no error. */
+typedef struct fr_needle fr_needle;
+int fr_upload_needle(fr_ctx* ctx, const uint8_t* blob, size_t len, fr_needle** out);
+int fr_needle_len(const fr_needle* needle, size_t* m);
+int fr_needle_free(fr_ctx* ctx, fr_needle* needle);
+/* fr_find: out = [the needle matches at some start p of [start_lo, start_hi) with p + m <= n_chars],
+ * the OR a has_match of the same literal gives.  fr_find_starts: out[p - start_lo] = [it matches at
+ * p], start_hi - start_lo booleans; a start that cannot fit the needle is a trivial 0, as
+ * fr_match_starts gives (at most 2^24 starts a call).  m > n_chars is no error: the constant.
+ * fr_find reads only the starts that fit, whatever start_hi.  Both run through the match
+ * engine: plan cache (the plan depends on m and the content's shape, never on the needle's
+ * ciphertext: a second needle of the same length is a hit), lanes, fr_set_async, stats.  Cost: one
+ * rotation per (content nibble, needle nibble) and start, then the AND per start and the OR.
+ * FR_ERR_INVALID for an RNS context, a needle of another (k, N) or of another context;
+ * FR_ERR_NO_DEVICE on a host-only context; nothing is launched then. */
+int fr_find(fr_ctx* ctx, const fr_ct* content, size_t n_chars, const fr_needle* needle, size_t start_lo,
+            size_t start_hi, fr_ct* out, fr_match_stats* stats);
+int fr_find_starts(fr_ctx* ctx, const fr_ct* content, size_t n_chars, const fr_needle* needle, size_t start_lo,
+                   size_t start_hi, fr_ct* out /* start_hi - start_lo */, fr_match_stats* stats);
+
 /* ----- one match split across ranks ----- */
 /* The reference folds ct_or over the branches of every start offset
  * (engine.rs:15-35, each branch a chain of execution.rs:76-190 calls); anchored
@@ -616,7 +665,9 @@ int fr_shard_free(fr_ctx* ctx, fr_shard* sh);
  * is the output of program gate in_ref[q], in_ref[q] < 0 content block
  * -1 - in_ref[q] (= 4 pos + block, LSB block first); job input s = offset/2 +
  * sum w_q in_q (units of Delta); kind 1: out_gate[0] = lut[0][s]; kind 0
- * (multi-value): out_gate[f] = lut[f][s], f < n_out; kind 2: [s > 0].  out3 =
+ * (multi-value): out_gate[f] = lut[f][s], f < n_out; kind 2: [s > 0]; kind 3 (private
+ * search): out_gate[0] = T[s] for the needle's table T of selector lut[0][0..3] (u32, little
+ * endian), which the schedule does not hold.  out3 =
  * (out_gate, out_w, out_const): result = out_const + out_w * gate (out_gate < 0:
  * the constant).  Pass jobs / level_off = NULL to query the sizes. */
 typedef struct {
@@ -646,6 +697,16 @@ int fr_schedule_match_starts(size_t n_chars, const char* pattern, size_t start_l
                              int32_t engine, int32_t grammar, int32_t multi_value, fr_job* jobs, size_t jobs_cap,
                              size_t* n_jobs, uint32_t* level_off, size_t level_cap, size_t* n_levels, int32_t* outs3,
                              size_t outs_cap, size_t* n_starts);
+/* The schedule of fr_find (starts = 0: one output) or fr_find_starts (starts = 1: one per start
+ * of the range) for a needle of m characters: level 1, the first entry of
+ * level_off, holds the kind-3 jobs alone. */
+int fr_schedule_find(size_t n_chars, size_t m, size_t start_lo, size_t start_hi, int32_t starts, fr_job* jobs,
+                     size_t jobs_cap, size_t* n_jobs, uint32_t* level_off, size_t level_cap, size_t* n_levels,
+                     int32_t* outs3, size_t outs_cap, size_t* n_outs);
+/* The lowered programs of fr_find_starts and fr_find evaluated in plaintext, gate by gate, with
+ * the tables in the clear: starts_out[p - start_lo] and *any. */
+int fr_plain_find(const char* content, size_t len, const uint16_t* masks, size_t m, size_t start_lo, size_t start_hi,
+                  uint8_t* starts_out, int32_t* any);
 
 /* ----- host-only introspection (tests; no device needed) ----- */
 /* Canonical AST string of parse(pattern) (parser.rs:146-185). */
@@ -764,6 +825,12 @@ int fr_dev_blind_rotate(fr_ctx* ctx, const uint64_t* in, const uint8_t* luts, si
  * rotated itself; else multi-value) -> out: n_out*(kN+1) */
 int fr_dev_blind_rotate_multi(fr_ctx* ctx, const uint64_t* in, const uint8_t* luts, int32_t n_out, int32_t direct,
                               uint64_t* out);
+/* one launch of `count` selector jobs (private search; FFT ring): rotation i starts from the
+ * GLWE ciphertext accs + i*(k+1)*N instead of a LUT's test polynomial -> out: count*(kN+1).  A
+ * trivial selector (zero masks, body the direct test polynomial of a LUT) gives
+ * fr_dev_blind_rotate's words.  The launch shape follows count, as every launch's does. */
+int fr_dev_blind_rotate_acc(fr_ctx* ctx, const uint64_t* in /* count*(n+1) */, const uint64_t* accs, size_t count,
+                            uint64_t* out);
 /* negacyclic product in Z_Q[X]/(X^N+1) (Q = 998244353 * 1004535809, inputs in
  * [0, Q)) through the device RNS NTT: count pairs */
 int fr_dev_ring_mul(fr_ctx* ctx, const uint64_t* a, const uint64_t* b, size_t count, uint64_t* out);
