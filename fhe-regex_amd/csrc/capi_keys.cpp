@@ -26,41 +26,37 @@ int fr_load_client_key(fr_ctx* ctx, const uint8_t* data, size_t len) {
     })
 }
 
-// Every draw below runs under one RngKey (chacha.h).  The seeded entry points build
-// theirs with from_seed and the keyed ones with from_bytes, or from_os for a NULL
-// key; both then share one body.  The host copy of the key is wiped on the way out.
+// Every draw below runs under one RngKey (chacha.h).  A seeded entry point and its keyed twin hand
+// their KeySource to one body, which checks its preconditions and then draws the key: from_seed,
+// from_bytes, or from_os for a NULL key.  The host copy of the key is wiped on the way out.
 namespace {
+struct KeySource {
+    bool seeded;
+    uint64_t seed = 0;
+    const uint8_t* key32 = nullptr;
+    KeySource(uint64_t s) : seeded(true), seed(s) {}
+    KeySource(const uint8_t* k) : seeded(false), key32(k) {}
+};
 struct ScopedKey {
     RngKey k;
-    explicit ScopedKey(uint64_t seed) : k(RngKey::from_seed(seed)) {}
-    explicit ScopedKey(const uint8_t* key32) : k(key32 ? RngKey::from_bytes(key32) : RngKey::from_os()) {}
+    explicit ScopedKey(const KeySource& s)
+        : k(s.seeded ? RngKey::from_seed(s.seed) : s.key32 ? RngKey::from_bytes(s.key32) : RngKey::from_os()) {}
     ~ScopedKey() { wipe_key(k); }
     ScopedKey(const ScopedKey&) = delete;
     ScopedKey& operator=(const ScopedKey&) = delete;
 };
 }  // namespace
 
-static void gen_client_key_with(fr_ctx* ctx, const RngKey& key) {
-    ctx->ck = gen_client_key(ctx->p, key);
+static void gen_client_key_from(fr_ctx* ctx, KeySource src) {
+    NEED(ctx);
+    ScopedKey key(src);
+    ctx->ck = gen_client_key(ctx->p, key.k);
     ctx->has_ck = true;
     ctx->has_sk = false;
 }
 
-int fr_gen_client_key(fr_ctx* ctx, uint64_t seed) {
-    FR_TRY({
-        NEED(ctx);
-        ScopedKey key(seed);
-        gen_client_key_with(ctx, key.k);
-    })
-}
-
-int fr_gen_client_key_keyed(fr_ctx* ctx, const uint8_t* key32) {
-    FR_TRY({
-        NEED(ctx);
-        ScopedKey key(key32);
-        gen_client_key_with(ctx, key.k);
-    })
-}
+int fr_gen_client_key(fr_ctx* ctx, uint64_t seed) { FR_TRY(gen_client_key_from(ctx, seed)) }
+int fr_gen_client_key_keyed(fr_ctx* ctx, const uint8_t* key32) { FR_TRY(gen_client_key_from(ctx, key32)) }
 
 int fr_serialize_client_key(fr_ctx* ctx, uint8_t* buf, size_t cap, size_t* written) {
     FR_TRY({
@@ -82,7 +78,11 @@ static bool server_keygen_on_device(fr_ctx* ctx) {
         throw Error(ctx->dev ? FR_ERR_INVALID : FR_ERR_NO_DEVICE, "device keygen needs a device and the FFT ring");
     return on_dev;
 }
-static void gen_server_key_with(fr_ctx* ctx, bool on_dev, const RngKey& key, bool compact = false) {
+static void gen_server_key_from(fr_ctx* ctx, KeySource src, bool compact) {
+    NEED(ctx);
+    const bool on_dev = server_keygen_on_device(ctx);
+    ScopedKey scoped(src);  // after the preconditions: a NULL key draws from the OS
+    const RngKey& key = scoped.k;
     if (compact && ctx->p.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "compact server key: FFT ring only");
     ctx->has_sk = false;
     ctx->sk_compact = false;
@@ -110,47 +110,16 @@ static void gen_server_key_with(fr_ctx* ctx, bool on_dev, const RngKey& key, boo
     ctx->has_sk = true;
 }
 
-int fr_gen_server_key(fr_ctx* ctx, uint64_t seed) {
-    FR_TRY({
-        NEED(ctx);
-        const bool on_dev = server_keygen_on_device(ctx);
-        ScopedKey key(seed);
-        gen_server_key_with(ctx, on_dev, key.k);
-    })
-}
-
-int fr_gen_server_key_keyed(fr_ctx* ctx, const uint8_t* key32) {
-    FR_TRY({
-        NEED(ctx);
-        const bool on_dev = server_keygen_on_device(ctx);
-        ScopedKey key(key32);
-        gen_server_key_with(ctx, on_dev, key.k);
-    })
-}
-
-int fr_gen_server_key_compact(fr_ctx* ctx, uint64_t seed) {
-    FR_TRY({
-        NEED(ctx);
-        const bool on_dev = server_keygen_on_device(ctx);
-        ScopedKey key(seed);
-        gen_server_key_with(ctx, on_dev, key.k, true);
-    })
-}
-
-int fr_gen_server_key_compact_keyed(fr_ctx* ctx, const uint8_t* key32) {
-    FR_TRY({
-        NEED(ctx);
-        const bool on_dev = server_keygen_on_device(ctx);
-        ScopedKey key(key32);
-        gen_server_key_with(ctx, on_dev, key.k, true);
-    })
-}
+int fr_gen_server_key(fr_ctx* ctx, uint64_t seed) { FR_TRY(gen_server_key_from(ctx, seed, false)) }
+int fr_gen_server_key_keyed(fr_ctx* ctx, const uint8_t* key32) { FR_TRY(gen_server_key_from(ctx, key32, false)) }
+int fr_gen_server_key_compact(fr_ctx* ctx, uint64_t seed) { FR_TRY(gen_server_key_from(ctx, seed, true)) }
+int fr_gen_server_key_compact_keyed(fr_ctx* ctx, const uint8_t* key32) { FR_TRY(gen_server_key_from(ctx, key32, true)) }
 
 int fr_server_key_sizes(fr_ctx* ctx, size_t* ksk_len, size_t* bsk_len) {
     FR_TRY({
         NEED(ctx);
         const Params& p = ctx->p;
-        if (ksk_len) *ksk_len = (size_t)p.big() * p.ks_level * (p.n + 1);
+        if (ksk_len) *ksk_len = p.ksk_len();
         if (bsk_len) *bsk_len = p.bsk_len();
     })
 }
@@ -178,7 +147,7 @@ int fr_load_server_key(fr_ctx* ctx, const uint64_t* ksk, size_t ksk_len, const u
     FR_TRY({
         NEED(ctx && ksk && bsk);
         const Params& p = ctx->p;
-        if (ksk_len != (size_t)p.big() * p.ks_level * (p.n + 1) || bsk_len != p.bsk_len())
+        if (ksk_len != p.ksk_len() || bsk_len != p.bsk_len())
             throw Error(FR_ERR_INVALID, "server key lengths do not match the context params (fr_server_key_sizes)");
         ctx->has_sk = false;
         ctx->sk_compact = false;
@@ -210,17 +179,13 @@ int fr_export_server_key_compact(fr_ctx* ctx, uint8_t* buf, size_t cap, size_t* 
         *written = need;
         if (!buf) return FR_OK;  // size query
         NEED(cap >= need);
-        std::vector<uint8_t> blob;
         if (ctx->sk_on_device) {
-            size_t kl = 0, bl = 0;
-            fr_server_key_sizes(ctx, &kl, &bl);
-            std::vector<uint64_t> k(kl), b(bl);
-            ctx->device().download_server_key(k.data(), kl, b.data(), bl);
-            blob = pack_compact(ctx->p, ctx->mask_key, k, b);
+            std::vector<uint64_t> k(ctx->p.ksk_len()), b(ctx->p.bsk_len());
+            ctx->device().download_server_key(k.data(), k.size(), b.data(), b.size());
+            pack_compact(ctx->p, ctx->mask_key, k, b, buf);
         } else {
-            blob = pack_compact(ctx->p, ctx->mask_key, ctx->ksk, ctx->bsk);
+            pack_compact(ctx->p, ctx->mask_key, ctx->ksk, ctx->bsk, buf);
         }
-        std::memcpy(buf, blob.data(), need);
     })
 }
 
@@ -237,8 +202,7 @@ int fr_load_server_key_compact(fr_ctx* ctx, const uint8_t* blob, size_t len) {
             ctx->sk_on_device = true;
         } else {
             std::vector<uint64_t> k, b;
-            RngKey m;
-            expand_compact(ctx->p, blob, len, k, b, m);
+            expand_compact(ctx->p, blob, len, k, b);
             ctx->has_sk = false;
             ctx->ksk = std::move(k);
             ctx->bsk = std::move(b);
@@ -252,9 +216,19 @@ int fr_load_server_key_compact(fr_ctx* ctx, const uint8_t* blob, size_t len) {
 
 // ---- packing key (keys.h): optional, beside the server key; nothing else depends on it
 
+// checked before a key is drawn
+static void check_gen_packing_key(fr_ctx* ctx) {
+    NEED(ctx);
+    if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
+    if (ctx->keygen == FR_KEYGEN_DEVICE && !ctx->dev) throw Error(FR_ERR_NO_DEVICE, "device keygen needs a device");
+}
+
 // compact: the compact form (keys.h) -- the masks under the public mask key, which is all a
 // kernel sees; the noise under `key` on the host either way
-static void gen_packing_key_with(fr_ctx* ctx, const RngKey& key, bool compact = false) {
+static void gen_packing_key_from(fr_ctx* ctx, KeySource src, bool compact) {
+    check_gen_packing_key(ctx);
+    ScopedKey scoped(src);
+    const RngKey& key = scoped.k;
     const bool on_dev = ctx->dev && ctx->keygen != FR_KEYGEN_HOST;
     RngKey mk{};  // public; the secret key is never copied
     if (compact) mk = derive_mask_key(key);
@@ -280,44 +254,11 @@ static void gen_packing_key_with(fr_ctx* ctx, const RngKey& key, bool compact = 
     ctx->pk_compact = compact;
     ctx->has_pk = true;
 }
-// checked before a key is drawn
-static void check_gen_packing_key(fr_ctx* ctx) {
-    NEED(ctx);
-    if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
-    if (ctx->keygen == FR_KEYGEN_DEVICE && !ctx->dev) throw Error(FR_ERR_NO_DEVICE, "device keygen needs a device");
-}
 
-int fr_gen_packing_key(fr_ctx* ctx, uint64_t seed) {
-    FR_TRY({
-        check_gen_packing_key(ctx);
-        ScopedKey key(seed);
-        gen_packing_key_with(ctx, key.k);
-    })
-}
-
-int fr_gen_packing_key_keyed(fr_ctx* ctx, const uint8_t* key32) {
-    FR_TRY({
-        check_gen_packing_key(ctx);
-        ScopedKey key(key32);
-        gen_packing_key_with(ctx, key.k);
-    })
-}
-
-int fr_gen_packing_key_compact(fr_ctx* ctx, uint64_t seed) {
-    FR_TRY({
-        check_gen_packing_key(ctx);
-        ScopedKey key(seed);
-        gen_packing_key_with(ctx, key.k, true);
-    })
-}
-
-int fr_gen_packing_key_compact_keyed(fr_ctx* ctx, const uint8_t* key32) {
-    FR_TRY({
-        check_gen_packing_key(ctx);
-        ScopedKey key(key32);
-        gen_packing_key_with(ctx, key.k, true);
-    })
-}
+int fr_gen_packing_key(fr_ctx* ctx, uint64_t seed) { FR_TRY(gen_packing_key_from(ctx, seed, false)) }
+int fr_gen_packing_key_keyed(fr_ctx* ctx, const uint8_t* key32) { FR_TRY(gen_packing_key_from(ctx, key32, false)) }
+int fr_gen_packing_key_compact(fr_ctx* ctx, uint64_t seed) { FR_TRY(gen_packing_key_from(ctx, seed, true)) }
+int fr_gen_packing_key_compact_keyed(fr_ctx* ctx, const uint8_t* key32) { FR_TRY(gen_packing_key_from(ctx, key32, true)) }
 
 static void gen_packing_rows_with(fr_ctx* ctx, const uint8_t* key32, bool compact, size_t row_lo, size_t row_hi,
                                   uint64_t* out) {
@@ -423,8 +364,7 @@ int fr_load_packing_key_compact(fr_ctx* ctx, const uint8_t* blob, size_t len) {
             ctx->dev->load_packing_key_compact(mk, blob + PKC_HEADER);  // drains every lane first
         } else {
             std::vector<uint64_t> rows;
-            RngKey m;
-            expand_pk_compact(ctx->p, blob, len, rows, m);
+            expand_pk_compact(ctx->p, blob, len, rows);
             ctx->pksk = std::move(rows);
         }
         ctx->pk_mask_key = mk;
@@ -433,29 +373,23 @@ int fr_load_packing_key_compact(fr_ctx* ctx, const uint8_t* blob, size_t len) {
     })
 }
 
-// preconditions of fr_encrypt_blocks[_keyed], checked before a key is drawn
-static void check_encrypt_blocks(fr_ctx* ctx, const uint8_t* msgs, size_t count, const uint64_t* out) {
+// (the preconditions are checked before a key is drawn)
+static void encrypt_blocks_from(fr_ctx* ctx, const uint8_t* msgs, size_t count, KeySource src, uint64_t first_block,
+                                uint64_t* out) {
     NEED(ctx && (msgs || !count) && (out || !count));
     if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
     for (size_t i = 0; i < count; ++i) NEED(msgs[i] < 16);
+    ScopedKey key(src);
+    encrypt_blocks(ctx->p, ctx->ck, msgs, count, key.k, first_block, out);
 }
 
 int fr_encrypt_blocks(fr_ctx* ctx, const uint8_t* msgs, size_t count, uint64_t seed, uint64_t first_block,
                       uint64_t* out) {
-    FR_TRY({
-        check_encrypt_blocks(ctx, msgs, count, out);
-        ScopedKey key(seed);
-        encrypt_blocks(ctx->p, ctx->ck, msgs, count, key.k, first_block, out);
-    })
+    FR_TRY(encrypt_blocks_from(ctx, msgs, count, seed, first_block, out))
 }
-
 int fr_encrypt_blocks_keyed(fr_ctx* ctx, const uint8_t* msgs, size_t count, const uint8_t* key32,
                             uint64_t first_block, uint64_t* out) {
-    FR_TRY({
-        check_encrypt_blocks(ctx, msgs, count, out);
-        ScopedKey key(key32);
-        encrypt_blocks(ctx->p, ctx->ck, msgs, count, key.k, first_block, out);
-    })
+    FR_TRY(encrypt_blocks_from(ctx, msgs, count, key32, first_block, out))
 }
 
 // radix messages of a string (ciphertext.rs:18-29: 4 blocks of 2 bits, least significant first)
@@ -470,58 +404,38 @@ static std::vector<uint8_t> str_blocks(const char* s, size_t len) {
     return msgs;
 }
 
-// radix messages of fr_encrypt_str[_keyed]'s string, after its preconditions
-static std::vector<uint8_t> check_encrypt_str(fr_ctx* ctx, const char* s, size_t len, const void* out) {
+static void encrypt_str_from(fr_ctx* ctx, const char* s, size_t len, KeySource src, uint64_t* out) {
     NEED(ctx && (s || !len) && (out || !len));
     if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
-    return str_blocks(s, len);
+    const std::vector<uint8_t> msgs = str_blocks(s, len);
+    ScopedKey key(src);
+    encrypt_blocks(ctx->p, ctx->ck, msgs.data(), msgs.size(), key.k, 0, out);
 }
 
 int fr_encrypt_str(fr_ctx* ctx, const char* s, size_t len, uint64_t seed, uint64_t* out) {
-    FR_TRY({
-        const std::vector<uint8_t> msgs = check_encrypt_str(ctx, s, len, out);
-        ScopedKey key(seed);
-        encrypt_blocks(ctx->p, ctx->ck, msgs.data(), msgs.size(), key.k, 0, out);
-    })
+    FR_TRY(encrypt_str_from(ctx, s, len, seed, out))
 }
-
 int fr_encrypt_str_keyed(fr_ctx* ctx, const char* s, size_t len, const uint8_t* key32, uint64_t* out) {
-    FR_TRY({
-        const std::vector<uint8_t> msgs = check_encrypt_str(ctx, s, len, out);
-        ScopedKey key(key32);
-        encrypt_blocks(ctx->p, ctx->ck, msgs.data(), msgs.size(), key.k, 0, out);
-    })
+    FR_TRY(encrypt_str_from(ctx, s, len, key32, out))
 }
 
-// preconditions of fr_encrypt_upload_str[_keyed] in the seeded call's order: client key,
-// device, ASCII content
-static std::vector<uint8_t> check_encrypt_upload_str(fr_ctx* ctx, const char* s, size_t len, const fr_ct* out) {
+// preconditions before the key is drawn, in this order: client key, device, ASCII content
+static void encrypt_upload_from(fr_ctx* ctx, const char* s, size_t len, KeySource src, fr_ct* out) {
     NEED(ctx && (s || !len) && (out || !len));
     if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
-    (void)ctx->device();
-    return str_blocks(s, len);
-}
-static void encrypt_upload_with(fr_ctx* ctx, const std::vector<uint8_t>& msgs, const RngKey& key, fr_ct* out) {
     Device& dev = ctx->device();
+    const std::vector<uint8_t> msgs = str_blocks(s, len);
+    ScopedKey key(src);
     Slots slots(dev, msgs.size());
-    dev.encrypt_to_slots(ctx->ck, msgs.data(), msgs.size(), key, 0, slots.data());
+    dev.encrypt_to_slots(ctx->ck, msgs.data(), msgs.size(), key.k, 0, slots.data());
     ctx->adopt(std::move(slots), true, out);
 }
 
 int fr_encrypt_upload_str(fr_ctx* ctx, const char* s, size_t len, uint64_t seed, fr_ct* out) {
-    FR_TRY({
-        const std::vector<uint8_t> msgs = check_encrypt_upload_str(ctx, s, len, out);
-        ScopedKey key(seed);
-        encrypt_upload_with(ctx, msgs, key.k, out);
-    })
+    FR_TRY(encrypt_upload_from(ctx, s, len, seed, out))
 }
-
 int fr_encrypt_upload_str_keyed(fr_ctx* ctx, const char* s, size_t len, const uint8_t* key32, fr_ct* out) {
-    FR_TRY({
-        const std::vector<uint8_t> msgs = check_encrypt_upload_str(ctx, s, len, out);
-        ScopedKey key(key32);
-        encrypt_upload_with(ctx, msgs, key.k, out);
-    })
+    FR_TRY(encrypt_upload_from(ctx, s, len, key32, out))
 }
 
 // ---- compact (seeded) content (keys.h): the client packs bodies + mask key, the server
@@ -538,8 +452,7 @@ int fr_compact_content_size(fr_ctx* ctx, size_t n_blocks, size_t* bytes) {
 // the size is answered before a key is drawn
 static void encrypt_compact_with(fr_ctx* ctx, const std::vector<uint8_t>& msgs, const uint8_t* key32,
                                  uint64_t first_block, uint8_t* buf, size_t cap, size_t* written) {
-    if (first_block > CONTENT_MAX_BLOCK || first_block + msgs.size() > CONTENT_MAX_BLOCK)
-        throw Error(FR_ERR_INVALID, "compact content: first_block + n_blocks exceeds 2^40");
+    check_content_range(first_block, msgs.size());
     const size_t need = content_blob_size(msgs.size());
     *written = need;
     if (!buf) return;  // size query

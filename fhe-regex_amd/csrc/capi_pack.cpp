@@ -43,10 +43,6 @@ static void pack_handles(fr_ctx* ctx, const fr_ct* bools, size_t n, uint64_t* ou
     for (size_t t = 0; compact && t < packed_compact_values(ctx->p, n); ++t) compact[t] = packed_round16(out[t]);
 }
 
-static void put_values16(const std::vector<uint16_t>& v, uint8_t* out) {
-    for (size_t t = 0; t < v.size(); ++t) out[2 * t] = (uint8_t)v[t], out[2 * t + 1] = (uint8_t)(v[t] >> 8);
-}
-
 extern "C" {
 
 int fr_packed_result_size(fr_ctx* ctx, size_t n, size_t* bytes) {
@@ -93,8 +89,7 @@ int fr_pack_bools_compact(fr_ctx* ctx, const fr_ct* bools, size_t n, uint8_t* bu
         NEED(cap >= need);
         std::vector<uint16_t> v(packed_compact_values(ctx->p, n));
         pack_handles(ctx, bools, n, nullptr, v.data());
-        write_packed_compact_header(ctx->p, n, buf);
-        put_values16(v, buf + PKCRES_HEADER);
+        write_packed_compact(ctx->p, n, v.data(), buf);
     })
 }
 
@@ -114,7 +109,7 @@ int fr_expand_packed_compact(fr_ctx* ctx, const uint8_t* blob, size_t len, uint6
     FR_TRY({
         NEED(ctx && blob && n);
         *n = check_packed_compact(ctx->p, blob, len);  // before anything is written
-        if (words) expand_packed_compact(ctx->p, blob, words);
+        if (words) expand_packed_compact(ctx->p, blob, len, words);
     })
 }
 
@@ -127,7 +122,7 @@ int fr_decrypt_packed_compact(fr_ctx* ctx, const uint8_t* blob, size_t len, uint
         if (!bits) return FR_OK;  // size query
         if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
         std::vector<uint64_t> ct(pk_row_words(ctx->p)), phase((size_t)ctx->p.N);
-        expand_packed_compact(ctx->p, blob, ct.data());
+        expand_packed_compact(ctx->p, blob, len, ct.data());
         glwe_phase(ctx->p, ctx->ck, ct.data(), phase.data());
         const uint64_t half = 1ULL << (DELTA_LOG - 1);
         // (the coefficients past n were not sent: nothing to check there)

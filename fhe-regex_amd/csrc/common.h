@@ -80,6 +80,7 @@ struct Params {
     // ring at k > 1 keeps one GGSW per coefficient
     int bsk_unroll() const { return (k == 1 || ring == FR_RING_FFT) ? 2 : 1; }
     size_t bsk_ggsw() const { return bsk_unroll() == 2 ? 3 * (size_t)((n + 1) / 2) : (size_t)n; }
+    size_t ksk_len() const { return (size_t)big() * ks_level * (n + 1); }
     size_t bsk_len() const { return bsk_ggsw() * (size_t)(k + 1) * (k + 1) * N; }
 };
 Params params_from_c(const fr_params* p);

@@ -14,6 +14,7 @@
 #include "keys.h"
 #include "plan.h"
 #include "regex.h"
+#include "wire.h"
 
 namespace fr {
 

@@ -7,7 +7,9 @@
 #include "keys.h"
 
 #include "chacha.h"
+#include "parallel.h"
 #include "rns.h"
+#include "wire.h"
 
 #include <sys/random.h>
 
@@ -17,7 +19,6 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
-#include <thread>
 
 namespace fr {
 
@@ -281,19 +282,6 @@ void ring_mul_q(const NttTables& T, const uint64_t* a, const uint64_t* b, uint64
 }
 
 // ---------------------------------------------------------------- keygen
-template <class F>
-static void parallel_for(int n, F&& fn) {
-    unsigned hw = std::thread::hardware_concurrency();
-    int T = (int)(hw ? (hw > 16 ? 16 : hw) : 4);
-    if (T > n) T = n > 0 ? n : 1;
-    std::vector<std::thread> th;
-    for (int t = 0; t < T; ++t)
-        th.emplace_back([&, t] {
-            for (int i = t; i < n; i += T) fn(i);
-        });
-    for (auto& x : th) x.join();
-}
-
 void gen_ksk(const Params& p, const ClientKey& ck, const RngKey& key, std::vector<uint64_t>& ksk) {
     gen_ksk(p, ck, key, key, ksk);
 }
@@ -301,7 +289,7 @@ void gen_ksk(const Params& p, const ClientKey& ck, const RngKey& key, std::vecto
 void gen_ksk(const Params& p, const ClientKey& ck, const RngKey& mask_key, const RngKey& noise_key,
              std::vector<uint64_t>& ksk) {
     const int big = p.big(), n = p.n, L = p.ks_level, B = p.ks_base_log;
-    ksk.assign((size_t)big * L * (n + 1), 0);
+    ksk.assign(p.ksk_len(), 0);
     parallel_for(big, [&](int i) {
         Rng rm(mask_key, STREAM_KSK_MASK), rn(noise_key, STREAM_KSK_NOISE);
         for (int j = 0; j < L; ++j) {
@@ -464,13 +452,9 @@ RngKey derive_mask_key(const RngKey& key) {
     return m;
 }
 
-static void need_fft_ring(const Params& p) {
-    if (p.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "compact server key: FFT ring only");
-}
-
 void gen_server_key_compact(const Params& p, const ClientKey& ck, const RngKey& key, std::vector<uint64_t>& ksk,
                             std::vector<uint64_t>& bsk, RngKey& mask_key) {
-    need_fft_ring(p);
+    if (p.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "compact server key: FFT ring only");
     mask_key = derive_mask_key(key);
     gen_ksk(p, ck, mask_key, key, ksk);
     gen_bsk_torus(p, ck, mask_key, key, true, bsk);
@@ -478,75 +462,6 @@ void gen_server_key_compact(const Params& p, const ClientKey& ck, const RngKey& 
 
 size_t compact_ksk_bodies(const Params& p) { return (size_t)p.big() * p.ks_level; }
 size_t compact_bsk_bodies(const Params& p) { return p.bsk_ggsw() * (size_t)(p.k + 1) * p.N; }
-size_t compact_size(const Params& p) { return COMPACT_HEADER + 8 * (compact_ksk_bodies(p) + compact_bsk_bodies(p)); }
-
-static const char COMPACT_MAGIC[9] = "FRCSKEY1";
-static void compact_params(const Params& p, int32_t v[8]) {
-    const int32_t w[8] = {p.k, p.N, p.n, p.ks_base_log, p.ks_level, p.pbs_base_log, p.pbs_level, p.ring};
-    std::memcpy(v, w, sizeof w);
-}
-static void put_le32(uint8_t* o, uint32_t v) {
-    for (int i = 0; i < 4; ++i) o[i] = (uint8_t)(v >> (8 * i));
-}
-static uint32_t get_le32(const uint8_t* o) {
-    return (uint32_t)o[0] | ((uint32_t)o[1] << 8) | ((uint32_t)o[2] << 16) | ((uint32_t)o[3] << 24);
-}
-
-RngKey check_compact(const Params& p, const uint8_t* blob, size_t len) {
-    need_fft_ring(p);
-    if (!blob || len != compact_size(p))
-        throw Error(FR_ERR_INVALID, "compact server key: length does not match the context params "
-                                    "(fr_server_key_compact_size)");
-    if (std::memcmp(blob, COMPACT_MAGIC, 8)) throw Error(FR_ERR_INVALID, "compact server key: bad magic");
-    int32_t want[8];
-    compact_params(p, want);
-    for (int i = 0; i < 8; ++i)
-        if (get_le32(blob + 8 + 4 * i) != (uint32_t)want[i])
-            throw Error(FR_ERR_INVALID, "compact server key: parameters do not match the context params");
-    return RngKey::from_bytes(blob + 40);
-}
-
-std::vector<uint8_t> pack_compact(const Params& p, const RngKey& mask_key, const std::vector<uint64_t>& ksk,
-                                  const std::vector<uint64_t>& bsk) {
-    need_fft_ring(p);
-    const size_t rows = compact_ksk_bodies(p), n = (size_t)p.n, N = (size_t)p.N, kp1 = (size_t)p.k + 1;
-    const size_t brows = p.bsk_ggsw() * kp1;
-    if (ksk.size() != rows * (n + 1) || bsk.size() != p.bsk_len())
-        throw Error(FR_ERR_INVALID, "compact server key: key array sizes");
-    std::vector<uint8_t> out(compact_size(p));
-    std::memcpy(out.data(), COMPACT_MAGIC, 8);
-    int32_t v[8];
-    compact_params(p, v);
-    for (int i = 0; i < 8; ++i) put_le32(out.data() + 8 + 4 * i, (uint32_t)v[i]);
-    for (int i = 0; i < 8; ++i) put_le32(out.data() + 40 + 4 * i, mask_key.w[i]);
-    uint8_t* o = out.data() + COMPACT_HEADER;
-    for (size_t row = 0; row < rows; ++row, o += 8) std::memcpy(o, &ksk[row * (n + 1) + n], 8);
-    for (size_t q = 0; q < brows; ++q, o += 8 * N) std::memcpy(o, &bsk[(q * kp1 + (kp1 - 1)) * N], 8 * N);
-    return out;
-}
-
-void expand_compact(const Params& p, const uint8_t* blob, size_t len, std::vector<uint64_t>& ksk,
-                    std::vector<uint64_t>& bsk, RngKey& mask_key) {
-    mask_key = check_compact(p, blob, len);
-    const size_t rows = compact_ksk_bodies(p), n = (size_t)p.n, N = (size_t)p.N, k = (size_t)p.k, kp1 = k + 1;
-    const size_t brows = p.bsk_ggsw() * kp1;
-    const uint8_t* kb = blob + COMPACT_HEADER;
-    const uint8_t* bb = kb + 8 * rows;
-    ksk.resize(rows * (n + 1));
-    bsk.resize(p.bsk_len());
-    parallel_for((int)rows, [&](int row) {
-        Rng rm(mask_key, STREAM_KSK_MASK);
-        uint64_t* o = ksk.data() + (size_t)row * (n + 1);
-        for (size_t t = 0; t < n; ++t) o[t] = rm.u64((uint64_t)row * n + t);
-        std::memcpy(o + n, kb + 8 * (size_t)row, 8);
-    });
-    parallel_for((int)brows, [&](int q) {
-        Rng rm(mask_key, STREAM_BSK_MASK);
-        uint64_t* o = bsk.data() + (size_t)q * kp1 * N;
-        for (size_t t = 0; t < k * N; ++t) o[t] = rm.u64((uint64_t)q * k * N + t);
-        std::memcpy(o + k * N, bb + 8 * (size_t)q * N, 8 * N);
-    });
-}
 
 // ---------------------------------------------------------------- client
 void encrypt_blocks(const Params& p, const ClientKey& ck, const uint8_t* msgs, size_t count, const RngKey& key,
@@ -572,73 +487,19 @@ void encrypt_blocks(const Params& p, const ClientKey& ck, const uint8_t* msgs, s
 }
 
 // ---------------------------------------------------------------- compact content
-static const char CONTENT_MAGIC[9] = "FRCCTXT1";
-static void put_le64(uint8_t* o, uint64_t v) {
-    for (int i = 0; i < 8; ++i) o[i] = (uint8_t)(v >> (8 * i));
-}
-static uint64_t get_le64(const uint8_t* o) {
-    uint64_t v = 0;
-    for (int i = 0; i < 8; ++i) v |= (uint64_t)o[i] << (8 * i);
-    return v;
-}
-
-size_t content_blob_size(size_t n_blocks) {
-    if (n_blocks > CONTENT_MAX_BLOCK) throw Error(FR_ERR_INVALID, "compact content: more than 2^40 blocks");
-    return CONTENT_HEADER + 8 * n_blocks;
-}
-
-ContentBlob check_content_blob(const Params& p, const uint8_t* blob, size_t len, bool radix) {
-    if (!blob || len < CONTENT_HEADER || (len - CONTENT_HEADER) % 8)
-        throw Error(FR_ERR_INVALID, "compact content: length is not 64 + 8 n_blocks (fr_compact_content_size)");
-    if (std::memcmp(blob, CONTENT_MAGIC, 8)) throw Error(FR_ERR_INVALID, "compact content: bad magic");
-    if (get_le32(blob + 8) != (uint32_t)p.k || get_le32(blob + 12) != (uint32_t)p.N)
-        throw Error(FR_ERR_INVALID, "compact content: k, N do not match the context params");
-    ContentBlob c;
-    c.first_block = get_le64(blob + 16);
-    const uint64_t nb = get_le64(blob + 24);
-    if (nb != (len - CONTENT_HEADER) / 8)
-        throw Error(FR_ERR_INVALID, "compact content: n_blocks does not match the length");
-    // (each term first: the sum of two u64 could wrap)
-    if (c.first_block > CONTENT_MAX_BLOCK || nb > CONTENT_MAX_BLOCK || c.first_block + nb > CONTENT_MAX_BLOCK)
-        throw Error(FR_ERR_INVALID, "compact content: first_block + n_blocks exceeds 2^40");
-    if (radix && nb % 4) throw Error(FR_ERR_INVALID, "compact content: a string is 4 blocks per character");
-    c.n_blocks = (size_t)nb;
-    c.mask_key = RngKey::from_bytes(blob + 32);
-    c.bodies = blob + CONTENT_HEADER;
-    return c;
-}
-
 std::vector<uint8_t> encrypt_content_blob(const Params& p, const ClientKey& ck, const uint8_t* msgs, size_t count,
                                           const RngKey& key, uint64_t first_block) {
-    if (first_block > CONTENT_MAX_BLOCK || count > CONTENT_MAX_BLOCK || first_block + count > CONTENT_MAX_BLOCK)
-        throw Error(FR_ERR_INVALID, "compact content: first_block + n_blocks exceeds 2^40");
+    check_content_range(first_block, count);
     const size_t big = (size_t)p.big();
     const RngKey mk = derive_mask_key(key);  // public
     std::vector<uint8_t> out(content_blob_size(count));
-    std::memcpy(out.data(), CONTENT_MAGIC, 8);
-    put_le32(out.data() + 8, (uint32_t)p.k);
-    put_le32(out.data() + 12, (uint32_t)p.N);
-    put_le64(out.data() + 16, first_block);
-    put_le64(out.data() + 24, count);
-    for (int i = 0; i < 8; ++i) put_le32(out.data() + 32 + 4 * i, mk.w[i]);
+    write_content_header(p, first_block, count, mk, out.data());
     std::vector<uint64_t> lwe(big + 1);  // one block at a time: only its body is kept
     for (size_t q = 0; q < count; ++q) {
         encrypt_blocks(p, ck, msgs + q, 1, mk, key, first_block + q, lwe.data());
         put_le64(out.data() + CONTENT_HEADER + 8 * q, lwe[big]);
     }
     return out;
-}
-
-void expand_content(const Params& p, const uint8_t* blob, size_t len, uint64_t* out) {
-    const ContentBlob c = check_content_blob(p, blob, len, false);
-    const uint64_t big = (uint64_t)p.big();
-    Rng rm(c.mask_key, STREAM_ENC_MASK);
-    for (size_t q = 0; q < c.n_blocks; ++q) {
-        uint64_t* o = out + q * (big + 1);
-        const uint64_t qb = c.first_block + q;
-        for (uint64_t t = 0; t < big; ++t) o[t] = rm.u64(qb * big + t);
-        o[big] = get_le64(c.bodies + 8 * q);
-    }
 }
 
 uint64_t lwe_phase(const Params& p, const ClientKey& ck, const uint64_t* lwe) {
@@ -703,98 +564,6 @@ void gen_pksk_noise(const Params& p, const RngKey& key, std::vector<int32_t>& e)
     if (!ok) throw Error(FR_ERR_INVALID, "GLWE noise outside int32 (sigma too large for the device key generator)");
 }
 
-static const char PK_MAGIC[9] = "FRPKKEY1";
-static const char PKRES_MAGIC[9] = "FRPKRES1";
-
-void write_pk_header(const Params& p, uint8_t* out) {
-    std::memcpy(out, PK_MAGIC, 8);
-    int32_t v[8];
-    compact_params(p, v);
-    for (int i = 0; i < 8; ++i) put_le32(out + 8 + 4 * i, (uint32_t)v[i]);
-    put_le32(out + 40, (uint32_t)PK_BASE_LOG);
-    put_le32(out + 44, (uint32_t)PK_LEVELS);
-}
-
-void check_pk_blob(const Params& p, const uint8_t* blob, size_t len) {
-    if (!blob || len != pk_blob_size(p))
-        throw Error(FR_ERR_INVALID, "packing key: length does not match the context params (fr_packing_key_size)");
-    if (std::memcmp(blob, PK_MAGIC, 8)) throw Error(FR_ERR_INVALID, "packing key: bad magic");
-    int32_t want[8];
-    compact_params(p, want);
-    for (int i = 0; i < 8; ++i)
-        if (get_le32(blob + 8 + 4 * i) != (uint32_t)want[i])
-            throw Error(FR_ERR_INVALID, "packing key: parameters do not match the context params");
-    if (get_le32(blob + 40) != (uint32_t)PK_BASE_LOG || get_le32(blob + 44) != (uint32_t)PK_LEVELS)
-        throw Error(FR_ERR_INVALID, "packing key: gadget other than base 2^7, 3 levels");
-}
-
-// ---------------------------------------------------------------- compact packing key
-static const char PKC_MAGIC[9] = "FRCPKEY1";
-
-void write_pk_compact_header(const Params& p, const RngKey& mask_key, uint8_t* out) {
-    std::memcpy(out, PKC_MAGIC, 8);
-    int32_t v[8];
-    compact_params(p, v);
-    for (int i = 0; i < 8; ++i) put_le32(out + 8 + 4 * i, (uint32_t)v[i]);
-    put_le32(out + 40, (uint32_t)PK_BASE_LOG);
-    put_le32(out + 44, (uint32_t)PK_LEVELS);
-    put_le32(out + 48, (uint32_t)PKC_BODY_BITS);
-    put_le32(out + 52, 0);
-    for (int i = 0; i < 8; ++i) put_le32(out + 56 + 4 * i, mask_key.w[i]);
-    std::memset(out + 88, 0, 8);
-}
-
-RngKey check_pk_compact(const Params& p, const uint8_t* blob, size_t len) {
-    if (!blob || len != pk_compact_size(p))
-        throw Error(FR_ERR_INVALID, "compact packing key: length does not match the context params "
-                                    "(fr_packing_key_compact_size)");
-    if (std::memcmp(blob, PKC_MAGIC, 8)) throw Error(FR_ERR_INVALID, "compact packing key: bad magic");
-    int32_t want[8];
-    compact_params(p, want);
-    for (int i = 0; i < 8; ++i)
-        if (get_le32(blob + 8 + 4 * i) != (uint32_t)want[i])
-            throw Error(FR_ERR_INVALID, "compact packing key: parameters do not match the context params");
-    if (get_le32(blob + 40) != (uint32_t)PK_BASE_LOG || get_le32(blob + 44) != (uint32_t)PK_LEVELS)
-        throw Error(FR_ERR_INVALID, "compact packing key: gadget other than base 2^7, 3 levels");
-    if (get_le32(blob + 48) != (uint32_t)PKC_BODY_BITS)
-        throw Error(FR_ERR_INVALID, "compact packing key: body bits other than 40");
-    if (get_le32(blob + 52) != 0) throw Error(FR_ERR_INVALID, "compact packing key: reserved word is not zero");
-    for (int i = 88; i < 96; ++i)
-        if (blob[i]) throw Error(FR_ERR_INVALID, "compact packing key: pad bytes are not zero");
-    return RngKey::from_bytes(blob + 56);
-}
-
-void pack_pk_compact(const Params& p, const uint64_t* rows, uint8_t* planes) {
-    const size_t R = pk_rows(p), N = (size_t)p.N, W = pk_row_words(p), kN = (size_t)p.k * N;
-    uint8_t* lo = planes + 4 * R * N;
-    parallel_for((int)R, [&](int r) {
-        const uint64_t* body = rows + (size_t)r * W + kN;
-        for (size_t t = 0; t < N; ++t) {
-            const uint64_t b40 = body[t] >> PKC_DROP_BITS;
-            put_le32(planes + 4 * ((size_t)r * N + t), (uint32_t)(b40 >> 8));
-            lo[(size_t)r * N + t] = (uint8_t)b40;
-        }
-    });
-}
-
-void expand_pk_compact(const Params& p, const uint8_t* blob, size_t len, std::vector<uint64_t>& rows,
-                       RngKey& mask_key) {
-    mask_key = check_pk_compact(p, blob, len);
-    const size_t R = pk_rows(p), N = (size_t)p.N, W = pk_row_words(p), kN = (size_t)p.k * N;
-    const uint8_t* hi = blob + PKC_HEADER;
-    const uint8_t* lo = hi + 4 * R * N;
-    rows.resize(pk_len(p));
-    parallel_for((int)R, [&](int r) {
-        Rng rm(mask_key, STREAM_PKSK_MASK);
-        uint64_t* o = rows.data() + (size_t)r * W;
-        for (size_t t = 0; t < kN; ++t) o[t] = rm.u64((uint64_t)r * kN + t);
-        for (size_t t = 0; t < N; ++t) {
-            const uint64_t b40 = ((uint64_t)get_le32(hi + 4 * ((size_t)r * N + t)) << 8) | lo[(size_t)r * N + t];
-            o[kN + t] = b40 << PKC_DROP_BITS;
-        }
-    });
-}
-
 // Rows of the key are streamed once per block of PACK_JB booleans, whose partial sums
 // (PACK_JB rows of (k+1) N words) stay in cache meanwhile.
 constexpr size_t PACK_JB = 16;
@@ -845,71 +614,6 @@ void pack_host(const Params& p, const uint64_t* pksk, const uint64_t* lwes, cons
         for (size_t t = 0; t < W; ++t) out[t] += acc[t];
 }
 
-void write_packed_result(const Params& p, size_t n, const uint64_t* words, uint8_t* out) {
-    std::memcpy(out, PKRES_MAGIC, 8);
-    put_le32(out + 8, (uint32_t)p.k);
-    put_le32(out + 12, (uint32_t)p.N);
-    put_le64(out + 16, n);
-    for (size_t t = 0; t < pk_row_words(p); ++t) put_le64(out + PKRES_HEADER + 8 * t, words[t]);
-}
-
-size_t check_packed_result(const Params& p, const uint8_t* blob, size_t len) {
-    if (!blob || len != packed_result_size(p))
-        throw Error(FR_ERR_INVALID, "packed result: length is not 24 + 8 (k+1) N (fr_packed_result_size)");
-    if (std::memcmp(blob, PKRES_MAGIC, 8)) throw Error(FR_ERR_INVALID, "packed result: bad magic");
-    if (get_le32(blob + 8) != (uint32_t)p.k || get_le32(blob + 12) != (uint32_t)p.N)
-        throw Error(FR_ERR_INVALID, "packed result: k, N do not match the context params");
-    const uint64_t n = get_le64(blob + 16);
-    if (n < 1 || n > (uint64_t)p.N) throw Error(FR_ERR_INVALID, "packed result: n outside 1..N");
-    return (size_t)n;
-}
-
-static const char PKCRES_MAGIC[9] = "FRCPRES1";
-
-void write_packed_compact_header(const Params& p, size_t n, uint8_t* out) {
-    std::memcpy(out, PKCRES_MAGIC, 8);
-    put_le32(out + 8, (uint32_t)p.k);
-    put_le32(out + 12, (uint32_t)p.N);
-    put_le64(out + 16, n);
-    put_le32(out + 24, (uint32_t)PKCRES_BITS);
-    put_le32(out + 28, 0);
-}
-
-void compress_packed(const Params& p, size_t n, const uint64_t* words, uint8_t* out) {
-    if (n < 1 || n > (size_t)p.N) throw Error(FR_ERR_INVALID, "compact packed result: n outside 1..N");
-    write_packed_compact_header(p, n, out);
-    // the body's first n coefficients follow the masks in the words as they do in the blob
-    for (size_t t = 0; t < packed_compact_values(p, n); ++t) {
-        const uint16_t v = packed_round16(words[t]);
-        out[PKCRES_HEADER + 2 * t] = (uint8_t)v;
-        out[PKCRES_HEADER + 2 * t + 1] = (uint8_t)(v >> 8);
-    }
-}
-
-size_t check_packed_compact(const Params& p, const uint8_t* blob, size_t len) {
-    if (!blob || len < PKCRES_HEADER)
-        throw Error(FR_ERR_INVALID, "compact packed result: length is not 32 + 2 (kN + n) (fr_packed_compact_size)");
-    if (std::memcmp(blob, PKCRES_MAGIC, 8)) throw Error(FR_ERR_INVALID, "compact packed result: bad magic");
-    if (get_le32(blob + 8) != (uint32_t)p.k || get_le32(blob + 12) != (uint32_t)p.N)
-        throw Error(FR_ERR_INVALID, "compact packed result: k, N do not match the context params");
-    const uint64_t n = get_le64(blob + 16);
-    if (n < 1 || n > (uint64_t)p.N) throw Error(FR_ERR_INVALID, "compact packed result: n outside 1..N");
-    if (get_le32(blob + 24) != (uint32_t)PKCRES_BITS)
-        throw Error(FR_ERR_INVALID, "compact packed result: coefficient bits other than 16");
-    if (get_le32(blob + 28) != 0) throw Error(FR_ERR_INVALID, "compact packed result: reserved word not zero");
-    if (len != packed_compact_size(p, (size_t)n))
-        throw Error(FR_ERR_INVALID, "compact packed result: length is not 32 + 2 (kN + n) (fr_packed_compact_size)");
-    return (size_t)n;
-}
-
-void expand_packed_compact(const Params& p, const uint8_t* blob, uint64_t* words) {
-    const size_t n = (size_t)get_le64(blob + 16), sent = packed_compact_values(p, n);
-    for (size_t t = 0; t < pk_row_words(p); ++t) {
-        const uint8_t* v = blob + PKCRES_HEADER + 2 * t;
-        words[t] = t < sent ? ((uint64_t)v[0] | ((uint64_t)v[1] << 8)) << PKCRES_DROP : 0;
-    }
-}
-
 void glwe_phase(const Params& p, const ClientKey& ck, const uint64_t* ct, uint64_t* phase) {
     const int k = p.k, N = p.N;
     std::vector<uint64_t> as((size_t)N, 0);
@@ -922,35 +626,10 @@ void glwe_phase(const Params& p, const ClientKey& ck, const uint64_t* ct, uint64
 }
 
 // ---------------------------------------------------------------- private search: the needle
-static const char NEEDLE_MAGIC[9] = "FRNEEDL1";
-
-size_t needle_blob_size(const Params& p, size_t m) {
-    if (m < 1 || m > NEEDLE_MAX_CHARS) throw Error(FR_ERR_INVALID, "needle: 1 <= m <= 64");
-    return NEEDLE_HEADER + 16 * m * (size_t)p.N;
-}
-
 uint64_t needle_test_poly(int N, int t, uint16_t table) {
     const int box = N / 16, half = box / 2, mm = (t + half) / box;
     const uint64_t v = (uint64_t)((table >> (mm < 16 ? mm : 0)) & 1) << DELTA_LOG;
     return mm < 16 ? v : (uint64_t)0 - v;
-}
-
-NeedleBlob check_needle_blob(const Params& p, const uint8_t* blob, size_t len) {
-    if (p.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "private search: FFT ring only");
-    if (!blob || len < NEEDLE_HEADER) throw Error(FR_ERR_INVALID, "needle: length is not 64 + 16 m N (fr_needle_size)");
-    if (std::memcmp(blob, NEEDLE_MAGIC, 8)) throw Error(FR_ERR_INVALID, "needle: bad magic");
-    if (get_le32(blob + 8) != (uint32_t)p.k || get_le32(blob + 12) != (uint32_t)p.N)
-        throw Error(FR_ERR_INVALID, "needle: k, N do not match the context params");
-    const uint64_t m = get_le64(blob + 16);
-    if (m < 1 || m > NEEDLE_MAX_CHARS) throw Error(FR_ERR_INVALID, "needle: 1 <= m <= 64");
-    if (len != needle_blob_size(p, (size_t)m))
-        throw Error(FR_ERR_INVALID, "needle: length is not 64 + 16 m N (fr_needle_size)");
-    if (get_le64(blob + 56) != 0) throw Error(FR_ERR_INVALID, "needle: reserved bytes are not zero");
-    NeedleBlob nb;
-    nb.m = (size_t)m;
-    nb.mask_key = RngKey::from_bytes(blob + 24);
-    nb.bodies = blob + NEEDLE_HEADER;
-    return nb;
 }
 
 std::vector<uint8_t> encrypt_needle_blob(const Params& p, const ClientKey& ck, const uint16_t* masks, size_t m,
@@ -960,12 +639,7 @@ std::vector<uint8_t> encrypt_needle_blob(const Params& p, const ClientKey& ck, c
     const int k = p.k, N = p.N;
     std::vector<uint8_t> out(needle_blob_size(p, m));
     const RngKey mk = derive_mask_key(key);  // public
-    std::memcpy(out.data(), NEEDLE_MAGIC, 8);
-    put_le32(out.data() + 8, (uint32_t)k);
-    put_le32(out.data() + 12, (uint32_t)N);
-    put_le64(out.data() + 16, m);
-    for (int i = 0; i < 8; ++i) put_le32(out.data() + 24 + 4 * i, mk.w[i]);
-    put_le64(out.data() + 56, 0);
+    write_needle_header(p, m, mk, out.data());
     parallel_for((int)(2 * m), [&](int q) {
         Rng rm(mk, STREAM_NEEDLE_MASK), rn(key, STREAM_NEEDLE_NOISE);
         std::vector<uint64_t> A((size_t)N), B((size_t)N, 0);
@@ -985,17 +659,6 @@ std::vector<uint8_t> encrypt_needle_blob(const Params& p, const ClientKey& ck, c
         explicit_bzero(B.data(), 8 * B.size());
     });
     return out;
-}
-
-void expand_needle(const Params& p, const uint8_t* blob, size_t len, uint64_t* out) {
-    const NeedleBlob nb = check_needle_blob(p, blob, len);
-    const size_t k = (size_t)p.k, N = (size_t)p.N;
-    parallel_for((int)(2 * nb.m), [&](int q) {
-        Rng rm(nb.mask_key, STREAM_NEEDLE_MASK);
-        uint64_t* o = out + (size_t)q * (k + 1) * N;
-        for (size_t t = 0; t < k * N; ++t) o[t] = rm.u64((uint64_t)q * k * N + t);
-        for (size_t t = 0; t < N; ++t) o[k * N + t] = get_le64(nb.bodies + 8 * ((size_t)q * N + t));
-    });
 }
 
 uint32_t decode16(uint64_t phase) {

@@ -1,5 +1,5 @@
 // Client key (reference fixture layout), deterministic server-key generation,
-// client-side encryption — host C++.
+// client-side encryption — host C++.  The wire blobs that carry them are wire.h's.
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -102,19 +102,9 @@ RngKey derive_mask_key(const RngKey& key);
 // the full arrays (gen_ksk's and gen_bsk's layouts) and the mask key
 void gen_server_key_compact(const Params& p, const ClientKey& ck, const RngKey& key, std::vector<uint64_t>& ksk,
                             std::vector<uint64_t>& bsk, RngKey& mask_key);
-// Wire blob (include/fheregex.h): "FRCSKEY1", eight int32 parameters, the mask key, the
-// KSK bodies [kN * ks_level], the BSK bodies [W][k+1][N]; little endian
-constexpr size_t COMPACT_HEADER = 72;
-size_t compact_ksk_bodies(const Params& p);  // u64 counts
+// the body counts of its wire blob (wire.h), u64 each
+size_t compact_ksk_bodies(const Params& p);
 size_t compact_bsk_bodies(const Params& p);
-size_t compact_size(const Params& p);        // bytes
-// Error(FR_ERR_INVALID) unless len, the magic and the eight parameters are p's; the mask key
-RngKey check_compact(const Params& p, const uint8_t* blob, size_t len);
-std::vector<uint8_t> pack_compact(const Params& p, const RngKey& mask_key, const std::vector<uint64_t>& ksk,
-                                  const std::vector<uint64_t>& bsk);
-// check_compact, then every mask from the mask key around the blob's bodies
-void expand_compact(const Params& p, const uint8_t* blob, size_t len, std::vector<uint64_t>& ksk,
-                    std::vector<uint64_t>& bsk, RngKey& mask_key);
 
 // Packing key (DESIGN.md §1 "Packed results"): row 3 i + l, i < kN, l < PK_LEVELS, is a GLWE
 // encryption under the GLWE key (the big key read as k polynomials) of the constant polynomial
@@ -134,13 +124,6 @@ void gen_packing_rows(const Params& p, const ClientKey& ck, const RngKey& mask_k
                       bool round40, size_t row_lo, size_t row_hi, uint64_t* out);
 // the body noise of every row for the device generator ([row][N], glwe sigma, torus units)
 void gen_pksk_noise(const Params& p, const RngKey& key, std::vector<int32_t>& e);
-// Wire blob: "FRPKKEY1", the eight int32 parameters of the compact server key blob,
-// PK_BASE_LOG, PK_LEVELS (int32), then the rows; little endian
-constexpr size_t PK_HEADER = 48;
-inline size_t pk_blob_size(const Params& p) { return PK_HEADER + 8 * pk_len(p); }
-void write_pk_header(const Params& p, uint8_t* out /* PK_HEADER bytes */);
-// Error(FR_ERR_INVALID) unless len, the magic, the parameters and the gadget are p's
-void check_pk_blob(const Params& p, const uint8_t* blob, size_t len);
 
 // Compact (seeded) packing key, every ring.  The masks are ChaCha20 words of
 // the public mask key M = derive_mask_key(K) at the standard generator's indices, the noise is
@@ -151,21 +134,8 @@ void check_pk_blob(const Params& p, const uint8_t* blob, size_t len);
 // The installed key is an ordinary packing key.
 constexpr int PKC_BODY_BITS = 40, PKC_DROP_BITS = 64 - PKC_BODY_BITS;
 inline uint64_t pk_round40(uint64_t body) { return (body + ((uint64_t)1 << (PKC_DROP_BITS - 1))) >> PKC_DROP_BITS; }
-// Wire blob (include/fheregex.h): "FRCPKEY1", the eight int32 parameters, the gadget, the body
-// bits, a reserved zero, the mask key, 8 zero bytes, then the high plane u32[3kN][N] (b40 >> 8)
-// and the low plane u8[3kN][N] (b40 & 0xFF); little endian
-constexpr size_t PKC_HEADER = 96;
+// The blob (wire.h) carries b40 in a u32 plane (b40 >> 8) and a u8 plane (b40 & 0xFF).
 inline size_t pk_compact_planes(const Params& p) { return 5 * pk_rows(p) * (size_t)p.N; }  // bytes
-inline size_t pk_compact_size(const Params& p) { return PKC_HEADER + pk_compact_planes(p); }
-void write_pk_compact_header(const Params& p, const RngKey& mask_key, uint8_t* out /* PKC_HEADER bytes */);
-// Error(FR_ERR_INVALID) unless len, the magic, the parameters, the gadget and the body bits are
-// p's and the reserved word and the pad are zero; the mask key
-RngKey check_pk_compact(const Params& p, const uint8_t* blob, size_t len);
-// the bodies of full rows [pk_rows][(k+1) N] into the two planes (pk_compact_planes bytes)
-void pack_pk_compact(const Params& p, const uint64_t* rows, uint8_t* planes);
-// check_pk_compact, then the full rows: every mask from the mask key, every body b40 << 24
-void expand_pk_compact(const Params& p, const uint8_t* blob, size_t len, std::vector<uint64_t>& rows,
-                       RngKey& mask_key);
 
 // Packing keyswitch, host restatement (plain loops; the device path is keyswitch.hip's):
 //   out = sum_j X^j ((0, .., 0, b_j) - sum_{i,l} d_{j,i,l} PKSK[3 i + l])
@@ -174,37 +144,16 @@ void expand_pk_compact(const Params& p, const uint8_t* blob, size_t len, std::ve
 // digits of the mask of c_j rounded to 21 bits.  Exact mod 2^64.
 void pack_host(const Params& p, const uint64_t* pksk, const uint64_t* lwes, const int32_t* w, const int32_t* off,
                size_t n, uint64_t* out /* (k+1) N */);
-// Packed result blob: "FRPKRES1", int32 k, N, u64 n, then the (k+1) N words; little endian
-constexpr size_t PKRES_HEADER = 24;
-inline size_t packed_result_size(const Params& p) { return PKRES_HEADER + 8 * pk_row_words(p); }
-void write_packed_result(const Params& p, size_t n, const uint64_t* words, uint8_t* out);
-// Error(FR_ERR_INVALID) unless len, the magic, k and N are p's and 1 <= n <= N; returns n
-size_t check_packed_result(const Params& p, const uint8_t* blob, size_t len);
 // Compact packed result.  A packed boolean is never bootstrapped again, so
 // only the client's rounding at Delta / 2 = 2^58 sees its error: every coefficient travels
 // rounded to its top 16 bits, v = ((x + 2^47) >> 48) mod 2^16, and is installed as v << 48, the
 // mask and the body alike; the body coefficients past n carry no boolean and are not sent.
 // The rounding adds std sqrt((h + 1) / 12) 2^48 to the phase, h the key's weight: 2^51.2 at
 // h = 1024 against the 2^58 threshold.
-// Wire blob: "FRCPRES1", int32 k, N, u64 n, u32 16 (coefficient bits), u32 0 (reserved), then
-// u16 mask[kN], u16 body[n]; little endian, exactly 32 + 2 (kN + n) bytes.
-// Decryption is glwe_phase of the expanded words and round(phase / 2^59) & 1 for j < n; the
-// coefficients past n were not sent (they expand to a zero body), so there is nothing to check
-// there, unlike check_packed_result's blob.
+// Decryption is glwe_phase of the expanded words and round(phase / 2^59) & 1 for j < n.
 constexpr int PKCRES_BITS = 16, PKCRES_DROP = 64 - PKCRES_BITS;
-constexpr size_t PKCRES_HEADER = 32;
 inline uint16_t packed_round16(uint64_t x) { return (uint16_t)((x + ((uint64_t)1 << (PKCRES_DROP - 1))) >> PKCRES_DROP); }
 inline size_t packed_compact_values(const Params& p, size_t n) { return (size_t)p.big() + n; }  // u16 values
-inline size_t packed_compact_size(const Params& p, size_t n) { return PKCRES_HEADER + 2 * packed_compact_values(p, n); }
-void write_packed_compact_header(const Params& p, size_t n, uint8_t* out /* PKCRES_HEADER bytes */);
-// the blob of a packed GLWE's (k+1) N words carrying n booleans: plain loops, the word-for-word
-// reference of the device's k_pack_compress
-void compress_packed(const Params& p, size_t n, const uint64_t* words, uint8_t* out);
-// Error(FR_ERR_INVALID) unless len, the magic, k and N are p's, 1 <= n <= N, the bit count is 16
-// and the reserved word is 0; returns n
-size_t check_packed_compact(const Params& p, const uint8_t* blob, size_t len);
-// a checked blob's (k+1) N words: v << 48, the body past n zero
-void expand_packed_compact(const Params& p, const uint8_t* blob, uint64_t* words);
 // phase B - sum_c A_c S_c (negacyclic) of a GLWE ciphertext under the client key: N words
 void glwe_phase(const Params& p, const ClientKey& ck, const uint64_t* ct, uint64_t* phase);
 
@@ -223,26 +172,10 @@ void encrypt_blocks(const Params& p, const ClientKey& ck, const uint8_t* msgs, s
 // indices (u64 number (first_block + q) kN + t of STREAM_ENC_MASK); the noise is the standard
 // encryptor's under the call's secret key K.  An LWE mask is public anyway, so no secret
 // touches a mask word, and the ciphertexts are their bodies and the 32 bytes of the mask key.
-// Wire blob (include/fheregex.h): "FRCCTXT1", int32 k, N, u64 first_block, u64 n_blocks, the
-// mask key, n_blocks u64 bodies; little endian, exactly 64 + 8 n_blocks bytes.
-constexpr size_t CONTENT_HEADER = 64;
-constexpr uint64_t CONTENT_MAX_BLOCK = (uint64_t)1 << 40;  // first_block + n_blocks: (f + q) kN / 8 cannot wrap
-struct ContentBlob {
-    RngKey mask_key;
-    uint64_t first_block = 0;
-    size_t n_blocks = 0;
-    const uint8_t* bodies = nullptr;  // n_blocks u64, little endian, any alignment
-};
-size_t content_blob_size(size_t n_blocks);  // bytes; Error(FR_ERR_INVALID) past CONTENT_MAX_BLOCK blocks
-// Error(FR_ERR_INVALID) unless len is exact, the magic matches, k and N are p's,
-// first_block + n_blocks <= 2^40 and (radix: the string entries) n_blocks % 4 == 0
-ContentBlob check_content_blob(const Params& p, const uint8_t* blob, size_t len, bool radix);
-// encrypt_blocks under (derive_mask_key(key), key), packed; `key` is the caller's to wipe
+// encrypt_blocks under (derive_mask_key(key), key) as the content blob of wire.h; `key` is the
+// caller's to wipe
 std::vector<uint8_t> encrypt_content_blob(const Params& p, const ClientKey& ck, const uint8_t* msgs, size_t count,
                                           const RngKey& key, uint64_t first_block);
-// check_content_blob (radix = false), then every mask from the mask key around the blob's
-// bodies; out has n_blocks * (kN+1) words.  Needs no client key.
-void expand_content(const Params& p, const uint8_t* blob, size_t len, uint64_t* out);
 // Private search: an encrypted needle, FFT ring.  A selector is a GLWE
 // ciphertext, k mask polynomials then the body, (k+1) N words, under the GLWE key (the big key
 // read as k polynomials) whose phase is the direct test polynomial V(T) of a 0/1 table T of
@@ -253,26 +186,11 @@ void expand_content(const Params& p, const uint8_t* blob, size_t len, uint64_t* 
 // number (q k + c) N + t of STREAM_NEEDLE_MASK under the public mask key M = derive_mask_key(K);
 // the noise is the gaussian (glwe sigma) of STREAM_NEEDLE_NOISE under the call's secret key K
 // at q N + t; body = sum_c A_c S_c + V(T_q) + e, negacyclic.  No secret touches a mask word.
-// Wire blob (include/fheregex.h): "FRNEEDL1", int32 k, N, u64 m, the mask key, 8 zero bytes,
-// then the 2 m body polynomials of N u64; little endian, exactly 64 + 16 m N bytes.
-constexpr size_t NEEDLE_HEADER = 64;
 inline size_t needle_words(const Params& p, size_t m) { return 2 * m * (size_t)(p.k + 1) * p.N; }
-size_t needle_blob_size(const Params& p, size_t m);  // Error(FR_ERR_INVALID) unless 1 <= m <= 64
 uint64_t needle_test_poly(int N, int t, uint16_t table);
-struct NeedleBlob {
-    RngKey mask_key;
-    size_t m = 0;
-    const uint8_t* bodies = nullptr;  // 2 m N u64, little endian, any alignment
-};
-// Error(FR_ERR_INVALID) unless the ring is the FFT ring, len is exact, the magic matches, k and N
-// are p's, 1 <= m <= 64 and the pad is zero; nothing is allocated
-NeedleBlob check_needle_blob(const Params& p, const uint8_t* blob, size_t len);
-// masks: lo, hi per character (2 m tables); `key` is the caller's to wipe
+// the needle blob of wire.h; masks: lo, hi per character (2 m tables); `key` is the caller's to wipe
 std::vector<uint8_t> encrypt_needle_blob(const Params& p, const ClientKey& ck, const uint16_t* masks, size_t m,
                                          const RngKey& key);
-// check_needle_blob, then every mask from the mask key around the blob's bodies: out has
-// needle_words(p, m) words, [selector][polynomial][N].  Needs no client key.
-void expand_needle(const Params& p, const uint8_t* blob, size_t len, uint64_t* out);
 uint64_t lwe_phase(const Params& p, const ClientKey& ck, const uint64_t* lwe);
 // tfhe-rs shortint decrypt_message_and_carry: round(phase / Delta) mod 16
 uint32_t decode16(uint64_t phase);

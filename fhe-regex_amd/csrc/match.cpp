@@ -279,11 +279,7 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
         if (reply->compact) {
             std::vector<uint16_t> v(packed_compact_values(ctx->p, nO));
             dev.pack_bools_compact(desc.data(), nO, v.data());
-            write_packed_compact_header(ctx->p, nO, reply->buf);
-            for (size_t t = 0; t < v.size(); ++t) {
-                reply->buf[PKCRES_HEADER + 2 * t] = (uint8_t)v[t];
-                reply->buf[PKCRES_HEADER + 2 * t + 1] = (uint8_t)(v[t] >> 8);
-            }
+            write_packed_compact(ctx->p, nO, v.data(), reply->buf);
         } else {
             std::vector<uint64_t> words(pk_row_words(ctx->p));
             dev.pack_bools(desc.data(), nO, words.data());

@@ -1453,33 +1453,33 @@ class ServerKey:
 
 
 COMPACT_MAGIC = b"FRCSKEY1"
+COMPACT_CONTENT_MAGIC = b"FRCCTXT1"
+COMPACT_PACKING_MAGIC = b"FRCPKEY1"
+# magic -> (the blob's name, the mask key's offset, the header's size) (include/fheregex.h)
+_MASK_KEY_AT = {COMPACT_MAGIC: ("server key", 40, 72), COMPACT_CONTENT_MAGIC: ("content", 32, 64),
+                COMPACT_PACKING_MAGIC: ("packing key", 56, 96)}
+
+
+def _mask_key(blob, magic: bytes) -> bytes:
+    what, at, header = _MASK_KEY_AT[magic]
+    if len(blob) < header or bytes(blob[:8]) != magic:
+        raise ValueError(f"not a compact {what} blob")
+    return bytes(blob[at:at + 32])
 
 
 def compact_mask_key(blob: bytes) -> bytes:
     """the public 32-byte mask key of a compact server-key blob (bytes 40..71)"""
-    if len(blob) < 72 or bytes(blob[:8]) != COMPACT_MAGIC:
-        raise ValueError("not a compact server key blob")
-    return bytes(blob[40:72])
-
-
-COMPACT_CONTENT_MAGIC = b"FRCCTXT1"
+    return _mask_key(blob, COMPACT_MAGIC)
 
 
 def compact_content_mask_key(blob: bytes) -> bytes:
     """the public 32-byte mask key of a compact content blob (bytes 32..63)"""
-    if len(blob) < 64 or bytes(blob[:8]) != COMPACT_CONTENT_MAGIC:
-        raise ValueError("not a compact content blob")
-    return bytes(blob[32:64])
-
-
-COMPACT_PACKING_MAGIC = b"FRCPKEY1"
+    return _mask_key(blob, COMPACT_CONTENT_MAGIC)
 
 
 def compact_packing_mask_key(blob) -> bytes:
     """the public 32-byte mask key of a compact packing-key blob (bytes 56..87)"""
-    if len(blob) < 96 or bytes(blob[:8]) != COMPACT_PACKING_MAGIC:
-        raise ValueError("not a compact packing key blob")
-    return bytes(blob[56:88])
+    return _mask_key(blob, COMPACT_PACKING_MAGIC)
 
 
 def gen_keys(client_key_blob: Optional[bytes] = None, seed=None, device: int = 0,
