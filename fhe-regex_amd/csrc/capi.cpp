@@ -508,6 +508,34 @@ int fr_plain_find(const char* content, size_t len, const uint16_t* masks, size_t
                                   masks, 2 * m);
     })
 }
+int fr_plain_find_clear(const uint8_t* content, size_t len, const uint16_t* masks, size_t m, size_t start_lo,
+                        size_t start_hi, uint8_t* starts_out, int32_t* any) {
+    FR_TRY({
+        NEED((content || !len) && masks && any && start_lo <= start_hi && (starts_out || start_lo == start_hi));
+        NEED(m >= 1 && m <= NEEDLE_MAX_CHARS);
+        std::vector<int> vals;
+        eval_program_parts(compile_needle_clear(len, m, start_lo, start_hi, true), content, len, vals, masks, 2 * m);
+        for (size_t j = 0; j < vals.size(); ++j) starts_out[j] = (uint8_t)vals[j];
+        *any = eval_program_parts(compile_needle_clear(len, m, start_lo, start_hi, false), content, len, vals, masks,
+                                  2 * m);
+    })
+}
+int fr_dev_select_sum(fr_ctx* ctx, const fr_needle* needle, const uint8_t* content, size_t len, const int32_t* terms,
+                      const int32_t* n_terms, size_t n_sums, uint64_t* out) {
+    FR_TRY({
+        NEED(ctx && needle && (content || !len) && terms && n_terms && out);
+        Device& dev = ctx->device();
+        if (needle->k != ctx->p.k || needle->N != ctx->p.N)
+            throw Error(FR_ERR_INVALID, "needle: k, N do not match the context params");
+        dev.select_sum_host(needle->dev, content, len, terms, n_terms, n_sums, out);
+    })
+}
+int fr_dev_select_sum_ms(fr_ctx* ctx, double* ms) {
+    FR_TRY({
+        NEED(ctx && ms);
+        *ms = ctx->device().select_sum_ms();
+    })
+}
 int fr_dev_ring_mul(fr_ctx* ctx, const uint64_t* a, const uint64_t* b, size_t count, uint64_t* out) {
     FR_TRY({
         NEED(ctx && a && b && out);

@@ -45,6 +45,16 @@ FR_HD uint32_t acc_selector(const DevGate& g) {
 inline void set_acc_selector(DevGate& g, uint32_t q) {
     for (int i = 0; i < 4; ++i) g.lut[0][i] = (uint8_t)(q >> (8 * i));
 }
+// An extract-sum (private search over clear content, select_sum.hip): the big LWE in out_slot
+// is the sum over its terms (selector q, content position pos, half h) of the sample extract
+// of selector q at coefficient ((content[pos] >> 4 h) & 15) N/16.  No job: no keyswitch, no rotation.
+constexpr int SUM_MAX_TERMS = 16;
+struct DevSum {
+    int32_t out_slot;
+    int32_t n_terms;
+    int32_t term[SUM_MAX_TERMS][3];  // (q, pos, h)
+};
+static_assert(sizeof(DevSum) == 200, "DevSum layout");
 // sum of squared w_f coefficients of a LUT (noise growth of its factored output)
 int lut_w_norm2(const uint8_t* lut);
 
@@ -200,6 +210,16 @@ class Device {
     // theirs).  nullptr: none bound.
     DevNeedle upload_needle(const uint64_t* words, size_t m);
     void bind_selectors(const uint64_t* table, size_t count);
+    // Private search over clear content (select_sum.hip).  bind_text: the call's n content bytes,
+    // copied before it returns and bound to the current lane in stream order through the lane's
+    // staging ring, as bind_content binds a map.  run_sums / run_sums_resident: one launch of n
+    // extract-sums over the selector table and the content bound last on the current lane, every
+    // index checked against both bounds first; staged descriptors (lane 0 only) or a batch
+    // already resident (upload_sums: validated, synchronous; the batch is a Plan's).
+    void bind_text(const uint8_t* text, size_t n);
+    void run_sums(const DevSum* sums, size_t n);
+    void run_sums_resident(const DevSum* d_sums, const DevSum* host, size_t n);
+    gpu::DevBuf<DevSum> upload_sums(const DevSum* sums, size_t n);
     // linear combination without bootstrap (NOT of a boolean): out = offset*2^58 + sum w*in
     void run_linear(const DevGate& g);
     void sync();
@@ -226,6 +246,12 @@ class Device {
     // one selector launch: job i starts from the GLWE ciphertext accs + i (k+1) N
     void blind_rotate_acc_host(const uint64_t* ks_in, const uint64_t* accs, size_t count, uint64_t* out);
     void ring_mul_host(const uint64_t* a, const uint64_t* b, size_t count, uint64_t* out);
+    // the extract-sum kernel alone: sum i has n_terms[i] terms, 3 words each (q, pos, h), one
+    // after the other in `terms`; lwe_len words per sum to `out`.  Lane 0, synchronous.
+    void select_sum_host(const DevNeedle& needle, const uint8_t* text, size_t len, const int32_t* terms,
+                         const int32_t* n_terms, size_t n, uint64_t* out);
+    // ms of the last select_sum_host's kernel under fr_set_profiling (HIP events)
+    double select_sum_ms() const { return select_sum_ms_; }
     // repeated full-PBS batches on resident inputs (bench / roofline)
     void bench_pbs(const std::vector<DevGate>& gates, int iters, double* br_ms, double* total_ms);
 
@@ -249,6 +275,8 @@ class Device {
         size_t cmap_n = 0;           // entries bound
         const uint64_t* sel = nullptr;  // selector table (bind_selectors)
         size_t sel_n = 0;               // selectors bound
+        gpu::StagingRing<uint8_t> text;  // clear content bytes (bind_text)
+        size_t text_n = 0;               // bytes bound
         gpu::Event done_ev;          // recorded on the lane's stream when it is left
         bool pending = false;        // work enqueued since lane 0 last waited for it
     };
@@ -328,6 +356,12 @@ class Device {
     size_t leading_selector_jobs(const DevGate* host, size_t n) const;
     void launch_jobs(const DevGate* d_gates, const DevGate* host, size_t n, bool acc);  // one keyswitch + rotation
     void run_br_jobs(const uint64_t* ks_in, std::vector<DevGate>& gates, uint64_t* out);  // the blind_rotate_*_host hooks
+    // select_sum.hip
+    void validate_sums(const DevSum* sums, size_t n, size_t n_sel, size_t text_n) const;
+    void check_sums(const DevSum* host, size_t n) const;  // against what the current lane has bound
+    void launch_select_sum(const uint64_t* table, const DevSum* d_sums, size_t n);
+    gpu::StagingRing<DevSum> sums_;  // staged extract-sums (lane 0), as gates_
+    double select_sum_ms_ = 0;
     // FR_RING_RNS (rns_br.hip)
     void init_rns();
     void upload_rns_bsk(const std::vector<uint64_t>& bsk);

@@ -3,8 +3,9 @@
 // of big-LWE slots and its packed slot copies, gate staging and validation, running a
 // dependency level (keyswitch + blind rotation), timers, and the single-stage entry points
 // of the parity tests.  The kernels of a level live with the methods that launch them:
-// rns_br.hip (RNS blind rotation), fft_br.hip (FFT blind rotation), keyswitch.hip, and
-// keygen.hip (server-key generation, encryption).
+// rns_br.hip (RNS blind rotation), fft_br.hip (FFT blind rotation), keyswitch.hip,
+// keygen.hip (server-key generation, encryption), and select_sum.hip (the extract-sums of a
+// find over clear content, which run before a plan's first level).
 //
 //   k_slots_to_buf, k_slots_to_buf_arg, k_buf_to_slots : packed copies between arena slots
 //                         and a device buffer of the caller

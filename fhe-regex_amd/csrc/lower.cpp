@@ -643,6 +643,7 @@ void compute_levels(Program& prog) {
     std::vector<size_t> width;
     for (auto& g : prog.gates) {
         g.level = gate_level(g, [&](int s) { return prog.gates[s].level; });
+        if (g.level == 0) continue;  // an extract-sum: no bootstrap, in no level's width
         maxl = std::max(maxl, g.level);
         if ((size_t)g.level >= width.size()) width.resize(g.level + 1, 0);
         width[g.level]++;
@@ -742,7 +743,7 @@ static int threshold_tree(Program& prog, bool is_and, std::vector<int> lits) {
     return lits[0];
 }
 
-Program compile_needle(size_t n_chars, size_t m, size_t lo, size_t hi, bool starts) {
+static Program compile_needle_over(size_t n_chars, size_t m, size_t lo, size_t hi, bool starts, bool clear) {
     if (m < 1 || m > NEEDLE_MAX_CHARS) throw Error(FR_ERR_INVALID, "needle: 1 <= m <= 64");
     if (lo > hi) throw Error(FR_ERR_INVALID, "needle: start range");
     if (n_chars > (size_t)1 << 24) throw Error(FR_ERR_INVALID, "needle: content too long");
@@ -757,15 +758,32 @@ Program compile_needle(size_t n_chars, size_t m, size_t lo, size_t hi, bool star
             continue;
         }
         std::vector<int> tests;
-        for (size_t i = 0; i < m; ++i)
-            for (int h = 0; h < 2; ++h) {
+        if (clear) {
+            // test 2 i + h is a term; a chunk of them, summed, feeds the SIGN gate that would AND them
+            for_balanced_chunks(2 * m, [&](size_t first, size_t len) {
+                PGate sum;
+                sum.kind = GATE_EXTRACT;
+                for (size_t t = first; t < first + len; ++t)
+                    sum.terms.push_back({(int32_t)t, (int32_t)(p + t / 2), (int32_t)(t % 2)});
                 PGate g;
-                g.kind = GATE_SELECT;
-                g.sel = (int32_t)(2 * i + h);
-                g.ins = {{cblk((int)(p + i), 2 * h + 1), 4}, {cblk((int)(p + i), 2 * h), 1}};
+                g.kind = GATE_SIGN;
+                g.ins = {{(int32_t)prog.gates.size(), 1}};
+                g.offset = 1 - 2 * (int)len;
+                prog.gates.push_back(std::move(sum));
                 tests.push_back((int)prog.gates.size());
                 prog.gates.push_back(std::move(g));
-            }
+            });
+        } else {
+            for (size_t i = 0; i < m; ++i)
+                for (int h = 0; h < 2; ++h) {
+                    PGate g;
+                    g.kind = GATE_SELECT;
+                    g.sel = (int32_t)(2 * i + h);
+                    g.ins = {{cblk((int)(p + i), 2 * h + 1), 4}, {cblk((int)(p + i), 2 * h), 1}};
+                    tests.push_back((int)prog.gates.size());
+                    prog.gates.push_back(std::move(g));
+                }
+        }
         const int a = threshold_tree(prog, true, std::move(tests));
         if (starts) prog.outs.push_back(ProgOut{a, 1, 0});
         else found.push_back(a);
@@ -775,9 +793,17 @@ Program compile_needle(size_t n_chars, size_t m, size_t lo, size_t hi, bool star
         else prog.outs.push_back(ProgOut{threshold_tree(prog, false, std::move(found)), 1, 0});
     }
     // topological order by construction, but a tree's gates follow their start's tests: the
-    // scheduler orders by level, and level 1 is the selector gates alone
+    // scheduler orders by level, and level 1 is the selector gates alone (clear: the sign gates
+    // over the sums, which are level 0)
     compute_levels(prog);
     return prog;
+}
+
+Program compile_needle(size_t n_chars, size_t m, size_t lo, size_t hi, bool starts) {
+    return compile_needle_over(n_chars, m, lo, hi, starts, false);
+}
+Program compile_needle_clear(size_t n_chars, size_t m, size_t lo, size_t hi, bool starts) {
+    return compile_needle_over(n_chars, m, lo, hi, starts, true);
 }
 
 int eval_program(const Program& prog, const uint8_t* content, size_t L) {
@@ -790,6 +816,14 @@ int eval_program_parts(const Program& prog, const uint8_t* content, size_t L, st
     std::vector<int> val(prog.gates.size(), 0);
     for (size_t g = 0; g < prog.gates.size(); ++g) {
         const PGate& G = prog.gates[g];
+        if (G.kind == GATE_EXTRACT) {
+            for (const PTerm& t : G.terms) {
+                if (t.sel < 0 || (size_t)t.sel >= n_tables) throw Error(FR_ERR_INVALID, "extract-sum without its table");
+                if (t.pos < 0 || (size_t)t.pos >= L) throw Error(FR_ERR_INVALID, "program references content past its end");
+                val[g] += (tables[t.sel] >> ((content[t.pos] >> (4 * (t.half & 1))) & 15)) & 1;
+            }
+            continue;
+        }
         int s = G.offset;  // half units
         for (auto& in : G.ins) {
             int v;

@@ -13,6 +13,11 @@
 //  * SELECT : a LUT gate whose table the server does not know (private search): out =
 //           T_sel[s] for the 0/1 table T_sel that selector `sel` of the call's needle encrypts.
 //           Inputs, offsets and level rule are a LUT gate's; the lut field is unused.
+//  * EXTRACT : an extract-sum (private search over clear content): no bootstrap.  out = the
+//           number of its terms (selector, content position, half) whose selector's table
+//           accepts that nibble of the clear content, an integer in [0, 16], formed as a sum of
+//           sample extracts of the selectors (device.h: DevSum).  No inputs, level 0: neither a
+//           job nor a rotation; only SIGN gates read it (weight 1), as they would read its terms.
 //
 // FR_LOWER_FAITHFUL: one gate group per reference op (eq/gt/le = 3 PBS, and/or
 //   = 1 PBS, not = linear), the decomposition of SURVEY App. D.3.
@@ -35,7 +40,12 @@ struct PIn {
     int32_t src;  // >= 0: gate index; < 0: content block -(1 + pos*4 + blk)
     int32_t w;
 };
-enum GateKind : int32_t { GATE_LUT = 0, GATE_SIGN = 1, GATE_SELECT = 2 };
+enum GateKind : int32_t { GATE_LUT = 0, GATE_SIGN = 1, GATE_SELECT = 2, GATE_EXTRACT = 3 };
+// one term of an extract-sum: selector `sel` of the needle looks up nibble `half` (0: low) of the
+// clear content byte at `pos`
+struct PTerm {
+    int32_t sel, pos, half;
+};
 struct PGate {
     std::vector<PIn> ins;
     int32_t offset = 0;  // units of Delta/2
@@ -43,6 +53,7 @@ struct PGate {
     uint8_t lut[16] = {0};
     int32_t level = 0;
     int32_t sel = 0;  // GATE_SELECT: the selector's index in the needle
+    std::vector<PTerm> terms;  // GATE_EXTRACT: 1..16 of them
 };
 // one boolean output: cst + w * gates[gate]   (gate == -1: the constant cst)
 struct ProgOut {
@@ -68,14 +79,16 @@ Program lower(const ValueDag& dag, int root, int mode, int max_parts = 1);
 // check); returns the result value (several parts: their OR).
 int eval_program(const Program& prog, const uint8_t* content, size_t L);
 // the same, and each output's value in `parts`; tables (n_tables 16-bit masks of accepted
-// values) are what the program's selector gates look up: bit s of tables[sel]
+// values) are what the program's selector gates look up: bit s of tables[sel]; an extract-sum
+// counts its terms with bit (content[pos] >> 4 half) & 15 of tables[sel] set
 int eval_program_parts(const Program& prog, const uint8_t* content, size_t L, std::vector<int>& parts,
                        const uint16_t* tables = nullptr, size_t n_tables = 0);
 void compute_levels(Program& prog);
-// a gate's level: one past its deepest gate input (content blocks are level 0);
-// level_of(g) gives the level of an earlier gate
+// a gate's level: one past its deepest gate input (content blocks are level 0, and so is an
+// extract-sum, which is no bootstrap); level_of(g) gives the level of an earlier gate
 template <class LevelOf>
 int gate_level(const PGate& g, LevelOf&& level_of) {
+    if (g.kind == GATE_EXTRACT) return 0;
     int l = 0;
     for (const PIn& in : g.ins)
         if (in.src >= 0) l = std::max(l, (int)level_of(in.src));
@@ -122,6 +135,13 @@ CompiledStarts compile_match_starts(const MatchSpec& spec, bool keep_dags = fals
 // constant 0, and so is the OR over no start.  1 <= m <= NEEDLE_MAX_CHARS (common.h); m > n_chars is no error.
 // The program depends on (n_chars, m, lo, hi, starts) alone.  starts: at most 2^24 of them.
 Program compile_needle(size_t n_chars, size_t m, size_t lo, size_t hi, bool starts);
+// The same search over content the server holds in the clear: compile_needle with its selector
+// layer replaced by extract-sums.  The AND of a start's 2 m tests is one SIGN gate over one
+// extract-sum of 2 m terms (offset 1 - 2 len, as the AND over the tests themselves); for
+// 2 m > 16 each balanced chunk of the tests gets its own sum and SIGN gate, and the chunks are
+// ANDed as before.  No gate reads an encrypted content block.  The program depends on
+// (n_chars, m, lo, hi, starts) alone, never on the content bytes.
+Program compile_needle_clear(size_t n_chars, size_t m, size_t lo, size_t hi, bool starts);
 
 // LUT builders
 void lut_eq(uint8_t* lut, int v);     // [x == v]

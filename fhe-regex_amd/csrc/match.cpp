@@ -28,11 +28,13 @@ namespace {
 // pattern's own text (which may contain '|' and digits) cannot make two keys collide.
 // needle_m > 0: a private search (fr_find*) for a needle of that many characters, the pattern
 // empty -- the plan does not depend on the needle's ciphertext, so the length stands for it.
+// clear: that search over clear content (fr_find_clear*), whose plan does not depend on the
+// content's bytes either; the field keeps it apart from fr_find's plan for the same (m, n).
 std::string match_key(fr_ctx* ctx, const char* pattern, size_t n, size_t M, size_t lo, size_t hi, size_t parts,
-                      int lane, bool starts, size_t needle_m) {
+                      int lane, bool starts, size_t needle_m, bool clear) {
     std::string k;
     for (size_t v : {(size_t)ctx->grammar, (size_t)ctx->engine, (size_t)ctx->lowering, (size_t)ctx->multi_value, n, M,
-                     lo, hi, parts, (size_t)lane, (size_t)starts, needle_m})
+                     lo, hi, parts, (size_t)lane, (size_t)starts, needle_m, (size_t)clear})
         k += std::to_string(v) + "|";
     k += pattern;
     return k;
@@ -141,9 +143,13 @@ struct PackedReply {
 };
 // needle (fr_find, fr_find_starts; M = 1, no pattern): the program is compile_needle's, its
 // selector jobs read the needle's table, bound to the match's lane around its launches.
+// clear (fr_find_clear, fr_find_clear_starts; with a needle): the content is the n bytes at `text`
+// and there are no content handles; the program is compile_needle_clear's, its extract-sums read
+// the needle's table and the bytes, both bound to the match's lane around its launches.
 void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const char* pattern, size_t lo, size_t hi,
                 fr_ct* outs, fr_match_stats* st, size_t parts = 1, size_t* n_parts = nullptr, bool starts = false,
-                const PackedReply* reply = nullptr, const fr_needle* needle = nullptr) {
+                const PackedReply* reply = nullptr, const fr_needle* needle = nullptr, bool clear = false,
+                const uint8_t* text = nullptr) {
     double t0 = now_ms();
     pattern = pattern ? pattern : "";
     Device& dev = ctx->keyed_device();
@@ -155,6 +161,8 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
         if (needle->dev.dev != &dev || !needle->dev.words) throw Error(FR_ERR_INVALID, "needle: uploaded to another context");
     }
     const size_t needle_m = needle ? needle->dev.m : 0;
+    if (clear && (!needle || M != 1 || content)) throw Error(FR_ERR_INVALID, "clear content: one needle, no handles");
+    const size_t n_handles = clear ? 0 : n * M;
     fr_plan_cache& pc = ctx->plans;
     CachedMatch* hit = nullptr;
     std::string key;
@@ -175,8 +183,8 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
         }
     } lane_scope{dev};
     if (pc.capacity) {
-        key = match_key(ctx, pattern, n, M, lo, hi, parts, lane, starts, needle_m);
-        sig = content_signature(ctx, content, n * M, &cmap);
+        key = match_key(ctx, pattern, n, M, lo, hi, parts, lane, starts, needle_m, clear);
+        sig = content_signature(ctx, content, n_handles, &cmap);
         for (auto& e : pc.entries)
             if (e->parts == parts && e->lane == lane && e->key == key && e->sig == sig) hit = e.get();
     }
@@ -193,7 +201,9 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
         rec = hit->rec;
     } else {
         ++pc.misses;
-        if (needle) {
+        if (clear) {
+            prog = compile_needle_clear(n, needle_m, lo, hi, starts);
+        } else if (needle) {
             prog = compile_needle(n, needle_m, lo, hi, starts);
         } else if (starts) {
             CompiledStarts cs = compile_match_starts(match_spec(ctx, pattern, n, lo, hi));
@@ -204,7 +214,7 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
             rec = cm.rec;
             prog = std::move(cm.prog);
         }
-        check_content(ctx, prog, content, n, M);
+        if (!clear) check_content(ctx, prog, content, n, M);
         // M copies: gate g of match m is m * G + g, content block cb of match m is 4 n m + cb
         const size_t G = prog.gates.size();
         std::vector<PGate> gates;
@@ -215,10 +225,10 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
                 for (auto& in : g.ins) in.src = in.src >= 0 ? in.src + (int)(m * G) : in.src - (int)(4 * n * m);
                 gates.push_back(std::move(g));
             }
-        std::vector<fr_ct> inputs(content, content + n * M);
+        std::vector<fr_ct> inputs(content, content + n_handles);
         const bool keep = pc.capacity && G && G * M <= pc.slot_cap;
         if (keep) evict_for(ctx, 1, G * M);  // before the new plan allocates its slots
-        fresh = compile_plan(ctx, gates, inputs, keep);
+        fresh = compile_plan(ctx, gates, inputs, keep, clear ? n : 0);
         if (keep) {
             // keep the plan: its slots stay allocated, its batches go to the device once; the
             // entry is complete before the cache sees it
@@ -233,6 +243,7 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
             e->last_use = ++pc.clock;
             e->plan = std::move(fresh);
             e->plan.d_gates = dev.upload_gates(e->plan.gates.data(), e->plan.gates.size(), e->plan.n_refs);
+            if (!e->plan.sums.empty()) e->plan.d_sums = dev.upload_sums(e->plan.sums.data(), e->plan.sums.size());
             c = e.get();
             pc.entries.push_back(std::move(e));
             pc.slots_held += c->plan.slot.size();
@@ -247,14 +258,20 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
         dev.bind_content(cmap.data(), cmap.size());
     }
     double t1 = now_ms();
-    struct SelectorScope {  // the needle's table, for this match's launches on this lane only
+    struct SelectorScope {  // the needle's table (and clear content), for this match's launches on this lane only
         Device& d;
-        bool on;
+        bool on, text;
         ~SelectorScope() {
             if (on) d.bind_selectors(nullptr, 0);
+            try {
+                if (text) d.bind_text(nullptr, 0);
+            } catch (...) {
+            }
         }
-    } selector_scope{dev, needle != nullptr};
+    } selector_scope{dev, needle != nullptr, clear};
     if (needle) dev.bind_selectors(needle->dev.words.get(), 2 * needle_m);
+    // the call's bytes, copied now and in stream order on this lane: the caller's buffer may go
+    if (clear) dev.bind_text(text, n);
     launch_plan(dev, plan);
     if (hit && !starts && (nO < 1 || nO > parts))  // the caller's out buffer holds M * parts handles
         throw Error(FR_ERR_INVALID, "cached plan has more outputs than the caller's parts");
@@ -445,6 +462,26 @@ int fr_find_starts(fr_ctx* ctx, const fr_ct* content, size_t n_chars, const fr_n
     })
 }
 
+int fr_find_clear(fr_ctx* ctx, const uint8_t* content, size_t n_chars, const fr_needle* needle, size_t start_lo,
+                  size_t start_hi, fr_ct* out, fr_match_stats* st) {
+    FR_TRY({
+        NEED(ctx && needle && out && (content || !n_chars) && start_lo <= start_hi);
+        // (the range is cut at the content's end, as fr_find cuts it)
+        const size_t hi = std::min(start_hi, n_chars), lo = std::min(start_lo, hi);
+        match_impl(ctx, nullptr, n_chars, 1, "", lo, hi, out, st, 1, nullptr, false, nullptr, needle, true, content);
+    })
+}
+
+int fr_find_clear_starts(fr_ctx* ctx, const uint8_t* content, size_t n_chars, const fr_needle* needle, size_t start_lo,
+                         size_t start_hi, fr_ct* out, fr_match_stats* st) {
+    FR_TRY({
+        NEED(ctx && needle && (content || !n_chars) && start_lo <= start_hi && (out || start_lo == start_hi));
+        NEED(start_hi - start_lo <= ((size_t)1 << 24));
+        match_impl(ctx, nullptr, n_chars, 1, "", start_lo, start_hi, out, st, 1, nullptr, true, nullptr, needle, true,
+                   content);
+    })
+}
+
 int fr_has_match_parts(fr_ctx* ctx, const fr_ct* content, size_t n, const char* pattern, size_t lo, size_t hi,
                        size_t max_parts, fr_ct* out, size_t* n_parts, fr_match_stats* st) {
     FR_TRY({
@@ -458,13 +495,14 @@ int fr_has_match_parts(fr_ctx* ctx, const fr_ct* content, size_t n, const char* 
 
 // the schedule of a lowered program over n_chars encrypted characters (each position an
 // encrypted radix character), and its outputs as (gate, w, cst) triples
+// (in_slot of a job that reads an extract-sum is that sum's gate index, as for any gate)
 static void schedule_program(const Program& prog, size_t n_chars, int32_t multi_value, fr_job* jobs, size_t jobs_cap,
                              size_t* n_jobs, uint32_t* level_off, size_t level_cap, size_t* n_levels, int32_t* outs3,
                              size_t* n_parts) {
     Schedule S = build_schedule(prog.gates, n_chars, multi_value != 0, [](int cb, int& key, int&) {
         key = cb;
         return true;
-    });
+    }, n_chars);
     *n_jobs = S.jobs.size();
     *n_levels = S.level_off.size() - 1;
     *n_parts = prog.outs.size();
@@ -639,6 +677,17 @@ int fr_schedule_find(size_t n_chars, size_t m, size_t start_lo, size_t start_hi,
         NEED(n_jobs && n_levels && n_outs && outs3 && start_lo <= start_hi && (starts == 0 || starts == 1));
         NEED(outs_cap >= (starts ? start_hi - start_lo : 1));
         const Program prog = compile_needle(n_chars, m, start_lo, start_hi, starts != 0);
+        schedule_program(prog, n_chars, 1, jobs, jobs_cap, n_jobs, level_off, level_cap, n_levels, outs3, n_outs);
+    })
+}
+
+int fr_schedule_find_clear(size_t n_chars, size_t m, size_t start_lo, size_t start_hi, int32_t starts, fr_job* jobs,
+                           size_t jobs_cap, size_t* n_jobs, uint32_t* level_off, size_t level_cap, size_t* n_levels,
+                           int32_t* outs3, size_t outs_cap, size_t* n_outs) {
+    FR_TRY({
+        NEED(n_jobs && n_levels && n_outs && outs3 && start_lo <= start_hi && (starts == 0 || starts == 1));
+        NEED(outs_cap >= (starts ? start_hi - start_lo : 1));
+        const Program prog = compile_needle_clear(n_chars, m, start_lo, start_hi, starts != 0);
         schedule_program(prog, n_chars, 1, jobs, jobs_cap, n_jobs, level_off, level_cap, n_levels, outs3, n_outs);
     })
 }

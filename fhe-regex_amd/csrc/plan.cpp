@@ -6,7 +6,8 @@
 
 namespace fr {
 
-Plan compile_plan(fr_ctx* ctx, const std::vector<PGate>& gates, const std::vector<fr_ct>& inputs, bool content_refs) {
+Plan compile_plan(fr_ctx* ctx, const std::vector<PGate>& gates, const std::vector<fr_ct>& inputs, bool content_refs,
+                  size_t n_text) {
     Device& dev = ctx->keyed_device();
     auto block_slot = [&](int cb) -> const Block& { return ctx->get(inputs[(size_t)(cb / 4)]).b[cb % 4]; };
     Schedule S = build_schedule(gates, inputs.size(), ctx->multi_value, [&](int cb, int& key, int& triv) {
@@ -17,7 +18,7 @@ Plan compile_plan(fr_ctx* ctx, const std::vector<PGate>& gates, const std::vecto
         }
         key = b.slot;
         return true;
-    });
+    }, n_text);
     Plan P;
     P.slot = Slots(dev, gates.size());
     P.gates = std::move(S.jobs);
@@ -28,9 +29,11 @@ Plan compile_plan(fr_ctx* ctx, const std::vector<PGate>& gates, const std::vecto
                                             : block_slot(-1 - d.in_slot[q]).slot;
         for (int f = 0; f < d.n_out; ++f) d.out_slot[f] = P.slot[d.out_slot[f]];
     }
+    P.sums = std::move(S.sums);
+    for (DevSum& d : P.sums) d.out_slot = P.slot[d.out_slot];
     P.n_refs = content_refs ? 4 * inputs.size() : 0;
     P.level_off = std::move(S.level_off);
-    P.pbs = gates.size();
+    P.pbs = gates.size() - P.sums.size();  // (an extract-sum is no bootstrap)
     P.rotations = P.gates.size();
     P.levels = S.levels;
     P.max_width = S.max_width;
@@ -38,6 +41,8 @@ Plan compile_plan(fr_ctx* ctx, const std::vector<PGate>& gates, const std::vecto
 }
 
 void launch_plan(Device& dev, const Plan& P) {
+    if (P.d_sums) dev.run_sums_resident(P.d_sums.get(), P.sums.data(), P.sums.size());
+    else dev.run_sums(P.sums.data(), P.sums.size());
     for (size_t l = 0; l + 1 < P.level_off.size(); ++l) {
         const size_t a = P.level_off[l], n = P.level_off[l + 1] - a;
         if (P.d_gates) dev.run_level_resident(P.d_gates.get() + a, P.gates.data() + a, n, P.n_refs);

@@ -30,6 +30,9 @@ constexpr int MV_MAX_NORM2 = 8;
 struct Schedule {
     std::vector<DevGate> jobs;      // levels concatenated
     std::vector<size_t> level_off;  // level l (0-based): jobs [level_off[l], level_off[l+1])
+    // the program's extract-sums (level 0: before every job, and no job themselves); out_slot is
+    // a program gate
+    std::vector<DevSum> sums;
     size_t n_gates = 0;
     uint64_t levels = 0, max_width = 0;
 };
@@ -38,17 +41,38 @@ struct Schedule {
 // else key identifies the block's ciphertext (the multi-value merge compares keys).
 // A template parameter, not a std::function: it is called per content reference of
 // every gate, twice, and the cold path of a match is this function.
+// n_text: the clear content bytes an extract-sum's terms may refer to.
 template <class BlockFn>
-Schedule build_schedule(const std::vector<PGate>& gates, size_t n_content, bool multi_value, BlockFn&& block) {
+Schedule build_schedule(const std::vector<PGate>& gates, size_t n_content, bool multi_value, BlockFn&& block,
+                        size_t n_text = 0) {
     // 1. validation: topological order, input range, fan-in, offsets
     std::vector<int> level(gates.size(), 0);
     int maxl = 0;
+    std::vector<DevSum> sums;
     for (size_t g = 0; g < gates.size(); ++g) {
         const PGate& G = gates[g];
+        if (G.kind == GATE_EXTRACT) {  // level 0 (the vector's initial value)
+            if (!G.ins.empty() || G.terms.empty() || G.terms.size() > (size_t)SUM_MAX_TERMS)
+                throw Error(FR_ERR_INVALID, "extract-sum: no inputs and 1..16 terms");
+            DevSum d;
+            std::memset(&d, 0, sizeof d);
+            d.out_slot = (int32_t)g;
+            for (const PTerm& t : G.terms) {
+                if (t.sel < 0 || t.sel >= MAX_SELECTORS || t.pos < 0 || (size_t)t.pos >= n_text || t.half < 0 || t.half > 1)
+                    throw Error(FR_ERR_INVALID, "extract-sum: term out of range");
+                int32_t* w = d.term[d.n_terms++];
+                w[0] = t.sel, w[1] = t.pos, w[2] = t.half;
+            }
+            sums.push_back(d);
+            continue;
+        }
         int nin = 0, off = G.offset;
         for (auto& in : G.ins) {
             if (in.src >= 0) {
                 if ((size_t)in.src >= g) throw Error(FR_ERR_INVALID, "gate program is not topologically ordered");
+                // a sum is not a boolean: only the AND it stands for may read it
+                if (gates[in.src].kind == GATE_EXTRACT && (G.kind != GATE_SIGN || in.w != 1))
+                    throw Error(FR_ERR_INVALID, "extract-sum read by other than a sign gate with weight 1");
                 ++nin;
                 continue;
             }
@@ -72,6 +96,7 @@ Schedule build_schedule(const std::vector<PGate>& gates, size_t n_content, bool 
             if ((gates[g].kind == GATE_SELECT) == (sel == 1)) by_level[level[g]].push_back((int)g);
     // 2. jobs, level by level
     Schedule S;
+    S.sums = std::move(sums);
     S.n_gates = gates.size();
     S.level_off.push_back(0);
     for (int l = 1; l <= maxl; ++l) {
@@ -166,6 +191,11 @@ struct Plan {
     uint64_t pbs = 0, rotations = 0, levels = 0, max_width = 0;
     size_t n_refs = 0;              // template plan: content references (4 per position)
     gpu::DevBuf<DevGate> d_gates;   // device-resident copy (cached plans)
+    // extract-sums (a find over clear content): launched before level 1 into the plan's own
+    // slots, over the needle and the content bytes the call bound to its lane; their
+    // device-resident copy goes with d_gates, under the same rule
+    std::vector<DevSum> sums;
+    gpu::DevBuf<DevSum> d_sums;
 
     Plan() = default;
     Plan(Plan&&) = default;
@@ -179,8 +209,9 @@ struct Plan {
     }
 };
 
+// n_text: the clear content bytes the program's extract-sums may refer to
 Plan compile_plan(fr_ctx* ctx, const std::vector<PGate>& gates, const std::vector<fr_ct>& inputs,
-                  bool content_refs = false);
+                  bool content_refs = false, size_t n_text = 0);
 // enqueue every level of a plan (async on the device stream)
 void launch_plan(Device& dev, const Plan& P);
 void add_plan_stats(const Plan& P, fr_match_stats* st);

@@ -194,6 +194,19 @@ _SIGS = {
     "fr_plain_find": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint16), C.c_size_t, C.c_size_t, C.c_size_t,
                                 C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]),
     "fr_dev_blind_rotate_acc": (C.c_int, [C.c_void_p, u64p, u64p, C.c_size_t, u64p]),
+    "fr_find_clear": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                C.POINTER(C.c_uint32), C.POINTER(MatchStats)]),
+    "fr_find_clear_starts": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                       C.POINTER(C.c_uint32), C.POINTER(MatchStats)]),
+    "fr_schedule_find_clear": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int32, C.POINTER(FrJob),
+                                         C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.c_size_t,
+                                         C.POINTER(C.c_size_t), C.POINTER(C.c_int32), C.c_size_t,
+                                         C.POINTER(C.c_size_t)]),
+    "fr_plain_find_clear": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint16), C.c_size_t, C.c_size_t,
+                                      C.c_size_t, C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]),
+    "fr_dev_select_sum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_int32), C.c_size_t, u64p]),
+    "fr_dev_select_sum_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "fr_encrypt_str": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint64, u64p]),
     "fr_encrypt_blocks": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, C.c_uint64, C.c_uint64, u64p]),
     "fr_decrypt_radix": (C.c_int, [C.c_void_p, u64p, u64p]),
@@ -976,6 +989,52 @@ class Context:
         _check(lib().fr_dev_blind_rotate_acc(self.h, _p(a), _p(g), a.shape[0], _p(out)))
         return out
 
+    # ---- private search over clear content (fr_find_clear*): the server's own bytes
+    def _find_clear(self, fn, text, needle, lo, hi, n_out):
+        if needle.h is None:
+            raise ValueError("needle is closed")
+        b = _text_bytes(text)
+        out = (C.c_uint32 * max(n_out, 1))()
+        st = MatchStats()
+        _check(fn(self.h, b, len(b), needle.h, lo, hi, out, C.byref(st)))
+        return list(out)[:n_out], st
+
+    def find_clear(self, text: bytes | str, needle: "Needle", lo: Optional[int] = None, hi: Optional[int] = None):
+        """fr_find_clear: (boolean handle, MatchStats): the needle matches the clear text at some
+        start of [lo, hi)"""
+        lo = 0 if lo is None else lo
+        hi = len(_text_bytes(text)) if hi is None else hi
+        out, st = self._find_clear(lib().fr_find_clear, text, needle, lo, hi, 1)
+        return out[0], st
+
+    def find_clear_starts(self, text: bytes | str, needle: "Needle", lo: Optional[int] = None,
+                          hi: Optional[int] = None, stats: bool = False):
+        """fr_find_clear_starts: one boolean handle per start offset of [lo, hi)"""
+        lo = 0 if lo is None else lo
+        hi = len(_text_bytes(text)) if hi is None else hi
+        hs, st = self._find_clear(lib().fr_find_clear_starts, text, needle, lo, hi, max(hi - lo, 0))
+        return (hs, st) if stats else hs
+
+    def dev_select_sum(self, needle: "Needle", text: bytes | str, sums: Sequence[Sequence[Tuple[int, int, int]]]
+                       ) -> np.ndarray:
+        """fr_dev_select_sum: the extract-sum kernel alone; sums[i] is the list of sum i's terms
+        (selector q, content position pos, half h) -> [len(sums)][k N + 1] u64"""
+        if needle.h is None:
+            raise ValueError("needle is closed")
+        b = _text_bytes(text)
+        flat = [int(v) for s in sums for t in s for v in t]
+        terms = (C.c_int32 * max(len(flat), 1))(*flat)
+        counts = (C.c_int32 * max(len(sums), 1))(*[len(s) for s in sums])
+        out = np.zeros((len(sums), self.lwe_len), dtype=np.uint64)
+        _check(lib().fr_dev_select_sum(self.h, needle.h, b, len(b), terms, counts, len(sums), _p(out)))
+        return out
+
+    def select_sum_timer(self) -> float:
+        """ms of the last dev_select_sum's kernel under set_profiling"""
+        ms = C.c_double()
+        _check(lib().fr_dev_select_sum_ms(self.h, C.byref(ms)))
+        return ms.value
+
     def content_expand_timer(self) -> float:
         """ms of the last upload_compact_*'s expansion kernel under set_profiling"""
         ms = C.c_double()
@@ -1254,6 +1313,25 @@ def needle_masks(s: bytes | str, ignore_case: bool = False, any_char: Optional[s
     return out
 
 
+def _text_bytes(text: bytes | str) -> bytes:
+    """clear content as bytes: a str is its latin-1 bytes (one byte per character)"""
+    return text.encode("latin-1") if isinstance(text, str) else bytes(text)
+
+
+def plain_find_clear(content: bytes | str, masks: Sequence[Tuple[int, int]], start_lo: int = 0,
+                     start_hi: Optional[int] = None) -> Tuple[List[int], int]:
+    """fr_plain_find_clear: the lowered programs of find_clear_starts and find_clear in
+    plaintext, extract-sums included: (starts, any)"""
+    b = _text_bytes(content)
+    hi = len(b) if start_hi is None else start_hi
+    flat = [v for lo_hi in masks for v in lo_hi]
+    arr = (C.c_uint16 * max(len(flat), 1))(*flat)
+    out = (C.c_uint8 * max(hi - start_lo, 1))()
+    any_ = C.c_int32()
+    _check(lib().fr_plain_find_clear(b, len(b), arr, len(masks), start_lo, hi, out, C.byref(any_)))
+    return list(out)[:max(hi - start_lo, 0)], any_.value
+
+
 def plain_find(content: bytes | str, masks: Sequence[Tuple[int, int]], start_lo: int = 0,
                start_hi: Optional[int] = None) -> Tuple[List[int], int]:
     """fr_plain_find: the lowered programs of find_starts and find in plaintext: (starts, any)"""
@@ -1401,6 +1479,26 @@ class ServerKey:
         forms): fr_find_starts, then one pack per chunk of N starts.  The handles are released."""
         N = self.ctx.params.N
         hs = self.ctx.find_starts(content, needle)
+        try:
+            pack = self.ctx.pack_bools_compact if compact else self.ctx.pack_bools
+            blobs = [pack(hs[i:i + N]) for i in range(0, len(hs), N)]
+        finally:
+            for h in hs:
+                self.ctx.release(h)
+        if compact:
+            return struct.pack("<II", COMPACT_REPLY, len(blobs)) + b"".join(blobs)
+        return struct.pack("<I", len(blobs)) + b"".join(blobs)
+
+    def find_clear(self, text: bytes | str, needle: Needle) -> int:
+        """boolean handle: the encrypted needle occurs in the server's own clear text"""
+        return self.ctx.find_clear(text, needle)[0]
+
+    def find_clear_starts(self, text: bytes | str, needle: Needle, compact: bool = False) -> bytes:
+        """where the needle occurs in the clear text, as find_starts' reply for
+        ClientKey.decrypt_starts (both forms): fr_find_clear_starts, then one pack per chunk of N
+        starts.  The handles are released."""
+        N = self.ctx.params.N
+        hs = self.ctx.find_clear_starts(text, needle)
         try:
             pack = self.ctx.pack_bools_compact if compact else self.ctx.pack_bools
             blobs = [pack(hs[i:i + N]) for i in range(0, len(hs), N)]
@@ -1842,8 +1940,15 @@ def schedule_match_starts(n_chars: int, pattern: str, start_lo: int = 0, start_h
     return Schedule(list(jobs[:nj.value]), list(off), first[0], first[1], first[2], n_gates, parts)
 
 
+def schedule_find_clear(n_chars: int, m: int, start_lo: int = 0, start_hi: Optional[int] = None,
+                        starts: bool = False) -> Schedule:
+    """fr_schedule_find_clear: schedule_find for find_clear / find_clear_starts (no selector job;
+    the extract-sums are level 0 and are no jobs)"""
+    return schedule_find(n_chars, m, start_lo, start_hi, starts, _fn="fr_schedule_find_clear")
+
+
 def schedule_find(n_chars: int, m: int, start_lo: int = 0, start_hi: Optional[int] = None,
-                  starts: bool = False) -> Schedule:
+                  starts: bool = False, _fn: str = "fr_schedule_find") -> Schedule:
     """fr_schedule_find: the schedule of find (one output) or find_starts (Schedule.parts: one
     (out_gate, out_w, out_const) per start) for a needle of m characters"""
     hi = n_chars if start_hi is None else start_hi
@@ -1851,11 +1956,11 @@ def schedule_find(n_chars: int, m: int, start_lo: int = 0, start_hi: Optional[in
     cap = max(hi - start_lo, 1)
     outs3 = (C.c_int32 * (3 * cap))()
     args = (n_chars, m, start_lo, hi, int(starts))
-    _check(lib().fr_schedule_find(*args, None, 0, C.byref(nj), None, 0, C.byref(nl), outs3, cap, C.byref(ns)))
+    fn = getattr(lib(), _fn)
+    _check(fn(*args, None, 0, C.byref(nj), None, 0, C.byref(nl), outs3, cap, C.byref(ns)))
     jobs = (FrJob * max(nj.value, 1))()
     off = (C.c_uint32 * (nl.value + 1))()
-    _check(lib().fr_schedule_find(*args, jobs, len(jobs), C.byref(nj), off, len(off), C.byref(nl), outs3, cap,
-                                  C.byref(ns)))
+    _check(fn(*args, jobs, len(jobs), C.byref(nj), off, len(off), C.byref(nl), outs3, cap, C.byref(ns)))
     n_gates = 1 + max([max(j.out_gate[f] for f in range(j.n_out)) for j in jobs[:nj.value]] or [-1])
     parts = [(outs3[3 * j], outs3[3 * j + 1], outs3[3 * j + 2]) for j in range(ns.value)]
     first = parts[0] if parts else (-1, 0, 0)

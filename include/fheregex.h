@@ -628,6 +628,33 @@ int fr_find(fr_ctx* ctx, const fr_ct* content, size_t n_chars, const fr_needle* 
 int fr_find_starts(fr_ctx* ctx, const fr_ct* content, size_t n_chars, const fr_needle* needle, size_t start_lo,
                    size_t start_hi, fr_ct* out /* start_hi - start_lo */, fr_match_stats* stats);
 
+/* ----- private search over clear content (FFT ring) ----- */
+/* The same search where the server holds the text itself (a corpus, a log, a mailbox it hosts)
+ * and only the needle is encrypted: fr_find_clear and fr_find_clear_starts give fr_find's and
+ * fr_find_starts' booleans for the n_chars bytes at `content` (a pointer and a length: every byte
+ * value is valid, 0x00 and bytes >= 0x80 included; copied before the call returns).  A blind
+ * rotation by a known nibble v is the monomial X^(-v N/16), so the first level needs no rotation:
+ * bit v of selector q's table is coefficient v N/16 of its phase, and the sample extract there
+ * is an LWE of that bit under the flattened GLWE key, with the selector's fresh noise alone.
+ * Extraction is linear, so the sum the per-start AND reads is formed straight from the needle's
+ * table by one kernel, one big LWE per gate (none per content nibble), and a find costs one
+ * rotation per start that fits for m <= 8 (two levels of them above that), plus fr_find_clear's
+ * OR tree.  The server learns m; the client learns the booleans.  Circuit privacy of the reply is
+ * not claimed: the outputs are bootstrap outputs, their noise the server key's, as every match's.
+ * Both run through the match engine: plan cache (the plan depends on m, n_chars and the range,
+ * never on the bytes or on the needle's ciphertext: a second text of the same length is a hit, and
+ * so is a second needle of the same length; fr_find's plans are kept apart), lanes, fr_set_async,
+ * stats (pbs and blind_rotations count rotations only).  The bytes travel per call, in stream
+ * order on the match's lane.  m > n_chars is no error: the constant; a start that cannot fit is
+ * a trivial 0.  FR_ERR_INVALID for an RNS context, a needle of another (k, N) or of another
+ * context, a NULL content with n_chars > 0, start_lo > start_hi; FR_ERR_NO_DEVICE on a host-only
+ * context; nothing is launched then. */
+int fr_find_clear(fr_ctx* ctx, const uint8_t* content, size_t n_chars, const fr_needle* needle, size_t start_lo,
+                  size_t start_hi, fr_ct* out, fr_match_stats* stats);
+int fr_find_clear_starts(fr_ctx* ctx, const uint8_t* content, size_t n_chars, const fr_needle* needle,
+                         size_t start_lo, size_t start_hi, fr_ct* out /* start_hi - start_lo */,
+                         fr_match_stats* stats);
+
 /* ----- one match split across ranks ----- */
 /* The reference folds ct_or over the branches of every start offset
  * (engine.rs:15-35, each branch a chain of execution.rs:76-190 calls); anchored
@@ -707,6 +734,17 @@ int fr_schedule_find(size_t n_chars, size_t m, size_t start_lo, size_t start_hi,
  * the tables in the clear: starts_out[p - start_lo] and *any. */
 int fr_plain_find(const char* content, size_t len, const uint16_t* masks, size_t m, size_t start_lo, size_t start_hi,
                   uint8_t* starts_out, int32_t* any);
+/* The schedule of fr_find_clear (starts = 0) or fr_find_clear_starts (starts = 1), shaped as
+ * fr_schedule_find.  There is no kind-3 job: the extract-sums are level 0, neither jobs nor
+ * rotations, and a kind-2 job of level 1 reads one of them as its single input (in_ref[0]: the
+ * sum's program gate, in_w[0] = 1), its offset the AND's over the sum's terms. */
+int fr_schedule_find_clear(size_t n_chars, size_t m, size_t start_lo, size_t start_hi, int32_t starts, fr_job* jobs,
+                           size_t jobs_cap, size_t* n_jobs, uint32_t* level_off, size_t level_cap, size_t* n_levels,
+                           int32_t* outs3, size_t outs_cap, size_t* n_outs);
+/* The lowered programs of fr_find_clear_starts and fr_find_clear evaluated in plaintext, the
+ * extract-sums included, with the tables in the clear: starts_out[p - start_lo] and *any. */
+int fr_plain_find_clear(const uint8_t* content, size_t len, const uint16_t* masks, size_t m, size_t start_lo,
+                        size_t start_hi, uint8_t* starts_out, int32_t* any);
 
 /* ----- host-only introspection (tests; no device needed) ----- */
 /* Canonical AST string of parse(pattern) (parser.rs:146-185). */
@@ -831,6 +869,15 @@ int fr_dev_blind_rotate_multi(fr_ctx* ctx, const uint64_t* in, const uint8_t* lu
  * fr_dev_blind_rotate's words.  The launch shape follows count, as every launch's does. */
 int fr_dev_blind_rotate_acc(fr_ctx* ctx, const uint64_t* in /* count*(n+1) */, const uint64_t* accs, size_t count,
                             uint64_t* out);
+/* the extract-sum kernel alone (private search over clear content; FFT ring): sum i < n_sums has
+ * n_terms[i] terms, each 3 words (selector q, content position pos, half h) following those of
+ * sum i - 1 in `terms`, and is the sum over them of the sample extract of the needle's selector q
+ * at coefficient ((content[pos] >> 4 h) & 15) N/16 -> out: n_sums*(kN+1), wrapping u64, exact.
+ * FR_ERR_INVALID for n_terms outside [1, 16], q >= 2 m, pos >= len, h > 1, before any launch.
+ * fr_dev_select_sum_ms: the kernel's HIP-event ms of the last call under fr_set_profiling. */
+int fr_dev_select_sum(fr_ctx* ctx, const fr_needle* needle, const uint8_t* content, size_t len,
+                      const int32_t* terms /* 3 per term */, const int32_t* n_terms, size_t n_sums, uint64_t* out);
+int fr_dev_select_sum_ms(fr_ctx* ctx, double* ms);
 /* negacyclic product in Z_Q[X]/(X^N+1) (Q = 998244353 * 1004535809, inputs in
  * [0, Q)) through the device RNS NTT: count pairs */
 int fr_dev_ring_mul(fr_ctx* ctx, const uint64_t* a, const uint64_t* b, size_t count, uint64_t* out);
