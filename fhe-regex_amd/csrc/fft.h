@@ -158,7 +158,11 @@ FR_HD double acc_reduce(double t) {
     static_assert(B == 64 - ACC_LOG, "the accumulator unit is the gadget's 2^(64-B)");
     return FR_FMA(-FR_RINT(t * (1.0 / (double)(1ULL << B))), (double)(1ULL << B), t);
 }
-// exact f64 of a u64 torus value (signed representative in [-2^63, 2^63)), in accumulator units
+// f64 of a u64 torus value (signed representative in [-2^63, 2^63)), in accumulator units: exact
+// for a value of at most 53 significant bits (every LUT polynomial: multiples of 2^58); a
+// selector's uniform 64-bit word rounds to the nearest f64, ties to even, at most 2^9 away (2^63 - 1
+// becomes 2^63, which torus_of wraps to -2^63).  The rounding is part of the specification: the
+// oracle's selector ladder converts the same way (tests/test_selector_oracle.py).
 FR_HD double acc_of_torus(uint64_t u) { return (double)(int64_t)u * 0x1p-41; }
 // the u64 torus value of an accumulator entry
 FR_HD uint64_t torus_of_acc(double t) { return torus_of(t * 0x1p41); }

@@ -113,6 +113,12 @@ def lib():
         L.or_torus_of.argtypes = [C.c_double]
         L.or_blind_rotate_exact.argtypes = [C.POINTER(Params), u64p, u64p, C.POINTER(C.c_uint8), C.c_int, C.c_int,
                                             C.c_size_t, u64p]
+        L.or_blind_rotate_exact_acc.argtypes = [C.POINTER(Params), u64p, u64p, u64p, C.c_size_t, u64p]
+        L.or_blind_rotate_acc.restype = C.c_int
+        L.or_blind_rotate_acc.argtypes = [C.c_void_p, u64p, u64p, C.c_size_t, u64p]
+        L.or_gates_sel.restype = C.c_int
+        L.or_gates_sel.argtypes = [C.c_void_p, u64p, C.POINTER(Gate), C.c_size_t, u64p, u64p, C.c_size_t,
+                                   C.POINTER(C.c_int32), u64p]
         L.or_num_threads.restype = C.c_int
         L.or_set_threads.argtypes = [C.c_int]
         _lib = L
@@ -259,13 +265,37 @@ class Oracle:
         lib().or_blind_rotate_multi(self._pk, ptr(a), flat, len(luts), int(direct), ptr(out))
         return out
 
-    def blind_rotate_exact(self, ks_lwes: np.ndarray, luts, direct: int = 1) -> np.ndarray:
+    def _glwes(self, accs, count: int) -> np.ndarray:
+        g = np.ascontiguousarray(accs, dtype=np.uint64)
+        assert g.size == count * (self.P.k + 1) * self.P.N, (g.shape, count)
+        return g
+
+    def blind_rotate_acc(self, ks_lwes: np.ndarray, accs) -> np.ndarray:
+        """The f64 ladder of a selector job: rotation i starts from the GLWE accs[i]
+        ([k+1][N] u64: mask polynomials, then the body) instead of (0, V(lut)); the direct
+        sample extract, no offset.  ks_lwes (count, n+1); returns (count, kN+1)."""
+        assert self.P.ring == RING_FFT and self._pk
+        a = np.ascontiguousarray(ks_lwes.reshape(-1, self.n + 1), dtype=np.uint64)
+        g = self._glwes(accs, a.shape[0])
+        out = np.zeros((a.shape[0], self.big + 1), dtype=np.uint64)
+        assert lib().or_blind_rotate_acc(self._pk, ptr(a), ptr(g), a.shape[0], ptr(out)) == 0
+        return out
+
+    def blind_rotate_exact(self, ks_lwes: np.ndarray, luts=None, direct: int = 1, accs=None) -> np.ndarray:
         """The torus ring's unrolled ladder in exact u64 arithmetic (schoolbook negacyclic
         products mod 2^64, no f64): ks_lwes (count, n+1); luts (count, n_out, 16) or
-        (count, 16) for direct jobs; returns (count, n_out, kN+1)."""
+        (count, 16) for direct jobs; returns (count, n_out, kN+1).  With accs (count GLWEs
+        [k+1][N], luts None) ladder i starts from accs[i], rotated in u64 with no rounding;
+        returns (count, kN+1)."""
         assert self.P.ring == RING_FFT and self.bsk is not None
         a = np.ascontiguousarray(ks_lwes.reshape(-1, self.n + 1), dtype=np.uint64)
         count = a.shape[0]
+        if accs is not None:
+            assert luts is None and direct == 1
+            g = self._glwes(accs, count)
+            out = np.zeros((count, self.big + 1), dtype=np.uint64)
+            lib().or_blind_rotate_exact_acc(C.byref(self.P), ptr(self.bsk), ptr(a), ptr(g), count, ptr(out))
+            return out
         l = np.ascontiguousarray(np.asarray(luts, dtype=np.uint8).reshape(count, -1, 16))
         n_out = 1 if direct else l.shape[1]
         out = np.zeros((count, n_out, self.big + 1), dtype=np.uint64)
@@ -273,10 +303,12 @@ class Oracle:
                                     count, ptr(out))
         return out
 
-    def gates(self, gates, slots: np.ndarray) -> np.ndarray:
+    def gates(self, gates, slots: np.ndarray, selectors=None) -> np.ndarray:
         """gates: list of (inputs [(slot, weight)], offset, luts, direct) jobs, offset
         in units of Delta/2; a bare 16-entry lut means one direct output; direct=2
-        is a sign gate (luts ignored).  Returns all outputs, job-major."""
+        is a sign gate (luts ignored); direct=3 is a selector job (fr_job's JOB_ACC):
+        its rotation starts from selectors[i] ([n_sel][k+1][N] u64), i the first four
+        bytes of luts[0], little endian.  Returns all outputs, job-major."""
         arr = (Gate * len(gates))()
         first = (C.c_int32 * len(gates))()
         total = 0
@@ -300,19 +332,29 @@ class Oracle:
             total += len(luts)
         s = np.ascontiguousarray(slots.reshape(-1, self.big + 1), dtype=np.uint64)
         out = np.zeros((total, self.big + 1), dtype=np.uint64)
-        lib().or_gates(self._pk, ptr(self.ksk), arr, len(gates), ptr(s), first, ptr(out))
+        sel, n_sel = None, 0
+        if selectors is not None:
+            table = np.ascontiguousarray(selectors, dtype=np.uint64).reshape(-1, self.P.k + 1, self.P.N)
+            sel, n_sel = ptr(table), table.shape[0]
+        rc = lib().or_gates_sel(self._pk, ptr(self.ksk), arr, len(gates), ptr(s), sel, n_sel, first, ptr(out))
+        assert rc == 0, "a selector job past the table of %d selectors (or not on the torus ring)" % n_sel
         return out
 
-    def run_schedule(self, S, content_lwes: np.ndarray, levels=None) -> np.ndarray:
+    def run_schedule(self, S, content_lwes: np.ndarray, levels=None, selectors=None, values=None) -> np.ndarray:
         """Evaluate a match schedule (fheregex.schedule_match: fr_job semantics)
         level by level, each level's jobs in one parallel or_gates call; returns
         the result LWE (block 0 of the boolean).  levels: optional range of levels
-        (the caller then reads self.sched_val)."""
-        content = content_lwes.reshape(-1, self.big + 1)
+        (the caller then reads self.sched_val).  selectors: the table the selector
+        jobs of a find schedule read (Oracle.gates).  values: {gate: LWE} of gates that
+        no job makes (the extract-sums of a find_clear schedule), seeded before level 1;
+        a schedule that reads no content takes content_lwes None."""
+        content = None if content_lwes is None else content_lwes.reshape(-1, self.big + 1)
         if levels is None:
             self.sched_val = {}
             levels = range(len(S.level_off) - 1)
         val = self.sched_val
+        if values is not None:
+            val.update({int(g): np.asarray(v, dtype=np.uint64) for g, v in values.items()})
         for l in levels:
             rows, index, jobs = [], {}, []
             js = S.jobs[S.level_off[l]:S.level_off[l + 1]]
@@ -325,7 +367,7 @@ class Oracle:
                         rows.append(val[r] if r >= 0 else content[-1 - r])
                     ins.append((index[r], j.in_w[q]))
                 jobs.append((ins, j.offset, [list(j.lut[f]) for f in range(j.n_out)], j.kind))
-            outs = self.gates(jobs, np.stack(rows))
+            outs = self.gates(jobs, np.stack(rows), selectors)
             k = 0
             for j in js:
                 for f in range(j.n_out):

@@ -707,7 +707,13 @@ static uint64_t apply_w(const uint64_t* poly, int N, int j, int nt, const int32_
 /* Torus ring: the unrolled blind rotation with the three Fourier GGSWs of a
  * pair, their monomial factors psi^(e L(j)) - 1 applied slot-wise, one
  * inverse transform per output polynomial; the accumulator is u64. */
-static void blind_rotate_torus(or_bsk* K, const uint64_t* ks_lwe, const uint8_t* luts, int n_out, int direct, uint64_t* outs) {
+/* acc0 != NULL (a selector job): the ladder starts from the caller's GLWE acc0 [k+1][N]
+ * instead of (0, .., 0, V): every polynomial is rotated by X^-b and converted with
+ * (double)(int64_t), which rounds a word of more than 53 significant bits to nearest even
+ * (fft.h acc_of_torus, up to its exact 2^-41 scale); luts is not read and the output is the
+ * direct sample extract with no post offset (the caller passes direct = 1). */
+static void blind_rotate_torus(or_bsk* K, const uint64_t* ks_lwe, const uint8_t* luts, int n_out, int direct,
+                               const uint64_t* acc0, uint64_t* outs) {
     const or_params* P = &K->P;
     const fft_plan* F = K->FP;
     int k = P->k, N = P->N, n = P->n, M = N / 2, log2N2 = ilog2(2 * N);
@@ -719,7 +725,8 @@ static void blind_rotate_torus(or_bsk* K, const uint64_t* ks_lwe, const uint8_t*
     uint64_t* V = malloc(8 * N);
     struct { double cr[3], ci[3]; }* SF = malloc(sizeof(*SF) * M); /* a step's slot factors */
     const uint64_t delta = 1ULL << 59;
-    if (direct == 1) {
+    if (acc0) { /* V is not used */
+    } else if (direct == 1) {
         int box = N / 16, half = box / 2;
         for (int j = 0; j < N; j++) {
             int m = (j + half) / box;
@@ -727,9 +734,12 @@ static void blind_rotate_torus(or_bsk* K, const uint64_t* ks_lwe, const uint8_t*
         }
     } else for (int j = 0; j < N; j++) V[j] = delta / 2;
     uint32_t b = mod_switch(ks_lwe[n], log2N2);
-    for (int j = 0; j < N; j++) {
-        int s = (j + (int)b) & (2 * N - 1);
-        dacc[(size_t)k * N + j] = (double)(int64_t)(s < N ? V[s] : (uint64_t)0 - V[s - N]);
+    for (size_t c = acc0 ? 0 : (size_t)k; c < kp1; c++) {
+        const uint64_t* A = acc0 ? acc0 + c * N : V;
+        for (int j = 0; j < N; j++) {
+            int s = (j + (int)b) & (2 * N - 1);
+            dacc[c * N + j] = (double)(int64_t)(s < N ? A[s] : (uint64_t)0 - A[s - N]);
+        }
     }
     for (int i = 0; i < n; i += 2) {
         uint32_t ai = mod_switch(ks_lwe[i], log2N2);
@@ -809,7 +819,7 @@ static void blind_rotate_torus(or_bsk* K, const uint64_t* ks_lwe, const uint8_t*
 
 void or_blind_rotate_multi(void* pk, const uint64_t* ks_lwe, const uint8_t* luts, int n_out, int direct, uint64_t* outs) {
     or_bsk* K = (or_bsk*)pk;
-    if (K->FP) { blind_rotate_torus(K, ks_lwe, luts, n_out, direct, outs); return; }
+    if (K->FP) { blind_rotate_torus(K, ks_lwe, luts, n_out, direct, NULL, outs); return; }
     const or_params* P = &K->P;
     int k = P->k, N = P->N, n = P->n, log2N2 = ilog2(2 * N);
     size_t kp1 = (size_t)k + 1, big = (size_t)k * N;
@@ -900,6 +910,19 @@ void or_blind_rotate_multi(void* pk, const uint64_t* ks_lwe, const uint8_t* luts
 void or_blind_rotate(void* pk, const uint64_t* ks_lwe, const uint8_t lut[16], uint64_t* out) {
     or_blind_rotate_multi(pk, ks_lwe, lut, 1, 1, out);
 }
+/* count independent f64 ladders from caller-supplied GLWE accumulators (selector jobs; torus
+ * ring only, OpenMP over them): ks_lwe count*(n+1), accs count*(k+1)*N, outs count*(kN+1).
+ * Returns 0, or -1 on the RNS ring (nothing written). */
+int or_blind_rotate_acc(void* pk, const uint64_t* ks_lwe, const uint64_t* accs, size_t count, uint64_t* outs) {
+    or_bsk* K = (or_bsk*)pk;
+    if (!K->FP) return -1;
+    const size_t big = (size_t)K->P.k * K->P.N, glwe = ((size_t)K->P.k + 1) * K->P.N;
+    #pragma omp parallel for schedule(dynamic, 1)
+    for (long q = 0; q < (long)count; q++)
+        blind_rotate_torus(K, ks_lwe + (size_t)q * (K->P.n + 1), NULL, 1, 1, accs + (size_t)q * glwe,
+                           outs + (size_t)q * (big + 1));
+    return 0;
+}
 
 /* ------------------------------------------- exact blind rotation (torus)
  * The torus ring's unrolled CMUX ladder (blind_rotate_torus above) restated in exact
@@ -941,8 +964,10 @@ static inline uint64_t rot_u64(const uint64_t* poly, int N, int t, int e) {
     s %= 2 * N; if (s < 0) s += 2 * N;
     return s < N ? poly[s] : (uint64_t)0 - poly[s - N];
 }
+/* acc0 != NULL: from the caller's GLWE acc0 [k+1][N], every polynomial rotated by X^-b in u64
+ * (no rounding); luts is not read, the caller passes direct = 1 */
 static void blind_rotate_exact(const or_params* P, const uint64_t* bsk, const uint64_t* ks_lwe, const uint8_t* luts,
-                               int n_out, int direct, uint64_t* outs, uint64_t* glwe_out) {
+                               int n_out, int direct, const uint64_t* acc0, uint64_t* outs, uint64_t* glwe_out) {
     const int k = P->k, N = P->N, n = P->n, log2N2 = ilog2(2 * N), B = P->pbs_base_log;
     const size_t kp1 = (size_t)k + 1, big = (size_t)k * N;
     uint64_t* acc = calloc(kp1 * N, 8);
@@ -951,7 +976,8 @@ static void blind_rotate_exact(const or_params* P, const uint64_t* bsk, const ui
     uint64_t* H = malloc(8 * kp1 * kp1 * N);
     uint64_t* V = malloc(8 * (size_t)N);
     const uint64_t delta = 1ULL << 59;
-    if (direct == 1) {
+    if (acc0) { /* V is not used */
+    } else if (direct == 1) {
         int box = N / 16, half = box / 2;
         for (int j = 0; j < N; j++) {
             int m = (j + half) / box;
@@ -959,7 +985,9 @@ static void blind_rotate_exact(const or_params* P, const uint64_t* bsk, const ui
         }
     } else for (int j = 0; j < N; j++) V[j] = delta / 2;
     uint32_t b = mod_switch(ks_lwe[n], log2N2);
-    for (int j = 0; j < N; j++) acc[(size_t)k * N + j] = rot_u64(V, N, j, (2 * N - (int)b) % (2 * N));
+    for (size_t c = acc0 ? 0 : (size_t)k; c < kp1; c++)
+        for (int j = 0; j < N; j++)
+            acc[c * N + j] = rot_u64(acc0 ? acc0 + c * N : V, N, j, (2 * N - (int)b) % (2 * N));
     for (int i = 0; i < n; i += 2) {
         uint32_t ai = mod_switch(ks_lwe[i], log2N2);
         uint32_t aj = i + 1 < n ? mod_switch(ks_lwe[i + 1], log2N2) : 0;
@@ -1018,14 +1046,25 @@ void or_blind_rotate_exact(const or_params* P, const uint64_t* bsk, const uint64
     const size_t big = (size_t)P->k * P->N, no = direct ? 1 : (size_t)n_out;
     #pragma omp parallel for schedule(dynamic, 1)
     for (long q = 0; q < (long)count; q++)
-        blind_rotate_exact(P, bsk, ks_lwe + (size_t)q * (P->n + 1), luts + (size_t)q * no * 16, n_out, direct,
+        blind_rotate_exact(P, bsk, ks_lwe + (size_t)q * (P->n + 1), luts + (size_t)q * no * 16, n_out, direct, NULL,
                            outs + (size_t)q * no * (big + 1), NULL);
+}
+/* the same from caller-supplied GLWE accumulators: accs count*(k+1)*N, outs count*(kN+1) */
+void or_blind_rotate_exact_acc(const or_params* P, const uint64_t* bsk, const uint64_t* ks_lwe, const uint64_t* accs,
+                               size_t count, uint64_t* outs) {
+    const size_t big = (size_t)P->k * P->N, glwe = ((size_t)P->k + 1) * P->N;
+    #pragma omp parallel for schedule(dynamic, 1)
+    for (long q = 0; q < (long)count; q++)
+        blind_rotate_exact(P, bsk, ks_lwe + (size_t)q * (P->n + 1), NULL, 1, 1, accs + (size_t)q * glwe,
+                           outs + (size_t)q * (big + 1), NULL);
 }
 
 /* ------------------------------------------------------------------ gates */
 /* A rotation job: c = offset*2^58 + sum_i w_i * in_i (mod 2^64), then one
  * blind rotation and n_out LUT outputs (direct: 0 multi-value, 1 the LUT
- * polynomial itself, 2 sign gate [c > 0]). */
+ * polynomial itself, 2 sign gate [c > 0], 3 a selector job: the rotation starts
+ * from selector number lut[0][0..3] (little endian) of the caller's table, one
+ * output; fr_job's JOB_ACC). */
 typedef struct {
     int32_t n_in;
     int32_t offset;
@@ -1048,10 +1087,20 @@ void or_lincomb(int big, const or_gate* g, const uint64_t* slots, uint64_t* out)
 
 /* Evaluate `count` independent jobs over `slots` (LWE big, torus 2^64), OpenMP.
  * Outputs of job q start at out + out_first[q] * (kN+1). */
-void or_gates(void* pk, const uint64_t* ksk, const or_gate* gates, size_t count, const uint64_t* slots,
-              const int32_t* out_first, uint64_t* out) {
+static uint32_t gate_selector(const or_gate* g) {
+    const uint8_t* l = g->lut[0];
+    return (uint32_t)l[0] | (uint32_t)l[1] << 8 | (uint32_t)l[2] << 16 | (uint32_t)l[3] << 24;
+}
+/* or_gates with a selector table [n_sel][k+1][N] for the jobs with direct == 3 (NULL, 0: none).
+ * Returns -1, with nothing evaluated, if a selector job has no table (or not the torus ring) or
+ * names a selector past the table. */
+int or_gates_sel(void* pk, const uint64_t* ksk, const or_gate* gates, size_t count, const uint64_t* slots,
+                 const uint64_t* selectors, size_t n_sel, const int32_t* out_first, uint64_t* out) {
     or_bsk* K = (or_bsk*)pk;
     int big = K->P.k * K->P.N, n = K->P.n;
+    const size_t glwe = ((size_t)K->P.k + 1) * K->P.N;
+    for (size_t q = 0; q < count; q++)
+        if (gates[q].direct == 3 && (!K->FP || !selectors || gate_selector(&gates[q]) >= n_sel)) return -1;
     #pragma omp parallel
     {
         uint64_t* lc = malloc(8 * (size_t)(big + 1));
@@ -1060,11 +1109,19 @@ void or_gates(void* pk, const uint64_t* ksk, const or_gate* gates, size_t count,
         for (long q = 0; q < (long)count; q++) {
             or_lincomb(big, &gates[q], slots, lc);
             or_keyswitch(&K->P, ksk, lc, 1, ks);
-            or_blind_rotate_multi(pk, ks, &gates[q].lut[0][0], gates[q].n_out, gates[q].direct,
-                                  out + (size_t)out_first[q] * (big + 1));
+            uint64_t* o = out + (size_t)out_first[q] * (big + 1);
+            if (gates[q].direct == 3)
+                blind_rotate_torus(K, ks, NULL, 1, 1, selectors + gate_selector(&gates[q]) * glwe, o);
+            else
+                or_blind_rotate_multi(pk, ks, &gates[q].lut[0][0], gates[q].n_out, gates[q].direct, o);
         }
         free(lc); free(ks);
     }
+    return 0;
+}
+void or_gates(void* pk, const uint64_t* ksk, const or_gate* gates, size_t count, const uint64_t* slots,
+              const int32_t* out_first, uint64_t* out) {
+    or_gates_sel(pk, ksk, gates, count, slots, NULL, 0, out_first, out);
 }
 
 int or_num_threads(void) {

@@ -1,7 +1,9 @@
 """Private search over clear content on the device: the extract-sum kernel (k_select_sum) word for
 word against the numpy restatement of tests/test_find_clear.py, fr_find_clear /
 fr_find_clear_starts end to end, the plan cache and the per-call binding of the content bytes,
-lanes, ownership of the sum slots, the packed replies and the refusals.
+lanes, ownership of the sum slots, the packed replies and the refusals.  Whole finds are also
+compared output by output with Oracle.run_schedule, its extract-sums seeded from the numpy
+restatement over the needle's expanded selectors: every level above the sums, word for word.
 
 Contexts and oracles are tests/test_gate_programs.py's, the end-to-end contexts (with a packing
 key) and the content tests/test_private_needle_gpu.py's, so that every find over clear content
@@ -12,6 +14,7 @@ import numpy as np
 import pytest
 
 import fheregex as F
+import selector_cases as sc
 import test_gate_programs as tg
 import test_private_needle_gpu as pn
 from test_find_clear import extract_sum
@@ -156,6 +159,62 @@ def test_find_clear_and_find_clear_starts(request, key_blob, pid, case):
                 c.release(h)
     finally:
         c.set_profiling(0)
+        nd.close()
+
+
+def device_find_clear_words(c, nd, text):
+    """block 0 of fr_find_clear's output, then of every output of fr_find_clear_starts"""
+    out, _ = c.find_clear(text, nd)
+    starts = c.find_clear_starts(text, nd)
+    try:
+        return pn.output_words(c, [out] + starts)
+    finally:
+        for h in [out] + starts:
+            c.release(h)
+
+
+def oracle_find_clear_words(O, sel, m, text):
+    return np.concatenate([sc.oracle_find(O, sel, m, text=text), sc.oracle_find(O, sel, m, text=text, starts=True)])
+
+
+@pytest.mark.parametrize("s", pn.WORD_NEEDLES)
+@pytest.mark.parametrize("pid", PIDS)
+def test_find_clear_words(request, key_blob, pid, s):
+    """Whole finds over clear content word for word: every output of fr_find_clear and
+    fr_find_clear_starts against Oracle.run_schedule on the same schedule, whose extract-sums are
+    extract_sum over fr_expand_needle's selectors (m = 9: two sums and a two-level AND a start)."""
+    c, ck, sk, _, _ = pn.e2e(key_blob, pid)
+    O = tg.oracle(request, pid)
+    text = CONTENT.encode()
+    blob = ck.encrypt_needle(s, seed=21)
+    sel = c.expand_needle(blob)
+    nd = sk.upload_needle(blob)
+    try:
+        got, want = device_find_clear_words(c, nd, text), oracle_find_clear_words(O, sel, len(s), text)
+        assert got.shape == want.shape == (1 + len(text), c.lwe_len)
+        bad = [i - 1 for i in range(len(got)) if not np.array_equal(got[i], want[i])]  # (-1: fr_find_clear's)
+        assert not bad, (pid, s, bad)
+    finally:
+        nd.close()
+
+
+def test_find_clear_words_on_two_lanes(request, key_blob):
+    """the same comparison with two lanes, asynchronous: the serial run's words and the oracle's"""
+    c, ck, sk, _, _ = pn.e2e(key_blob, "k1n2048")
+    O = tg.oracle(request, "k1n2048")
+    text = CONTENT.encode()
+    blob = ck.encrypt_needle("abc", seed=21)
+    want = oracle_find_clear_words(O, c.expand_needle(blob), 3, text)
+    nd = sk.upload_needle(blob)
+    try:
+        serial = device_find_clear_words(c, nd, text)
+        assert np.array_equal(serial, want)
+        c.set_lanes(2)
+        c.set_async(True)
+        for rep in range(2):  # (the first round compiles each lane's plan copy)
+            assert np.array_equal(device_find_clear_words(c, nd, text), serial), rep
+    finally:
+        c.set_lanes(1)
         nd.close()
 
 

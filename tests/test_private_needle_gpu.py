@@ -2,6 +2,14 @@
 (k_blind_rotate_fft_acc), encrypted selectors, fr_find / fr_find_starts end to end, the plan
 cache, lanes and the needle's release, and the refusals.
 
+The kernel is pinned to the oracle word for word with trivial selectors (zero masks, body V(lut):
+Oracle.blind_rotate) and with real ones (uniform mask words: Oracle.blind_rotate_acc, the f64
+ladder from a caller's GLWE, itself pinned on the CPU by tests/test_selector_oracle.py): launches
+of 1, 2, 3 and 64 jobs whose pair workgroups hold different selectors, the blind rotation's edge
+rows, and one step against the exact ladder.  Whole finds are compared output by output with
+Oracle.run_schedule on the same content LWEs and the needle's expanded selectors, which pins the
+selector index the plan gives every job and every level above the first.
+
 The launch shape follows the job count, so small launches are forced into every shape with the
 environment switches a context reads at creation, one context per setting (shared with
 tests/test_gate_programs.py where the setting is one of its own)."""
@@ -11,7 +19,10 @@ import numpy as np
 import pytest
 
 import fheregex as F
+import gate_programs as gp
+import selector_cases as sc
 import test_gate_programs as tg  # its oracles and contexts, computed once for both
+from test_exact_br import ONE_STEP_BOUND, one_step_inputs, word_gap
 
 pytestmark = pytest.mark.gpu
 
@@ -25,7 +36,7 @@ SHAPES = {
     "k2-throughput-e8": ("k2n1024", {"FR_FFT_SMALL_BATCH": 0}),
     "k2-throughput-e4": ("k2n1024", {"FR_FFT_SMALL_BATCH": 0, "FR_FFT_LANE_ELEMS": 4}),
 }
-_INPUTS, _NIBBLES = {}, {}
+_INPUTS, _NIBBLES, _REAL, _EDGE_ACC, _ONE_STEP = {}, {}, {}, {}, {}
 
 
 def direct_poly(N, lut):
@@ -103,23 +114,102 @@ def nibbles(request, pid):
     return _NIBBLES[pid]
 
 
+def real_selector_launches(request, c, pid):
+    """(the 4 selectors of TABLES, [(keyswitched rows, one selector per row, the oracle's rows)]),
+    once per point.  The first launch is the 64 jobs of test_encrypted_selectors; then 1, 2 and 3
+    nibble jobs and the idle-step row of inputs() alone, in a pair and as the odd tail, the jobs
+    of every pair workgroup on different selectors."""
+    if pid not in _REAL:
+        O = tg.oracle(request, pid)
+        nib = nibbles(request, pid)
+        ks9 = inputs(request, pid)[0]
+        sel = c.expand_needle(c.encrypt_needle([(TABLES[0], TABLES[1]), (TABLES[2], TABLES[3])], seed=402))
+        launches = [(np.tile(nib, (4, 1)), np.repeat(sel, 16, axis=0))]
+        for rows, which in ((nib[[5]], [0]), (nib[[5, 6]], [1, 2]), (nib[[9, 5, 14]], [3, 0, 2]),
+                            (ks9[[8]], [1]), (ks9[[7, 8]], [0, 2]), (ks9[[6, 7, 8]], [3, 1, 2])):
+            assert all(a != b for a, b in zip(which[0::2], which[1::2]))
+            launches.append((rows, sel[which]))
+        _REAL[pid] = sel, [(ks, acc, O.blind_rotate_acc(ks, acc)) for ks, acc in launches]
+    return _REAL[pid]
+
+
 @pytest.mark.parametrize("shape", list(SHAPES))
 def test_encrypted_selectors(request, key_blob, monkeypatch, shape):
     """16 nibbles against one encrypted selector per table, one launch of 64 jobs per shape: every
     output decrypts to lut[nibble], and its phase error is below 2^53, the bound
-    tests/test_noise.py holds bootstrap outputs to (the selector's fresh noise adds 2^12.4)."""
+    tests/test_noise.py holds bootstrap outputs to (the selector's fresh noise adds 2^12.4).
+    And every word of every output equals Oracle.blind_rotate_acc's, in that launch and in
+    launches of 1, 2 and 3 jobs (the pair shape's odd tail) whose pair workgroups hold two
+    different selectors, with and without idle steps: the prologue's load, rotation and sign of
+    the mask polynomials, the polynomial index at k = 2 and the per-job selector pointer."""
     pid, c = ctx_of(key_blob, monkeypatch, shape)
     O = tg.oracle(request, pid)
     ks = nibbles(request, pid)
-    sel = c.expand_needle(c.encrypt_needle([(TABLES[0], TABLES[1]), (TABLES[2], TABLES[3])], seed=402))
+    sel, launches = real_selector_launches(request, c, pid)
     assert sel[:, :-1].any()  # real masks
     got = c.dev_blind_rotate_acc(np.tile(ks, (4, 1)), np.repeat(sel, 16, axis=0))
+    for at, (rows, accs, words) in enumerate(launches):
+        dev = got if at == 0 else c.dev_blind_rotate_acc(rows, accs)
+        bad = [q for q in range(len(rows)) if not np.array_equal(dev[q], words[q])]
+        assert not bad, (shape, "launch %d of %d jobs" % (at, len(rows)), bad[:12])
     want = np.array([(t >> v) & 1 for t in TABLES for v in range(16)], dtype=U)
     assert list(O.decode16(got)) == list(want), shape
     err = (O.phase(got) - (want << U(59))).view(np.int64)
     worst = int(np.abs(err).max())
     print("%s: largest phase error 2^%.1f" % (shape, np.log2(max(worst, 1))))
     assert worst < 2 ** 53, (shape, np.log2(worst))
+
+
+def edge_selectors(request, pid):
+    """the unique edge rows of gate_programs.edge_rows, a uniform-random accumulator with the
+    planted words of selector_cases for each, and the oracle's rows"""
+    if pid not in _EDGE_ACC:
+        O = tg.oracle(request, pid)
+        names, ks, _, _ = tg.edge(request, pid)
+        acc = sc.random_accs(len(names), O.P.k, O.P.N, seed=83)
+        _EDGE_ACC[pid] = names, ks, acc, O.blind_rotate_acc(ks, acc)
+    return _EDGE_ACC[pid]
+
+
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_edge_rows_with_a_real_selector(request, key_blob, monkeypatch, shape):
+    """The mask and body edge rows (idle ladders and pairs, exponents that cancel, rounding ties,
+    bodies on box boundaries and the wrap body) from full-magnitude accumulators that hold the
+    conversion's edge words in every polynomial, word for word against Oracle.blind_rotate_acc.
+    The pair shape runs them behind the workgroup pairs of gate_programs.EDGE_HEAD."""
+    pid, c = ctx_of(key_blob, monkeypatch, shape)
+    names, ks, acc, words = edge_selectors(request, pid)
+    order = gp.edge_order(names, 41) if shape == "k1-pair" else list(range(len(names)))
+    got = c.dev_blind_rotate_acc(ks[order], acc[order])
+    bad = [(i, names[u]) for i, u in enumerate(order) if not np.array_equal(got[i], words[u])]
+    assert not bad, (shape, len(bad), bad[:12])
+
+
+def one_step_selectors(request, pid):
+    """24 one-step ladders from uniform-random accumulators: the exact ladder's and the f64
+    ladder's rows"""
+    if pid not in _ONE_STEP:
+        O = tg.oracle(request, pid)
+        ks, _ = one_step_inputs(O, 24, seed=91)
+        acc = sc.random_accs(24, O.P.k, O.P.N, seed=92)
+        _ONE_STEP[pid] = ks, acc, O.blind_rotate_exact(ks, accs=acc), O.blind_rotate_acc(ks, acc)
+    return _ONE_STEP[pid]
+
+
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_device_one_step_from_a_selector_against_exact(request, key_blob, monkeypatch, shape):
+    """tests/test_exact_br.py's test_device_one_step_against_exact from full-magnitude
+    accumulators: every output word of the device within 2^44 (DESIGN §2.1's per-product bound)
+    of the exact ladder's, which rotates the accumulator in u64 with no rounding; and equal to
+    the f64 ladder's."""
+    pid, c = ctx_of(key_blob, monkeypatch, shape)
+    ks, acc, exact, f64 = one_step_selectors(request, pid)
+    dev = c.dev_blind_rotate_acc(ks, acc)
+    worst = max(word_gap(dev[q], exact[q]) for q in range(len(ks)))
+    print("%s: max |device - exact| = 2^%.2f over %d one-step ladders from uniform accumulators"
+          % (shape, np.log2(max(worst, 1)), len(ks)))
+    assert worst <= ONE_STEP_BOUND, (shape, np.log2(worst))
+    assert np.array_equal(dev, f64), shape
 
 
 # ------------------------------------------------------------------ end to end
@@ -168,6 +258,72 @@ def test_find_and_find_starts(key_blob, pid, needle):
         for compact in (False, True):
             assert ck.decrypt_starts(sk.find_starts(content, nd, compact=compact)) == want, (pid, s, compact)
     nd.close()
+
+
+WORD_NEEDLES = ["abc", "xxabcxxAb"]  # one AND gate per start; 18 tests per start: a two-level AND
+
+
+def output_words(c, handles):
+    return np.stack([c.download_radix(h)[0] for h in handles])
+
+
+def device_find_words(c, nd, content):
+    """block 0 of fr_find's output, then of every output of fr_find_starts"""
+    out, _ = c.find(content, nd)
+    starts = c.find_starts(content, nd)
+    try:
+        return output_words(c, [out] + starts)
+    finally:
+        for h in [out] + starts:
+            c.release(h)
+
+
+def oracle_find_words(c, O, sel, m, content):
+    """the same rows from Oracle.run_schedule on the handles' own LWEs and the selector table"""
+    lwes = np.stack([c.download_radix(h) for h in content])
+    return np.concatenate([sc.oracle_find(O, sel, m, content_lwes=lwes),
+                           sc.oracle_find(O, sel, m, content_lwes=lwes, starts=True)])
+
+
+@pytest.mark.parametrize("s", WORD_NEEDLES)
+@pytest.mark.parametrize("pid", ["k1n2048", "k2n1024"])
+def test_find_words(request, key_blob, pid, s):
+    """Whole finds word for word: every output of fr_find and fr_find_starts against
+    Oracle.run_schedule over the selector table fr_expand_needle gives for the same blob, on
+    fresh content and on content whose first four characters are trivial."""
+    c, ck, sk, hs, mixed = e2e(key_blob, pid)
+    O = tg.oracle(request, pid)
+    blob = ck.encrypt_needle(s, seed=21)
+    sel = c.expand_needle(blob)
+    nd = sk.upload_needle(blob)
+    try:
+        for what, content in (("fresh", hs), ("mixed", mixed)):
+            got, want = device_find_words(c, nd, content), oracle_find_words(c, O, sel, len(s), content)
+            assert got.shape == want.shape == (1 + len(CONTENT), c.lwe_len)
+            bad = [i - 1 for i in range(len(got)) if not np.array_equal(got[i], want[i])]  # (-1: fr_find's)
+            assert not bad, (pid, s, what, bad)
+    finally:
+        nd.close()
+
+
+def test_find_words_on_two_lanes(request, key_blob):
+    """the same comparison with two lanes, asynchronous: the serial run's words and the oracle's"""
+    c, ck, sk, hs, _ = e2e(key_blob, "k1n2048")
+    O = tg.oracle(request, "k1n2048")
+    blob = ck.encrypt_needle("abc", seed=21)
+    sel = c.expand_needle(blob)
+    want = oracle_find_words(c, O, sel, 3, hs)
+    nd = sk.upload_needle(blob)
+    try:
+        serial = device_find_words(c, nd, hs)
+        assert np.array_equal(serial, want)
+        c.set_lanes(2)
+        c.set_async(True)
+        for rep in range(2):  # (the first round compiles each lane's plan copy)
+            assert np.array_equal(device_find_words(c, nd, hs), serial), rep
+    finally:
+        c.set_lanes(1)
+        nd.close()
 
 
 def test_needle_longer_than_the_content_is_the_constant(key_blob):
