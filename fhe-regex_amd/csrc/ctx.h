@@ -88,6 +88,7 @@ struct fr_ctx {
     bool multi_value = true;  // merge same-input small-norm LUTs into one blind rotation
     bool async_match = true;  // has_match returns once its launches are enqueued (fr_set_async)
     uint64_t next_lane = 0;   // fr_set_lanes: consecutive asynchronous matches round-robin over the lanes
+    uint64_t scan_classes = 0, scan_padded = 0;  // the last scan's distinct windows, and their padded count (fr_scan_classes)
     fr_plan_cache plans;  // after dev: the cached plans go while the device is alive (Plan, plan.h)
     // content_signature scratch: canonical id of an arena slot, valid while sig_gen[slot] == gen
     std::vector<int32_t> sig_id;

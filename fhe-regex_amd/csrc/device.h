@@ -151,6 +151,13 @@ class Device {
     // packed GLWE's k N mask coefficients and its first n body coefficients, each rounded to its
     // top 16 bits by k_pack_compress; only these k N + n u16 values are downloaded.
     void pack_bools_compact(const DevGate* gates, size_t n, uint16_t* out_host /* kN + n */);
+    // The pack of n starts that share R <= n rows (keys.h: pack_host_mapped computes the same
+    // words): start j < n <= N is boolean rows[map[j]], or the constant 0 where map[j] < 0.  The
+    // digits and the GEMM run over the R rows, k_pack_map_sum over the n starts; one of out_words
+    // ((k+1) N words) and out_c16 (kN + n values) receives the result as in the packs above.
+    // Refused before anything is staged: an entry >= R, a row no start reads, R < 1 (check_pack_map).
+    void pack_mapped(const DevGate* rows, size_t R, const int32_t* map, size_t n, uint64_t* out_words,
+                     uint16_t* out_c16);
     // HIP-event ms of the last pack under fr_set_profiling: digits (with the zeroing of the
     // scratch), GEMM, rotate-sum, and the compact form's rounding (0 for pack_bools)
     const double* pack_ms() const { return pack_ms_; }
@@ -268,6 +275,7 @@ class Device {
         gpu::DevBuf<int8_t> pk_dig;  // pack_bools: digits [rows][3 kN], allocated at the first pack
         gpu::DevBuf<uint64_t> pk_g;  // pack_bools: keyswitched rows [n][(k+1) N], then the packed GLWE
         gpu::DevBuf<uint16_t> pk_c16;  // pack_bools_compact: the k N + N rounded coefficients
+        gpu::DevBuf<int32_t> pk_map;   // pack_mapped: the row of each start, N entries
         // key products of the lane's smallest launches [bootstrap][step][P][own, other][m][lane]
         // (fft_br.hip: k_key_products), allocated at the first such launch, grown to the largest
         gpu::DevBuf<double> kpre;
@@ -391,7 +399,9 @@ class Device {
     LimbKey pksk_;                  // packing key: 3 kN rows of (k+1) N words (pack_bools)
     double pack_ms_[4] = {0, 0, 0, 0};
     // both forms of the pack: the words to out_words, or (out_c16) the rounded values alone
-    void pack_launch(const DevGate* gates, size_t n, uint64_t* out_words, uint16_t* out_c16);
+    // (R rows, n starts; map NULL: start j reads row j and R == n)
+    void pack_launch(const DevGate* gates, size_t R, const int32_t* map, size_t n, uint64_t* out_words,
+                     uint16_t* out_c16);
     int pk_split_ = 0;              // FR_PK_SPLIT: K slices of the packing GEMM (a divisor of 24; 0: auto)
     bool ks_mfma_ = true;         // FR_KS_MFMA=0: the VALU lincomb+keyswitch kernel
     size_t ks_mr4_min_ = 96;      // FR_KS_MR4_MIN: batches from this size use 4 row tiles per wave (k_ks_glds; ab_ks_glds.log: 100 gates 44 -> 37 us, 64 gates no gain)

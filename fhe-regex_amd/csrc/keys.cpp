@@ -567,43 +567,52 @@ void gen_pksk_noise(const Params& p, const RngKey& key, std::vector<int32_t>& e)
 // Rows of the key are streamed once per block of PACK_JB booleans, whose partial sums
 // (PACK_JB rows of (k+1) N words) stay in cache meanwhile.
 constexpr size_t PACK_JB = 16;
+// G[jj] = (0, .., 0, b_j) - D[j] x PKSK for the booleans j = j0 + jj, jj < nj: nj rows of (k+1) N words
+static void pack_rows_host(const Params& p, const uint64_t* pksk, const uint64_t* lwes, const int32_t* w,
+                           const int32_t* off, size_t j0, size_t nj, uint64_t* G) {
+    const int big = p.big();
+    const size_t W = pk_row_words(p), KD = pk_rows(p), L = (size_t)p.lwe_len();
+    std::fill(G, G + nj * W, 0);
+    std::vector<int8_t> dig(nj * KD, 0);
+    for (size_t jj = 0; jj < nj; ++jj) {
+        const size_t j = j0 + jj;
+        const uint64_t wj = (uint64_t)(int64_t)(w ? w[j] : 1);
+        uint64_t body = (uint64_t)(int64_t)(off ? off[j] : 0) << (DELTA_LOG - 1);
+        if (wj) {
+            const uint64_t* c = lwes + j * L;
+            body += wj * c[big];
+            for (int i = 0; i < big; ++i) {
+                int32_t d[PK_LEVELS];
+                ks_decompose<PK_BASE_LOG, PK_LEVELS>(wj * c[i], d);
+                for (int l = 0; l < PK_LEVELS; ++l) dig[jj * KD + (size_t)i * PK_LEVELS + l] = (int8_t)d[l];
+            }
+        }
+        G[jj * W + (size_t)big] = body;  // coefficient 0 of the body polynomial
+    }
+    for (size_t r = 0; r < KD; ++r) {
+        const uint64_t* row = pksk + r * W;
+        for (size_t jj = 0; jj < nj; ++jj) {
+            const int8_t d = dig[jj * KD + r];
+            if (!d) continue;
+            const uint64_t m = (uint64_t)(int64_t)d;
+            uint64_t* g = G + jj * W;
+            for (size_t t = 0; t < W; ++t) g[t] -= m * row[t];
+        }
+    }
+}
+
 void pack_host(const Params& p, const uint64_t* pksk, const uint64_t* lwes, const int32_t* w, const int32_t* off,
                size_t n, uint64_t* out) {
-    const int N = p.N, big = p.big();
-    const size_t W = pk_row_words(p), KD = pk_rows(p), L = (size_t)p.lwe_len();
+    const int N = p.N;
+    const size_t W = pk_row_words(p);
     if (n < 1 || n > (size_t)N) throw Error(FR_ERR_INVALID, "pack: 1 <= n <= N booleans");
     std::fill(out, out + W, 0);
     const size_t blocks = (n + PACK_JB - 1) / PACK_JB;
     std::vector<std::vector<uint64_t>> part(blocks);
     parallel_for((int)blocks, [&](int b) {
         const size_t j0 = (size_t)b * PACK_JB, nj = std::min(PACK_JB, n - j0);
-        std::vector<uint64_t> G(nj * W, 0);
-        std::vector<int8_t> dig(nj * KD, 0);
-        for (size_t jj = 0; jj < nj; ++jj) {
-            const size_t j = j0 + jj;
-            const uint64_t wj = (uint64_t)(int64_t)(w ? w[j] : 1);
-            uint64_t body = (uint64_t)(int64_t)(off ? off[j] : 0) << (DELTA_LOG - 1);
-            if (wj) {
-                const uint64_t* c = lwes + j * L;
-                body += wj * c[big];
-                for (int i = 0; i < big; ++i) {
-                    int32_t d[PK_LEVELS];
-                    ks_decompose<PK_BASE_LOG, PK_LEVELS>(wj * c[i], d);
-                    for (int l = 0; l < PK_LEVELS; ++l) dig[jj * KD + (size_t)i * PK_LEVELS + l] = (int8_t)d[l];
-                }
-            }
-            G[jj * W + (size_t)big] = body;  // coefficient 0 of the body polynomial
-        }
-        for (size_t r = 0; r < KD; ++r) {
-            const uint64_t* row = pksk + r * W;
-            for (size_t jj = 0; jj < nj; ++jj) {
-                const int8_t d = dig[jj * KD + r];
-                if (!d) continue;
-                const uint64_t m = (uint64_t)(int64_t)d;
-                uint64_t* g = G.data() + jj * W;
-                for (size_t t = 0; t < W; ++t) g[t] -= m * row[t];
-            }
-        }
+        std::vector<uint64_t> G(nj * W);
+        pack_rows_host(p, pksk, lwes, w, off, j0, nj, G.data());
         std::vector<uint64_t>& acc = part[(size_t)b];
         acc.assign(W, 0);
         for (size_t jj = 0; jj < nj; ++jj)
@@ -612,6 +621,36 @@ void pack_host(const Params& p, const uint64_t* pksk, const uint64_t* lwes, cons
     });
     for (const auto& acc : part)
         for (size_t t = 0; t < W; ++t) out[t] += acc[t];
+}
+
+void check_pack_map(const int32_t* map, size_t n, size_t R, size_t N) {
+    if (R < 1 || R > n || n > N) throw Error(FR_ERR_INVALID, "mapped pack: 1 <= R <= n <= N");
+    std::vector<uint8_t> read(R, 0);
+    for (size_t j = 0; j < n; ++j) {
+        if (map[j] >= 0 && (size_t)map[j] >= R) throw Error(FR_ERR_INVALID, "mapped pack: a map entry past the rows");
+        if (map[j] >= 0) read[(size_t)map[j]] = 1;
+    }
+    for (size_t r = 0; r < R; ++r)
+        if (!read[r]) throw Error(FR_ERR_INVALID, "mapped pack: a row no start reads");
+}
+
+void pack_host_mapped(const Params& p, const uint64_t* pksk, const uint64_t* lwes, const int32_t* w,
+                      const int32_t* off, size_t R, const int32_t* map, size_t n, uint64_t* out) {
+    const int N = p.N;
+    const size_t W = pk_row_words(p);
+    check_pack_map(map, n, R, (size_t)N);
+    std::vector<uint64_t> G(R * W);
+    const size_t blocks = (R + PACK_JB - 1) / PACK_JB;
+    parallel_for((int)blocks, [&](int b) {
+        const size_t r0 = (size_t)b * PACK_JB;
+        pack_rows_host(p, pksk, lwes, w, off, r0, std::min(PACK_JB, R - r0), G.data() + r0 * W);
+    });
+    std::fill(out, out + W, 0);
+    for (size_t j = 0; j < n; ++j) {
+        if (map[j] < 0) continue;
+        for (int c = 0; c <= p.k; ++c)
+            add_rotated(out + (size_t)c * N, G.data() + (size_t)map[j] * W + (size_t)c * N, (int)j, N);
+    }
 }
 
 void glwe_phase(const Params& p, const ClientKey& ck, const uint64_t* ct, uint64_t* phase) {

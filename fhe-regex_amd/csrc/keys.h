@@ -144,6 +144,14 @@ inline size_t pk_compact_planes(const Params& p) { return 5 * pk_rows(p) * (size
 // digits of the mask of c_j rounded to 21 bits.  Exact mod 2^64.
 void pack_host(const Params& p, const uint64_t* pksk, const uint64_t* lwes, const int32_t* w, const int32_t* off,
                size_t n, uint64_t* out /* (k+1) N */);
+// The same pack where several starts share a row (a scan's window classes, fr_scan_clear_starts):
+//   out = sum_{j < n, map[j] >= 0} X^j G[map[j]]
+// with G[r] the keyswitched row of boolean r < R as above (lwes, w, off have R entries).  By
+// linearity this is pack_host over the rows expanded start by start, a start with map[j] < 0 the
+// constant 0.  check_pack_map refuses R < 1, R > n, n > N, an entry >= R and a row no start reads.
+void check_pack_map(const int32_t* map, size_t n, size_t R, size_t N);
+void pack_host_mapped(const Params& p, const uint64_t* pksk, const uint64_t* lwes, const int32_t* w,
+                      const int32_t* off, size_t R, const int32_t* map, size_t n, uint64_t* out /* (k+1) N */);
 // Compact packed result.  A packed boolean is never bootstrapped again, so
 // only the client's rounding at Delta / 2 = 2^58 sees its error: every coefficient travels
 // rounded to its top 16 bits, v = ((x + 2^47) >> 48) mod 2^16, and is installed as v << 48, the

@@ -652,6 +652,27 @@ __global__ void __launch_bounds__(256) k_pack_rotate_sum(const uint64_t* __restr
     if (c < W && acc != 0) atomicAdd(&out[c], (unsigned long long)acc);
 }
 
+// The same sum where start j reads row map[j] (a scan's window classes: several starts share a
+// row): out[c][t] += sum_{j0 <= j < j1, map[j] >= 0} +-G[map[j]][c][(t - j) mod N].  The geometry
+// is k_pack_rotate_sum's.  j comes from blockIdx and the loop counter alone, so map[j] is the same
+// in every lane: one scalar load per start, a branch the whole wave takes or skips, and for a
+// fixed j still 64 consecutive words of one row.  Every entry is < the row count (check_pack_map).
+__global__ void __launch_bounds__(256) k_pack_map_sum(const uint64_t* __restrict__ G, const int* __restrict__ map, int n,
+                                                      int N, int W, int jper, unsigned long long* __restrict__ out) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    const int t = c & (N - 1), base = c - t;
+    const int j0 = blockIdx.y * jper, j1 = min(n, j0 + jper);
+    uint64_t acc = 0;
+    for (int j = j0; j < j1; ++j) {
+        const int r = map[j];
+        if (r < 0) continue;
+        const int d = t - j;
+        const uint64_t v = G[(size_t)r * W + base + (d >= 0 ? d : d + N)];
+        acc = d >= 0 ? acc + v : acc - v;
+    }
+    if (c < W && acc != 0) atomicAdd(&out[c], (unsigned long long)acc);
+}
+
 // The compact reply (keys.h: packed_round16): out[c] = ((in[c] + 2^47) >> 48) mod 2^16 for the
 // total = kN + n coefficients the blob carries; the body's first n follow the masks in the words
 // as they do in the blob, so input and output share the index.  A separate launch: the
@@ -696,17 +717,28 @@ void Device::packing_limb_column(int col, uint64_t* out_host) {
     HIP_CHECK(hipStreamSynchronize(STREAM));
 }
 
-void Device::pack_bools(const DevGate* gates, size_t n, uint64_t* out_host) { pack_launch(gates, n, out_host, nullptr); }
+void Device::pack_bools(const DevGate* gates, size_t n, uint64_t* out_host) {
+    pack_launch(gates, n, nullptr, n, out_host, nullptr);
+}
 void Device::pack_bools_compact(const DevGate* gates, size_t n, uint16_t* out_host) {
-    pack_launch(gates, n, nullptr, out_host);
+    pack_launch(gates, n, nullptr, n, nullptr, out_host);
+}
+void Device::pack_mapped(const DevGate* rows, size_t R, const int32_t* map, size_t n, uint64_t* out_words,
+                         uint16_t* out_c16) {
+    if (!map || !out_words == !out_c16) throw Error(FR_ERR_INVALID, "mapped pack: a map and one output form");
+    check_pack_map(map, n, R, (size_t)p_.N);  // before anything is staged
+    pack_launch(rows, R, map, n, out_words, out_c16);
 }
 
-void Device::pack_launch(const DevGate* gates, size_t n, uint64_t* out_words, uint16_t* out_c16) {
+// R rows through the digits and the GEMM, then n starts: start j reads row map[j] (map NULL:
+// row j, R == n)
+void Device::pack_launch(const DevGate* gates, size_t R, const int32_t* map, size_t n, uint64_t* out_words,
+                         uint16_t* out_c16) {
     if (!has_packing_key()) throw Error(FR_ERR_INVALID, "no packing key on the device");
     const int N = p_.N, big = p_.big(), KD = pksk_.KD, W = pksk_.ncols;
     if (n < 1 || n > (size_t)N) throw Error(FR_ERR_INVALID, "pack: 1 <= n <= N booleans");
     if (KD % 256 || big % 16 || W % 256) throw Error(FR_ERR_INVALID, "pack: kN must be a multiple of 256");
-    for (size_t j = 0; j < n; ++j) {
+    for (size_t j = 0; j < R; ++j) {
         const DevGate& g = gates[j];
         if (g.n_in < 0 || g.n_in > 16) throw Error(FR_ERR_INVALID, "pack: bad descriptor");
         for (int q = 0; q < g.n_in; ++q)
@@ -714,30 +746,32 @@ void Device::pack_launch(const DevGate* gates, size_t n, uint64_t* out_words, ui
     }
     const hipStream_t s = STREAM;
     LaneState& l = cur();
-    KsShape sh = ks_shape(n);  // (one column tile and the LDS-DMA ring, whatever FR_KS_MC / FR_KS_LDS say)
+    KsShape sh = ks_shape(R);  // (one column tile and the LDS-DMA ring, whatever FR_KS_MC / FR_KS_LDS say)
     const size_t bp = sh.padded;  // rows of whole tiles, as launch_ks
-    // scratch: the descriptors, digits [bp][KD], G [n][W] and the packed GLWE behind it, and the compact form's
+    // scratch: the descriptors, digits [bp][KD], G [R][W] and the packed GLWE behind it, and the compact form's
     // W rounded values (kN + n <= W of them used); allocated at the first pack of the lane, doubled from there
-    if (bp * KD > l.pk_dig.size() || (n + 1) * (size_t)W > l.pk_g.size() || n > l.pk_gates.size() || !l.pk_c16) {
+    if (bp * KD > l.pk_dig.size() || (R + 1) * (size_t)W > l.pk_g.size() || R > l.pk_gates.size() || !l.pk_c16) {
         HIP_CHECK(hipStreamSynchronize(s));
         l.pk_dig.grow(bp * KD, (size_t)128 * KD);
-        l.pk_g.grow((n + 1) * (size_t)W, (size_t)129 * W);
-        l.pk_gates.grow(n, 128);
+        l.pk_g.grow((R + 1) * (size_t)W, (size_t)129 * W);
+        l.pk_gates.grow(R, 128);
         l.pk_c16.grow((size_t)W, (size_t)W);
     }
+    if (map && !l.pk_map) l.pk_map.alloc((size_t)N);  // n <= N entries
     int8_t* d_dig = l.pk_dig.get();
     uint64_t* d_g = l.pk_g.get();
-    uint64_t* d_out = d_g + n * (size_t)W;
+    uint64_t* d_out = d_g + R * (size_t)W;
     DevGate* d_gates = l.pk_gates.get();
-    HIP_CHECK(hipMemcpyAsync(d_gates, gates, sizeof(DevGate) * n, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_gates, gates, sizeof(DevGate) * R, hipMemcpyHostToDevice, s));
+    if (map) HIP_CHECK(hipMemcpyAsync(l.pk_map.get(), map, sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
     StageTimer<4> timer(profiling_ != 0, s);
     // the digit pass zeroes the mask columns of G and writes column kN: the rest of the body
     // polynomial's columns (from kN, ahead of that write) and the output row are zeroed here,
     // inside the first stage's time
     timer.mark(0);
-    HIP_CHECK(hipMemset2DAsync(d_g + big, 8 * (size_t)W, 0, 8 * (size_t)N, n, s));
+    HIP_CHECK(hipMemset2DAsync(d_g + big, 8 * (size_t)W, 0, 8 * (size_t)N, R, s));
     HIP_CHECK(hipMemsetAsync(d_out, 0, 8 * (size_t)W, s));
-    launch_ks_digits<PK_BASE_LOG, PK_LEVELS>(d_gates, n, bp, d_dig, d_g, big, W, nullptr);
+    launch_ks_digits<PK_BASE_LOG, PK_LEVELS>(d_gates, R, bp, d_dig, d_g, big, W, nullptr);
     timer.mark(1);
     // Tiles for 32768 limb columns: GY = 256 column groups (the LWE keyswitch has 47) fill the
     // 256 CUs without K slices, so the four-row-tile shape runs unsliced (tools/pack_probe.py,
@@ -745,11 +779,12 @@ void Device::pack_launch(const DevGate* gates, size_t n, uint64_t* out_words, ui
     // 540 / 939) and one row tile per wave takes 2 (16 rows: 33 us at 2 and 4, 38 at 1)
     sh.GZ = sh.MR == 1 ? 2 : 1;  // a divisor of KD / 256 = 24
     if (pk_split_ > 0 && (KD / 256) % pk_split_ == 0) sh.GZ = pk_split_;
-    launch_limb_gemm(d_dig, pksk_, n, sh, d_g, W, nullptr);
+    launch_limb_gemm(d_dig, pksk_, R, sh, d_g, W, nullptr);
     timer.mark(2);
     const int jper = 32, slices = (int)((n + jper - 1) / jper);
-    k_pack_rotate_sum<<<dim3((unsigned)(W / 256), (unsigned)slices), 256, 0, s>>>(d_g, (int)n, N, W, jper,
-                                                                                   (unsigned long long*)d_out);
+    const dim3 grid((unsigned)(W / 256), (unsigned)slices);
+    if (map) k_pack_map_sum<<<grid, 256, 0, s>>>(d_g, l.pk_map.get(), (int)n, N, W, jper, (unsigned long long*)d_out);
+    else k_pack_rotate_sum<<<grid, 256, 0, s>>>(d_g, (int)n, N, W, jper, (unsigned long long*)d_out);
     HIP_CHECK(hipGetLastError());
     timer.mark(3);
     if (out_c16) {

@@ -8,6 +8,7 @@
 #include <tuple>
 #include <cstring>
 #include <iterator>
+#include <string_view>
 #include <unordered_map>
 
 namespace fr {
@@ -743,7 +744,10 @@ static int threshold_tree(Program& prog, bool is_and, std::vector<int> lits) {
     return lits[0];
 }
 
-static Program compile_needle_over(size_t n_chars, size_t m, size_t lo, size_t hi, bool starts, bool clear) {
+// stride: the content position of start p's first character is p * stride (1: the text itself;
+// m, clear only: window p of a compacted text, compile_needle_windows)
+static Program compile_needle_over(size_t n_chars, size_t m, size_t lo, size_t hi, bool starts, bool clear,
+                                   size_t stride = 1) {
     if (m < 1 || m > NEEDLE_MAX_CHARS) throw Error(FR_ERR_INVALID, "needle: 1 <= m <= 64");
     if (lo > hi) throw Error(FR_ERR_INVALID, "needle: start range");
     if (n_chars > (size_t)1 << 24) throw Error(FR_ERR_INVALID, "needle: content too long");
@@ -753,7 +757,8 @@ static Program compile_needle_over(size_t n_chars, size_t m, size_t lo, size_t h
     Program prog;
     std::vector<int> found;  // the AND of each start that fits
     for (size_t p = lo; p < end; ++p) {
-        if (p + m > n_chars || p + m < p) {
+        const size_t at = p * stride;  // (p < 2^24 and stride <= 64: no overflow)
+        if (at + m > n_chars || at + m < at) {
             if (starts) prog.outs.push_back(ProgOut{-1, 0, 0});
             continue;
         }
@@ -764,7 +769,7 @@ static Program compile_needle_over(size_t n_chars, size_t m, size_t lo, size_t h
                 PGate sum;
                 sum.kind = GATE_EXTRACT;
                 for (size_t t = first; t < first + len; ++t)
-                    sum.terms.push_back({(int32_t)t, (int32_t)(p + t / 2), (int32_t)(t % 2)});
+                    sum.terms.push_back({(int32_t)t, (int32_t)(at + t / 2), (int32_t)(t % 2)});
                 PGate g;
                 g.kind = GATE_SIGN;
                 g.ins = {{(int32_t)prog.gates.size(), 1}};
@@ -804,6 +809,37 @@ Program compile_needle(size_t n_chars, size_t m, size_t lo, size_t hi, bool star
 }
 Program compile_needle_clear(size_t n_chars, size_t m, size_t lo, size_t hi, bool starts) {
     return compile_needle_over(n_chars, m, lo, hi, starts, true);
+}
+Program compile_needle_windows(size_t n_windows, size_t m, bool starts) {
+    if (m < 1 || m > NEEDLE_MAX_CHARS) throw Error(FR_ERR_INVALID, "needle: 1 <= m <= 64");
+    if (n_windows > ((size_t)1 << 24) / m) throw Error(FR_ERR_INVALID, "scan: more than 2^24 window bytes");
+    return compile_needle_over(n_windows * m, m, 0, n_windows, starts, true, m);
+}
+
+void pad_window_text(WindowClasses& wc, size_t m) {
+    if (wc.first.empty()) return;
+    const std::vector<uint8_t> w0(wc.text.begin(), wc.text.begin() + (long)m);
+    for (size_t d = wc.first.size(); d < scan_padded(wc.first.size()); ++d)
+        wc.text.insert(wc.text.end(), w0.begin(), w0.end());
+}
+
+WindowClasses window_classes(const uint8_t* text, size_t n, size_t m, size_t lo, size_t hi) {
+    if (m < 1 || m > NEEDLE_MAX_CHARS) throw Error(FR_ERR_INVALID, "needle: 1 <= m <= 64");
+    if (lo > hi) throw Error(FR_ERR_INVALID, "needle: start range");
+    WindowClasses wc;
+    const size_t end = std::min(hi, n);
+    wc.cls.assign(end > lo ? end - lo : 0, -1);
+    // the window's bytes are the key: equal hashes alone never make two windows one class
+    std::unordered_map<std::string_view, int32_t> seen;
+    const char* t = (const char*)text;
+    for (size_t p = lo; p < end && p + m <= n; ++p) {
+        const auto ins = seen.emplace(std::string_view(t + p, m), (int32_t)seen.size());
+        if (ins.second) wc.first.push_back(p);
+        wc.cls[p - lo] = ins.first->second;
+    }
+    wc.text.reserve(wc.first.size() * m);
+    for (size_t p : wc.first) wc.text.insert(wc.text.end(), text + p, text + p + m);
+    return wc;
 }
 
 int eval_program(const Program& prog, const uint8_t* content, size_t L) {

@@ -143,6 +143,33 @@ Program compile_needle(size_t n_chars, size_t m, size_t lo, size_t hi, bool star
 // (n_chars, m, lo, hi, starts) alone, never on the content bytes.
 Program compile_needle_clear(size_t n_chars, size_t m, size_t lo, size_t hi, bool starts);
 
+// A scan of a long clear text (fr_scan_clear*): a start's result depends only on the m bytes of
+// its window, so the search runs once per distinct window and every start reads its class.
+// window_classes takes the starts p of [lo, min(hi, n)): cls[p - lo] is the index of p's window
+// among the distinct windows in order of first appearance (-1: p + m > n, the start does not fit),
+// first[d] the start at which class d first appears, and text the compacted text
+// window_0 | window_1 | .. | window_{D-1} (D m bytes, D = first.size()).  Windows are compared
+// byte for byte; every byte value is valid.
+struct WindowClasses {
+    std::vector<int32_t> cls;
+    std::vector<size_t> first;
+    std::vector<uint8_t> text;
+};
+WindowClasses window_classes(const uint8_t* text, size_t n, size_t m, size_t lo, size_t hi);
+// The class count a scan's plan is compiled for: D rounded up to a multiple of SCAN_BUCKET, the
+// spare windows copies of window 0 (harmless in an OR, referenced by no start).  Two texts with
+// nearby D share one cached plan at the price of at most SCAN_BUCKET - 1 spare rotations.
+constexpr size_t SCAN_BUCKET = 64;
+inline size_t scan_padded(size_t D) { return (D + SCAN_BUCKET - 1) / SCAN_BUCKET * SCAN_BUCKET; }
+// wc.text grown to scan_padded(D) windows of m bytes: the text a scan's plan reads
+void pad_window_text(WindowClasses& wc, size_t m);
+// compile_needle_clear over a compacted text of n_windows windows of m bytes: start d reads the
+// bytes from d m on (the clear layer at stride m), so window d's term t is (sel t, pos d m + t / 2,
+// half t % 2); above the extract-sums the program is compile_needle_clear's for n_windows starts
+// that all fit.  m = 1 is compile_needle_clear(n_windows, 1, 0, n_windows, starts) gate for gate.
+// The program depends on (n_windows, m, starts) alone.  n_windows m <= 2^24.
+Program compile_needle_windows(size_t n_windows, size_t m, bool starts);
+
 // LUT builders
 void lut_eq(uint8_t* lut, int v);     // [x == v]
 void lut_sign(uint8_t* lut, int v);   // x < v -> 0, x == v -> 1, x > v -> 2

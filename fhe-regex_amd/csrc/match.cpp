@@ -29,9 +29,11 @@ namespace {
 // needle_m > 0: a private search (fr_find*) for a needle of that many characters, the pattern
 // empty -- the plan does not depend on the needle's ciphertext, so the length stands for it.
 // clear: that search over clear content (fr_find_clear*), whose plan does not depend on the
-// content's bytes either; the field keeps it apart from fr_find's plan for the same (m, n).
+// content's bytes either; the field keeps it apart from fr_find's plan for the same (m, n).  A
+// scan (fr_scan_clear*) is the field's third value with n its padded class count, so its plan is
+// never fr_find_clear's for the same numbers.
 std::string match_key(fr_ctx* ctx, const char* pattern, size_t n, size_t M, size_t lo, size_t hi, size_t parts,
-                      int lane, bool starts, size_t needle_m, bool clear) {
+                      int lane, bool starts, size_t needle_m, int clear) {
     std::string k;
     for (size_t v : {(size_t)ctx->grammar, (size_t)ctx->engine, (size_t)ctx->lowering, (size_t)ctx->multi_value, n, M,
                      lo, hi, parts, (size_t)lane, (size_t)starts, needle_m, (size_t)clear})
@@ -140,26 +142,52 @@ void fill_stats(fr_match_stats& s, const Recorded& rec, const Plan& P) {
 struct PackedReply {
     bool compact;  // FRCPRES1, else FRPKRES1
     uint8_t* buf;  // packed_compact_size / packed_result_size bytes
+    // a scan (fr_scan_clear_starts): the plan's outputs are window classes and start j of the
+    // call's n_starts reads output cls[j] (-1: the constant 0); buf receives one blob per chunk
+    // of N starts, back to back (scan_reply_size bytes); no start: no chunk, cls may be null
+    const int32_t* cls = nullptr;
+    size_t n_starts = 0;
 };
+// the bytes of a scan's reply over n_starts starts
+size_t scan_reply_size(const Params& p, size_t n_starts, bool compact) {
+    size_t need = 0;
+    for (size_t j0 = 0; j0 < n_starts; j0 += (size_t)p.N)
+        need += compact ? packed_compact_size(p, std::min((size_t)p.N, n_starts - j0)) : packed_result_size(p);
+    return need;
+}
+// The private-search arguments of a match (fr_find*, fr_find_clear*, fr_scan_clear*).
+enum ClearKind : int { CLEAR_NONE = 0, CLEAR_FIND = 1, CLEAR_SCAN = 2 };
+struct Search {
+    const fr_needle* needle = nullptr;
+    ClearKind clear = CLEAR_NONE;
+    const uint8_t* text = nullptr;  // clear: the bytes the extract-sums read,
+    size_t text_n = 0;              // and how many (a find: n; a scan: n windows of m bytes)
+};
+// refused before anything is planned or launched
+void check_needle(fr_ctx* ctx, Device& dev, const fr_needle* needle) {
+    if (ctx->p.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "private search: FFT ring only");
+    if (needle->k != ctx->p.k || needle->N != ctx->p.N)
+        throw Error(FR_ERR_INVALID, "needle: k, N do not match the context params");
+    if (needle->dev.dev != &dev || !needle->dev.words) throw Error(FR_ERR_INVALID, "needle: uploaded to another context");
+}
 // needle (fr_find, fr_find_starts; M = 1, no pattern): the program is compile_needle's, its
 // selector jobs read the needle's table, bound to the match's lane around its launches.
 // clear (fr_find_clear, fr_find_clear_starts; with a needle): the content is the n bytes at `text`
 // and there are no content handles; the program is compile_needle_clear's, its extract-sums read
 // the needle's table and the bytes, both bound to the match's lane around its launches.
+// scan (fr_scan_clear, fr_scan_clear_starts): clear content compacted to its n distinct windows
+// (padded); the program is compile_needle_windows' over [0, n), and a packed reply reads it
+// through the starts' classes (PackedReply::cls).
 void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const char* pattern, size_t lo, size_t hi,
                 fr_ct* outs, fr_match_stats* st, size_t parts = 1, size_t* n_parts = nullptr, bool starts = false,
-                const PackedReply* reply = nullptr, const fr_needle* needle = nullptr, bool clear = false,
-                const uint8_t* text = nullptr) {
+                const PackedReply* reply = nullptr, const Search& search = {}) {
     double t0 = now_ms();
     pattern = pattern ? pattern : "";
     Device& dev = ctx->keyed_device();
     if (M == 0) throw Error(FR_ERR_INVALID, "no matches");
-    if (needle) {  // refused before anything is planned or launched
-        if (ctx->p.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "private search: FFT ring only");
-        if (needle->k != ctx->p.k || needle->N != ctx->p.N)
-            throw Error(FR_ERR_INVALID, "needle: k, N do not match the context params");
-        if (needle->dev.dev != &dev || !needle->dev.words) throw Error(FR_ERR_INVALID, "needle: uploaded to another context");
-    }
+    const fr_needle* needle = search.needle;
+    const ClearKind clear = search.clear;
+    if (needle) check_needle(ctx, dev, needle);
     const size_t needle_m = needle ? needle->dev.m : 0;
     if (clear && (!needle || M != 1 || content)) throw Error(FR_ERR_INVALID, "clear content: one needle, no handles");
     const size_t n_handles = clear ? 0 : n * M;
@@ -201,7 +229,9 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
         rec = hit->rec;
     } else {
         ++pc.misses;
-        if (clear) {
+        if (clear == CLEAR_SCAN) {
+            prog = compile_needle_windows(n, needle_m, starts);
+        } else if (clear) {
             prog = compile_needle_clear(n, needle_m, lo, hi, starts);
         } else if (needle) {
             prog = compile_needle(n, needle_m, lo, hi, starts);
@@ -228,7 +258,7 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
         std::vector<fr_ct> inputs(content, content + n_handles);
         const bool keep = pc.capacity && G && G * M <= pc.slot_cap;
         if (keep) evict_for(ctx, 1, G * M);  // before the new plan allocates its slots
-        fresh = compile_plan(ctx, gates, inputs, keep, clear ? n : 0);
+        fresh = compile_plan(ctx, gates, inputs, keep, search.text_n);
         if (keep) {
             // keep the plan: its slots stay allocated, its batches go to the device once; the
             // entry is complete before the cache sees it
@@ -268,10 +298,10 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
             } catch (...) {
             }
         }
-    } selector_scope{dev, needle != nullptr, clear};
+    } selector_scope{dev, needle != nullptr, clear != CLEAR_NONE};
     if (needle) dev.bind_selectors(needle->dev.words.get(), 2 * needle_m);
     // the call's bytes, copied now and in stream order on this lane: the caller's buffer may go
-    if (clear) dev.bind_text(text, n);
+    if (clear) dev.bind_text(search.text, search.text_n);
     launch_plan(dev, plan);
     if (hit && !starts && (nO < 1 || nO > parts))  // the caller's out buffer holds M * parts handles
         throw Error(FR_ERR_INVALID, "cached plan has more outputs than the caller's parts");
@@ -293,7 +323,45 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
                 g.in_w[0] = o.w;
             }
         }
-        if (reply->compact) {
+        if (clear == CLEAR_SCAN) {  // (no start at all: cls may be null, and no chunk is written)
+            // A scan: per chunk of N starts, the rows are the classes that occur in it (in order of
+            // first occurrence) and the map sends each start to its row; one mapped pack per chunk.
+            const size_t N = (size_t)ctx->p.N;
+            std::vector<int32_t> row_of(nO, -1), map;
+            std::vector<DevGate> rows;
+            std::vector<uint16_t> v;
+            std::vector<uint64_t> words;
+            uint8_t* at = reply->buf;
+            for (size_t j0 = 0; j0 < reply->n_starts; j0 += N) {
+                const size_t nc = std::min(N, reply->n_starts - j0);
+                rows.clear();
+                map.assign(nc, -1);
+                for (size_t j = 0; j < nc; ++j) {
+                    const int32_t d = reply->cls[j0 + j];
+                    if (d < 0) continue;
+                    if ((size_t)d >= nO) throw Error(FR_ERR_INVALID, "scan: a class past the plan's outputs");
+                    if (row_of[(size_t)d] < 0) {
+                        row_of[(size_t)d] = (int32_t)rows.size();
+                        rows.push_back(desc[(size_t)d]);
+                    }
+                    map[j] = row_of[(size_t)d];
+                }
+                for (size_t j = 0; j < nc; ++j)  // (the next chunk numbers its rows anew)
+                    if (reply->cls[j0 + j] >= 0) row_of[(size_t)reply->cls[j0 + j]] = -1;
+                // a chunk with no fitting start is the packing of nc constants 0: all zero words
+                if (reply->compact) {
+                    v.assign(packed_compact_values(ctx->p, nc), 0);
+                    if (!rows.empty()) dev.pack_mapped(rows.data(), rows.size(), map.data(), nc, nullptr, v.data());
+                    write_packed_compact(ctx->p, nc, v.data(), at);
+                    at += packed_compact_size(ctx->p, nc);
+                } else {
+                    words.assign(pk_row_words(ctx->p), 0);
+                    if (!rows.empty()) dev.pack_mapped(rows.data(), rows.size(), map.data(), nc, words.data(), nullptr);
+                    write_packed_result(ctx->p, nc, words.data(), at);
+                    at += packed_result_size(ctx->p);
+                }
+            }
+        } else if (reply->compact) {
             std::vector<uint16_t> v(packed_compact_values(ctx->p, nO));
             dev.pack_bools_compact(desc.data(), nO, v.data());
             write_packed_compact(ctx->p, nO, v.data(), reply->buf);
@@ -339,6 +407,20 @@ void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const cha
             st->br_gates = after.br_gates - before.br_gates;
         }
     }
+}
+
+// A scan's host part: the classes of the starts of [lo, hi), the padded class count and the text
+// the plan reads (pad_window_text).  The counts are left in the context for fr_scan_classes.
+WindowClasses scan_windows(fr_ctx* ctx, const uint8_t* content, size_t n_chars, size_t m, size_t lo, size_t hi,
+                           size_t* Dpad) {
+    if (n_chars > (size_t)1 << 24) throw Error(FR_ERR_INVALID, "scan: content longer than 2^24");
+    WindowClasses wc = window_classes(content, n_chars, m, lo, hi);
+    *Dpad = scan_padded(wc.first.size());
+    if (*Dpad * m > (size_t)1 << 24) throw Error(FR_ERR_INVALID, "scan: more than 2^24 window bytes");
+    pad_window_text(wc, m);
+    ctx->scan_classes = wc.first.size();
+    ctx->scan_padded = *Dpad;
+    return wc;
 }
 
 }  // namespace
@@ -449,7 +531,7 @@ int fr_find(fr_ctx* ctx, const fr_ct* content, size_t n_chars, const fr_needle* 
         NEED(ctx && needle && out && (content || !n_chars) && start_lo <= start_hi);
         // no start past the content fits: the range is cut there (one plan for every such range)
         const size_t hi = std::min(start_hi, n_chars), lo = std::min(start_lo, hi);
-        match_impl(ctx, content, n_chars, 1, "", lo, hi, out, st, 1, nullptr, false, nullptr, needle);
+        match_impl(ctx, content, n_chars, 1, "", lo, hi, out, st, 1, nullptr, false, nullptr, Search{needle});
     })
 }
 
@@ -458,7 +540,7 @@ int fr_find_starts(fr_ctx* ctx, const fr_ct* content, size_t n_chars, const fr_n
     FR_TRY({
         NEED(ctx && needle && (content || !n_chars) && start_lo <= start_hi && (out || start_lo == start_hi));
         NEED(start_hi - start_lo <= ((size_t)1 << 24));
-        match_impl(ctx, content, n_chars, 1, "", start_lo, start_hi, out, st, 1, nullptr, true, nullptr, needle);
+        match_impl(ctx, content, n_chars, 1, "", start_lo, start_hi, out, st, 1, nullptr, true, nullptr, Search{needle});
     })
 }
 
@@ -468,7 +550,8 @@ int fr_find_clear(fr_ctx* ctx, const uint8_t* content, size_t n_chars, const fr_
         NEED(ctx && needle && out && (content || !n_chars) && start_lo <= start_hi);
         // (the range is cut at the content's end, as fr_find cuts it)
         const size_t hi = std::min(start_hi, n_chars), lo = std::min(start_lo, hi);
-        match_impl(ctx, nullptr, n_chars, 1, "", lo, hi, out, st, 1, nullptr, false, nullptr, needle, true, content);
+        match_impl(ctx, nullptr, n_chars, 1, "", lo, hi, out, st, 1, nullptr, false, nullptr,
+                   Search{needle, CLEAR_FIND, content, n_chars});
     })
 }
 
@@ -477,8 +560,58 @@ int fr_find_clear_starts(fr_ctx* ctx, const uint8_t* content, size_t n_chars, co
     FR_TRY({
         NEED(ctx && needle && (content || !n_chars) && start_lo <= start_hi && (out || start_lo == start_hi));
         NEED(start_hi - start_lo <= ((size_t)1 << 24));
-        match_impl(ctx, nullptr, n_chars, 1, "", start_lo, start_hi, out, st, 1, nullptr, true, nullptr, needle, true,
-                   content);
+        match_impl(ctx, nullptr, n_chars, 1, "", start_lo, start_hi, out, st, 1, nullptr, true, nullptr,
+                   Search{needle, CLEAR_FIND, content, n_chars});
+    })
+}
+
+int fr_scan_clear(fr_ctx* ctx, const uint8_t* content, size_t n_chars, const fr_needle* needle, size_t start_lo,
+                  size_t start_hi, fr_ct* out, fr_match_stats* st) {
+    FR_TRY({
+        NEED(ctx && needle && out && (content || !n_chars) && start_lo <= start_hi);
+        check_needle(ctx, ctx->keyed_device(), needle);  // before the text is classed
+        const size_t hi = std::min(start_hi, n_chars), lo = std::min(start_lo, hi);
+        size_t Dpad = 0;
+        const double t0 = now_ms();
+        const WindowClasses wc = scan_windows(ctx, content, n_chars, needle->dev.m, lo, hi, &Dpad);
+        const double classing_ms = now_ms() - t0;
+        match_impl(ctx, nullptr, Dpad, 1, "", 0, Dpad, out, st, 1, nullptr, false, nullptr,
+                   Search{needle, CLEAR_SCAN, wc.text.data(), wc.text.size()});
+        if (st) st->host_ms += classing_ms;  // the classing is the scan's host work too
+    })
+}
+
+int fr_scan_clear_starts(fr_ctx* ctx, const uint8_t* content, size_t n_chars, const fr_needle* needle, size_t start_lo,
+                         size_t start_hi, int32_t compact, uint8_t* buf, size_t cap, size_t* written,
+                         fr_match_stats* st) {
+    FR_TRY({
+        NEED(ctx && needle && written && (content || !n_chars) && start_lo <= start_hi);
+        NEED(compact == 0 || compact == 1);
+        NEED(start_hi - start_lo <= ((size_t)1 << 24));
+        check_needle(ctx, ctx->keyed_device(), needle);  // a host-only or keyless context refuses as fr_find_clear does
+        if (!ctx->has_pk)                                // ... and nothing is launched without a packing key
+            throw Error(FR_ERR_INVALID, "packing needs a packing key (fr_gen_packing_key, fr_load_packing_key)");
+        const size_t n_starts = start_hi - start_lo, need = scan_reply_size(ctx->p, n_starts, compact != 0);
+        *written = need;
+        if (!buf) return FR_OK;  // size query
+        NEED(cap >= need);
+        size_t Dpad = 0;
+        const double t0 = now_ms();
+        WindowClasses wc = scan_windows(ctx, content, n_chars, needle->dev.m, start_lo, start_hi, &Dpad);
+        wc.cls.resize(n_starts, -1);  // a start past the content: the constant 0
+        const double classing_ms = now_ms() - t0;
+        const PackedReply reply{compact != 0, buf, wc.cls.data(), n_starts};
+        match_impl(ctx, nullptr, Dpad, 1, "", 0, Dpad, nullptr, st, 1, nullptr, true, &reply,
+                   Search{needle, CLEAR_SCAN, wc.text.data(), wc.text.size()});
+        if (st) st->host_ms += classing_ms;
+    })
+}
+
+int fr_scan_classes(fr_ctx* ctx, uint64_t* classes, uint64_t* padded) {
+    FR_TRY({
+        NEED(ctx);
+        if (classes) *classes = ctx->scan_classes;
+        if (padded) *padded = ctx->scan_padded;
     })
 }
 
@@ -689,6 +822,18 @@ int fr_schedule_find_clear(size_t n_chars, size_t m, size_t start_lo, size_t sta
         NEED(outs_cap >= (starts ? start_hi - start_lo : 1));
         const Program prog = compile_needle_clear(n_chars, m, start_lo, start_hi, starts != 0);
         schedule_program(prog, n_chars, 1, jobs, jobs_cap, n_jobs, level_off, level_cap, n_levels, outs3, n_outs);
+    })
+}
+
+int fr_schedule_scan_clear(size_t n_windows, size_t m, int32_t starts, fr_job* jobs, size_t jobs_cap, size_t* n_jobs,
+                           uint32_t* level_off, size_t level_cap, size_t* n_levels, int32_t* outs3, size_t outs_cap,
+                           size_t* n_outs) {
+    FR_TRY({
+        NEED(n_jobs && n_levels && n_outs && outs3 && (starts == 0 || starts == 1));
+        NEED(n_windows <= ((size_t)1 << 24) && outs_cap >= (starts ? n_windows : 1));
+        const Program prog = compile_needle_windows(n_windows, m, starts != 0);
+        // (the extract-sums read n_windows m bytes of compacted text)
+        schedule_program(prog, n_windows * m, 1, jobs, jobs_cap, n_jobs, level_off, level_cap, n_levels, outs3, n_outs);
     })
 }
 

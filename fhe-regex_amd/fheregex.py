@@ -207,6 +207,25 @@ _SIGS = {
     "fr_dev_select_sum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_int32),
                                     C.POINTER(C.c_int32), C.c_size_t, u64p]),
     "fr_dev_select_sum_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "fr_scan_clear": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                C.POINTER(C.c_uint32), C.POINTER(MatchStats)]),
+    "fr_scan_clear_starts": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                       C.c_int32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                       C.POINTER(MatchStats)]),
+    "fr_scan_classes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "fr_window_classes": (C.c_int, [C.c_char_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_int32),
+                                    C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                    C.c_char_p, C.c_size_t]),
+    "fr_schedule_scan_clear": (C.c_int, [C.c_size_t, C.c_size_t, C.c_int32, C.POINTER(FrJob), C.c_size_t,
+                                         C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.c_size_t,
+                                         C.POINTER(C.c_size_t), C.POINTER(C.c_int32), C.c_size_t,
+                                         C.POINTER(C.c_size_t)]),
+    "fr_plain_scan_clear": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint16), C.c_size_t, C.c_size_t,
+                                      C.c_size_t, C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]),
+    "fr_dev_pack_mapped": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_int32), C.c_size_t,
+                                     C.c_int32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fr_pack_lwes_mapped": (C.c_int, [C.c_void_p, u64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_size_t,
+                                      C.POINTER(C.c_int32), C.c_size_t, u64p]),
     "fr_encrypt_str": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint64, u64p]),
     "fr_encrypt_blocks": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, C.c_uint64, C.c_uint64, u64p]),
     "fr_decrypt_radix": (C.c_int, [C.c_void_p, u64p, u64p]),
@@ -1015,6 +1034,66 @@ class Context:
         hs, st = self._find_clear(lib().fr_find_clear_starts, text, needle, lo, hi, max(hi - lo, 0))
         return (hs, st) if stats else hs
 
+    # ---- scan of a long clear text (fr_scan_clear*): one rotation per distinct window
+    def scan_clear(self, text: bytes | str, needle: "Needle", lo: Optional[int] = None, hi: Optional[int] = None):
+        """fr_scan_clear: find_clear's (boolean handle, MatchStats) at one rotation per distinct
+        window of the text"""
+        lo = 0 if lo is None else lo
+        hi = len(_text_bytes(text)) if hi is None else hi
+        out, st = self._find_clear(lib().fr_scan_clear, text, needle, lo, hi, 1)
+        return out[0], st
+
+    def scan_clear_starts(self, text: bytes | str, needle: "Needle", lo: Optional[int] = None,
+                          hi: Optional[int] = None, compact: bool = True, stats: bool = False):
+        """fr_scan_clear_starts: the blobs of the chunks of N starts of [lo, hi), back to back
+        (compact: FRCPRES1, else FRPKRES1), with no handle in between; with stats=True also the
+        MatchStats"""
+        if needle.h is None:
+            raise ValueError("needle is closed")
+        b = _text_bytes(text)
+        lo = 0 if lo is None else lo
+        hi = len(b) if hi is None else hi
+        n = C.c_size_t()
+        st = MatchStats()
+        args = (self.h, b, len(b), needle.h, lo, hi, int(compact))
+        _check(lib().fr_scan_clear_starts(*args, None, 0, C.byref(n), None))
+        buf = C.create_string_buffer(max(n.value, 1))
+        _check(lib().fr_scan_clear_starts(*args, buf, n.value, C.byref(n), C.byref(st)))
+        return (buf.raw[:n.value], st) if stats else buf.raw[:n.value]
+
+    def scan_classes(self) -> Tuple[int, int]:
+        """fr_scan_classes: (D, padded D) of this context's last scan"""
+        d, dp = C.c_uint64(), C.c_uint64()
+        _check(lib().fr_scan_classes(self.h, C.byref(d), C.byref(dp)))
+        return d.value, dp.value
+
+    def dev_pack_mapped(self, handles: Sequence[int], map_: Sequence[int], compact: bool = False) -> bytes:
+        """fr_dev_pack_mapped: the mapped pack alone; start j is the boolean handles[map_[j]]
+        (map_[j] < 0: the constant 0) -> the blob of the len(map_) starts"""
+        hs = (C.c_uint32 * max(len(handles), 1))(*handles)
+        mp = (C.c_int32 * max(len(map_), 1))(*[int(v) for v in map_])
+        n = C.c_size_t()
+        args = (self.h, hs, len(handles), mp, len(map_), int(compact))
+        _check(lib().fr_dev_pack_mapped(*args, None, 0, C.byref(n)))
+        buf = C.create_string_buffer(n.value)
+        _check(lib().fr_dev_pack_mapped(*args, buf, n.value, C.byref(n)))
+        return buf.raw[:n.value]
+
+    def pack_lwes_mapped(self, lwes: Optional[np.ndarray], map_: Sequence[int], w=None, off=None,
+                         n_rows: Optional[int] = None) -> np.ndarray:
+        """fr_pack_lwes_mapped: pack_lwes where start j reads row map_[j] of the n_rows booleans
+        off[r] 2^58 + w[r] lwes[r] (map_[j] < 0: the constant 0), in plain host loops"""
+        if lwes is not None:
+            lwes = np.ascontiguousarray(lwes, dtype=np.uint64).reshape(-1, self.lwe_len)
+            n_rows = len(lwes)
+        wa = None if w is None else (C.c_int32 * max(n_rows, 1))(*[int(x) for x in w])
+        oa = None if off is None else (C.c_int32 * max(n_rows, 1))(*[int(x) for x in off])
+        mp = (C.c_int32 * max(len(map_), 1))(*[int(v) for v in map_])
+        out = np.zeros((self.params.k + 1) * self.params.N, dtype=np.uint64)
+        _check(lib().fr_pack_lwes_mapped(self.h, None if lwes is None else _p(lwes), wa, oa, n_rows, mp, len(map_),
+                                         _p(out)))
+        return out
+
     def dev_select_sum(self, needle: "Needle", text: bytes | str, sums: Sequence[Sequence[Tuple[int, int, int]]]
                        ) -> np.ndarray:
         """fr_dev_select_sum: the extract-sum kernel alone; sums[i] is the list of sum i's terms
@@ -1332,6 +1411,36 @@ def plain_find_clear(content: bytes | str, masks: Sequence[Tuple[int, int]], sta
     return list(out)[:max(hi - start_lo, 0)], any_.value
 
 
+def plain_scan_clear(content: bytes | str, masks: Sequence[Tuple[int, int]], start_lo: int = 0,
+                     start_hi: Optional[int] = None) -> Tuple[List[int], int]:
+    """fr_plain_scan_clear: plain_find_clear by the scan's route (windows classed, the lowered
+    programs over the compacted text, every start its class's output): (starts, any)"""
+    b = _text_bytes(content)
+    hi = len(b) if start_hi is None else start_hi
+    flat = [v for lo_hi in masks for v in lo_hi]
+    arr = (C.c_uint16 * max(len(flat), 1))(*flat)
+    out = (C.c_uint8 * max(hi - start_lo, 1))()
+    any_ = C.c_int32()
+    _check(lib().fr_plain_scan_clear(b, len(b), arr, len(masks), start_lo, hi, out, C.byref(any_)))
+    return list(out)[:max(hi - start_lo, 0)], any_.value
+
+
+def window_classes(text: bytes | str, m: int, start_lo: int = 0, start_hi: Optional[int] = None
+                   ) -> Tuple[List[int], int, int, bytes]:
+    """fr_window_classes: (cls, D, padded D, the D distinct windows side by side) for the starts
+    of [start_lo, min(start_hi, len(text))); cls[p - start_lo] = -1 where the window does not fit"""
+    b = _text_bytes(text)
+    hi = len(b) if start_hi is None else start_hi
+    n_cls, d, dp = C.c_size_t(), C.c_uint64(), C.c_uint64()
+    _check(lib().fr_window_classes(b, len(b), m, start_lo, hi, None, 0, C.byref(n_cls), C.byref(d), C.byref(dp),
+                                   None, 0))
+    cls = (C.c_int32 * max(n_cls.value, 1))()
+    win = C.create_string_buffer(max(d.value * m, 1))
+    _check(lib().fr_window_classes(b, len(b), m, start_lo, hi, cls, n_cls.value, C.byref(n_cls), C.byref(d),
+                                   C.byref(dp), win, d.value * m))
+    return list(cls)[:n_cls.value], d.value, dp.value, win.raw[:d.value * m]
+
+
 def plain_find(content: bytes | str, masks: Sequence[Tuple[int, int]], start_lo: int = 0,
                start_hi: Optional[int] = None) -> Tuple[List[int], int]:
     """fr_plain_find: the lowered programs of find_starts and find in plaintext: (starts, any)"""
@@ -1508,6 +1617,22 @@ class ServerKey:
         if compact:
             return struct.pack("<II", COMPACT_REPLY, len(blobs)) + b"".join(blobs)
         return struct.pack("<I", len(blobs)) + b"".join(blobs)
+
+    def scan_clear(self, text: bytes | str, needle: Needle) -> int:
+        """find_clear for a long text: one rotation per distinct window of len(needle) bytes
+        instead of one per start (fr_scan_clear)"""
+        return self.ctx.scan_clear(text, needle)[0]
+
+    def scan_clear_starts(self, text: bytes | str, needle: Needle, compact: bool = False) -> bytes:
+        """find_clear_starts' reply, byte for byte, from one fr_scan_clear_starts call: no handle
+        per start, one rotation per distinct window, one mapped pack per chunk of N starts"""
+        N = self.ctx.params.N
+        n = len(_text_bytes(text))
+        blobs = self.ctx.scan_clear_starts(text, needle, compact=compact)
+        chunks = (n + N - 1) // N
+        if compact:
+            return struct.pack("<II", COMPACT_REPLY, chunks) + blobs
+        return struct.pack("<I", chunks) + blobs
 
     def save(self, path: str, packing_path: Optional[str] = None):
         """the server key as an .npz of its (ksk, bsk) arrays (fr_export_server_key's layout);
@@ -1945,6 +2070,24 @@ def schedule_find_clear(n_chars: int, m: int, start_lo: int = 0, start_hi: Optio
     """fr_schedule_find_clear: schedule_find for find_clear / find_clear_starts (no selector job;
     the extract-sums are level 0 and are no jobs)"""
     return schedule_find(n_chars, m, start_lo, start_hi, starts, _fn="fr_schedule_find_clear")
+
+
+def schedule_scan_clear(n_windows: int, m: int, starts: bool = False) -> Schedule:
+    """fr_schedule_scan_clear: the schedule of scan_clear (one output) or of scan_clear_starts'
+    plan (Schedule.parts: one output per window) over n_windows windows of m bytes"""
+    nj, nl, ns = C.c_size_t(), C.c_size_t(), C.c_size_t()
+    cap = max(n_windows, 1)
+    outs3 = (C.c_int32 * (3 * cap))()
+    args = (n_windows, m, int(starts))
+    fn = lib().fr_schedule_scan_clear
+    _check(fn(*args, None, 0, C.byref(nj), None, 0, C.byref(nl), outs3, cap, C.byref(ns)))
+    jobs = (FrJob * max(nj.value, 1))()
+    off = (C.c_uint32 * (nl.value + 1))()
+    _check(fn(*args, jobs, len(jobs), C.byref(nj), off, len(off), C.byref(nl), outs3, cap, C.byref(ns)))
+    n_gates = 1 + max([max(j.out_gate[f] for f in range(j.n_out)) for j in jobs[:nj.value]] or [-1])
+    parts = [(outs3[3 * j], outs3[3 * j + 1], outs3[3 * j + 2]) for j in range(ns.value)]
+    first = parts[0] if parts else (-1, 0, 0)
+    return Schedule(list(jobs[:nj.value]), list(off), first[0], first[1], first[2], n_gates, parts)
 
 
 def schedule_find(n_chars: int, m: int, start_lo: int = 0, start_hi: Optional[int] = None,

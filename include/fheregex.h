@@ -655,6 +655,43 @@ int fr_find_clear_starts(fr_ctx* ctx, const uint8_t* content, size_t n_chars, co
                          size_t start_lo, size_t start_hi, fr_ct* out /* start_hi - start_lo */,
                          fr_match_stats* stats);
 
+/* ----- scan of a long clear text (FFT ring) ----- */
+/* fr_find_clear spends one rotation per start; a start's result depends only on the m bytes of
+ * its window, and the server knows the text, so a scan spends one rotation per *distinct window*.
+ * The starts of the range are classed on the host (fr_window_classes), the distinct windows are
+ * laid side by side, their count D padded to the next multiple of 64 by repeating window 0
+ * (harmless in an OR, read by no start; texts with nearby D share one plan), and the search runs
+ * over the windows alone: the plan depends on (m, padded D) and never on the bytes, so a second
+ * text or needle of the same (m, padded D) is a cache hit; its plans are kept apart from
+ * fr_find_clear's.  fr_scan_clear is fr_find_clear's boolean.  fr_scan_clear_starts is
+ * fr_find_clear_starts followed by the packs of its handles, without the handles: buf receives the
+ * blobs of the ceil((start_hi - start_lo) / N) chunks of N starts back to back, FRPKRES1
+ * (compact = 0) or FRCPRES1 (1), chunk c carrying starts start_lo + c N onward in order, byte for
+ * byte what fr_pack_bools_blob / fr_pack_bools_compact give for fr_find_clear_starts' handles.
+ * One plan launch serves every chunk; per chunk the packing keyswitch runs over the classes that
+ * occur in it and start j of class d is X^j times row d (linearity), on the match's lane after
+ * the plan's launches.  A start that cannot fit, or lies past the content, is the constant 0.
+ * *written receives the reply's size; buf NULL is a size query; cap too small is FR_ERR_INVALID
+ * with *written set and nothing launched.  Stats count rotations as every match's (host_ms
+ * includes the classing);
+ * fr_scan_classes gives D and padded D of the context's last scan.  Limits: n_chars <= 2^24,
+ * start_hi - start_lo <= 2^24, padded D times m <= 2^24.  Refusals, lanes, fr_set_async and the
+ * needle's release are fr_find_clear's; fr_scan_clear_starts needs the packing key. */
+int fr_scan_clear(fr_ctx* ctx, const uint8_t* content, size_t n_chars, const fr_needle* needle, size_t start_lo,
+                  size_t start_hi, fr_ct* out, fr_match_stats* stats);
+int fr_scan_clear_starts(fr_ctx* ctx, const uint8_t* content, size_t n_chars, const fr_needle* needle,
+                         size_t start_lo, size_t start_hi, int32_t compact, uint8_t* buf, size_t cap, size_t* written,
+                         fr_match_stats* stats);
+int fr_scan_classes(fr_ctx* ctx, uint64_t* classes, uint64_t* padded);
+/* The classing alone, on the host: for the starts p of [start_lo, min(start_hi, n_chars)),
+ * cls[p - start_lo] is the index of p's window text[p .. p + m) among the distinct windows in order
+ * of first appearance, or -1 where p + m > n_chars; *n_cls entries are written (cls NULL: none).
+ * *classes is D, *padded the plan's count, and windows (NULL: skipped) receives the D windows side
+ * by side, D m bytes.  Windows are compared byte for byte; every byte value is valid. */
+int fr_window_classes(const uint8_t* text, size_t n_chars, size_t m, size_t start_lo, size_t start_hi, int32_t* cls,
+                      size_t cls_cap, size_t* n_cls, uint64_t* classes, uint64_t* padded, uint8_t* windows,
+                      size_t windows_cap);
+
 /* ----- one match split across ranks ----- */
 /* The reference folds ct_or over the branches of every start offset
  * (engine.rs:15-35, each branch a chain of execution.rs:76-190 calls); anchored
@@ -744,6 +781,17 @@ int fr_schedule_find_clear(size_t n_chars, size_t m, size_t start_lo, size_t sta
 /* The lowered programs of fr_find_clear_starts and fr_find_clear evaluated in plaintext, the
  * extract-sums included, with the tables in the clear: starts_out[p - start_lo] and *any. */
 int fr_plain_find_clear(const uint8_t* content, size_t len, const uint16_t* masks, size_t m, size_t start_lo,
+                        size_t start_hi, uint8_t* starts_out, int32_t* any);
+/* The schedule of fr_scan_clear (starts = 0) or of fr_scan_clear_starts' plan (starts = 1) over
+ * n_windows windows of m bytes, shaped as fr_schedule_find_clear: window d's extract-sum terms
+ * read the compacted text from byte d m on.  m = 1 is fr_schedule_find_clear(n_windows, 1, 0,
+ * n_windows) job for job. */
+int fr_schedule_scan_clear(size_t n_windows, size_t m, int32_t starts, fr_job* jobs, size_t jobs_cap, size_t* n_jobs,
+                           uint32_t* level_off, size_t level_cap, size_t* n_levels, int32_t* outs3, size_t outs_cap,
+                           size_t* n_outs);
+/* fr_plain_find_clear by the scan's route: the windows classed and padded, both lowered programs
+ * evaluated over the compacted text, every start given its class's output. */
+int fr_plain_scan_clear(const uint8_t* content, size_t len, const uint16_t* masks, size_t m, size_t start_lo,
                         size_t start_hi, uint8_t* starts_out, int32_t* any);
 
 /* ----- host-only introspection (tests; no device needed) ----- */
@@ -878,6 +926,17 @@ int fr_dev_blind_rotate_acc(fr_ctx* ctx, const uint64_t* in /* count*(n+1) */, c
 int fr_dev_select_sum(fr_ctx* ctx, const fr_needle* needle, const uint8_t* content, size_t len,
                       const int32_t* terms /* 3 per term */, const int32_t* n_terms, size_t n_sums, uint64_t* out);
 int fr_dev_select_sum_ms(fr_ctx* ctx, double* ms);
+/* The mapped pack alone (a scan's reply): n_rows boolean handles, and n starts of which start j
+ * is the boolean bools[map[j]] or, where map[j] < 0, the constant 0; buf receives the FRPKRES1
+ * (compact = 0) or FRCPRES1 blob of the n starts (buf NULL: size query).  The identity map gives
+ * fr_pack_bools_blob's bytes.  FR_ERR_INVALID before anything is staged for n_rows < 1,
+ * n_rows > n, n > N, an entry >= n_rows and a row no start reads.  fr_device_timers_pack holds its
+ * stages.  fr_pack_lwes_mapped is the host restatement (plain loops, exact mod 2^64) in
+ * fr_pack_lwes' terms: lwes, w, off have n_rows entries. */
+int fr_dev_pack_mapped(fr_ctx* ctx, const fr_ct* bools, size_t n_rows, const int32_t* map, size_t n, int32_t compact,
+                       uint8_t* buf, size_t cap, size_t* written);
+int fr_pack_lwes_mapped(fr_ctx* ctx, const uint64_t* lwes, const int32_t* w, const int32_t* off, size_t n_rows,
+                        const int32_t* map, size_t n, uint64_t* out_words);
 /* negacyclic product in Z_Q[X]/(X^N+1) (Q = 998244353 * 1004535809, inputs in
  * [0, Q)) through the device RNS NTT: count pairs */
 int fr_dev_ring_mul(fr_ctx* ctx, const uint64_t* a, const uint64_t* b, size_t count, uint64_t* out);
