@@ -494,18 +494,26 @@ int fr_dev_blind_rotate_acc(fr_ctx* ctx, const uint64_t* in, const uint64_t* acc
         ctx->device().blind_rotate_acc_host(in, accs, count, out);
     })
 }
+// A needle search on a plaintext, both lowered programs gate by gate: the per-start values from
+// the starts program, `any` from the boolean program's OR tree.  cls (a scan): start j reads the
+// output of its class (none, or past the classed starts: 0); else start j reads output j.
+static void plain_needle(MatchKind kind, const uint8_t* text, size_t len, size_t n, size_t m, size_t lo, size_t hi,
+                         const uint16_t* masks, const std::vector<int32_t>* cls, uint8_t* starts_out, int32_t* any) {
+    std::vector<int> vals;
+    eval_program_parts(needle_program(kind, n, m, lo, hi, true), text, len, vals, masks, 2 * m);
+    for (size_t j = 0; j < (cls ? hi - lo : vals.size()); ++j) {
+        const long o = !cls ? (long)j : j < cls->size() ? (*cls)[j] : -1;
+        starts_out[j] = o >= 0 ? (uint8_t)vals[(size_t)o] : 0;
+    }
+    *any = eval_program_parts(needle_program(kind, n, m, lo, hi, false), text, len, vals, masks, 2 * m);
+}
 int fr_plain_find(const char* content, size_t len, const uint16_t* masks, size_t m, size_t start_lo, size_t start_hi,
                   uint8_t* starts_out, int32_t* any) {
     FR_TRY({
         NEED((content || !len) && masks && any && start_lo <= start_hi && (starts_out || start_lo == start_hi));
         NEED(m >= 1 && m <= NEEDLE_MAX_CHARS);
-        // both lowered programs, evaluated gate by gate: the per-start outputs and the OR tree's root
-        std::vector<int> vals;
-        eval_program_parts(compile_needle(len, m, start_lo, start_hi, true), (const uint8_t*)content, len, vals, masks,
-                           2 * m);
-        for (size_t j = 0; j < vals.size(); ++j) starts_out[j] = (uint8_t)vals[j];
-        *any = eval_program_parts(compile_needle(len, m, start_lo, start_hi, false), (const uint8_t*)content, len, vals,
-                                  masks, 2 * m);
+        plain_needle(MATCH_NEEDLE, (const uint8_t*)content, len, len, m, start_lo, start_hi, masks, nullptr, starts_out,
+                     any);
     })
 }
 int fr_plain_find_clear(const uint8_t* content, size_t len, const uint16_t* masks, size_t m, size_t start_lo,
@@ -513,11 +521,7 @@ int fr_plain_find_clear(const uint8_t* content, size_t len, const uint16_t* mask
     FR_TRY({
         NEED((content || !len) && masks && any && start_lo <= start_hi && (starts_out || start_lo == start_hi));
         NEED(m >= 1 && m <= NEEDLE_MAX_CHARS);
-        std::vector<int> vals;
-        eval_program_parts(compile_needle_clear(len, m, start_lo, start_hi, true), content, len, vals, masks, 2 * m);
-        for (size_t j = 0; j < vals.size(); ++j) starts_out[j] = (uint8_t)vals[j];
-        *any = eval_program_parts(compile_needle_clear(len, m, start_lo, start_hi, false), content, len, vals, masks,
-                                  2 * m);
+        plain_needle(MATCH_NEEDLE_CLEAR, content, len, len, m, start_lo, start_hi, masks, nullptr, starts_out, any);
     })
 }
 int fr_window_classes(const uint8_t* text, size_t n_chars, size_t m, size_t start_lo, size_t start_hi, int32_t* cls,
@@ -544,71 +548,11 @@ int fr_plain_scan_clear(const uint8_t* content, size_t len, const uint16_t* mask
     FR_TRY({
         NEED((content || !len) && masks && any && start_lo <= start_hi && (starts_out || start_lo == start_hi));
         NEED(m >= 1 && m <= NEEDLE_MAX_CHARS && start_hi - start_lo <= ((size_t)1 << 24));
-        // the scan's own route: class the windows, evaluate both lowered programs over the padded
-        // compacted text, and give every start its class's output
+        // the scan's own route: class the windows, then the programs over the padded compacted text
         WindowClasses wc = window_classes(content, len, m, start_lo, start_hi);
-        const size_t Dpad = scan_padded(wc.first.size());
         pad_window_text(wc, m);
-        std::vector<int> vals;
-        eval_program_parts(compile_needle_windows(Dpad, m, true), wc.text.data(), wc.text.size(), vals, masks, 2 * m);
-        for (size_t j = 0; j < start_hi - start_lo; ++j)
-            starts_out[j] = j < wc.cls.size() && wc.cls[j] >= 0 ? (uint8_t)vals[(size_t)wc.cls[j]] : 0;
-        *any = eval_program_parts(compile_needle_windows(Dpad, m, false), wc.text.data(), wc.text.size(), vals, masks,
-                                  2 * m);
-    })
-}
-int fr_pack_lwes_mapped(fr_ctx* ctx, const uint64_t* lwes, const int32_t* w, const int32_t* off, size_t n_rows,
-                        const int32_t* map, size_t n, uint64_t* out_words) {
-    FR_TRY({
-        NEED(ctx && out_words && map && (lwes || w));
-        if (!lwes)
-            for (size_t r = 0; r < n_rows; ++r) NEED(w[r] == 0);
-        if (!ctx->has_pk)
-            throw Error(FR_ERR_INVALID, "packing needs a packing key (fr_gen_packing_key, fr_load_packing_key)");
-        check_pack_map(map, n, n_rows, (size_t)ctx->p.N);
-        if (ctx->dev) {  // the rows live on the device: a host copy for this call
-            std::vector<uint64_t> rows(pk_len(ctx->p));
-            ctx->dev->download_packing_key(rows.data());
-            pack_host_mapped(ctx->p, rows.data(), lwes, w, off, n_rows, map, n, out_words);
-        } else {
-            pack_host_mapped(ctx->p, ctx->pksk.data(), lwes, w, off, n_rows, map, n, out_words);
-        }
-    })
-}
-int fr_dev_pack_mapped(fr_ctx* ctx, const fr_ct* bools, size_t n_rows, const int32_t* map, size_t n, int32_t compact,
-                       uint8_t* buf, size_t cap, size_t* written) {
-    FR_TRY({
-        NEED(ctx && bools && map && written && (compact == 0 || compact == 1));
-        NEED(n >= 1 && n <= (size_t)ctx->p.N);
-        Device& dev = ctx->device();
-        const size_t need = compact ? packed_compact_size(ctx->p, n) : packed_result_size(ctx->p);
-        *written = need;
-        if (!buf) return FR_OK;  // size query
-        NEED(cap >= need);
-        check_pack_map(map, n, n_rows, (size_t)ctx->p.N);  // (before bools is read: n_rows of them)
-        std::vector<DevGate> rows(n_rows);
-        for (size_t r = 0; r < n_rows; ++r) {  // fr_pack_bools' descriptors
-            const HandleRec& h = ctx->get(bools[r]);
-            if (!h.is_bool) throw Error(FR_ERR_INVALID, "fr_dev_pack_mapped: every handle must be a boolean");
-            DevGate& g = rows[r];
-            std::memset(&g, 0, sizeof g);
-            if (h.b[0].slot >= 0) {
-                g.n_in = 1;
-                g.in_slot[0] = h.b[0].slot;
-                g.in_w[0] = 1;
-            } else {
-                g.offset = 2 * (h.b[0].triv & 1);
-            }
-        }
-        if (compact) {
-            std::vector<uint16_t> v(packed_compact_values(ctx->p, n));
-            dev.pack_mapped(rows.data(), n_rows, map, n, nullptr, v.data());
-            write_packed_compact(ctx->p, n, v.data(), buf);
-        } else {
-            std::vector<uint64_t> words(pk_row_words(ctx->p));
-            dev.pack_mapped(rows.data(), n_rows, map, n, words.data(), nullptr);
-            write_packed_result(ctx->p, n, words.data(), buf);
-        }
+        plain_needle(MATCH_NEEDLE_WINDOWS, wc.text.data(), wc.text.size(), scan_padded(wc.first.size()), m, start_lo,
+                     start_hi, masks, &wc.cls, starts_out, any);
     })
 }
 int fr_dev_select_sum(fr_ctx* ctx, const fr_needle* needle, const uint8_t* content, size_t len, const int32_t* terms,

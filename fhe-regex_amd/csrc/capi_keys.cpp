@@ -63,9 +63,7 @@ int fr_serialize_client_key(fr_ctx* ctx, uint8_t* buf, size_t cap, size_t* writt
         NEED(ctx && written);
         if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
         const std::vector<uint8_t> b = serialize_client_key(ctx->ck);
-        *written = b.size();
-        if (!buf) return FR_OK;  // size query
-        NEED(cap >= b.size());
+        if (answer_size(written, b.size(), buf, cap)) return FR_OK;
         std::memcpy(buf, b.data(), b.size());
     })
 }
@@ -176,9 +174,7 @@ int fr_export_server_key_compact(fr_ctx* ctx, uint8_t* buf, size_t cap, size_t* 
             throw Error(FR_ERR_INVALID, "the installed server key was not generated in compact form: its masks are "
                                         "not expandable from a mask key (fr_gen_server_key_compact)");
         const size_t need = compact_size(ctx->p);
-        *written = need;
-        if (!buf) return FR_OK;  // size query
-        NEED(cap >= need);
+        if (answer_size(written, need, buf, cap)) return FR_OK;
         if (ctx->sk_on_device) {
             std::vector<uint64_t> k(ctx->p.ksk_len()), b(ctx->p.bsk_len());
             ctx->device().download_server_key(k.data(), k.size(), b.data(), b.size());
@@ -291,9 +287,7 @@ int fr_export_packing_key(fr_ctx* ctx, uint8_t* buf, size_t cap, size_t* written
         NEED(ctx && written);
         if (!ctx->has_pk) throw Error(FR_ERR_INVALID, "no packing key (fr_gen_packing_key, fr_load_packing_key)");
         const size_t need = pk_blob_size(ctx->p);
-        *written = need;
-        if (!buf) return FR_OK;  // size query
-        NEED(cap >= need);
+        if (answer_size(written, need, buf, cap)) return FR_OK;
         write_pk_header(ctx->p, buf);
         // (a little-endian host: the rows are their wire form; PK_HEADER is a multiple of 8, but
         // buf may sit anywhere)
@@ -343,9 +337,7 @@ int fr_export_packing_key_compact(fr_ctx* ctx, uint8_t* buf, size_t cap, size_t*
             throw Error(FR_ERR_INVALID, "the installed packing key was not generated in compact form: its masks are "
                                         "not expandable from a mask key (fr_gen_packing_key_compact)");
         const size_t need = pk_compact_size(ctx->p);
-        *written = need;
-        if (!buf) return FR_OK;  // size query
-        NEED(cap >= need);
+        if (answer_size(written, need, buf, cap)) return FR_OK;
         write_pk_compact_header(ctx->p, ctx->pk_mask_key, buf);
         // the device gathers the planes from its resident rows: 5 of every 8 (k+1) bytes come back
         if (ctx->dev) ctx->dev->download_packing_key_compact(buf + PKC_HEADER);
@@ -454,9 +446,7 @@ static void encrypt_compact_with(fr_ctx* ctx, const std::vector<uint8_t>& msgs, 
                                  uint64_t first_block, uint8_t* buf, size_t cap, size_t* written) {
     check_content_range(first_block, msgs.size());
     const size_t need = content_blob_size(msgs.size());
-    *written = need;
-    if (!buf) return;  // size query
-    NEED(cap >= need);
+    if (answer_size(written, need, buf, cap)) return;
     ScopedKey key(key32);
     const std::vector<uint8_t> blob = encrypt_content_blob(ctx->p, ctx->ck, msgs.data(), msgs.size(), key.k, first_block);
     std::memcpy(buf, blob.data(), need);
@@ -533,9 +523,7 @@ int fr_encrypt_needle_keyed(fr_ctx* ctx, const uint16_t* masks, size_t m, const 
         if (ctx->p.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "private search: FFT ring only");
         if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
         const size_t need = needle_blob_size(ctx->p, m);
-        *written = need;
-        if (!buf) return FR_OK;  // size query
-        NEED(cap >= need);
+        if (answer_size(written, need, buf, cap)) return FR_OK;
         ScopedKey key(key32);
         const std::vector<uint8_t> blob = encrypt_needle_blob(ctx->p, ctx->ck, masks, m, key.k);
         std::memcpy(buf, blob.data(), need);
@@ -591,9 +579,7 @@ int fr_radix_serialize(fr_ctx* ctx, const uint64_t* blocks, size_t n_blocks, uin
         NEED(ctx && (blocks || !n_blocks) && written);
         const size_t L = (size_t)ctx->p.lwe_len();
         const size_t need = 8 + n_blocks * (8 * (L + 4));
-        *written = need;
-        if (!buf) return FR_OK;  // size query
-        NEED(cap >= need);
+        if (answer_size(written, need, buf, cap)) return FR_OK;
         uint8_t* o = buf;
         auto put = [&](uint64_t v) {
             std::memcpy(o, &v, 8);

@@ -1,5 +1,6 @@
 // C-ABI entries of the packed results (include/fheregex.h): the packing keyswitch of boolean
-// handles into one GLWE ciphertext under the client's key, its wire blob and its decryption.
+// handles into one GLWE ciphertext under the client's key, its wire blob and its decryption; the
+// one pack-to-blob step every reply goes through (pack_rows, pack_to_blob) and the mapped-pack hooks.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -8,39 +9,60 @@
 
 using namespace fr;
 
-static void need_packing_key(fr_ctx* ctx) {
-    if (!ctx->has_pk)
-        throw Error(FR_ERR_INVALID, "packing needs a packing key (fr_gen_packing_key, fr_load_packing_key)");
+// every handle is checked before anything runs; a boolean is one slot or a trivial value
+static std::vector<DevGate> bool_rows(fr_ctx* ctx, const fr_ct* bools, size_t n, const char* not_bool) {
+    std::vector<DevGate> rows(n);
+    for (size_t j = 0; j < n; ++j) rows[j] = bool_gate(ctx->get(bools[j]), not_bool);
+    return rows;
+}
+// the rows of fr_pack_bools' n handles, after its refusals
+static std::vector<DevGate> handle_rows(fr_ctx* ctx, const fr_ct* bools, size_t n) {
+    NEED(ctx && bools);
+    NEED(n >= 1 && n <= (size_t)ctx->p.N);
+    ctx->need_packing_key();
+    return bool_rows(ctx, bools, n, "fr_pack_bools: every handle must be a boolean");
+}
+// the packing key's rows on the host: a host-only context's own, else a copy for this call
+static const uint64_t* host_packing_key(fr_ctx* ctx, std::vector<uint64_t>& copy) {
+    if (!ctx->dev) return ctx->pksk.data();
+    copy.resize(pk_len(ctx->p));
+    ctx->dev->download_packing_key(copy.data());
+    return copy.data();
 }
 
-// the (k+1) N words of the handles' packed GLWE, or (compact) its blob's k N + n rounded values
-static void pack_handles(fr_ctx* ctx, const fr_ct* bools, size_t n, uint64_t* out, uint16_t* compact = nullptr) {
-    NEED(ctx && bools && (out || compact));
-    NEED(n >= 1 && n <= (size_t)ctx->p.N);
-    need_packing_key(ctx);
-    // every handle is checked before anything runs; a boolean is one slot or a trivial value
-    std::vector<DevGate> gates(n);
-    std::vector<int32_t> off(n), w(n, 0);
-    for (size_t j = 0; j < n; ++j) {
-        const HandleRec& h = ctx->get(bools[j]);
-        if (!h.is_bool) throw Error(FR_ERR_INVALID, "fr_pack_bools: every handle must be a boolean");
-        DevGate& g = gates[j];
-        std::memset(&g, 0, sizeof g);
-        if (h.b[0].slot >= 0) {
-            g.n_in = 1;
-            g.in_slot[0] = h.b[0].slot;
-            g.in_w[0] = 1;
-        } else {
-            g.offset = 2 * (h.b[0].triv & 1);  // units of Delta / 2
-        }
-        off[j] = g.offset;
-    }
-    if (ctx->dev && compact) return ctx->dev->pack_bools_compact(gates.data(), n, compact);
-    if (ctx->dev) return ctx->dev->pack_bools(gates.data(), n, out);
-    std::vector<uint64_t> words(compact ? pk_row_words(ctx->p) : 0);
-    if (compact) out = words.data();
-    pack_host(ctx->p, ctx->pksk.data(), nullptr, w.data(), off.data(), n, out);  // trivial handles only
-    for (size_t t = 0; compact && t < packed_compact_values(ctx->p, n); ++t) compact[t] = packed_round16(out[t]);
+void fr::pack_rows(fr_ctx* ctx, const DevGate* rows, size_t n_rows, const int32_t* map, size_t n, uint64_t* words,
+                   uint16_t* v) {
+    if (ctx->dev && map) return ctx->dev->pack_mapped(rows, n_rows, map, n, words, v);
+    if (ctx->dev && v) return ctx->dev->pack_bools_compact(rows, n, v);
+    if (ctx->dev) return ctx->dev->pack_bools(rows, n, words);
+    std::vector<int32_t> off(n), w(n, 0);  // trivial handles only: no row reads a slot
+    for (size_t j = 0; j < n; ++j) off[j] = rows[j].offset;
+    std::vector<uint64_t> full(v ? pk_row_words(ctx->p) : 0);
+    if (v) words = full.data();
+    pack_host(ctx->p, ctx->pksk.data(), nullptr, w.data(), off.data(), n, words);
+    for (size_t t = 0; v && t < packed_compact_values(ctx->p, n); ++t) v[t] = packed_round16(words[t]);
+}
+
+size_t fr::pack_to_blob(fr_ctx* ctx, const DevGate* rows, size_t n_rows, const int32_t* map, size_t n, bool compact,
+                        uint8_t* buf) {
+    std::vector<uint16_t> v(compact ? packed_compact_values(ctx->p, n) : 0);
+    std::vector<uint64_t> words(compact ? 0 : pk_row_words(ctx->p));
+    if (n_rows) pack_rows(ctx, rows, n_rows, map, n, compact ? nullptr : words.data(), compact ? v.data() : nullptr);
+    if (compact) write_packed_compact(ctx->p, n, v.data(), buf);
+    else write_packed_result(ctx->p, n, words.data(), buf);
+    return compact ? packed_compact_size(ctx->p, n) : packed_result_size(ctx->p);
+}
+
+// fr_pack_bools_blob and fr_pack_bools_compact
+static int pack_bools_to(fr_ctx* ctx, const fr_ct* bools, size_t n, bool compact, uint8_t* buf, size_t cap,
+                         size_t* written) {
+    FR_TRY({
+        NEED(ctx && written);
+        NEED(n >= 1 && n <= (size_t)ctx->p.N);
+        if (answer_size(written, compact ? packed_compact_size(ctx->p, n) : packed_result_size(ctx->p), buf, cap))
+            return FR_OK;
+        pack_to_blob(ctx, handle_rows(ctx, bools, n).data(), n, nullptr, n, compact, buf);
+    })
 }
 
 extern "C" {
@@ -54,21 +76,14 @@ int fr_packed_result_size(fr_ctx* ctx, size_t n, size_t* bytes) {
 }
 
 int fr_pack_bools(fr_ctx* ctx, const fr_ct* bools, size_t n, uint64_t* out_words) {
-    FR_TRY(pack_handles(ctx, bools, n, out_words))
+    FR_TRY({
+        NEED(out_words);
+        pack_rows(ctx, handle_rows(ctx, bools, n).data(), n, nullptr, n, out_words, nullptr);
+    })
 }
 
 int fr_pack_bools_blob(fr_ctx* ctx, const fr_ct* bools, size_t n, uint8_t* buf, size_t cap, size_t* written) {
-    FR_TRY({
-        NEED(ctx && written);
-        NEED(n >= 1 && n <= (size_t)ctx->p.N);
-        const size_t need = packed_result_size(ctx->p);
-        *written = need;
-        if (!buf) return FR_OK;  // size query
-        NEED(cap >= need);
-        std::vector<uint64_t> words(pk_row_words(ctx->p));
-        pack_handles(ctx, bools, n, words.data());
-        write_packed_result(ctx->p, n, words.data(), buf);
-    })
+    return pack_bools_to(ctx, bools, n, false, buf, cap, written);
 }
 
 int fr_packed_compact_size(fr_ctx* ctx, size_t n, size_t* bytes) {
@@ -80,17 +95,7 @@ int fr_packed_compact_size(fr_ctx* ctx, size_t n, size_t* bytes) {
 }
 
 int fr_pack_bools_compact(fr_ctx* ctx, const fr_ct* bools, size_t n, uint8_t* buf, size_t cap, size_t* written) {
-    FR_TRY({
-        NEED(ctx && written);
-        NEED(n >= 1 && n <= (size_t)ctx->p.N);
-        const size_t need = packed_compact_size(ctx->p, n);
-        *written = need;
-        if (!buf) return FR_OK;  // size query
-        NEED(cap >= need);
-        std::vector<uint16_t> v(packed_compact_values(ctx->p, n));
-        pack_handles(ctx, bools, n, nullptr, v.data());
-        write_packed_compact(ctx->p, n, v.data(), buf);
-    })
+    return pack_bools_to(ctx, bools, n, true, buf, cap, written);
 }
 
 int fr_compress_packed(fr_ctx* ctx, const uint64_t* words, size_t n, uint8_t* buf, size_t cap, size_t* written) {
@@ -137,14 +142,37 @@ int fr_pack_lwes(fr_ctx* ctx, const uint64_t* lwes, const int32_t* w, const int3
         NEED(n >= 1 && n <= (size_t)ctx->p.N);
         if (!lwes)
             for (size_t j = 0; j < n; ++j) NEED(w[j] == 0);
-        need_packing_key(ctx);
-        if (ctx->dev) {  // the rows live on the device: a host copy for this call
-            std::vector<uint64_t> rows(pk_len(ctx->p));
-            ctx->dev->download_packing_key(rows.data());
-            pack_host(ctx->p, rows.data(), lwes, w, off, n, out_words);
-        } else {
-            pack_host(ctx->p, ctx->pksk.data(), lwes, w, off, n, out_words);
-        }
+        ctx->need_packing_key();
+        std::vector<uint64_t> copy;
+        pack_host(ctx->p, host_packing_key(ctx, copy), lwes, w, off, n, out_words);
+    })
+}
+
+int fr_pack_lwes_mapped(fr_ctx* ctx, const uint64_t* lwes, const int32_t* w, const int32_t* off, size_t n_rows,
+                        const int32_t* map, size_t n, uint64_t* out_words) {
+    FR_TRY({
+        NEED(ctx && out_words && map && (lwes || w));
+        if (!lwes)
+            for (size_t r = 0; r < n_rows; ++r) NEED(w[r] == 0);
+        ctx->need_packing_key();
+        check_pack_map(map, n, n_rows, (size_t)ctx->p.N);
+        std::vector<uint64_t> copy;
+        pack_host_mapped(ctx->p, host_packing_key(ctx, copy), lwes, w, off, n_rows, map, n, out_words);
+    })
+}
+
+int fr_dev_pack_mapped(fr_ctx* ctx, const fr_ct* bools, size_t n_rows, const int32_t* map, size_t n, int32_t compact,
+                       uint8_t* buf, size_t cap, size_t* written) {
+    FR_TRY({
+        NEED(ctx && bools && map && written && (compact == 0 || compact == 1));
+        NEED(n >= 1 && n <= (size_t)ctx->p.N);
+        ctx->device();
+        if (answer_size(written, compact ? packed_compact_size(ctx->p, n) : packed_result_size(ctx->p), buf, cap))
+            return FR_OK;
+        check_pack_map(map, n, n_rows, (size_t)ctx->p.N);  // (before bools is read: n_rows of them)
+        const std::vector<DevGate> rows =
+            bool_rows(ctx, bools, n_rows, "fr_dev_pack_mapped: every handle must be a boolean");
+        pack_to_blob(ctx, rows.data(), n_rows, map, n, compact != 0, buf);
     })
 }
 
@@ -180,7 +208,7 @@ int fr_decrypt_packed(fr_ctx* ctx, const uint8_t* blob, size_t len, uint8_t* bit
 int fr_dev_packing_limb_column(fr_ctx* ctx, int32_t col, uint64_t* out) {
     FR_TRY({
         NEED(ctx && out);
-        need_packing_key(ctx);
+        ctx->need_packing_key();
         ctx->device().packing_limb_column(col, out);
     })
 }

@@ -105,6 +105,11 @@ struct fr_ctx {
         if (!has_sk || !d.has_keys()) throw fr::Error(FR_ERR_NO_KEY, "server key not generated");
         return d;
     }
+    // every pack refuses here, before anything is launched
+    void need_packing_key() const {
+        if (!has_pk)
+            throw fr::Error(FR_ERR_INVALID, "packing needs a packing key (fr_gen_packing_key, fr_load_packing_key)");
+    }
     fr_ct new_handle(const fr::HandleRec& r) {
         uint32_t h;
         if (!free_handles.empty()) {
@@ -157,6 +162,27 @@ struct fr_ctx {
     }
 };
 
+namespace fr {
+
+// the pack row of a boolean handle: its slot, or its trivial value; `not_bool` is the caller's
+// refusal of any other handle
+inline DevGate bool_gate(const HandleRec& h, const char* not_bool) {
+    if (!h.is_bool) throw Error(FR_ERR_INVALID, not_bool);
+    return affine_gate(h.b[0].slot, 1, h.b[0].slot >= 0 ? 0 : h.b[0].triv & 1);
+}
+// n results packed under the packing key on the current lane (capi_pack.cpp): result j is
+// rows[map[j]] (-1: the constant 0), or rows[j] without a map (n_rows == n) -- the (k+1) N words
+// of the packed GLWE, or (v) the compact blob's rounded values.  A host-only context packs
+// trivial rows, unmapped.
+void pack_rows(fr_ctx* ctx, const DevGate* rows, size_t n_rows, const int32_t* map, size_t n, uint64_t* words,
+               uint16_t* v);
+// the same as the wire blob at buf (compact: FRCPRES1, else FRPKRES1); returns its bytes.  No row
+// at all is the packing of n constants 0: all-zero words, nothing launched.
+size_t pack_to_blob(fr_ctx* ctx, const DevGate* rows, size_t n_rows, const int32_t* map, size_t n, bool compact,
+                    uint8_t* buf);
+
+}  // namespace fr
+
 // a needle uploaded to a device context (private search): its selectors and the (k, N) they are for
 struct fr_needle {
     fr::DevNeedle dev;
@@ -185,3 +211,12 @@ struct fr_needle {
     do {                                                                      \
         if (!(x)) throw fr::Error(FR_ERR_INVALID, "invalid argument: " #x);   \
     } while (0)
+
+// The size query of an entry that writes `need` bytes: *written = need either way; true if the
+// call only asked (no buffer) and is done, else the buffer holds them.
+inline bool answer_size(size_t* written, size_t need, const void* buf, size_t cap) {
+    *written = need;
+    if (!buf) return true;
+    NEED(cap >= need);
+    return false;
+}

@@ -5,6 +5,7 @@
 // themselves in reverse order of declaration.
 #pragma once
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "common.h"
@@ -36,6 +37,19 @@ struct DevGate {
     uint8_t lut[MAX_OUT][16];
 };
 static_assert(sizeof(DevGate) == 304, "DevGate layout");
+// the input side of the affine value cst + w * arena[slot] (cst in units of Delta; slot < 0: the
+// constant alone), what a pack row or a linear op reads; outputs and LUTs are left zero
+inline DevGate affine_gate(int slot, int w, int cst) {
+    DevGate g;
+    std::memset(&g, 0, sizeof g);
+    g.offset = 2 * cst;
+    if (slot >= 0) {
+        g.n_in = 1;
+        g.in_slot[0] = slot;
+        g.in_w[0] = w;
+    }
+    return g;
+}
 // a selector job's index: the first four bytes of lut[0], little endian
 constexpr int MAX_SELECTORS = 2 * (int)NEEDLE_MAX_CHARS;
 FR_HD uint32_t acc_selector(const DevGate& g) {

@@ -815,6 +815,14 @@ Program compile_needle_windows(size_t n_windows, size_t m, bool starts) {
     if (n_windows > ((size_t)1 << 24) / m) throw Error(FR_ERR_INVALID, "scan: more than 2^24 window bytes");
     return compile_needle_over(n_windows * m, m, 0, n_windows, starts, true, m);
 }
+Program needle_program(MatchKind kind, size_t n, size_t m, size_t lo, size_t hi, bool starts) {
+    switch (kind) {
+        case MATCH_NEEDLE: return compile_needle(n, m, lo, hi, starts);
+        case MATCH_NEEDLE_CLEAR: return compile_needle_clear(n, m, lo, hi, starts);
+        case MATCH_NEEDLE_WINDOWS: return compile_needle_windows(n, m, starts);
+        default: throw Error(FR_ERR_INVALID, "a pattern match has no needle program");
+    }
+}
 
 void pad_window_text(WindowClasses& wc, size_t m) {
     if (wc.first.empty()) return;

@@ -169,6 +169,10 @@ void pad_window_text(WindowClasses& wc, size_t m);
 // that all fit.  m = 1 is compile_needle_clear(n_windows, 1, 0, n_windows, starts) gate for gate.
 // The program depends on (n_windows, m, starts) alone.  n_windows m <= 2^24.
 Program compile_needle_windows(size_t n_windows, size_t m, bool starts);
+// What a match is over (match.cpp: the request), and the one place that maps a needle kind to its
+// compile function above; windows: n its windows, [lo, hi) not used.
+enum MatchKind : int { MATCH_PATTERN, MATCH_NEEDLE, MATCH_NEEDLE_CLEAR, MATCH_NEEDLE_WINDOWS };
+Program needle_program(MatchKind kind, size_t n, size_t m, size_t lo, size_t hi, bool starts);
 
 // LUT builders
 void lut_eq(uint8_t* lut, int v);     // [x == v]

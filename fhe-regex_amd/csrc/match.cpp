@@ -1,12 +1,59 @@
-// The match engine behind the C ABI: the plan cache, has_match and its batch / range /
-// parts forms, the level-sharded match and the host-only schedule.
+// The match engine behind the C ABI: one request through three stages (the plan, by way of the
+// plan cache; the launch; the reply) for has_match and its batch / range / parts / starts forms and
+// the private searches, then the level-sharded match and the host-only schedule.
 #include <climits>
+#include <variant>
 
 #include "ctx.h"
 
 using namespace fr;
 
 namespace {
+
+// ------------------------------------------------------------ the request
+// One match as the engine sees it: what is matched and where the result goes.  Every entry of
+// fr_has_match*, fr_match_starts*, fr_find*, fr_find_clear* and fr_scan_clear* fills one and
+// makes one call (run_match); validate states which combinations are legal.
+// Handles: outs[m * P + j] for the P outputs of match m, P into *n_parts if asked for.
+struct ToHandles {
+    fr_ct* outs;
+    size_t* n_parts;
+};
+// One packed blob of the starts (compact: FRCPRES1, else FRPKRES1), with no handle in between:
+// packed_compact_size / packed_result_size bytes at buf.
+struct ToBlob {
+    bool compact;
+    uint8_t* buf;
+};
+// A scan's reply: the plan's outputs are window classes and start j of the call's n_starts reads
+// output cls[j] (-1: the constant 0); buf receives one blob per chunk of N starts, back to back
+// (scan_reply_size bytes).
+struct ToScanBlobs {
+    bool compact;
+    uint8_t* buf;
+    const int32_t* cls;
+    size_t n_starts;
+};
+using Sink = std::variant<ToHandles, ToBlob, ToScanBlobs>;
+struct MatchRequest {
+    // pattern: `pattern` over content handles.  The needle kinds (fr_find*: no pattern) match the
+    // needle's encrypted tables, bound to the match's lane around its launches: over content
+    // handles (compile_needle), over the n clear bytes at `text` (compile_needle_clear), or over a
+    // clear text compacted to its n distinct windows, padded (compile_needle_windows over [0, n)).
+    MatchKind kind = MATCH_PATTERN;
+    bool starts = false;  // one boolean per start offset of [lo, hi) instead of their OR
+    const char* pattern = "";
+    // M independent matches over M contents of n positions each, content[m * n + q], in one plan;
+    // parts > 1: each match returns up to `parts` booleans whose OR is its result
+    const fr_ct* content = nullptr;
+    size_t n = 0, M = 1, lo = 0, hi = 0, parts = 1;
+    const fr_needle* needle = nullptr;
+    const uint8_t* text = nullptr;  // clear kinds: the bytes the extract-sums read,
+    size_t text_n = 0;              // and how many (a find: n; a scan: n windows of m bytes)
+    Sink sink = ToHandles{nullptr, nullptr};
+
+    bool clear() const { return kind == MATCH_NEEDLE_CLEAR || kind == MATCH_NEEDLE_WINDOWS; }
+};
 
 // ------------------------------------------------------------ plan cache
 // The circuit of a match is data-oblivious: it depends on (pattern, grammar,
@@ -32,13 +79,14 @@ namespace {
 // content's bytes either; the field keeps it apart from fr_find's plan for the same (m, n).  A
 // scan (fr_scan_clear*) is the field's third value with n its padded class count, so its plan is
 // never fr_find_clear's for the same numbers.
-std::string match_key(fr_ctx* ctx, const char* pattern, size_t n, size_t M, size_t lo, size_t hi, size_t parts,
-                      int lane, bool starts, size_t needle_m, int clear) {
+std::string match_key(const fr_ctx* ctx, const MatchRequest& rq, int lane) {
+    const size_t needle_m = rq.needle ? rq.needle->dev.m : 0;
+    const size_t clear = rq.kind == MATCH_NEEDLE_CLEAR ? 1 : rq.kind == MATCH_NEEDLE_WINDOWS ? 2 : 0;
     std::string k;
-    for (size_t v : {(size_t)ctx->grammar, (size_t)ctx->engine, (size_t)ctx->lowering, (size_t)ctx->multi_value, n, M,
-                     lo, hi, parts, (size_t)lane, (size_t)starts, needle_m, (size_t)clear})
+    for (size_t v : {(size_t)ctx->grammar, (size_t)ctx->engine, (size_t)ctx->lowering, (size_t)ctx->multi_value, rq.n,
+                     rq.M, rq.lo, rq.hi, rq.parts, (size_t)lane, (size_t)rq.starts, needle_m, clear})
         k += std::to_string(v) + "|";
-    k += pattern;
+    k += rq.pattern;
     return k;
 }
 // Canonical shape of the content: per position and block, the trivial value
@@ -130,24 +178,6 @@ void fill_stats(fr_match_stats& s, const Recorded& rec, const Plan& P) {
     add_plan_stats(P, &s);
 }
 
-// M independent matches of one pattern over M contents of n positions each
-// (content[m * n + q]): one plan whose program is M copies of the match's lowered
-// program, so every level of the M matches shares its launches (M = 1: has_match).
-// parts > 1 (fr_has_match_parts): each match returns up to `parts` booleans whose OR is
-// its result, outs[m * P + j] with P = *n_parts (the same for every m).
-// starts (fr_match_starts, M = 1): the program is compile_match_starts', its hi - lo outputs
-// one boolean per start offset.
-// reply (fr_match_starts_packed; starts, M = 1): no handles -- the outputs go straight into one
-// packing keyswitch on the match's own lane, and reply->buf receives the blob (`outs` unused).
-struct PackedReply {
-    bool compact;  // FRCPRES1, else FRPKRES1
-    uint8_t* buf;  // packed_compact_size / packed_result_size bytes
-    // a scan (fr_scan_clear_starts): the plan's outputs are window classes and start j of the
-    // call's n_starts reads output cls[j] (-1: the constant 0); buf receives one blob per chunk
-    // of N starts, back to back (scan_reply_size bytes); no start: no chunk, cls may be null
-    const int32_t* cls = nullptr;
-    size_t n_starts = 0;
-};
 // the bytes of a scan's reply over n_starts starts
 size_t scan_reply_size(const Params& p, size_t n_starts, bool compact) {
     size_t need = 0;
@@ -155,14 +185,6 @@ size_t scan_reply_size(const Params& p, size_t n_starts, bool compact) {
         need += compact ? packed_compact_size(p, std::min((size_t)p.N, n_starts - j0)) : packed_result_size(p);
     return need;
 }
-// The private-search arguments of a match (fr_find*, fr_find_clear*, fr_scan_clear*).
-enum ClearKind : int { CLEAR_NONE = 0, CLEAR_FIND = 1, CLEAR_SCAN = 2 };
-struct Search {
-    const fr_needle* needle = nullptr;
-    ClearKind clear = CLEAR_NONE;
-    const uint8_t* text = nullptr;  // clear: the bytes the extract-sums read,
-    size_t text_n = 0;              // and how many (a find: n; a scan: n windows of m bytes)
-};
 // refused before anything is planned or launched
 void check_needle(fr_ctx* ctx, Device& dev, const fr_needle* needle) {
     if (ctx->p.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "private search: FFT ring only");
@@ -170,243 +192,283 @@ void check_needle(fr_ctx* ctx, Device& dev, const fr_needle* needle) {
         throw Error(FR_ERR_INVALID, "needle: k, N do not match the context params");
     if (needle->dev.dev != &dev || !needle->dev.words) throw Error(FR_ERR_INVALID, "needle: uploaded to another context");
 }
-// needle (fr_find, fr_find_starts; M = 1, no pattern): the program is compile_needle's, its
-// selector jobs read the needle's table, bound to the match's lane around its launches.
-// clear (fr_find_clear, fr_find_clear_starts; with a needle): the content is the n bytes at `text`
-// and there are no content handles; the program is compile_needle_clear's, its extract-sums read
-// the needle's table and the bytes, both bound to the match's lane around its launches.
-// scan (fr_scan_clear, fr_scan_clear_starts): clear content compacted to its n distinct windows
-// (padded); the program is compile_needle_windows' over [0, n), and a packed reply reads it
-// through the starts' classes (PackedReply::cls).
-void match_impl(fr_ctx* ctx, const fr_ct* content, size_t n, size_t M, const char* pattern, size_t lo, size_t hi,
-                fr_ct* outs, fr_match_stats* st, size_t parts = 1, size_t* n_parts = nullptr, bool starts = false,
-                const PackedReply* reply = nullptr, const Search& search = {}) {
-    double t0 = now_ms();
-    pattern = pattern ? pattern : "";
-    Device& dev = ctx->keyed_device();
-    if (M == 0) throw Error(FR_ERR_INVALID, "no matches");
-    const fr_needle* needle = search.needle;
-    const ClearKind clear = search.clear;
-    if (needle) check_needle(ctx, dev, needle);
-    const size_t needle_m = needle ? needle->dev.m : 0;
-    if (clear && (!needle || M != 1 || content)) throw Error(FR_ERR_INVALID, "clear content: one needle, no handles");
-    const size_t n_handles = clear ? 0 : n * M;
+
+// Every legality rule of a request, before anything is planned or launched.
+void validate(const MatchRequest& rq) {
+    if (rq.M == 0) throw Error(FR_ERR_INVALID, "no matches");
+    if ((rq.kind != MATCH_PATTERN) != (rq.needle != nullptr))
+        throw Error(FR_ERR_INVALID, "a needle kind has a needle, a pattern none");
+    if (rq.clear() && (rq.M != 1 || rq.content)) throw Error(FR_ERR_INVALID, "clear content: one needle, no handles");
+    if (!std::holds_alternative<ToHandles>(rq.sink) && (!rq.starts || rq.M != 1))
+        throw Error(FR_ERR_INVALID, "a packed reply holds the starts of one match");
+    if (std::holds_alternative<ToScanBlobs>(rq.sink) && rq.kind != MATCH_NEEDLE_WINDOWS)
+        throw Error(FR_ERR_INVALID, "chunked blobs are a scan's reply");
+}
+
+// ------------------------------------------------------------ stage 1: the plan
+// The one place that maps a request to its compile function: the lowered program of one match
+// and the recording's counters (a needle search records nothing).
+struct Compiled {
+    Program prog;
+    Recorded rec;
+};
+Compiled program_for(const fr_ctx* ctx, const MatchRequest& rq) {
+    if (rq.kind != MATCH_PATTERN)
+        return {needle_program(rq.kind, rq.n, rq.needle->dev.m, rq.lo, rq.hi, rq.starts), Recorded{}};
+    if (rq.starts) {
+        CompiledStarts cs = compile_match_starts(match_spec(ctx, rq.pattern, rq.n, rq.lo, rq.hi));
+        return {std::move(cs.prog), cs.rec};
+    }
+    CompiledMatch cm = compile_match(match_spec(ctx, rq.pattern, rq.n, rq.lo, rq.hi, rq.parts));
+    return {std::move(cm.prog), cm.rec};
+}
+
+// M copies of one match's gates, so every level of the M matches shares its launches: gate g of
+// match m is m * G + g, content block cb of match m is 4 n m + cb
+std::vector<PGate> fold_gates(const std::vector<PGate>& one, size_t n, size_t M) {
+    const size_t G = one.size();
+    std::vector<PGate> gates;
+    gates.reserve(G * M);
+    for (size_t m = 0; m < M; ++m)
+        for (const PGate& g0 : one) {
+            PGate g = g0;
+            for (auto& in : g.ins) in.src = in.src >= 0 ? in.src + (int)(m * G) : in.src - (int)(4 * n * m);
+            gates.push_back(std::move(g));
+        }
+    return gates;
+}
+
+// What a request runs: c holds the plan, one match's outputs and gate count and the recording's
+// counters.  It is the cache's entry (a hit, or this call's plan once kept) or, for a plan that
+// runs uncached, the call's own.
+struct PlanView {
+    CachedMatch* c = nullptr;
+    std::unique_ptr<CachedMatch> own;
+    bool hit = false;
+    int lane = 0;           // the lane a cached plan runs on
+    std::vector<int> cmap;  // the call's content map, for a cached plan's references
+};
+PlanView acquire_plan(fr_ctx* ctx, Device& dev, const MatchRequest& rq) {
     fr_plan_cache& pc = ctx->plans;
-    CachedMatch* hit = nullptr;
-    std::string key;
-    std::vector<int32_t> sig;
-    std::vector<int> cmap;
+    PlanView v;
+    const size_t n_handles = rq.clear() ? 0 : rq.n * rq.M;
     // lanes (fr_set_lanes): an asynchronous match of a cacheable plan runs on the next lane,
     // with a plan of its own (its intermediate slots), so consecutive matches overlap
-    const int lane =
+    v.lane =
         (ctx->async_match && dev.match_lanes() > 0 && pc.capacity) ? 1 + (int)(ctx->next_lane++ % dev.match_lanes()) : 0;
-    struct LaneScope {  // left on every exit, exceptions included
-        Device& d;
-        bool in = false;
-        void enter(int i) {
-            if (i > 0) d.enter_lane(i), in = true;
-        }
-        ~LaneScope() {
-            if (in) d.leave_lane();
-        }
-    } lane_scope{dev};
+    std::string key;
+    std::vector<int32_t> sig;
     if (pc.capacity) {
-        key = match_key(ctx, pattern, n, M, lo, hi, parts, lane, starts, needle_m, clear);
-        sig = content_signature(ctx, content, n_handles, &cmap);
+        key = match_key(ctx, rq, v.lane);
+        sig = content_signature(ctx, rq.content, n_handles, &v.cmap);
         for (auto& e : pc.entries)
-            if (e->parts == parts && e->lane == lane && e->key == key && e->sig == sig) hit = e.get();
+            if (e->parts == rq.parts && e->lane == v.lane && e->key == key && e->sig == sig) v.c = e.get();
     }
-    DeviceTimers before = dev.timers();
-    // 1. the plan and one match's outputs: the cached entry `c` (a hit, or this call's plan
-    // once kept), else the uncached plan `fresh` with the outputs of `prog`
-    CachedMatch* c = hit;
-    Recorded rec;
-    Program prog;
-    Plan fresh;
-    if (hit) {
+    if (v.c) {
+        v.hit = true;
         ++pc.hits;
-        hit->last_use = ++pc.clock;
-        rec = hit->rec;
-    } else {
-        ++pc.misses;
-        if (clear == CLEAR_SCAN) {
-            prog = compile_needle_windows(n, needle_m, starts);
-        } else if (clear) {
-            prog = compile_needle_clear(n, needle_m, lo, hi, starts);
-        } else if (needle) {
-            prog = compile_needle(n, needle_m, lo, hi, starts);
-        } else if (starts) {
-            CompiledStarts cs = compile_match_starts(match_spec(ctx, pattern, n, lo, hi));
-            rec = cs.rec;
-            prog = std::move(cs.prog);
-        } else {
-            CompiledMatch cm = compile_match(match_spec(ctx, pattern, n, lo, hi, parts));
-            rec = cm.rec;
-            prog = std::move(cm.prog);
-        }
-        if (!clear) check_content(ctx, prog, content, n, M);
-        // M copies: gate g of match m is m * G + g, content block cb of match m is 4 n m + cb
-        const size_t G = prog.gates.size();
-        std::vector<PGate> gates;
-        gates.reserve(G * M);
-        for (size_t m = 0; m < M; ++m)
-            for (const PGate& g0 : prog.gates) {
-                PGate g = g0;
-                for (auto& in : g.ins) in.src = in.src >= 0 ? in.src + (int)(m * G) : in.src - (int)(4 * n * m);
-                gates.push_back(std::move(g));
-            }
-        std::vector<fr_ct> inputs(content, content + n_handles);
-        const bool keep = pc.capacity && G && G * M <= pc.slot_cap;
-        if (keep) evict_for(ctx, 1, G * M);  // before the new plan allocates its slots
-        fresh = compile_plan(ctx, gates, inputs, keep, search.text_n);
-        if (keep) {
-            // keep the plan: its slots stay allocated, its batches go to the device once; the
-            // entry is complete before the cache sees it
-            auto e = std::make_unique<CachedMatch>();
-            e->key = std::move(key);
-            e->parts = parts;
-            e->lane = lane;
-            e->sig = std::move(sig);
-            e->n_gates = G;
-            e->outs = prog.outs;
-            e->rec = rec;
-            e->last_use = ++pc.clock;
-            e->plan = std::move(fresh);
-            e->plan.d_gates = dev.upload_gates(e->plan.gates.data(), e->plan.gates.size(), e->plan.n_refs);
-            if (!e->plan.sums.empty()) e->plan.d_sums = dev.upload_sums(e->plan.sums.data(), e->plan.sums.size());
-            c = e.get();
-            pc.entries.push_back(std::move(e));
-            pc.slots_held += c->plan.slot.size();
-        }
+        v.c->last_use = ++pc.clock;
+        return v;
     }
-    // 2. launch and emit
-    Plan& plan = c ? c->plan : fresh;
-    const std::vector<ProgOut>& po = c ? c->outs : prog.outs;
-    const size_t G = c ? c->n_gates : prog.gates.size(), nO = po.size();
-    if (c) {
-        lane_scope.enter(lane);
-        dev.bind_content(cmap.data(), cmap.size());
+    ++pc.misses;  // (counted even if the request then fails to compile)
+    Compiled cp = program_for(ctx, rq);
+    if (!rq.clear()) check_content(ctx, cp.prog, rq.content, rq.n, rq.M);
+    const size_t G = cp.prog.gates.size();
+    const std::vector<PGate> gates = fold_gates(cp.prog.gates, rq.n, rq.M);
+    const bool keep = pc.capacity && G && G * rq.M <= pc.slot_cap;
+    if (keep) evict_for(ctx, 1, G * rq.M);  // before the new plan allocates its slots
+    auto e = std::make_unique<CachedMatch>();
+    e->plan = compile_plan(ctx, gates, std::vector<fr_ct>(rq.content, rq.content + n_handles), keep, rq.text_n);
+    e->key = std::move(key);
+    e->parts = rq.parts;
+    e->lane = v.lane;
+    e->sig = std::move(sig);
+    e->n_gates = G;
+    e->outs = std::move(cp.prog.outs);
+    e->rec = cp.rec;
+    v.c = e.get();
+    if (!keep) {
+        v.own = std::move(e);
+        return v;
     }
-    double t1 = now_ms();
-    struct SelectorScope {  // the needle's table (and clear content), for this match's launches on this lane only
-        Device& d;
-        bool on, text;
-        ~SelectorScope() {
-            if (on) d.bind_selectors(nullptr, 0);
-            try {
-                if (text) d.bind_text(nullptr, 0);
-            } catch (...) {
-            }
-        }
-    } selector_scope{dev, needle != nullptr, clear != CLEAR_NONE};
-    if (needle) dev.bind_selectors(needle->dev.words.get(), 2 * needle_m);
-    // the call's bytes, copied now and in stream order on this lane: the caller's buffer may go
-    if (clear) dev.bind_text(search.text, search.text_n);
-    launch_plan(dev, plan);
-    if (hit && !starts && (nO < 1 || nO > parts))  // the caller's out buffer holds M * parts handles
-        throw Error(FR_ERR_INVALID, "cached plan has more outputs than the caller's parts");
-    if (reply) {
-        // Each output o.cst + o.w * gate is an affine descriptor over the plan's own gate slot (a
-        // constant start: no input), so no handle, no arena slot and no k_linear launch stands
-        // between the plan and the pack.  Still inside the lane scope: the pack follows the plan's
-        // launches on this lane's stream, uses this lane's scratch and waits for this stream only.
-        if (nO != hi - lo) throw Error(FR_ERR_INVALID, "cached plan's outputs are not the call's starts");
-        std::vector<DevGate> desc(nO);
-        for (size_t j = 0; j < nO; ++j) {
-            const ProgOut& o = po[j];
-            DevGate& g = desc[j];
-            std::memset(&g, 0, sizeof g);
-            g.offset = 2 * o.cst;  // units of Delta / 2
-            if (o.gate >= 0) {
-                g.n_in = 1;
-                g.in_slot[0] = plan.slot[o.gate];
-                g.in_w[0] = o.w;
-            }
-        }
-        if (clear == CLEAR_SCAN) {  // (no start at all: cls may be null, and no chunk is written)
-            // A scan: per chunk of N starts, the rows are the classes that occur in it (in order of
-            // first occurrence) and the map sends each start to its row; one mapped pack per chunk.
-            const size_t N = (size_t)ctx->p.N;
-            std::vector<int32_t> row_of(nO, -1), map;
-            std::vector<DevGate> rows;
-            std::vector<uint16_t> v;
-            std::vector<uint64_t> words;
-            uint8_t* at = reply->buf;
-            for (size_t j0 = 0; j0 < reply->n_starts; j0 += N) {
-                const size_t nc = std::min(N, reply->n_starts - j0);
-                rows.clear();
-                map.assign(nc, -1);
-                for (size_t j = 0; j < nc; ++j) {
-                    const int32_t d = reply->cls[j0 + j];
-                    if (d < 0) continue;
-                    if ((size_t)d >= nO) throw Error(FR_ERR_INVALID, "scan: a class past the plan's outputs");
-                    if (row_of[(size_t)d] < 0) {
-                        row_of[(size_t)d] = (int32_t)rows.size();
-                        rows.push_back(desc[(size_t)d]);
-                    }
-                    map[j] = row_of[(size_t)d];
-                }
-                for (size_t j = 0; j < nc; ++j)  // (the next chunk numbers its rows anew)
-                    if (reply->cls[j0 + j] >= 0) row_of[(size_t)reply->cls[j0 + j]] = -1;
-                // a chunk with no fitting start is the packing of nc constants 0: all zero words
-                if (reply->compact) {
-                    v.assign(packed_compact_values(ctx->p, nc), 0);
-                    if (!rows.empty()) dev.pack_mapped(rows.data(), rows.size(), map.data(), nc, nullptr, v.data());
-                    write_packed_compact(ctx->p, nc, v.data(), at);
-                    at += packed_compact_size(ctx->p, nc);
-                } else {
-                    words.assign(pk_row_words(ctx->p), 0);
-                    if (!rows.empty()) dev.pack_mapped(rows.data(), rows.size(), map.data(), nc, words.data(), nullptr);
-                    write_packed_result(ctx->p, nc, words.data(), at);
-                    at += packed_result_size(ctx->p);
-                }
-            }
-        } else if (reply->compact) {
-            std::vector<uint16_t> v(packed_compact_values(ctx->p, nO));
-            dev.pack_bools_compact(desc.data(), nO, v.data());
-            write_packed_compact(ctx->p, nO, v.data(), reply->buf);
-        } else {
-            std::vector<uint64_t> words(pk_row_words(ctx->p));
-            dev.pack_bools(desc.data(), nO, words.data());
-            write_packed_result(ctx->p, nO, words.data(), reply->buf);
-        }
-    } else {
-        // an uncached plan's one output takes its gate's slot; parts get copies (two parts may read one gate)
-        const bool take = !c && nO == 1;
-        size_t made = 0;  // handles written so far, released if a later one fails: the caller gets a code only
+    // keep the plan: its slots stay allocated, its batches go to the device once; the entry is
+    // complete before the cache sees it
+    e->last_use = ++pc.clock;
+    e->plan.d_gates = dev.upload_gates(e->plan.gates.data(), e->plan.gates.size(), e->plan.n_refs);
+    if (!e->plan.sums.empty()) e->plan.d_sums = dev.upload_sums(e->plan.sums.data(), e->plan.sums.size());
+    pc.entries.push_back(std::move(e));
+    pc.slots_held += v.c->plan.slot.size();
+    return v;
+}
+
+// ------------------------------------------------------------ stage 2: the launch
+// This match's lane, content map, selector table and text: bound in that order around its
+// launches and its emit, and let go on every exit, exceptions included.
+struct Bound {
+    Device& d;
+    bool lane = false, selectors = false, text = false;
+    // a cached plan runs on its lane, its content references bound to the call's slots
+    void plan(const PlanView& v) {
+        if (v.own) return;
+        if (v.lane > 0) d.enter_lane(v.lane), lane = true;
+        d.bind_content(v.cmap.data(), v.cmap.size());
+    }
+    // the needle's table and the clear content, for this match's launches on this lane only
+    void search(const MatchRequest& rq) {
+        selectors = rq.needle != nullptr, text = rq.clear();
+        if (selectors) d.bind_selectors(rq.needle->dev.words.get(), 2 * rq.needle->dev.m);
+        // the call's bytes, copied now and in stream order on this lane: the caller's buffer may go
+        if (text) d.bind_text(rq.text, rq.text_n);
+    }
+    ~Bound() {
+        if (selectors) d.bind_selectors(nullptr, 0);
         try {
-            for (size_t m = 0; m < M; ++m)
-                for (size_t j = 0; j < nO; ++j, ++made) {
-                    ProgOut o = po[j];
-                    if (o.gate >= 0) o.gate += (int)(m * G);
-                    outs[m * nO + j] = make_output(ctx, o, plan.slot, take);
-                }
+            if (text) d.bind_text(nullptr, 0);
         } catch (...) {
-            while (made) ctx->release(outs[--made]);
-            throw;
         }
+        if (lane) d.leave_lane();
     }
-    if (n_parts) *n_parts = nO;
-    if (!c) fresh.slot.reset();  // later users of these slots are ordered after the launches (one stream)
+};
+// enqueues the plan, bound to its match; returns when the call's host part ended (the plan bound)
+double launch(Bound& bound, const PlanView& v, const MatchRequest& rq) {
+    bound.plan(v);
+    const double t1 = now_ms();
+    bound.search(rq);
+    launch_plan(bound.d, v.c->plan);
+    return t1;
+}
+
+// ------------------------------------------------------------ stage 3: the reply
+// All three run inside the launch's scope: a pack follows the plan's launches on this lane's
+// stream, uses this lane's scratch and waits for this stream only.
+
+// handles: outs[m * P + j] for the P outputs of each of the M matches
+void emit(fr_ctx* ctx, PlanView& v, const MatchRequest& rq, const ToHandles& to) {
+    const std::vector<ProgOut>& po = v.c->outs;
+    const size_t nO = po.size();
+    if (v.hit && !rq.starts && (nO < 1 || nO > rq.parts))  // the caller's out buffer holds M * parts handles
+        throw Error(FR_ERR_INVALID, "cached plan has more outputs than the caller's parts");
+    // an uncached plan's one output takes its gate's slot; parts get copies (two parts may read one gate)
+    const bool take = v.own && nO == 1;
+    size_t made = 0;  // handles written so far, released if a later one fails: the caller gets a code only
+    try {
+        for (size_t m = 0; m < rq.M; ++m)
+            for (size_t j = 0; j < nO; ++j, ++made) {
+                ProgOut o = po[j];
+                if (o.gate >= 0) o.gate += (int)(m * v.c->n_gates);
+                to.outs[m * nO + j] = make_output(ctx, o, v.c->plan.slot, take);
+            }
+    } catch (...) {
+        while (made) ctx->release(to.outs[--made]);
+        throw;
+    }
+    if (to.n_parts) *to.n_parts = nO;
+}
+
+// Each output o.cst + o.w * gate as a pack row over the plan's own gate slot (a constant start:
+// no input), so no handle, no arena slot and no k_linear launch stands between the plan and the
+// pack.  One per start of the request, or the plan is not this request's.
+std::vector<DevGate> output_rows(const PlanView& v, const MatchRequest& rq) {
+    const std::vector<ProgOut>& po = v.c->outs;
+    if (po.size() != rq.hi - rq.lo) throw Error(FR_ERR_INVALID, "cached plan's outputs are not the call's starts");
+    std::vector<DevGate> rows(po.size());
+    for (size_t j = 0; j < po.size(); ++j)
+        rows[j] = affine_gate(po[j].gate >= 0 ? v.c->plan.slot[po[j].gate] : -1, po[j].w, po[j].cst);
+    return rows;
+}
+void emit(fr_ctx* ctx, PlanView& v, const MatchRequest& rq, const ToBlob& to) {
+    const std::vector<DevGate> rows = output_rows(v, rq);
+    pack_to_blob(ctx, rows.data(), rows.size(), nullptr, rows.size(), to.compact, to.buf);
+}
+
+// One chunk of a scan's starts, on the host alone: `classes` are the classes that occur among
+// cls[0, nc) in order of first occurrence (the chunk's rows) and map[j] is the row of start j
+// (-1: the constant 0).  The numbering is the chunk's own.  row_of is scratch over the n_classes
+// classes, all -1 before and after.
+void chunk_classes(const int32_t* cls, size_t nc, size_t n_classes, std::vector<int32_t>& row_of,
+                   std::vector<int32_t>& classes, std::vector<int32_t>& map) {
+    classes.clear();
+    map.assign(nc, -1);
+    for (size_t j = 0; j < nc; ++j) {
+        const int32_t d = cls[j];
+        if (d < 0) continue;
+        if ((size_t)d >= n_classes) throw Error(FR_ERR_INVALID, "scan: a class past the plan's outputs");
+        if (row_of[(size_t)d] < 0) {
+            row_of[(size_t)d] = (int32_t)classes.size();
+            classes.push_back(d);
+        }
+        map[j] = row_of[(size_t)d];
+    }
+    for (int32_t d : classes) row_of[(size_t)d] = -1;
+}
+// a scan: the plan's outputs are window classes; one mapped pack per chunk of N starts, the
+// blobs back to back (no start at all: cls may be null, and no chunk is written)
+void emit(fr_ctx* ctx, PlanView& v, const MatchRequest& rq, const ToScanBlobs& to) {
+    const std::vector<DevGate> outs = output_rows(v, rq);
+    const size_t N = (size_t)ctx->p.N;
+    std::vector<int32_t> row_of(outs.size(), -1), classes, map;
+    std::vector<DevGate> rows;
+    uint8_t* at = to.buf;
+    for (size_t j0 = 0; j0 < to.n_starts; j0 += N) {
+        const size_t nc = std::min(N, to.n_starts - j0);
+        chunk_classes(to.cls + j0, nc, outs.size(), row_of, classes, map);
+        rows.clear();
+        for (int32_t d : classes) rows.push_back(outs[(size_t)d]);
+        at += pack_to_blob(ctx, rows.data(), rows.size(), map.data(), nc, to.compact, at);
+    }
+}
+
+// after: the device's timers once a blocking call has synchronised, which resolved this match's;
+// null for an asynchronous call, which returns before its kernels ran: its kernel timers are
+// left 0 (read them with fr_device_timers after a synchronising call instead)
+void match_stats(fr_match_stats* st, const DeviceTimers& before, const DeviceTimers* after, double t0, double t1,
+                 double t2, const PlanView& v) {
+    std::memset(st, 0, sizeof *st);
+    fill_stats(*st, v.c->rec, v.c->plan);
+    st->host_ms = t1 - t0;
+    st->device_ms = t2 - t1;
+    st->plan_cached = v.hit ? 1 : 0;
+    if (!after) return;
+    st->br_kernel_ms = after->br_ms - before.br_ms;
+    st->ks_kernel_ms = after->ks_ms - before.ks_ms;
+    st->br_launches = after->br_launches - before.br_launches;
+    st->br_gates = after->br_gates - before.br_gates;
+}
+
+// One match request through its stages: the plan, the launch, the reply.
+void run_match(fr_ctx* ctx, const MatchRequest& rq, fr_match_stats* st) {
+    const double t0 = now_ms();
+    Device& dev = ctx->keyed_device();
+    validate(rq);
+    if (rq.needle) check_needle(ctx, dev, rq.needle);
+    const DeviceTimers before = dev.timers();
+    PlanView v = acquire_plan(ctx, dev, rq);
+    Bound bound{dev};
+    const double t1 = launch(bound, v, rq);
+    std::visit([&](const auto& to) { emit(ctx, v, rq, to); }, rq.sink);
+    if (v.own) v.own->plan.slot.reset();  // later users of these slots are ordered after the launches (one stream)
     if (!ctx->async_match) dev.sync();
-    double t2 = now_ms();
-    if (st) {
-        std::memset(st, 0, sizeof *st);
-        fill_stats(*st, rec, plan);
-        st->host_ms = t1 - t0;
-        st->device_ms = t2 - t1;
-        st->plan_cached = hit ? 1 : 0;
-        if (!ctx->async_match) {
-            // blocking call: this match's timers resolved at its sync.  An asynchronous
-            // call returns before its kernels ran, so its timers are left 0 here (read
-            // them with fr_device_timers after a synchronising call instead)
-            const DeviceTimers& after = dev.timers();
-            st->br_kernel_ms = after.br_ms - before.br_ms;
-            st->ks_kernel_ms = after.ks_ms - before.ks_ms;
-            st->br_launches = after.br_launches - before.br_launches;
-            st->br_gates = after.br_gates - before.br_gates;
-        }
-    }
+    if (st) match_stats(st, before, ctx->async_match ? nullptr : &dev.timers(), t0, t1, now_ms(), v);
+}
+
+// a pattern's request over n content handles and the starts of [lo, hi)
+MatchRequest pattern_request(const fr_ct* content, size_t n, const char* pattern, size_t lo, size_t hi, Sink sink) {
+    MatchRequest rq;
+    rq.pattern = pattern;
+    rq.content = content;
+    rq.n = n, rq.lo = lo, rq.hi = hi;
+    rq.sink = sink;
+    return rq;
+}
+// a needle's request of one kind over n positions (windows: n classes, the whole range); the
+// entry adds what the kind reads, content handles or text
+MatchRequest needle_request(MatchKind kind, const fr_needle* needle, size_t n, size_t lo, size_t hi, Sink sink) {
+    MatchRequest rq;
+    rq.kind = kind;
+    rq.needle = needle;
+    rq.n = n, rq.lo = lo, rq.hi = hi;
+    rq.sink = sink;
+    return rq;
 }
 
 // A scan's host part: the classes of the starts of [lo, hi), the padded class count and the text
@@ -430,7 +492,7 @@ extern "C" {
 int fr_has_match(fr_ctx* ctx, const fr_ct* content, size_t n, const char* pattern, fr_ct* out, fr_match_stats* st) {
     FR_TRY({
         NEED(ctx && out && pattern && (content || !n));
-        match_impl(ctx, content, n, 1, pattern, 0, n, out, st);
+        run_match(ctx, pattern_request(content, n, pattern, 0, n, ToHandles{out, nullptr}), st);
     })
 }
 
@@ -486,7 +548,9 @@ int fr_has_match_batch(fr_ctx* ctx, const fr_ct* content, size_t n_chars, size_t
                        fr_ct* out, fr_match_stats* st) {
     FR_TRY({
         NEED(ctx && out && pattern && n_matches && (content || !n_chars));
-        match_impl(ctx, content, n_chars, n_matches, pattern, 0, n_chars, out, st);
+        MatchRequest rq = pattern_request(content, n_chars, pattern, 0, n_chars, ToHandles{out, nullptr});
+        rq.M = n_matches;
+        run_match(ctx, rq, st);
     })
 }
 
@@ -494,7 +558,7 @@ int fr_has_match_range(fr_ctx* ctx, const fr_ct* content, size_t n, const char* 
                        fr_ct* out, fr_match_stats* st) {
     FR_TRY({
         NEED(ctx && out && pattern && (content || !n) && lo <= hi);
-        match_impl(ctx, content, n, 1, pattern, lo, hi, out, st);
+        run_match(ctx, pattern_request(content, n, pattern, lo, hi, ToHandles{out, nullptr}), st);
     })
 }
 
@@ -503,7 +567,9 @@ int fr_match_starts(fr_ctx* ctx, const fr_ct* content, size_t n, const char* pat
     FR_TRY({
         NEED(ctx && pattern && (content || !n) && lo <= hi && (out || lo == hi));
         // (the key's `starts` field keeps these plans apart from has_match's of the same range)
-        match_impl(ctx, content, n, 1, pattern, lo, hi, out, st, 1, nullptr, true);
+        MatchRequest rq = pattern_request(content, n, pattern, lo, hi, ToHandles{out, nullptr});
+        rq.starts = true;
+        run_match(ctx, rq, st);
     })
 }
 
@@ -513,15 +579,13 @@ int fr_match_starts_packed(fr_ctx* ctx, const fr_ct* content, size_t n, const ch
         NEED(ctx && pattern && written && (content || !n) && lo < hi && hi - lo <= (size_t)ctx->p.N);
         NEED(compact == 0 || compact == 1);
         ctx->keyed_device();  // a host-only or keyless context refuses as fr_match_starts does
-        if (!ctx->has_pk)     // ... and nothing is launched without a packing key
-            throw Error(FR_ERR_INVALID, "packing needs a packing key (fr_gen_packing_key, fr_load_packing_key)");
+        ctx->need_packing_key();  // ... and nothing is launched without a packing key
         const size_t need = compact ? packed_compact_size(ctx->p, hi - lo) : packed_result_size(ctx->p);
-        *written = need;
-        if (!buf) return FR_OK;  // size query
-        NEED(cap >= need);
-        const PackedReply reply{compact != 0, buf};
+        if (answer_size(written, need, buf, cap)) return FR_OK;
         // the plans are fr_match_starts' own (same key): one compiled by either call serves the other
-        match_impl(ctx, content, n, 1, pattern, lo, hi, nullptr, st, 1, nullptr, true, &reply);
+        MatchRequest rq = pattern_request(content, n, pattern, lo, hi, ToBlob{compact != 0, buf});
+        rq.starts = true;
+        run_match(ctx, rq, st);
     })
 }
 
@@ -531,7 +595,9 @@ int fr_find(fr_ctx* ctx, const fr_ct* content, size_t n_chars, const fr_needle* 
         NEED(ctx && needle && out && (content || !n_chars) && start_lo <= start_hi);
         // no start past the content fits: the range is cut there (one plan for every such range)
         const size_t hi = std::min(start_hi, n_chars), lo = std::min(start_lo, hi);
-        match_impl(ctx, content, n_chars, 1, "", lo, hi, out, st, 1, nullptr, false, nullptr, Search{needle});
+        MatchRequest rq = needle_request(MATCH_NEEDLE, needle, n_chars, lo, hi, ToHandles{out, nullptr});
+        rq.content = content;
+        run_match(ctx, rq, st);
     })
 }
 
@@ -540,7 +606,10 @@ int fr_find_starts(fr_ctx* ctx, const fr_ct* content, size_t n_chars, const fr_n
     FR_TRY({
         NEED(ctx && needle && (content || !n_chars) && start_lo <= start_hi && (out || start_lo == start_hi));
         NEED(start_hi - start_lo <= ((size_t)1 << 24));
-        match_impl(ctx, content, n_chars, 1, "", start_lo, start_hi, out, st, 1, nullptr, true, nullptr, Search{needle});
+        MatchRequest rq = needle_request(MATCH_NEEDLE, needle, n_chars, start_lo, start_hi, ToHandles{out, nullptr});
+        rq.starts = true;
+        rq.content = content;
+        run_match(ctx, rq, st);
     })
 }
 
@@ -550,8 +619,9 @@ int fr_find_clear(fr_ctx* ctx, const uint8_t* content, size_t n_chars, const fr_
         NEED(ctx && needle && out && (content || !n_chars) && start_lo <= start_hi);
         // (the range is cut at the content's end, as fr_find cuts it)
         const size_t hi = std::min(start_hi, n_chars), lo = std::min(start_lo, hi);
-        match_impl(ctx, nullptr, n_chars, 1, "", lo, hi, out, st, 1, nullptr, false, nullptr,
-                   Search{needle, CLEAR_FIND, content, n_chars});
+        MatchRequest rq = needle_request(MATCH_NEEDLE_CLEAR, needle, n_chars, lo, hi, ToHandles{out, nullptr});
+        rq.text = content, rq.text_n = n_chars;
+        run_match(ctx, rq, st);
     })
 }
 
@@ -560,8 +630,11 @@ int fr_find_clear_starts(fr_ctx* ctx, const uint8_t* content, size_t n_chars, co
     FR_TRY({
         NEED(ctx && needle && (content || !n_chars) && start_lo <= start_hi && (out || start_lo == start_hi));
         NEED(start_hi - start_lo <= ((size_t)1 << 24));
-        match_impl(ctx, nullptr, n_chars, 1, "", start_lo, start_hi, out, st, 1, nullptr, true, nullptr,
-                   Search{needle, CLEAR_FIND, content, n_chars});
+        MatchRequest rq =
+            needle_request(MATCH_NEEDLE_CLEAR, needle, n_chars, start_lo, start_hi, ToHandles{out, nullptr});
+        rq.starts = true;
+        rq.text = content, rq.text_n = n_chars;
+        run_match(ctx, rq, st);
     })
 }
 
@@ -575,8 +648,9 @@ int fr_scan_clear(fr_ctx* ctx, const uint8_t* content, size_t n_chars, const fr_
         const double t0 = now_ms();
         const WindowClasses wc = scan_windows(ctx, content, n_chars, needle->dev.m, lo, hi, &Dpad);
         const double classing_ms = now_ms() - t0;
-        match_impl(ctx, nullptr, Dpad, 1, "", 0, Dpad, out, st, 1, nullptr, false, nullptr,
-                   Search{needle, CLEAR_SCAN, wc.text.data(), wc.text.size()});
+        MatchRequest rq = needle_request(MATCH_NEEDLE_WINDOWS, needle, Dpad, 0, Dpad, ToHandles{out, nullptr});
+        rq.text = wc.text.data(), rq.text_n = wc.text.size();
+        run_match(ctx, rq, st);
         if (st) st->host_ms += classing_ms;  // the classing is the scan's host work too
     })
 }
@@ -589,20 +663,19 @@ int fr_scan_clear_starts(fr_ctx* ctx, const uint8_t* content, size_t n_chars, co
         NEED(compact == 0 || compact == 1);
         NEED(start_hi - start_lo <= ((size_t)1 << 24));
         check_needle(ctx, ctx->keyed_device(), needle);  // a host-only or keyless context refuses as fr_find_clear does
-        if (!ctx->has_pk)                                // ... and nothing is launched without a packing key
-            throw Error(FR_ERR_INVALID, "packing needs a packing key (fr_gen_packing_key, fr_load_packing_key)");
-        const size_t n_starts = start_hi - start_lo, need = scan_reply_size(ctx->p, n_starts, compact != 0);
-        *written = need;
-        if (!buf) return FR_OK;  // size query
-        NEED(cap >= need);
+        ctx->need_packing_key();                         // ... and nothing is launched without a packing key
+        const size_t n_starts = start_hi - start_lo;
+        if (answer_size(written, scan_reply_size(ctx->p, n_starts, compact != 0), buf, cap)) return FR_OK;
         size_t Dpad = 0;
         const double t0 = now_ms();
         WindowClasses wc = scan_windows(ctx, content, n_chars, needle->dev.m, start_lo, start_hi, &Dpad);
         wc.cls.resize(n_starts, -1);  // a start past the content: the constant 0
         const double classing_ms = now_ms() - t0;
-        const PackedReply reply{compact != 0, buf, wc.cls.data(), n_starts};
-        match_impl(ctx, nullptr, Dpad, 1, "", 0, Dpad, nullptr, st, 1, nullptr, true, &reply,
-                   Search{needle, CLEAR_SCAN, wc.text.data(), wc.text.size()});
+        MatchRequest rq = needle_request(MATCH_NEEDLE_WINDOWS, needle, Dpad, 0, Dpad,
+                                         ToScanBlobs{compact != 0, buf, wc.cls.data(), n_starts});
+        rq.starts = true;
+        rq.text = wc.text.data(), rq.text_n = wc.text.size();
+        run_match(ctx, rq, st);
         if (st) st->host_ms += classing_ms;
     })
 }
@@ -620,7 +693,9 @@ int fr_has_match_parts(fr_ctx* ctx, const fr_ct* content, size_t n, const char* 
     FR_TRY({
         NEED(ctx && out && n_parts && pattern && (content || !n) && lo <= hi);
         NEED(max_parts >= 1 && max_parts <= (size_t)MAX_FANIN);
-        match_impl(ctx, content, n, 1, pattern, lo, hi, out, st, max_parts, n_parts);
+        MatchRequest rq = pattern_request(content, n, pattern, lo, hi, ToHandles{out, n_parts});
+        rq.parts = max_parts;
+        run_match(ctx, rq, st);
     })
 }
 
@@ -809,7 +884,7 @@ int fr_schedule_find(size_t n_chars, size_t m, size_t start_lo, size_t start_hi,
     FR_TRY({
         NEED(n_jobs && n_levels && n_outs && outs3 && start_lo <= start_hi && (starts == 0 || starts == 1));
         NEED(outs_cap >= (starts ? start_hi - start_lo : 1));
-        const Program prog = compile_needle(n_chars, m, start_lo, start_hi, starts != 0);
+        const Program prog = needle_program(MATCH_NEEDLE, n_chars, m, start_lo, start_hi, starts != 0);
         schedule_program(prog, n_chars, 1, jobs, jobs_cap, n_jobs, level_off, level_cap, n_levels, outs3, n_outs);
     })
 }
@@ -820,7 +895,7 @@ int fr_schedule_find_clear(size_t n_chars, size_t m, size_t start_lo, size_t sta
     FR_TRY({
         NEED(n_jobs && n_levels && n_outs && outs3 && start_lo <= start_hi && (starts == 0 || starts == 1));
         NEED(outs_cap >= (starts ? start_hi - start_lo : 1));
-        const Program prog = compile_needle_clear(n_chars, m, start_lo, start_hi, starts != 0);
+        const Program prog = needle_program(MATCH_NEEDLE_CLEAR, n_chars, m, start_lo, start_hi, starts != 0);
         schedule_program(prog, n_chars, 1, jobs, jobs_cap, n_jobs, level_off, level_cap, n_levels, outs3, n_outs);
     })
 }
@@ -831,7 +906,7 @@ int fr_schedule_scan_clear(size_t n_windows, size_t m, int32_t starts, fr_job* j
     FR_TRY({
         NEED(n_jobs && n_levels && n_outs && outs3 && (starts == 0 || starts == 1));
         NEED(n_windows <= ((size_t)1 << 24) && outs_cap >= (starts ? n_windows : 1));
-        const Program prog = compile_needle_windows(n_windows, m, starts != 0);
+        const Program prog = needle_program(MATCH_NEEDLE_WINDOWS, n_windows, m, 0, n_windows, starts != 0);
         // (the extract-sums read n_windows m bytes of compacted text)
         schedule_program(prog, n_windows * m, 1, jobs, jobs_cap, n_jobs, level_off, level_cap, n_levels, outs3, n_outs);
     })

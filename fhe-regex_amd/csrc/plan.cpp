@@ -67,12 +67,8 @@ Slots execute_gates(fr_ctx* ctx, const std::vector<PGate>& gates, const std::vec
 
 Slots linear_to_new_slot(Device& dev, int slot, int w, int offset) {
     Slots out(dev, 1);
-    DevGate d;
-    std::memset(&d, 0, sizeof d);
-    d.n_in = 1;
-    d.in_slot[0] = slot;
-    d.in_w[0] = w;
-    d.offset = offset;
+    DevGate d = affine_gate(slot, w, 0);
+    d.offset = offset;  // (units of Delta / 2)
     d.out_slot[0] = out[0];
     dev.run_linear(d);
     return out;

@@ -975,11 +975,19 @@ class Context:
         _check(lib().fr_upload_needle(self.h, blob, len(blob), C.byref(h)))
         return Needle(self, h)
 
-    def _find(self, fn, content, needle, lo, hi, n_out):
+    def _find(self, fn, content, needle, lo, hi, starts, clear=False):
+        """one fr_find* / fr_find_clear* / fr_scan_clear call over the starts [lo, hi) (default: all
+        of the content): ([handles], MatchStats).  clear: the content is a text, else handles"""
         if needle.h is None:
             raise ValueError("needle is closed")
-        content = np.ascontiguousarray(content, dtype=np.uint32)
-        arr = content.ctypes.data_as(C.POINTER(C.c_uint32))
+        if clear:
+            arr = content = _text_bytes(content)
+        else:
+            content = np.ascontiguousarray(content, dtype=np.uint32)
+            arr = content.ctypes.data_as(C.POINTER(C.c_uint32))
+        lo = 0 if lo is None else lo
+        hi = len(content) if hi is None else hi
+        n_out = max(hi - lo, 0) if starts else 1
         out = (C.c_uint32 * max(n_out, 1))()
         st = MatchStats()
         _check(fn(self.h, arr, len(content), needle.h, lo, hi, out, C.byref(st)))
@@ -987,17 +995,13 @@ class Context:
 
     def find(self, content: Sequence[int], needle: "Needle", lo: Optional[int] = None, hi: Optional[int] = None):
         """fr_find: (boolean handle, MatchStats): the needle matches at some start of [lo, hi)"""
-        lo = 0 if lo is None else lo
-        hi = len(content) if hi is None else hi
-        out, st = self._find(lib().fr_find, content, needle, lo, hi, 1)
+        out, st = self._find(lib().fr_find, content, needle, lo, hi, False)
         return out[0], st
 
     def find_starts(self, content: Sequence[int], needle: "Needle", lo: Optional[int] = None,
                     hi: Optional[int] = None, stats: bool = False):
         """fr_find_starts: one boolean handle per start offset of [lo, hi)"""
-        lo = 0 if lo is None else lo
-        hi = len(content) if hi is None else hi
-        hs, st = self._find(lib().fr_find_starts, content, needle, lo, hi, max(hi - lo, 0))
+        hs, st = self._find(lib().fr_find_starts, content, needle, lo, hi, True)
         return (hs, st) if stats else hs
 
     def dev_blind_rotate_acc(self, ks: np.ndarray, accs: np.ndarray) -> np.ndarray:
@@ -1009,38 +1013,23 @@ class Context:
         return out
 
     # ---- private search over clear content (fr_find_clear*): the server's own bytes
-    def _find_clear(self, fn, text, needle, lo, hi, n_out):
-        if needle.h is None:
-            raise ValueError("needle is closed")
-        b = _text_bytes(text)
-        out = (C.c_uint32 * max(n_out, 1))()
-        st = MatchStats()
-        _check(fn(self.h, b, len(b), needle.h, lo, hi, out, C.byref(st)))
-        return list(out)[:n_out], st
-
     def find_clear(self, text: bytes | str, needle: "Needle", lo: Optional[int] = None, hi: Optional[int] = None):
         """fr_find_clear: (boolean handle, MatchStats): the needle matches the clear text at some
         start of [lo, hi)"""
-        lo = 0 if lo is None else lo
-        hi = len(_text_bytes(text)) if hi is None else hi
-        out, st = self._find_clear(lib().fr_find_clear, text, needle, lo, hi, 1)
+        out, st = self._find(lib().fr_find_clear, text, needle, lo, hi, False, clear=True)
         return out[0], st
 
     def find_clear_starts(self, text: bytes | str, needle: "Needle", lo: Optional[int] = None,
                           hi: Optional[int] = None, stats: bool = False):
         """fr_find_clear_starts: one boolean handle per start offset of [lo, hi)"""
-        lo = 0 if lo is None else lo
-        hi = len(_text_bytes(text)) if hi is None else hi
-        hs, st = self._find_clear(lib().fr_find_clear_starts, text, needle, lo, hi, max(hi - lo, 0))
+        hs, st = self._find(lib().fr_find_clear_starts, text, needle, lo, hi, True, clear=True)
         return (hs, st) if stats else hs
 
     # ---- scan of a long clear text (fr_scan_clear*): one rotation per distinct window
     def scan_clear(self, text: bytes | str, needle: "Needle", lo: Optional[int] = None, hi: Optional[int] = None):
         """fr_scan_clear: find_clear's (boolean handle, MatchStats) at one rotation per distinct
         window of the text"""
-        lo = 0 if lo is None else lo
-        hi = len(_text_bytes(text)) if hi is None else hi
-        out, st = self._find_clear(lib().fr_scan_clear, text, needle, lo, hi, 1)
+        out, st = self._find(lib().fr_scan_clear, text, needle, lo, hi, False, clear=True)
         return out[0], st
 
     def scan_clear_starts(self, text: bytes | str, needle: "Needle", lo: Optional[int] = None,
@@ -1397,32 +1386,31 @@ def _text_bytes(text: bytes | str) -> bytes:
     return text.encode("latin-1") if isinstance(text, str) else bytes(text)
 
 
-def plain_find_clear(content: bytes | str, masks: Sequence[Tuple[int, int]], start_lo: int = 0,
-                     start_hi: Optional[int] = None) -> Tuple[List[int], int]:
-    """fr_plain_find_clear: the lowered programs of find_clear_starts and find_clear in
-    plaintext, extract-sums included: (starts, any)"""
+def _plain_needle(fn, content, masks, start_lo, start_hi) -> Tuple[List[int], int]:
+    """one of the three plaintext needle evaluators (fn) over the starts of [start_lo, start_hi)
+    (default: to the content's end): (starts, any)"""
     b = _text_bytes(content)
     hi = len(b) if start_hi is None else start_hi
     flat = [v for lo_hi in masks for v in lo_hi]
     arr = (C.c_uint16 * max(len(flat), 1))(*flat)
     out = (C.c_uint8 * max(hi - start_lo, 1))()
     any_ = C.c_int32()
-    _check(lib().fr_plain_find_clear(b, len(b), arr, len(masks), start_lo, hi, out, C.byref(any_)))
+    _check(fn(b, len(b), arr, len(masks), start_lo, hi, out, C.byref(any_)))
     return list(out)[:max(hi - start_lo, 0)], any_.value
+
+
+def plain_find_clear(content: bytes | str, masks: Sequence[Tuple[int, int]], start_lo: int = 0,
+                     start_hi: Optional[int] = None) -> Tuple[List[int], int]:
+    """fr_plain_find_clear: the lowered programs of find_clear_starts and find_clear in
+    plaintext, extract-sums included: (starts, any)"""
+    return _plain_needle(lib().fr_plain_find_clear, content, masks, start_lo, start_hi)
 
 
 def plain_scan_clear(content: bytes | str, masks: Sequence[Tuple[int, int]], start_lo: int = 0,
                      start_hi: Optional[int] = None) -> Tuple[List[int], int]:
     """fr_plain_scan_clear: plain_find_clear by the scan's route (windows classed, the lowered
     programs over the compacted text, every start its class's output): (starts, any)"""
-    b = _text_bytes(content)
-    hi = len(b) if start_hi is None else start_hi
-    flat = [v for lo_hi in masks for v in lo_hi]
-    arr = (C.c_uint16 * max(len(flat), 1))(*flat)
-    out = (C.c_uint8 * max(hi - start_lo, 1))()
-    any_ = C.c_int32()
-    _check(lib().fr_plain_scan_clear(b, len(b), arr, len(masks), start_lo, hi, out, C.byref(any_)))
-    return list(out)[:max(hi - start_lo, 0)], any_.value
+    return _plain_needle(lib().fr_plain_scan_clear, content, masks, start_lo, start_hi)
 
 
 def window_classes(text: bytes | str, m: int, start_lo: int = 0, start_hi: Optional[int] = None
@@ -1444,19 +1432,19 @@ def window_classes(text: bytes | str, m: int, start_lo: int = 0, start_hi: Optio
 def plain_find(content: bytes | str, masks: Sequence[Tuple[int, int]], start_lo: int = 0,
                start_hi: Optional[int] = None) -> Tuple[List[int], int]:
     """fr_plain_find: the lowered programs of find_starts and find in plaintext: (starts, any)"""
-    b = content.encode("latin-1") if isinstance(content, str) else bytes(content)
-    hi = len(b) if start_hi is None else start_hi
-    flat = [v for lo_hi in masks for v in lo_hi]
-    arr = (C.c_uint16 * max(len(flat), 1))(*flat)
-    out = (C.c_uint8 * max(hi - start_lo, 1))()
-    any_ = C.c_int32()
-    _check(lib().fr_plain_find(b, len(b), arr, len(masks), start_lo, hi, out, C.byref(any_)))
-    return list(out)[:max(hi - start_lo, 0)], any_.value
+    return _plain_needle(lib().fr_plain_find, content, masks, start_lo, start_hi)
 
 
 # ------------------------------------------------------------- reference API
 # first word of a compact match_starts reply; never a chunk count of the full form's framing
 COMPACT_REPLY = 0xFFFFFFFF
+
+
+def _starts_reply(chunks: int, blobs: bytes, compact: bool) -> bytes:
+    """the frame of a starts reply around its chunks' blobs, back to back: a u32 count of chunks
+    (FRPKRES1 blobs), or u32 COMPACT_REPLY and the u32 count (FRCPRES1 blobs)"""
+    head = struct.pack("<II", COMPACT_REPLY, chunks) if compact else struct.pack("<I", chunks)
+    return head + blobs
 
 
 @dataclass
@@ -1566,14 +1554,20 @@ class ServerKey:
         if compact:
             blobs = [self.ctx.match_starts_packed(content, pattern, lo, min(lo + N, len(content)))
                      for lo in range(0, len(content), N)]
-            return struct.pack("<II", COMPACT_REPLY, len(blobs)) + b"".join(blobs)
-        hs = self.ctx.match_starts(content, pattern)
+        else:
+            blobs = self._packed_chunks(self.ctx.match_starts(content, pattern), False)
+        return _starts_reply(len(blobs), b"".join(blobs), compact)
+
+    def _packed_chunks(self, hs: Sequence[int], compact: bool) -> List[bytes]:
+        """one blob per chunk of N of the boolean handles hs (compact: FRCPRES1, else FRPKRES1);
+        the handles are released, whether the packs succeed or not"""
+        N = self.ctx.params.N
+        pack = self.ctx.pack_bools_compact if compact else self.ctx.pack_bools
         try:
-            blobs = [self.ctx.pack_bools(hs[i:i + N]) for i in range(0, len(hs), N)]
+            return [pack(hs[i:i + N]) for i in range(0, len(hs), N)]
         finally:
             for h in hs:
                 self.ctx.release(h)
-        return struct.pack("<I", len(blobs)) + b"".join(blobs)
 
     def upload_needle(self, blob: bytes) -> Needle:
         """a client's needle blob (ClientKey.encrypt_needle) on the device; no client key needed"""
@@ -1586,17 +1580,8 @@ class ServerKey:
     def find_starts(self, content: Sequence[int], needle: Needle, compact: bool = False) -> bytes:
         """where the needle occurs, as match_starts' reply for ClientKey.decrypt_starts (both
         forms): fr_find_starts, then one pack per chunk of N starts.  The handles are released."""
-        N = self.ctx.params.N
-        hs = self.ctx.find_starts(content, needle)
-        try:
-            pack = self.ctx.pack_bools_compact if compact else self.ctx.pack_bools
-            blobs = [pack(hs[i:i + N]) for i in range(0, len(hs), N)]
-        finally:
-            for h in hs:
-                self.ctx.release(h)
-        if compact:
-            return struct.pack("<II", COMPACT_REPLY, len(blobs)) + b"".join(blobs)
-        return struct.pack("<I", len(blobs)) + b"".join(blobs)
+        blobs = self._packed_chunks(self.ctx.find_starts(content, needle), compact)
+        return _starts_reply(len(blobs), b"".join(blobs), compact)
 
     def find_clear(self, text: bytes | str, needle: Needle) -> int:
         """boolean handle: the encrypted needle occurs in the server's own clear text"""
@@ -1606,17 +1591,8 @@ class ServerKey:
         """where the needle occurs in the clear text, as find_starts' reply for
         ClientKey.decrypt_starts (both forms): fr_find_clear_starts, then one pack per chunk of N
         starts.  The handles are released."""
-        N = self.ctx.params.N
-        hs = self.ctx.find_clear_starts(text, needle)
-        try:
-            pack = self.ctx.pack_bools_compact if compact else self.ctx.pack_bools
-            blobs = [pack(hs[i:i + N]) for i in range(0, len(hs), N)]
-        finally:
-            for h in hs:
-                self.ctx.release(h)
-        if compact:
-            return struct.pack("<II", COMPACT_REPLY, len(blobs)) + b"".join(blobs)
-        return struct.pack("<I", len(blobs)) + b"".join(blobs)
+        blobs = self._packed_chunks(self.ctx.find_clear_starts(text, needle), compact)
+        return _starts_reply(len(blobs), b"".join(blobs), compact)
 
     def scan_clear(self, text: bytes | str, needle: Needle) -> int:
         """find_clear for a long text: one rotation per distinct window of len(needle) bytes
@@ -1627,12 +1603,8 @@ class ServerKey:
         """find_clear_starts' reply, byte for byte, from one fr_scan_clear_starts call: no handle
         per start, one rotation per distinct window, one mapped pack per chunk of N starts"""
         N = self.ctx.params.N
-        n = len(_text_bytes(text))
-        blobs = self.ctx.scan_clear_starts(text, needle, compact=compact)
-        chunks = (n + N - 1) // N
-        if compact:
-            return struct.pack("<II", COMPACT_REPLY, chunks) + blobs
-        return struct.pack("<I", chunks) + blobs
+        chunks = (len(_text_bytes(text)) + N - 1) // N
+        return _starts_reply(chunks, self.ctx.scan_clear_starts(text, needle, compact=compact), compact)
 
     def save(self, path: str, packing_path: Optional[str] = None):
         """the server key as an .npz of its (ksk, bsk) arrays (fr_export_server_key's layout);

@@ -196,6 +196,23 @@ def test_plain_scan_clear_against_python():
     assert 40 < hits < 190 and shared > 40  # both answers occur often, and so do shared windows
 
 
+def test_three_plain_evaluators_on_one_text():
+    """fr_plain_find, fr_plain_find_clear and fr_plain_scan_clear evaluate through one body: all
+    three against the Python search on one 12-byte text whose 3-byte window recurs, a 3-character
+    needle -- the whole range, a range cut at the text's end, empty ranges -- and a needle longer
+    than the text (the random cases above reach these only by chance, and never all three calls)"""
+    text = b"abcxabcabcyz"
+    assert F.window_classes(text, 3)[1] == 8  # ten windows fit; abc is three of them
+    evaluators = (F.plain_find, F.plain_find_clear, F.plain_scan_clear)
+    for needle in (b"abc", b"abcxabcabcyzq"):
+        masks = F.needle_masks(needle)
+        for lo, hi in ((0, 12), (0, None), (3, 17), (11, 14), (12, 15), (4, 4), (0, 0), (12, 12)):
+            want = py_find(text, masks, lo, 12 if hi is None else hi)
+            for f in evaluators:
+                assert f(text, masks, lo, hi) == (want, int(any(want))), (f.__name__, needle, lo, hi)
+    assert py_find(text, F.needle_masks(b"abc"), 0, 12) == [1, 0, 0, 0, 1, 0, 0, 1, 0, 0, 0, 0]
+
+
 # ------------------------------------------------------------------ the mapped pack on the host
 @pytest.fixture(scope="module")
 def keyed(key_blob):
