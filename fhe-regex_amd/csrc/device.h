@@ -83,6 +83,10 @@ struct DeviceTimers {
     uint64_t pair_launches = 0, pair_gates = 0;
 };
 
+// The launch shape of a blind rotation, chosen by Device::br_shape from the batch size (FFT
+// ring: fft_br.hip, FbrShape; RNS ring: Latency / Throughput pick the lane geometry)
+enum class BrShape { LatencyKP, Latency, Dual, Pair, Throughput };
+
 struct ClientKey;
 struct RngKey;
 class Device;
@@ -459,9 +463,9 @@ class Device {
         size_t gates, outs;
         bool lat, pair, ks;
         bool chain;  // BR timed from the keyswitch's end event (no start event on the BR launch)
+        void count_as(BrShape shape);  // lat / pair: the timers' per-shape sums
     };
-    bool latency_shape(size_t n) const;  // launch_br's shape choice for n bootstraps
-    bool pair_shape(size_t n) const;     // (FFT ring, k = 1: the pair shape)
+    BrShape br_shape(size_t n, bool acc) const;  // launch_br's shape choice for n bootstraps (acc: selector jobs)
     std::vector<PendingTimer> pending_;
     std::vector<gpu::Event> event_pool_;
     int profiling_ = 0;  // fr_set_profiling level

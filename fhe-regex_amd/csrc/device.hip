@@ -311,8 +311,20 @@ void Device::upload_keys(const std::vector<uint64_t>& ksk, const std::vector<uin
     key_guard.dismiss();
 }
 
-bool Device::latency_shape(size_t n) const { return n <= (p_.ring == FR_RING_FFT ? fft_small_ : small_batch_); }
-bool Device::pair_shape(size_t n) const { return p_.ring == FR_RING_FFT && !latency_shape(n) && n <= fft_pair_; }
+// The one place that decides a launch's shape: launch_br_fft and launch_br_rns switch on it and
+// the timers read it.  Small launches (at most one bootstrap per CU): the latency shape, the
+// smallest (FFT ring, k = 1, at most fft_kpre_) with their key products formed first.  Selector
+// launches take the shape by count alone: never the key products, never the dual.
+BrShape Device::br_shape(size_t n, bool acc) const {
+    if (p_.ring != FR_RING_FFT) return n <= small_batch_ ? BrShape::Latency : BrShape::Throughput;
+    if (n <= fft_small_) return n <= fft_kpre_ && p_.k == 1 && !acc ? BrShape::LatencyKP : BrShape::Latency;
+    if (n <= fft_pair_ && p_.k == 1) return fft_dual_ && !acc ? BrShape::Dual : BrShape::Pair;
+    return BrShape::Throughput;
+}
+void Device::PendingTimer::count_as(BrShape shape) {
+    lat = shape == BrShape::Latency || shape == BrShape::LatencyKP;
+    pair = shape == BrShape::Pair;  // (the dual: one bootstrap per workgroup)
+}
 
 void Device::launch_br(const DevGate* d_gates, const uint64_t* d_ks, size_t n, hipEvent_t ev_start, hipEvent_t ev_stop,
                        bool acc) {
@@ -453,8 +465,7 @@ void Device::launch_jobs(const DevGate* d_gates, const DevGate* host, size_t n, 
     HIP_CHECK(hipGetLastError());
     if (profiling_) {
         t.gates = n;
-        t.lat = latency_shape(n);
-        t.pair = pair_shape(n) && (!fft_dual_ || acc);  // FR_FFT_DUAL launches: one bootstrap per workgroup
+        t.count_as(br_shape(n, acc));
         t.ks = profiling_ >= 2;
         t.outs = 0;
         for (size_t i = 0; i < n; ++i) t.outs += host[i].n_out;
@@ -579,8 +590,7 @@ void Device::run_br_jobs(const uint64_t* ks_in, std::vector<DevGate>& gates, uin
     if (profiling_) {
         t.ev[2] = take_event(), t.ev[3] = take_event();
         t.gates = count, t.outs = n_out;
-        t.lat = latency_shape(count);
-        t.pair = pair_shape(count) && (!fft_dual_ || a != 0);
+        t.count_as(br_shape(count, a != 0));
     }
     launch_br(gates_.device(), d_ks, count, t.ev[2].get(), t.ev[3].get(), a != 0);
     if (profiling_) {

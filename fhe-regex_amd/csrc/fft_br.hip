@@ -3,13 +3,16 @@
 // specified in fft.h; oracle/tfhe_oracle.c restates the same sequence.
 // (File named fft_br.hip so its object does not collide with fft.cpp.)
 //
-//   k_blind_rotate_fft<N,E>: modulus switch, test-polynomial accumulator (u64),
-//     the unrolled blind rotation (k = 1: one step per pair of LWE
-//     coefficients, three GGSWs, see rns_br.hip), multi-value w-step and
-//     sample extract -- outputs are already torus LWEs, no ring conversion.
+//   k_blind_rotate_fft<N,K,E,LAT,B> (and its _kp, _acc and _dual variants): modulus
+//     switch, test-polynomial accumulator (u64), the unrolled blind rotation (one
+//     step per pair of LWE coefficients, three GGSWs, see rns_br.hip), multi-value
+//     w-step and sample extract -- outputs are already torus LWEs, no ring
+//     conversion.  Every compile-time fact of a launch shape -- geometry, threads,
+//     key-load schedule, LDS layout -- is a constant of FbrShape (FbrDualShape).
+//   k_key_products<N>: the MAC's key-only half, ahead of the smallest launches.
 //
-// Geometry: one workgroup per bootstrap, 2 * M/E lanes (M = N/2 complex
-// points per polynomial, E per lane, whole waves per polynomial).  The
+// Geometry: one workgroup per bootstrap (pair shape: two), (K + 1) * M/E lanes (M = N/2
+// complex points per polynomial, E per lane, whole waves per polynomial).  The
 // log2 M transform stages run as register phases of log2 E stages joined by
 // LDS exchanges of 16-B complex values (conflict-free maps of geo.h with
 // 8-lane b128 groups).  Per step a lane: gadget digits of its 2E accumulator
@@ -112,62 +115,7 @@ __device__ __forceinline__ void finv_phase_lds(double2 (&x)[E], const double2* t
 
 // Latency shape: a lane's twiddles are the same every step (they depend on the
 // lane, the stage and the element only), so they are read from LDS once and
-// kept in registers: LOG * E / 2 complex values, index (s, k-th butterfly of s).
-// phases of the latency shape's forward FFT after which its 2nd and 3rd non-prefetched GGSW groups load
-#ifndef FR_LAT_LOAD1
-#define FR_LAT_LOAD1 2
-#endif
-#ifndef FR_LAT_LOAD2
-#define FR_LAT_LOAD2 3
-#endif
-// latency shape: how many of a step's three GGSW groups are loaded right after the
-// previous step's MAC (the rest across the step's own forward FFT)
-#ifndef FR_LAT_PF
-#define FR_LAT_PF 2
-#endif
-// the same for k = 2 (tools/ab_k2.sh: 0 / 1 / 2 / 3 groups: one bootstrap 1.75 / 1.71 / 1.67 / 1.81 ms)
-#ifndef FR_LAT_PF2
-#define FR_LAT_PF2 2
-#endif
-// pair shape: the forward phase after which a step's third GGSW group loads (tools/ab_libs.sh,
-// profiles/r03/ab_pair_variants.log: after phase 0 / 1 / 2 / 3: 2.93 / 2.83 / 2.73 / 2.82 ms per
-// 512 bootstraps; the psi lookups moved ahead of the MAC barrier: 2.75, not kept)
-#ifndef FR_PAIR_LOAD
-#define FR_PAIR_LOAD 2
-#endif
-// pair shape A/B knobs: key groups loaded a step ahead (FR_PAIR_PF; with 1 the third group
-// loads after forward phase FR_PAIR_LOAD2), and the inverse's c ca recomputed per phase (1) or
-// kept (0).  Round 4 (profiles/r04/ab_key_placement{,2,3}.log, 512 / 2048 bootstraps): one group
-// ahead, the second after forward phase 2 and the third after phase 4 (in the MAC barrier's
-// shadow, its registers free across the transform) 2.66-2.67 / 9.48-9.51 ms, against 2.72-2.75 /
-// 9.81-9.83 for two groups ahead and the third after phase 2; the third after phase 3: 9.65-9.67
-#ifndef FR_PAIR_PF
-#define FR_PAIR_PF 1
-#endif
-#ifndef FR_PAIR_LOAD2
-#define FR_PAIR_LOAD2 4
-#endif
-#ifndef FR_PAIR_CC
-#define FR_PAIR_CC 1
-#endif
-// latency shape, k = 1: the lane's twiddles in registers (1) or read from LDS (0)
-#ifndef FR_LAT_TWR
-#define FR_LAT_TWR 1
-#endif
-// Round-3 latency-shape experiments, measured and not kept (logs under profiles/r03/):
-//  * per-polynomial synchronisation: LDS arrival counters in place of the workgroup
-//    barriers around each polynomial's cross-wave exchanges, and the MAC waiting for the
-//    other polynomial only where it reads it: 1.49 against 1.34 ms per bootstrap, at any
-//    start skew; the late MAC wait alone: 1.35 (ab_poly_sync.log);
-//  * the MAC's key products computed in the shadow of the forward cross-wave exchange,
-//    the next step's key loaded right after them: 1.38 ms (ab_kearly.log);
-//  * k = 1 throughput shapes with E = 8 / 16 (two waves / one wave per polynomial): 12.0 /
-//    13.4 against 10.8 ms per 2048 bootstraps (ab_lane_elems_k1.log);
-//  * a 16-wave latency shape (E = 2): 2.03 ms with the twiddles
-//    from LDS, 2.27 with them in registers (spilled at the 128-VGPR cap of 4 waves per
-//    SIMD), against 1.34: nine exchanges per transform, three of them cross-wave
-//    (ab_lat_e2_16wave.log).
-
+// kept in registers (FTwr): LOG * E / 2 complex values, index (s, k-th butterfly of s).
 // The twiddles of phase p are wave-uniform when every lane of a wave reads the same table
 // entry for each of the phase's stages (the index bits the entry depends on sit on element or
 // wave bits of that layout: phases 0 and 1 of the k = 1 geometry).  Those stay in SGPRs, which
@@ -191,13 +139,8 @@ __device__ __forceinline__ double2 fwave_uniform(double2 v) {
     return make_double2(__longlong_as_double((long long)(((unsigned long long)a1 << 32) | a0)),
                         __longlong_as_double((long long)(((unsigned long long)b1 << 32) | b0)));
 }
-// Measured (profiles/r04/ab_r04c.log): the pair shape gains (512 bootstraps 2.62-2.69 -> 2.53-2.56 ms,
-// its 16 spilled VGPRs gone); the latency shape lost 5% (one bootstrap 1.31 -> 1.38 ms, a worse
-// schedule at 190 VGPRs), so it keeps the twiddles in VGPRs
-#ifndef FR_TW_SGPR_PAIR
-#define FR_TW_SGPR_PAIR 1
-#endif
-
+// (UNI of ftw_load_phase: the pair and dual shapes; the latency shape lost 5% to a worse schedule at
+// 190 VGPRs and keeps its twiddles in VGPRs: tools/README.md, FR_TW_SGPR_PAIR)
 template <int M, int E>
 constexpr int ftw_index(int s, int m) {
     const int d = FGeo<M, E>::LOG - 1 - s - FGeo<M, E>::lo(s / FGeo<M, E>::e);
@@ -314,16 +257,12 @@ __device__ __forceinline__ void fperm_exchange(double2 (&x)[E]) {
 // Cross-wave exchanges that only transpose the element bits with the wave bits (lane bits
 // 6, 7), position by position, with every other lane bit in place: a lane keeps the element
 // whose index equals its wave bits, in the same register (forward 0 -> 1, inverse 1 -> 0 of
-// k = 1), so it writes and reads E - 1 elements instead of E (FR_XKEEP).  Throughput shape
-// only (XK): 512 bootstraps 2.80 -> 2.74 ms, 2048 10.66 -> 10.43 ms; the latency shape lost 3%
-// to the wave-uniform branches (tools/ab_libs.sh)
-#ifndef FR_XKEEP
-#define FR_XKEEP 1
-#endif
+// k = 1), so it writes and reads E - 1 elements instead of E.  Throughput shape only (XK): the
+// latency shape lost 3% to the wave-uniform branches (tools/README.md, FR_XKEEP)
 template <int M, int E, int PF, int PT>
 constexpr bool fxkeep_ok() {
     using G = FGeo<M, E>;
-    if (!FR_XKEEP || (1 << (6 + G::e)) > G::T || PF == PT) return false;
+    if ((1 << (6 + G::e)) > G::T || PF == PT) return false;
     for (int b = 0; (1 << b) < G::T; ++b) {
         if (b >= 6 && b < 6 + G::e) {
             if (G::lane_bit(PF, b) != G::lo(PT) + (b - 6) || G::lane_bit(PT, b) != G::lo(PF) + (b - 6)) return false;
@@ -414,7 +353,7 @@ __device__ __forceinline__ void fforward_from(double2 (&x)[B][E], double2* row, 
 template <int M, int E, int p, bool NOPRE, bool TWR, int B, int BS, bool CARRY = false>
 __device__ __forceinline__ void finverse_from(double2 (&x)[B][E], double2* row, const FTwr<M, TWR ? E : 2>& twr,
                                               const double2* tw, const double2* twc, int tl) {
-    if constexpr (TWR && B > 1 && fradix4<M, E>() && FR_PAIR_CC) {
+    if constexpr (TWR && B > 1 && fradix4<M, E>()) {
         // pair shape: cc = c ca recomputed per phase (20 fewer live VGPRs; the same
         // fft::cmul as ftw_load_phase, so the same bits), shared by the B transforms
         const double2 c = twr.v[3 * p], ca = twr.v[3 * p + 1];
@@ -436,35 +375,6 @@ __device__ __forceinline__ void finverse_from(double2 (&x)[B][E], double2* row, 
     }
 }
 
-// (K + 1) polynomials of M / E lanes each
-template <int N, int K, int E>
-constexpr int fbr_threads() {
-    return (K + 1) * (N / 2 / E);
-}
-// Launch shapes (Device::launch_br_fft picks one by batch size):
-//  * latency, LAT (E = 4; launches of at most one bootstrap per CU): one
-//    workgroup per CU (k = 1: 8 waves; k = 2, N = 1024: 6 waves), 256 VGPRs; the
-//    step's 3 x (k+1) x E Fourier GGSW slots are loaded at the top of the step
-//    (they land during the digits and the forward FFT); the whole psi^k table
-//    (k < 2N: no sign flips on lookup) and two sets of exchange rows (forward + MAC /
-//    inverse: 3 barriers per step instead of 5) in LDS.  k = 1 keeps the lane's
-//    twiddles in registers (TWR); k = 2 reads them from LDS (the 36 GGSW values
-//    take the registers).
-//  * latency with key products (k = 1, KP; launches of at most fft_kpre_): k_key_products forms
-//    every step's K_own, K_oth on the idle CUs first; the rotation loads the 2 E products of
-//    the next unskipped step right after the MAC and nothing inside a step: no key, no psi
-//    table, no slot factors; 491 instructions per wave-step against 722, 148 VGPRs.
-//  * pair (k = 1, B = 2; launches between the latency shape's limit and fft_pair_): the
-//    latency geometry with two bootstraps per workgroup.  One set of key loads, twiddle
-//    registers and barriers serves both (the two workgroups a CU would run side by side
-//    in the throughput shape each load the whole key and wait at their own barriers), and
-//    the two transforms give each other's exchanges independent work.  LDS: both row
-//    sets per bootstrap (139 KB) + the quadrant psi table; twiddles load from global once.
-//  * throughput (k = 1, E = 4: 8 waves, 128 VGPRs; E = 8: 4 waves): two workgroups per
-//    CU (<= 80 KB of LDS each) hide each other's barriers and loads; a slot's
-//    GGSW values are loaded one slot ahead in the MAC; psi^k from the quadrant
-//    table (k < N/2) + quarter turns.  k = 2, N = 1024: E = 8 is one wave per
-//    polynomial (every transform exchange wave-local), three workgroups per CU.
 // LDS slot of psi^k in the monomial table.  A lane's lookup index is k = e L mod 2N
 // with L = 1 + 4 brv(lane slot base), so the 16 lanes of a b128 read group share
 // k mod 32 (every lookup one bank quad: ~13-way conflicts).  Folding bits 5..9 into
@@ -533,39 +443,131 @@ __device__ __forceinline__ void key_products(const double (&bre)[2][NB], const d
         }
     }
 }
-// twiddles in registers (latency shape, k = 1)
-template <int K, bool LAT>
-constexpr bool fbr_twr() {
-    return LAT && K == 1 && FR_LAT_TWR;
-}
-// radix-4 inverse with LDS twiddles: the product table c ca (M/2 entries, indexed like c)
-template <int N, int K, int E, bool LAT>
-constexpr int fbr_twc_entries() {
-    return fradix4<N / 2, E>() && !fbr_twr<K, LAT>() ? N / 4 : 0;
-}
-// LDS of a shape with B bootstraps per workgroup.  The pair shape (B = 2) keeps the
-// latency shape's two row sets per bootstrap (139 KB at k = 1) by dropping the forward
-// twiddle table (its registers load from global memory once) and using the quadrant
-// psi table; its multi-value terms live in the inverse rows after the loop.
-// (KP, the key-products variant of the latency shape: no psi table)
-template <int N, int K, int E, bool LAT, int B = 1, bool KP = false>
-constexpr size_t fbr_smem_bytes() {
-    return 16 * ((LAT ? 2 : 1) * B * (K + 1) * (size_t)FGeo<N / 2, E>::NP + (B == 1 ? (size_t)N / 2 : 0) +
-                 (KP ? 0 : LAT && B == 1 ? 2 * (size_t)N : (size_t)N / 2) + (size_t)fbr_twc_entries<N, K, E, LAT>()) +
-           B * (16 * MAX_OUT + 2 * 1026) + (B == 1 ? 4 * 17 * MAX_OUT : 0) + 2 * 514;
-}
-// workgroups per CU of the throughput shapes (LDS: fbr_smem_bytes * this <= 160 KB)
-template <int K, int E>
-constexpr int fbr_tp_groups() {
-    return K == 1 ? 2 : (E == 8 ? 3 : 2);
-}
-// waves per SIMD the register allocation must allow
-template <int N, int K, int E, bool LAT>
-constexpr int fbr_min_waves() {
-    if (LAT) return 2;
-    if (K == 1) return E == 4 ? 4 : 2;
-    return E == 4 ? 3 : 2;  // k = 2: 2 x 6 waves (E = 4); E = 8: the one-slot-ahead loads need > 168 VGPRs
-}
+// Launch shapes (Device::br_shape picks one by batch size).  What a shape is -- its geometry,
+// thread count, key-load schedule and LDS layout -- is written once, in FbrShape below:
+//  * latency, LAT (E = 4; launches of at most one bootstrap per CU): one
+//    workgroup per CU (k = 1: 8 waves; k = 2, N = 1024: 6 waves), 256 VGPRs; a step's
+//    3 x (k+1) x E Fourier GGSW slots are held in registers, loaded by the schedule KEYS
+//    (two groups a step ahead, the third at the top of the step or late in the forward
+//    FFT); the whole psi^k table (k < 2N: no sign flips on lookup) and two sets of
+//    exchange rows (forward + MAC / inverse: 3 barriers per step instead of 5) in LDS.
+//    k = 1 keeps the lane's twiddles in registers (TWR); k = 2 reads them from LDS (the
+//    36 GGSW values take the registers).
+//  * latency with key products (k = 1, KP; launches of at most fft_kpre_): k_key_products forms
+//    every step's K_own, K_oth on the idle CUs first; the rotation loads the 2 E products of
+//    the next unskipped step right after the MAC and nothing inside a step: no key, no psi
+//    table, no slot factors; 491 instructions per wave-step against 722, 148 VGPRs.
+//  * pair (k = 1, B = 2; launches between the latency shape's limit and fft_pair_): the
+//    latency geometry with two bootstraps per workgroup.  One set of key loads, twiddle
+//    registers and barriers serves both (the two workgroups a CU would run side by side
+//    in the throughput shape each load the whole key and wait at their own barriers), and
+//    the two transforms give each other's exchanges independent work.  LDS: both row
+//    sets per bootstrap (139 KB) + the quadrant psi table; twiddles load from global once.
+//  * throughput (k = 1, E = 4: 8 waves, 128 VGPRs; E = 8: 4 waves): TP_GROUPS workgroups per
+//    CU (<= 80 KB of LDS each) hide each other's barriers and loads; a slot's
+//    GGSW values are loaded one slot ahead in the MAC; psi^k from the quadrant
+//    table (k < N/2) + quarter turns.  k = 2, N = 1024: E = 8 is one wave per
+//    polynomial (every transform exchange wave-local), three workgroups per CU.
+//  * dual (k = 1, FR_FFT_DUAL=1): FbrDualShape, at its kernel.
+//
+// When a step's Fourier GGSW group g is loaded (FbrShape::KEYS.g[g]): a forward phase p >= 0
+// (after its butterflies, before its exchange), or
+constexpr int KEY_AHEAD = -1;  // a step ahead: right after the previous step's MAC, when its registers are dead
+constexpr int KEY_TOP = -2;    // at the top of its own step
+constexpr int KEY_NEVER = -3;  // not by group: slot by slot inside the MAC (throughput), or not at all (KP)
+struct FbrKeySchedule {
+    int g[3];
+    // the group loaded at `when` (KEY_TOP or a forward phase), 3: none
+    constexpr int group_at(int when) const {
+        for (int i = 0; i < 3; ++i)
+            if (g[i] == when) return i;
+        return 3;
+    }
+    // groups 0 .. ahead() - 1 are the ones loaded a step ahead
+    constexpr int ahead() const { return (g[0] == KEY_AHEAD) + (g[1] == KEY_AHEAD) + (g[2] == KEY_AHEAD); }
+    // ahead groups first; every other group at a place of its own, and a forward phase that
+    // exists (< nph): a load after a missing phase would be skipped and the MAC would read
+    // stale key registers
+    constexpr bool ok(int nph) const {
+        for (int i = 0; i < 3; ++i) {
+            if ((g[i] == KEY_AHEAD) != (i < ahead())) return false;
+            if (g[i] != KEY_AHEAD && g[i] != KEY_NEVER && (group_at(g[i]) != i || g[i] >= nph)) return false;
+        }
+        return true;
+    }
+};
+
+template <int N_, int K_, int E_, bool LAT_, int B_ = 1, bool KP_ = false>
+struct FbrShape {
+    static constexpr int N = N_, K = K_, E = E_, B = B_;  // B bootstraps per workgroup
+    static constexpr bool LAT = LAT_, KP = KP_;
+    static constexpr int M = N / 2;
+    using G = FGeo<M, E>;
+    static_assert(fexchanges_conflict_free<M, E>(), "LDS maps must make every exchange conflict-free");
+    static_assert(G::base_matches_geo(), "base<p> must be the index map the LDS-map proofs reason about");
+    static_assert(G::key_slot_matches_idx(), "the Fourier key's lane layout is the last-phase layout");
+    static_assert(!LAT || E == 4, "the latency shape holds a step's GGSW values in registers: E = 4");
+    static_assert(B == 1 || (B == 2 && LAT && K == 1 && E == 4), "pair shape: the k = 1 latency geometry");
+    static_assert(!KP || (LAT && B == 1 && K == 1 && E == 4), "key products: the k = 1 latency shape");
+
+    static constexpr int T = M / E;         // lanes per polynomial
+    static constexpr int NT = (K + 1) * T;  // threads: (K + 1) polynomials of M / E lanes each
+    // waves per SIMD the register allocation must allow (k = 2: 2 x 6 waves (E = 4); E = 8: the
+    // one-slot-ahead loads need > 168 VGPRs)
+    static constexpr int MIN_WAVES = LAT ? 2 : K == 1 ? (E == 4 ? 4 : 2) : (E == 4 ? 3 : 2);
+    static constexpr int TP_GROUPS = K == 1 ? 2 : (E == 8 ? 3 : 2);  // throughput shapes: workgroups per CU
+    static constexpr int NB = E >= 4 ? E / 4 : 1;                    // psi bases per lane (slots m >> 2 share one)
+    static constexpr int LAST = G::NPH - 1, XL = G::XL;
+    static constexpr int LOG2N2 = G::LOG + 2;        // log2(2N)
+    static constexpr bool TWR = LAT && K == 1;       // twiddles in registers
+    static constexpr int BS = (K + 1) * G::NP;       // one bootstrap's exchange rows
+    static constexpr bool PSIQ = !LAT || B > 1;      // psi^k from the quadrant table (k < N/2) + quarter turns
+    static constexpr int NPSI = KP ? 0 : PSIQ ? N / 2 : 2 * N;  // (latency shape: the whole circle, no sign flips)
+    // radix-4 inverse with LDS twiddles: the product table c ca (M/2 entries, indexed like c)
+    static constexpr int NTWC = fradix4<M, E>() && !TWR ? N / 4 : 0;
+
+    // The key-load schedule.  Latency: two groups ahead; the third at the top of the step for
+    // k = 1 and after forward phase 3 for k = 2.  Pair: one group ahead, the second after
+    // forward phase 2 and the third after phase 4, right before the MAC barrier (the pair's 64
+    // live transform values leave no room for a group across the whole transform).  The
+    // measurements behind each entry: tools/README.md, "Retired switches".
+    static constexpr FbrKeySchedule KEYS = !LAT || KP ? FbrKeySchedule{{KEY_NEVER, KEY_NEVER, KEY_NEVER}}
+                                           : B > 1    ? FbrKeySchedule{{KEY_AHEAD, 2, 4}}
+                                           : K == 1   ? FbrKeySchedule{{KEY_AHEAD, KEY_AHEAD, KEY_TOP}}
+                                                      : FbrKeySchedule{{KEY_AHEAD, KEY_AHEAD, 3}};
+    static constexpr int NPF = KEYS.ahead();
+    static_assert(KEYS.ok(G::NPH), "key schedule: ahead groups first, then distinct places that exist");
+
+    // The LDS layout, once: the kernel forms its pointers from these offsets and the host takes
+    // BYTES.  Complex regions (offsets in double2) first, byte regions (offsets in bytes) after.
+    // The pair shape (B = 2) keeps the latency shape's two row sets per bootstrap (139 KB at
+    // k = 1) by dropping the forward twiddle table (its registers load from global memory once)
+    // and using the quadrant psi table; its multi-value terms live in the inverse rows after the
+    // loop.  (KP: no psi table)
+    struct Lds {
+        static constexpr int XBUF = 0;  // B x (K+1) rows of NP complex: bootstrap b, row P at b BS + P NP
+        static constexpr int IBUF = LAT ? XBUF + B * BS : XBUF;  // inverse-transform rows (latency shapes: separate)
+        static constexpr int TW = IBUF + B * BS;                 // M forward twiddles (B = 1)
+        static constexpr int PSI = TW + (B == 1 ? M : 0);        // psi^k, k < NPSI
+        static constexpr int TWC = PSI + NPSI;                   // radix-4 products c ca
+        static constexpr size_t LUT = 16 * (size_t)(TWC + NTWC);  // [B][16 * MAX_OUT]
+        static constexpr size_t ABAR = LUT + B * 16 * MAX_OUT;    // [B][1026] u16: n (<= 1024), zero-padded to even
+        static constexpr size_t ABAR_END = ABAR + B * 2 * 1026;
+        // multi-value terms [B][16 MAX_OUT] u32 and their counts [B][MAX_OUT]
+        static constexpr size_t WTERMS = B == 1 ? ABAR_END : 16 * (size_t)IBUF;
+        static constexpr size_t WCNT = WTERMS + 4 * B * 16 * MAX_OUT;
+        static constexpr size_t WCNT_END = WCNT + 4 * B * MAX_OUT;
+        static constexpr size_t NXT = B == 1 ? WCNT_END : ABAR_END;  // [514] u16 (latency shapes): next unskipped step
+        static constexpr size_t BYTES = NXT + 2 * 514;
+    };
+    static_assert(B == 1 || Lds::WCNT_END <= 16 * (size_t)(Lds::IBUF + B * BS),
+                  "pair shape: the terms inside the inverse rows");
+    static_assert(Lds::BYTES == 16 * (size_t)((LAT ? 2 : 1) * B * BS + (B == 1 ? M : 0) + NPSI + NTWC) +
+                                    B * (16 * MAX_OUT + 2 * 1026) + (B == 1 ? 4 * 17 * MAX_OUT : 0) + 2 * 514,
+                  "LDS total: the end of the last region is the sum of the regions");
+    static_assert(Lds::BYTES <= (LAT ? 160 * 1024 : 160 * 1024 / TP_GROUPS), "LDS per workgroup of the shape");
+};
+
 // Fourier-key loads: buffer loads with the key's resource in SGPRs, the uniform part
 // of the offset (step, GGSW, row, slot) in soffset and the lane's byte offset as the
 // only VGPR operand, so a load costs no VALU address arithmetic (gfx950 raw buffer
@@ -586,21 +588,41 @@ template <int K>
 __device__ __forceinline__ int other_row(int P, int q) {
     return q < P ? q : q + 1;
 }
+// index inside a step's key of Fourier GGSW g, row r, output column c, slot m, lane 0
+// ([g][r][c][m][lane] complex values, T lanes per slot): times 16, the uniform part of a
+// lane's load address
+template <int K, int M, int T>
+__device__ __forceinline__ constexpr uint32_t ggsw_off(int g, int r, int c, int m) {
+    constexpr uint32_t GG = (uint32_t)(K + 1) * (K + 1) * M;  // complex values per Fourier GGSW
+    return g * GG + (uint32_t)(r * (K + 1) + c) * M + (uint32_t)m * T;
+}
+// bytes of a step's three Fourier GGSWs
+template <int K, int M>
+constexpr uint32_t ggsw_step_bytes() {
+    return 3u * 16u * (uint32_t)((K + 1) * (K + 1) * M);
+}
 // the 3 (K+1) Fourier GGSW values of slot m for this lane: [g][own row, other rows...]
-// (Fourier GGSW [r][c][m][lane]: row r, output column c = P; sbase: the step's byte offset)
+// (row r, output column c = P; sbase: the step's byte offset)
 template <int M, int T, int K>
 __device__ __forceinline__ void load_slot(double2 (&B)[3][K + 1], __amdgpu_buffer_rsrc_t rs, uint32_t sbase, int P,
                                           int m, uint32_t lane_off) {
-    constexpr uint32_t GG = (uint32_t)(K + 1) * (K + 1) * M;
 #pragma unroll
     for (int gg = 0; gg < 3; ++gg) {
-        B[gg][0] = bsk_load(rs, lane_off, sbase + 16u * (gg * GG + (uint32_t)(P * (K + 1) + P) * M + (uint32_t)m * T));
+        B[gg][0] = bsk_load(rs, lane_off, sbase + 16u * ggsw_off<K, M, T>(gg, P, P, m));
 #pragma unroll
         for (int q = 0; q < K; ++q)
-            B[gg][1 + q] = bsk_load(
-                rs, lane_off, sbase + 16u * (gg * GG + (uint32_t)(other_row<K>(P, q) * (K + 1) + P) * M + (uint32_t)m * T));
+            B[gg][1 + q] = bsk_load(rs, lane_off, sbase + 16u * ggsw_off<K, M, T>(gg, other_row<K>(P, q), P, m));
     }
 }
+// leaf exponent mod M of the lane's slot m: L(j) = 1 + 4 brv(j) (fft::Tables::leaf, checked
+// against the table in tests/test_fft.py)
+template <class G>
+__device__ __forceinline__ uint32_t leaf_exp(int tl, int m) {
+    return (1u + 4u * (__brev((uint32_t)G::template idx<G::NPH - 1>(tl, m)) >> (32 - G::LOG))) &
+           (uint32_t)((1 << G::LOG) - 1);
+}
+// slot m of a lane has L = Lb + M s_m with s_m = brv2(m & 3), Lb shared by the slots of equal m >> 2
+__device__ __forceinline__ constexpr uint32_t brv2(int m) { return ((m & 1) << 1) | ((m >> 1) & 1); }
 
 // value of the test polynomial at position t < N: the LUT polynomial (box N/16,
 // recentred by half a box, -f(0) in the last half box) or (Delta/2) * sum X^j
@@ -694,34 +716,21 @@ __device__ __forceinline__ void fbr_rotate(const uint64_t* ks, int ks_stride, in
                                            const double2* bsk, const double2* tw_g, const double2* psi_g,
                                            const uint16_t* leaf_g, uint64_t* arena, int slot_stride, const double2* kpre,
                                            const uint64_t* sel = nullptr) {
-    constexpr int M = N / 2;
-    static_assert(!KP || (LAT && B == 1 && K == 1 && E == 4), "key products: the k = 1 latency shape");
+    using S = FbrShape<N, K, E, LAT, B, KP>;
+    using G = typename S::G;
+    using L = typename S::Lds;
     static_assert(!(ACC && KP), "selector launches never take the key-products path");
-    using G = FGeo<M, E>;
-    static_assert(fexchanges_conflict_free<M, E>(), "LDS maps must make every exchange conflict-free");
-    static_assert(G::base_matches_geo(), "base<p> must be the index map the LDS-map proofs reason about");
-    static_assert(G::key_slot_matches_idx(), "the Fourier key's lane layout is the last-phase layout");
-    static_assert(!LAT || E == 4, "the latency shape holds a step's GGSW values in registers: E = 4");
-    static_assert(B == 1 || (B == 2 && LAT && K == 1 && E == 4), "pair shape: the k = 1 latency geometry");
-    constexpr int NB = E >= 4 ? E / 4 : 1;  // psi bases per lane (slots m >> 2 share one)
-    constexpr int T = M / E, NT = (K + 1) * T, LAST = G::NPH - 1, XL = G::XL;
-    constexpr int LOG2N2 = G::LOG + 2;  // log2(2N)
-    constexpr bool TWR = fbr_twr<K, LAT>();  // twiddles in registers
-    constexpr int BS = (K + 1) * G::NP;      // one bootstrap's exchange rows
-    constexpr bool PSIQ = !LAT || B > 1;     // psi^k from the quadrant table (k < N/2) + quarter turns
+    constexpr int M = S::M, T = S::T, NT = S::NT, NB = S::NB, BS = S::BS, LAST = S::LAST, XL = S::XL;
+    constexpr int LOG2N2 = S::LOG2N2, NPSI = S::NPSI, NTWC = S::NTWC, NPF = S::NPF;
+    constexpr bool TWR = S::TWR, PSIQ = S::PSIQ;
     extern __shared__ __attribute__((aligned(16))) double2 fsm[];
-    double2* xbuf = fsm;                  // B x (K+1) rows of NP complex: bootstrap b, row P at b BS + P NP
-    double2* ibuf = LAT ? xbuf + B * BS : xbuf;  // inverse-transform rows (latency shapes: separate)
-    double2* tw = xbuf + (LAT ? 2 : 1) * B * BS;  // M forward twiddles (B = 1)
-    constexpr int NPSI = KP ? 0 : PSIQ ? N / 2 : 2 * N;  // (latency shape: the whole circle, no sign flips)
-    double2* psi = tw + (B == 1 ? M : 0);  // psi^k, k < NPSI
-    double2* twc = psi + NPSI;            // radix-4 products c ca (fbr_twc_entries)
-    constexpr int NTWC = fbr_twc_entries<N, K, E, LAT>();
-    uint8_t* lut = (uint8_t*)(twc + NTWC);                 // [B][16 * MAX_OUT]
-    uint16_t* abar = (uint16_t*)(lut + B * 16 * MAX_OUT);  // [B][1026]: n (<= 1024), zero-padded to even
-    uint32_t* wterms = B == 1 ? (uint32_t*)(abar + 1026) : (uint32_t*)ibuf;  // multi-value terms, [B][16 MAX_OUT]
-    int* wcnt = (int*)(wterms + B * 16 * MAX_OUT);                           // [B][MAX_OUT]
-    uint16_t* nxt = B == 1 ? (uint16_t*)(wcnt + MAX_OUT) : abar + B * 1026;  // (latency shapes) next unskipped step
+    uint8_t* const fsb = (uint8_t*)fsm;
+    double2 *xbuf = fsm + L::XBUF, *ibuf = fsm + L::IBUF, *tw = fsm + L::TW, *psi = fsm + L::PSI, *twc = fsm + L::TWC;
+    uint8_t* lut = fsb + L::LUT;
+    uint16_t* abar = (uint16_t*)(fsb + L::ABAR);
+    uint32_t* wterms = (uint32_t*)(fsb + L::WTERMS);
+    int* wcnt = (int*)(fsb + L::WCNT);
+    uint16_t* nxt = (uint16_t*)(fsb + L::NXT);
 
     const int tid = threadIdx.x;
     const int P = __builtin_amdgcn_readfirstlane(tid / T), tl = tid % T;  // wave-uniform polynomial
@@ -760,12 +769,9 @@ __device__ __forceinline__ void fbr_rotate(const uint64_t* ks, int ks_stride, in
         if (tid == 0) ab[n] = 0;  // pad an odd n
         bbar[b] = mod_switch(in[b][n], LOG2N2);
     }
-    // leaf exponents mod M of this lane's slot bases (slots 4b): L(j) = 1 + 4 brv(j)
-    // (fft::Tables::leaf, checked against the table in tests/test_fft.py)
-    uint32_t Lb[NB];
+    uint32_t Lb[NB];  // leaf exponents of this lane's slot bases (slots 4b)
 #pragma unroll
-    for (int bb = 0; bb < NB; ++bb)
-        Lb[bb] = (1u + 4u * (__brev((uint32_t)G::template idx<LAST>(tl, 4 * bb)) >> (32 - G::LOG))) & (uint32_t)(M - 1);
+    for (int bb = 0; bb < NB; ++bb) Lb[bb] = leaf_exp<G>(tl, 4 * bb);
     __syncthreads();
 
     // accumulator (f64 torus, fft.h), natural order: lane holds coefficients j and
@@ -815,7 +821,6 @@ __device__ __forceinline__ void fbr_rotate(const uint64_t* ks, int ks_stride, in
     const double2* orow_bl[K];  // the other polynomials' rows, ascending
 #pragma unroll
     for (int q = 0; q < K; ++q) orow_bl[q] = xbuf + other_row<K>(P, q) * G::NP + G::template at<XL>(bl);
-    constexpr uint32_t GG = (uint32_t)(K + 1) * (K + 1) * M;  // complex values per Fourier GGSW: [r][c][m][lane]
     const __amdgpu_buffer_rsrc_t rs = bsk_rsrc(bsk);
     const uint32_t lane_off = 16u * (uint32_t)tl;
     const int steps = (n + 1) / 2;
@@ -825,7 +830,7 @@ __device__ __forceinline__ void fbr_rotate(const uint64_t* ks, int ks_stride, in
     double2 gv[3][K + 1][LAT && !KP ? E : 1];
     double2 kv[K + 1][KP ? E : 1];
     FTwr<M, TWR ? E : 2> twr;
-    if constexpr (TWR) ftw_load_phase<M, E, 0, B == 1 ? false : FR_TW_SGPR_PAIR>(twr, B == 1 ? tw : tw_g, tl);
+    if constexpr (TWR) ftw_load_phase<M, E, 0, (B > 1)>(twr, B == 1 ? tw : tw_g, tl);  // (pair: wave-uniform ones in SGPRs)
 #ifdef FR_BR_TIMING
     uint64_t tseg[6] = {0, 0, 0, 0, 0, 0};
     uint64_t tlast = __builtin_amdgcn_s_memtime();
@@ -834,16 +839,14 @@ __device__ __forceinline__ void fbr_rotate(const uint64_t* ks, int ks_stride, in
     // latency shape: GGSW g's slots of step tt for this lane ([g][own, other rows][m])
     auto load_ggsw = [&](int gg, int tt) {
         if constexpr (!KP) {
-            const uint32_t sb = (uint32_t)__builtin_amdgcn_readfirstlane(tt) * (3u * GG * 16u);
+            const uint32_t sb = (uint32_t)__builtin_amdgcn_readfirstlane(tt) * ggsw_step_bytes<K, M>();
 #pragma unroll
             for (int m = 0; m < E; ++m) {
-                gv[gg][0][m] =
-                    bsk_load(rs, lane_off, sb + 16u * (gg * GG + (uint32_t)(P * (K + 1) + P) * M + (uint32_t)m * T));
+                gv[gg][0][m] = bsk_load(rs, lane_off, sb + 16u * ggsw_off<K, M, T>(gg, P, P, m));
 #pragma unroll
                 for (int q = 0; q < K; ++q)
-                    gv[gg][1 + q][m] = bsk_load(
-                        rs, lane_off,
-                        sb + 16u * (gg * GG + (uint32_t)(other_row<K>(P, q) * (K + 1) + P) * M + (uint32_t)m * T));
+                    gv[gg][1 + q][m] =
+                        bsk_load(rs, lane_off, sb + 16u * ggsw_off<K, M, T>(gg, other_row<K>(P, q), P, m));
             }
         }
     };
@@ -860,7 +863,7 @@ __device__ __forceinline__ void fbr_rotate(const uint64_t* ks, int ks_stride, in
                     kv[r][m] = bsk_load(rk, lane_off, sb + 16u * (uint32_t)(((P * (K + 1) + r) * E + m) * T));
         }
     };
-    // latency shape, LATPF: groups 0 .. NPF-1 of a step's key values are loaded one
+    // latency shape, LATPF: groups 0 .. NPF-1 of a step's key values (S::KEYS) are loaded one
     // step ahead -- right after the previous step's MAC, when their registers are dead --
     // so that they have the inverse FFT, the accumulate and the forward FFT to land (a
     // single CU streams ~50 GB/s of key at 3.9 us per step); the others across the
@@ -868,7 +871,6 @@ __device__ __forceinline__ void fbr_rotate(const uint64_t* ks, int ks_stride, in
     // control flow around the prefetch, which keeps it after the MAC's last use).
     // KP: the whole of the next unskipped step's products in that place, nothing loaded inside
     // a step.
-    constexpr int NPF = KP ? 0 : LAT ? (B > 1 ? FR_PAIR_PF : K == 1 ? FR_LAT_PF : FR_LAT_PF2) : 0;
     constexpr bool LATPF = NPF > 0;
     // step t is skipped when every bootstrap's pair is (0, 0): X^0 acc - acc = 0.  The pair
     // shape runs a step that is zero for one bootstrap only: its factors c - 1 are exact
@@ -894,23 +896,10 @@ __device__ __forceinline__ void fbr_rotate(const uint64_t* ks, int ks_stride, in
         if (idle(t)) continue;  // (uniform branch)
         BR_STAMP(0);
         // the step's byte offset in the key (uniform: soffset of every load)
-        const uint32_t sbase = (uint32_t)__builtin_amdgcn_readfirstlane(t) * (3u * GG * 16u);
-        // groups NPF.. of this step: G_TOP at the top of the step, G_L1 / G_L2 after forward
-        // phases FR_LAT_LOAD1 / FR_LAT_LOAD2 (3: none).  k = 1, NPF = 2: the third group at the
-        // top (tools/ab_libs.sh: 1.34 ms; after forward phase 0 / 2 / 3: 1.33 / 1.38 / 1.38 ms;
-        // after the previous inverse: 1.35 ms); k = 2 keeps it after phase 3 (1.67 vs 1.71 ms)
-        // The pair shape (NPF = 1) loads its second group after forward phase FR_PAIR_LOAD and
-        // its third after FR_PAIR_LOAD2 = 4, right before the MAC barrier (the pair's 64 live
-        // transform values leave no room for a group across the whole transform).
-        constexpr int G_TOP = !LAT || KP || B > 1 ? 3 : (NPF < 2 || K == 1) ? NPF : 3;
-        constexpr int G_L1 = !LAT || KP ? 3 : B > 1 ? NPF : G_TOP + 1 < 3 ? G_TOP + 1 : 3;
-        constexpr int G_L2 = !LAT || KP ? 3 : B > 1 ? (NPF + 1 < 3 ? NPF + 1 : 3) : G_TOP == 3 ? NPF : G_TOP + 2 < 3 ? G_TOP + 2 : 3;
-        constexpr int PH_L1 = B > 1 ? FR_PAIR_LOAD : FR_LAT_LOAD1;
-        constexpr int PH_L2 = B > 1 ? FR_PAIR_LOAD2 : FR_LAT_LOAD2;
-        // a group loaded after a forward phase needs that phase to exist: an out-of-range
-        // -D knob would skip the load and leave the MAC reading stale key registers
-        static_assert(G_L1 >= 3 || PH_L1 < G::NPH, "FR_PAIR_LOAD / FR_LAT_LOAD1 past the last forward phase");
-        static_assert(G_L2 >= 3 || PH_L2 < G::NPH, "FR_PAIR_LOAD2 / FR_LAT_LOAD2 past the last forward phase");
+        const uint32_t sbase = (uint32_t)__builtin_amdgcn_readfirstlane(t) * ggsw_step_bytes<K, M>();
+        // groups NPF.. of this step, where S::KEYS places them: here, or after a forward phase
+        // (the group as a constant of its own: looked up in load_ggsw's argument, gv went to scratch)
+        constexpr int G_TOP = S::KEYS.group_at(KEY_TOP);
         if constexpr (G_TOP < 3) {
             __builtin_amdgcn_sched_barrier(0);
             load_ggsw(G_TOP, t);
@@ -941,20 +930,13 @@ __device__ __forceinline__ void fbr_rotate(const uint64_t* ks, int ks_stride, in
             for (int m = 0; m < E; ++m)
                 x[b][m] = make_double2(fft::acc_digit<23>(alo[b][m]), fft::acc_digit<23>(ahi[b][m]));
         BR_STAMP(1);
-        // 2. forward FFT (latency shape: GGSW groups 1 and 2 issued at phase boundaries)
+        // 2. forward FFT (latency shapes: the key groups that S::KEYS places after a phase)
         fforward_from<M, E, 0, LAT, TWR, B, BS>(x, row, twr, tw, tl, [&](auto ph) {
-            if constexpr (LAT) {
-                constexpr int p = decltype(ph)::value;
-                if constexpr (p == PH_L1 && G_L1 < 3) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    load_ggsw(G_L1, t);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                if constexpr (p == PH_L2 && G_L2 < 3) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    load_ggsw(G_L2, t);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+            constexpr int g = S::KEYS.group_at(decltype(ph)::value);
+            if constexpr (g < 3) {
+                __builtin_amdgcn_sched_barrier(0);
+                load_ggsw(g, t);
+                __builtin_amdgcn_sched_barrier(0);
             }
         });
         BR_STAMP(2);
@@ -1001,7 +983,7 @@ __device__ __forceinline__ void fbr_rotate(const uint64_t* ks, int ks_stride, in
 #pragma unroll
                     for (int q = 0; q < K; ++q) kxr[q] = kv[1 + q][m].x, kxi[q] = kv[1 + q][m].y;
                 } else {
-                    const uint32_t sm = ((m & 1) << 1) | ((m >> 1) & 1);  // brv2(m & 3)
+                    const uint32_t sm = brv2(m);
                     auto key_at = [&](int gg, int r) __attribute__((always_inline)) {
                         return LAT ? gv[gg][r][LAT ? m : 0] : Bc[gg][r];
                     };
@@ -1072,7 +1054,7 @@ __device__ __forceinline__ void fbr_rotate(const uint64_t* ks, int ks_stride, in
 }
 
 template <int N, int K, int E, bool LAT, int B = 1>
-__global__ void __launch_bounds__((fbr_threads<N, K, E>()), (fbr_min_waves<N, K, E, LAT>()))
+__global__ void __launch_bounds__((FbrShape<N, K, E, LAT, B>::NT), (FbrShape<N, K, E, LAT, B>::MIN_WAVES))
 k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const DevGate* __restrict__ gates,
                    int n_gates, const double2* __restrict__ bsk, const double2* __restrict__ tw_g,
                    const double2* __restrict__ psi_g, const uint16_t* __restrict__ leaf_g, uint64_t* __restrict__ arena,
@@ -1084,7 +1066,7 @@ k_blind_rotate_fft(const uint64_t* __restrict__ ks, int ks_stride, int n, const 
 // kernel of its own name with the same <N, K, E, LAT, B>, so tools that read the shape off a
 // kernel's template arguments (tools/pmc_summary.py) read it as a latency-shape launch.
 template <int N, int K, int E, bool LAT, int B = 1>
-__global__ void __launch_bounds__((fbr_threads<N, K, E>()), (fbr_min_waves<N, K, E, LAT>()))
+__global__ void __launch_bounds__((FbrShape<N, K, E, LAT, B>::NT), (FbrShape<N, K, E, LAT, B>::MIN_WAVES))
 k_blind_rotate_fft_kp(const uint64_t* __restrict__ ks, int ks_stride, int n, const DevGate* __restrict__ gates,
                       int n_gates, const double2* __restrict__ tw_g, uint64_t* __restrict__ arena, int slot_stride,
                       const double2* __restrict__ kpre) {
@@ -1095,7 +1077,7 @@ k_blind_rotate_fft_kp(const uint64_t* __restrict__ ks, int ks_stride, int n, con
 // The selector variant of every shape (ACC), after the same pattern: kernels of their own name
 // with the shape's <N, K, E, LAT, B>, and the selector table as one more argument.
 template <int N, int K, int E, bool LAT, int B = 1>
-__global__ void __launch_bounds__((fbr_threads<N, K, E>()), (fbr_min_waves<N, K, E, LAT>()))
+__global__ void __launch_bounds__((FbrShape<N, K, E, LAT, B>::NT), (FbrShape<N, K, E, LAT, B>::MIN_WAVES))
 k_blind_rotate_fft_acc(const uint64_t* __restrict__ ks, int ks_stride, int n, const DevGate* __restrict__ gates,
                        int n_gates, const double2* __restrict__ bsk, const double2* __restrict__ tw_g,
                        const double2* __restrict__ psi_g, const uint16_t* __restrict__ leaf_g,
@@ -1112,30 +1094,31 @@ k_blind_rotate_fft_acc(const uint64_t* __restrict__ ks, int ks_stride, int n, co
 // contiguous.  The key is read once per launch whatever the batch; the steps are independent,
 // so the grid fills the CUs the latency shape leaves idle.
 template <int N>
-__global__ void __launch_bounds__(N / 8)
+__global__ void __launch_bounds__((FbrShape<N, 1, 4, true>::T))
 k_key_products(const uint64_t* __restrict__ ks, int ks_stride, int n, int n_gates, const double2* __restrict__ bsk,
                const double2* __restrict__ psi_g, double2* __restrict__ kpre) {
-    constexpr int K = 1, E = 4, M = N / 2, T = M / E;
-    using G = FGeo<M, E>;
-    static_assert(G::key_slot_matches_idx(), "the Fourier key's lane layout is the last-phase layout");
-    constexpr int LAST = G::NPH - 1, LOG2N2 = G::LOG + 2;
-    constexpr uint32_t GG = (uint32_t)(K + 1) * (K + 1) * M;
+    using S = FbrShape<N, 1, 4, true>;  // the lanes and key loads of the latency shape's polynomial
+    using G = typename S::G;
+    constexpr int K = S::K, E = S::E, M = S::M, T = S::T, LOG2N2 = S::LOG2N2;
+    constexpr uint32_t GG = (uint32_t)(K + 1) * (K + 1) * M;  // complex values per Fourier GGSW
     __shared__ __attribute__((aligned(16))) double2 psi[N / 2];  // quadrant table psi^k, k < N/2
     const int tl = threadIdx.x, t = (int)blockIdx.x, P = (int)blockIdx.y;
     const int steps = (n + 1) / 2;
     for (int i = tl; i < N / 2; i += T) psi[psi_slot(i)] = psi_g[i];
     const __amdgpu_buffer_rsrc_t rs = bsk_rsrc(bsk);
-    const uint32_t lane_off = 16u * (uint32_t)tl, sb = (uint32_t)t * (3u * GG * 16u);
+    const uint32_t lane_off = 16u * (uint32_t)tl, sb = (uint32_t)t * ggsw_step_bytes<K, M>();
     double2 gv[3][K + 1][E];
 #pragma unroll
     for (int gg = 0; gg < 3; ++gg)
 #pragma unroll
         for (int m = 0; m < E; ++m) {
+            // (ggsw_off, written out: through the helper this kernel's scalar address arithmetic
+            // compiles to other instructions)
             gv[gg][0][m] = bsk_load(rs, lane_off, sb + 16u * (gg * GG + (uint32_t)(P * (K + 1) + P) * M + (uint32_t)m * T));
             gv[gg][1][m] = bsk_load(
                 rs, lane_off, sb + 16u * (gg * GG + (uint32_t)(other_row<K>(P, 0) * (K + 1) + P) * M + (uint32_t)m * T));
         }
-    const uint32_t Lb = (1u + 4u * (__brev((uint32_t)G::template idx<LAST>(tl, 0)) >> (32 - G::LOG))) & (uint32_t)(M - 1);
+    const uint32_t Lb = leaf_exp<G>(tl, 0);
     __syncthreads();
     for (int b = 0; b < n_gates; ++b) {
         const uint64_t* in = ks + (size_t)b * ks_stride;
@@ -1148,7 +1131,7 @@ k_key_products(const uint64_t* __restrict__ ks, int ks_stride, int n, int n_gate
         double2* out = kpre + (((size_t)b * steps + t) * (K + 1) + P) * ((K + 1) * M) + tl;
 #pragma unroll
         for (int m = 0; m < E; ++m) {
-            const uint32_t sm = ((m & 1) << 1) | ((m >> 1) & 1);  // brv2(m & 3)
+            const uint32_t sm = brv2(m);
             double kor, koi, kxr[K], kxi[K];
             key_products<K>(br, bi, 0, ei, ej, sm, [&](int gg, int r) __attribute__((always_inline)) { return gv[gg][r][m]; },
                             kor, koi, kxr, kxi);
@@ -1180,36 +1163,50 @@ extern template __global__ void k_blind_rotate_fft_acc<2048, 1, 4, true, 2>(cons
 // barrier: the lane computes both output columns from all four (r, c) key values of its
 // slots (the same operation sequence per output as the other shapes: bit-identical).  The
 // forward and inverse share one row set (pre-barriers, as the throughput shape: 4 barriers
-// per step), 54 KB of LDS per workgroup.  Each workgroup streams the whole key (the pair
+// per step), 54 KB of LDS per workgroup (FbrDualShape::Lds).  Each workgroup streams the whole key (the pair
 // shape shares it between two bootstraps); the two workgroups of a CU have their own
 // barriers, so one computes while the other waits.
+template <int N_>
+struct FbrDualShape {
+    using C = FbrShape<N_, 1, 4, false>;  // the k = 1, E = 4 geometry: M, T, G and its proofs
+    using G = typename C::G;
+    static_assert(fradix4<C::M, C::E>(), "dual shape: the k = 1 geometry (radix-4 inverse)");
+    static constexpr int N = N_, K = 1, E = 4, M = C::M, T = C::T, LAST = C::LAST, LOG2N2 = C::LOG2N2;
+    static constexpr int B = 2;       // the polynomials of the one bootstrap
+    static constexpr int NT = T;      // threads
+    static constexpr int BS = G::NP;  // polynomial P's exchange row at P BS
+    static constexpr int GROUPS = 2;  // workgroups per CU
+    struct Lds {                      // complex regions (offsets in double2), then byte regions (in bytes)
+        static constexpr int XBUF = 0;
+        static constexpr int PSI = XBUF + B * BS;  // quadrant table psi^k, k < N/2
+        static constexpr size_t LUT = 16 * (size_t)(PSI + N / 2);
+        static constexpr size_t ABAR = LUT + 16 * MAX_OUT;
+        static constexpr size_t WTERMS = ABAR + 2 * 1026;
+        static constexpr size_t WCNT = WTERMS + 4 * 16 * MAX_OUT;
+        static constexpr size_t BYTES = WCNT + 4 * MAX_OUT;
+    };
+    static_assert(Lds::BYTES == 16 * (size_t)(B * BS + N / 2) + 16 * MAX_OUT + 2 * 1026 + 4 * 17 * MAX_OUT,
+                  "LDS total: the end of the last region is the sum of the regions");
+    static_assert(Lds::BYTES <= 160 * 1024 / GROUPS, "dual shape: two workgroups per CU");
+};
 template <int N>
-constexpr size_t fbr_dual_smem_bytes() {
-    return 16 * (2 * (size_t)FGeo<N / 2, 4>::NP + (size_t)N / 2) + 16 * MAX_OUT + 2 * 1026 + 4 * 16 * MAX_OUT +
-           4 * MAX_OUT;
-}
-template <int N>
-__global__ void __launch_bounds__(N / 8, 2)
+__global__ void __launch_bounds__((FbrDualShape<N>::NT), (FbrDualShape<N>::GROUPS))
 k_blind_rotate_fft_dual(const uint64_t* __restrict__ ks, int ks_stride, int n, const DevGate* __restrict__ gates,
                         int n_gates, const double2* __restrict__ bsk, const double2* __restrict__ tw_g,
                         const double2* __restrict__ psi_g, const uint16_t* __restrict__ leaf_g,
                         uint64_t* __restrict__ arena, int slot_stride) {
-    constexpr int K = 1, E = 4, M = N / 2, B = 2;
-    using G = FGeo<M, E>;
-    static_assert(fexchanges_conflict_free<M, E>(), "LDS maps must make every exchange conflict-free");
-    static_assert(G::base_matches_geo(), "base<p> must be the index map the LDS-map proofs reason about");
-    static_assert(G::key_slot_matches_idx(), "the Fourier key's lane layout is the last-phase layout");
-    static_assert(fradix4<M, E>(), "dual shape: the k = 1 geometry (radix-4 inverse)");
-    constexpr int T = M / E, NT = T, LAST = G::NPH - 1;
-    constexpr int LOG2N2 = G::LOG + 2;
-    constexpr int BS = G::NP;  // polynomial P's exchange row at P BS
+    using S = FbrDualShape<N>;
+    using G = typename S::G;
+    using L = typename S::Lds;
+    constexpr int K = S::K, E = S::E, M = S::M, B = S::B, T = S::T, NT = S::NT, LAST = S::LAST, BS = S::BS;
+    constexpr int LOG2N2 = S::LOG2N2;
     extern __shared__ __attribute__((aligned(16))) double2 fsm[];
-    double2* xbuf = fsm;
-    double2* psi = xbuf + B * BS;  // quadrant table psi^k, k < N/2
-    uint8_t* lut = (uint8_t*)(psi + N / 2);
-    uint16_t* abar = (uint16_t*)(lut + 16 * MAX_OUT);
-    uint32_t* wterms = (uint32_t*)(abar + 1026);
-    int* wcnt = (int*)(wterms + 16 * MAX_OUT);
+    uint8_t* const fsb = (uint8_t*)fsm;
+    double2 *xbuf = fsm + L::XBUF, *psi = fsm + L::PSI;
+    uint8_t* lut = fsb + L::LUT;
+    uint16_t* abar = (uint16_t*)(fsb + L::ABAR);
+    uint32_t* wterms = (uint32_t*)(fsb + L::WTERMS);
+    int* wcnt = (int*)(fsb + L::WCNT);
 
     const int tl = threadIdx.x;
     const int gi = (int)blockIdx.x;
@@ -1220,7 +1217,7 @@ k_blind_rotate_fft_dual(const uint64_t* __restrict__ ks, int ks_stride, int n, c
     for (int i = tl; i < n; i += NT) abar[i] = (uint16_t)mod_switch(in[i], LOG2N2);
     if (tl == 0) abar[n] = 0;
     const uint32_t bbar = mod_switch(in[n], LOG2N2);
-    const uint32_t Lb = (1u + 4u * (__brev((uint32_t)G::template idx<LAST>(tl, 0)) >> (32 - G::LOG))) & (uint32_t)(M - 1);
+    const uint32_t Lb = leaf_exp<G>(tl, 0);
     __syncthreads();
 
     double alo[B][E], ahi[B][E];
@@ -1243,12 +1240,11 @@ k_blind_rotate_fft_dual(const uint64_t* __restrict__ ks, int ks_stride, int n, c
             }
         }
     }
-    constexpr uint32_t GG = (uint32_t)(K + 1) * (K + 1) * M;
     const __amdgpu_buffer_rsrc_t rs = bsk_rsrc(bsk);
     const uint32_t lane_off = 16u * (uint32_t)tl;
     const int steps = (n + 1) / 2;
     FTwr<M, E> twr;
-    ftw_load_phase<M, E, 0, FR_TW_SGPR_PAIR>(twr, tw_g, tl);
+    ftw_load_phase<M, E, 0, true>(twr, tw_g, tl);  // (wave-uniform twiddles in SGPRs, as the pair)
     // slot m's key values [g][r][c] (Fourier GGSW [r][c][m][lane])
     auto load_keys = [&](double2 (&Bk)[3][2][2], uint32_t sbase, int m) {
 #pragma unroll
@@ -1257,12 +1253,11 @@ k_blind_rotate_fft_dual(const uint64_t* __restrict__ ks, int ks_stride, int n, c
             for (int r = 0; r < 2; ++r)
 #pragma unroll
                 for (int c = 0; c < 2; ++c)
-                    Bk[gg][r][c] =
-                        bsk_load(rs, lane_off, sbase + 16u * (gg * GG + (uint32_t)(r * 2 + c) * M + (uint32_t)m * T));
+                    Bk[gg][r][c] = bsk_load(rs, lane_off, sbase + 16u * ggsw_off<K, M, T>(gg, r, c, m));
     };
     for (int t = 0; t < steps; ++t) {
         if ((abar[2 * t] | abar[2 * t + 1]) == 0) continue;  // (uniform) X^0 acc - acc = 0
-        const uint32_t sbase = (uint32_t)__builtin_amdgcn_readfirstlane(t) * (3u * GG * 16u);
+        const uint32_t sbase = (uint32_t)__builtin_amdgcn_readfirstlane(t) * ggsw_step_bytes<K, M>();
         double2 Bc[3][2][2];
         load_keys(Bc, sbase, 0);  // slot 0 lands during the digits and the forward FFT
         const uint32_t ei = __builtin_amdgcn_readfirstlane((uint32_t)abar[2 * t]);
@@ -1287,7 +1282,7 @@ k_blind_rotate_fft_dual(const uint64_t* __restrict__ ks, int ks_stride, int n, c
             double2 Bn[3][2][2];
             if (m + 1 < E) load_keys(Bn, sbase, m + 1);
             __builtin_amdgcn_sched_barrier(0);
-            const uint32_t sm = ((m & 1) << 1) | ((m >> 1) & 1);  // brv2(m & 3)
+            const uint32_t sm = brv2(m);
             double cr[3], ci[3];
 #pragma unroll
             for (int h = 1; h < 3; ++h) slot_factor(bre[h - 1], bim[h - 1], h == 1 ? ei : ej, sm, cr[h], ci[h]);
@@ -1357,14 +1352,15 @@ constexpr bool fft_supported(int K, int N, int E) {
     return (K == 1 && N == 2048 && E == 4) || (K == 2 && N == 1024 && (E == 4 || E == 8));
 }
 
+// the dynamic LDS a shape's kernel may ask for: the shape's own total
+template <class S, class Kernel>
+static void fft_attr(Kernel kernel) {
+    HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S::Lds::BYTES));
+}
 template <int N, int K, int E, bool LAT, int B = 1>
 static void fft_attr() {
-    static_assert(fbr_smem_bytes<N, K, E, LAT, B>() <= (LAT ? 160 * 1024 : 160 * 1024 / fbr_tp_groups<K, E>()),
-                  "LDS per workgroup of the shape");
-    HIP_CHECK(hipFuncSetAttribute((const void*)k_blind_rotate_fft<N, K, E, LAT, B>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)fbr_smem_bytes<N, K, E, LAT, B>()));
-    HIP_CHECK(hipFuncSetAttribute((const void*)k_blind_rotate_fft_acc<N, K, E, LAT, B>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)fbr_smem_bytes<N, K, E, LAT, B>()));
+    fft_attr<FbrShape<N, K, E, LAT, B>>(k_blind_rotate_fft<N, K, E, LAT, B>);
+    fft_attr<FbrShape<N, K, E, LAT, B>>(k_blind_rotate_fft_acc<N, K, E, LAT, B>);
 }
 
 // run body(N, K) with the compile-time ring dimensions of the parameters
@@ -1391,13 +1387,8 @@ void Device::init_fft() {
         fft_attr<N, K, 4, false>();
         if constexpr (K == 1) {
             fft_attr<N, K, 4, true, 2>();
-            static_assert(fbr_smem_bytes<N, K, 4, true, 1, true>() <= 160 * 1024, "LDS per workgroup of the shape");
-            HIP_CHECK(hipFuncSetAttribute((const void*)k_blind_rotate_fft_kp<N, K, 4, true, 1>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)fbr_smem_bytes<N, K, 4, true, 1, true>()));
-            static_assert(fbr_dual_smem_bytes<N>() <= 80 * 1024, "dual shape: two workgroups per CU");
-            HIP_CHECK(hipFuncSetAttribute((const void*)k_blind_rotate_fft_dual<N>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)fbr_dual_smem_bytes<N>()));
+            fft_attr<FbrShape<N, K, 4, true, 1, true>>(k_blind_rotate_fft_kp<N, K, 4, true, 1>);
+            fft_attr<FbrDualShape<N>>(k_blind_rotate_fft_dual<N>);
         }
         if constexpr (fft_supported(K, N, 8)) fft_attr<N, K, 8, false>();
     });
@@ -1442,37 +1433,30 @@ void Device::launch_br_fft(const DevGate* d_gates, const uint64_t* d_ks, size_t 
     // (a selector launch: the table bound to the lane as one more)
     const uint64_t* sel = cur().sel;
     if (acc && !sel) throw Error(FR_ERR_INVALID, "selector jobs: no selector table bound");
-    auto launch = [&](auto kernel, size_t grid, int threads, size_t lds, int E, auto... more) {
-        hipExtLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), (uint32_t)lds, s, ev_start, ev_stop, 0, d_ks,
-                              p_.ks_stride(), p_.n, d_gates, (int)n, (const double2*)d_fbsk_[fbsk_index(E)].get(),
-                              (const double2*)d_ftw_.get(), (const double2*)d_fqt_.get(),
-                              (const uint16_t*)d_fleaf_.get(), d_arena_.get(), p_.slot_stride(), more...);
+    // (threads, LDS bytes and the key's lane layout E: the shape's own constants)
+    auto launch = [&](auto shape, auto kernel, size_t grid, auto... more) {
+        using S = decltype(shape);
+        hipExtLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(S::NT), (uint32_t)S::Lds::BYTES, s, ev_start, ev_stop, 0,
+                              d_ks, p_.ks_stride(), p_.n, d_gates, (int)n,
+                              (const double2*)d_fbsk_[fbsk_index(S::E)].get(), (const double2*)d_ftw_.get(),
+                              (const double2*)d_fqt_.get(), (const uint16_t*)d_fleaf_.get(), d_arena_.get(),
+                              p_.slot_stride(), more...);
     };
     fft_dispatch(p_, [&](auto nc, auto kc) {
         constexpr int N = decltype(nc)::value, K = decltype(kc)::value;
-        auto go = [&](auto ec, auto lat, auto bc) {
-            constexpr int E = decltype(ec)::value;
-            constexpr bool LAT = decltype(lat)::value;
-            constexpr int B = decltype(bc)::value;
-            if constexpr (fft_supported(K, N, E) && (B == 1 || K == 1)) {
-                if (acc)
-                    launch(k_blind_rotate_fft_acc<N, K, E, LAT, B>, (n + B - 1) / B, fbr_threads<N, K, E>(),
-                           fbr_smem_bytes<N, K, E, LAT, B>(), E, sel);
-                else
-                    launch(k_blind_rotate_fft<N, K, E, LAT, B>, (n + B - 1) / B, fbr_threads<N, K, E>(),
-                           fbr_smem_bytes<N, K, E, LAT, B>(), E);
-            }
+        auto go = [&](auto shape) {
+            using S = decltype(shape);
+            const size_t grid = (n + S::B - 1) / S::B;
+            if (acc) launch(shape, k_blind_rotate_fft_acc<N, K, S::E, S::LAT, S::B>, grid, sel);
+            else launch(shape, k_blind_rotate_fft<N, K, S::E, S::LAT, S::B>, grid);
         };
-        using I4 = std::integral_constant<int, 4>;
-        using I8 = std::integral_constant<int, 8>;
-        using B1 = std::integral_constant<int, 1>;
-        // small launches (at most one bootstrap per CU): the latency shape; the smallest
-        // (k = 1, at most fft_kpre_) as the producer of their key products, then the variant that
-        // loads them, in stream order: the pair of kernels lies between ev_start and ev_stop, so
-        // the producer's time counts as blind rotation
-        // (selector launches: the shape by count alone -- never the key products, never the dual)
-        if (n <= fft_small_ && n <= fft_kpre_ && K == 1 && !acc) {
+        switch (br_shape(n, acc)) {
+        case BrShape::LatencyKP:
+            // the producer of the launch's key products, then the variant that loads them, in
+            // stream order: the pair of kernels lies between ev_start and ev_stop, so the
+            // producer's time counts as blind rotation
             if constexpr (K == 1) {
+                using S = FbrShape<N, K, 4, true, 1, true>;
                 const int steps = (p_.n + 1) / 2;
                 const size_t per = (size_t)steps * (kpre_step_bytes<N, K>() / 8);  // doubles per bootstrap
                 gpu::DevBuf<double>& kpre = cur().kpre;
@@ -1480,22 +1464,28 @@ void Device::launch_br_fft(const DevGate* d_gates, const uint64_t* d_ks, size_t 
                     HIP_CHECK(hipStreamSynchronize(s));  // the lane's queued rotations read the old scratch
                     kpre.alloc(n * per);
                 }
-                hipExtLaunchKernelGGL(k_key_products<N>, dim3((unsigned)steps, K + 1), dim3(N / 8), 0, s, ev_start,
+                hipExtLaunchKernelGGL(k_key_products<N>, dim3((unsigned)steps, K + 1), dim3(S::T), 0, s, ev_start,
                                       nullptr, 0, d_ks, p_.ks_stride(), p_.n, (int)n,
-                                      (const double2*)d_fbsk_[fbsk_index(4)].get(), (const double2*)d_fqt_.get(),
+                                      (const double2*)d_fbsk_[fbsk_index(S::E)].get(), (const double2*)d_fqt_.get(),
                                       (double2*)kpre.get());
-                hipExtLaunchKernelGGL((k_blind_rotate_fft_kp<N, K, 4, true, 1>), dim3((unsigned)n),
-                                      dim3(fbr_threads<N, K, 4>()), (uint32_t)fbr_smem_bytes<N, K, 4, true, 1, true>(), s,
-                                      nullptr, ev_stop, 0, d_ks, p_.ks_stride(), p_.n, d_gates, (int)n,
-                                      (const double2*)d_ftw_.get(), d_arena_.get(), p_.slot_stride(),
+                hipExtLaunchKernelGGL((k_blind_rotate_fft_kp<N, K, 4, true, 1>), dim3((unsigned)n), dim3(S::NT),
+                                      (uint32_t)S::Lds::BYTES, s, nullptr, ev_stop, 0, d_ks, p_.ks_stride(), p_.n,
+                                      d_gates, (int)n, (const double2*)d_ftw_.get(), d_arena_.get(), p_.slot_stride(),
                                       (const double2*)kpre.get());
             }
-        } else if (n <= fft_small_) go(I4{}, std::true_type{}, B1{});
-        else if (n <= fft_pair_ && K == 1 && fft_dual_ && !acc) {
-            if constexpr (K == 1) launch(k_blind_rotate_fft_dual<N>, n, N / 8, fbr_dual_smem_bytes<N>(), 4);
-        } else if (n <= fft_pair_) go(I4{}, std::true_type{}, std::integral_constant<int, 2>{});  // (k = 1)
-        else if (fft_e_ == 4) go(I4{}, std::false_type{}, B1{});
-        else go(I8{}, std::false_type{}, B1{});
+            break;
+        case BrShape::Latency: go(FbrShape<N, K, 4, true>{}); break;
+        case BrShape::Dual:
+            if constexpr (K == 1) launch(FbrDualShape<N>{}, k_blind_rotate_fft_dual<N>, n);
+            break;
+        case BrShape::Pair:
+            if constexpr (K == 1) go(FbrShape<N, K, 4, true, 2>{});
+            break;
+        case BrShape::Throughput:
+            if (fft_e_ == 4) go(FbrShape<N, K, 4, false>{});
+            else if constexpr (fft_supported(K, N, 8)) go(FbrShape<N, K, 8, false>{});
+            break;
+        }
     });
     HIP_CHECK(hipGetLastError());
 }

@@ -179,17 +179,8 @@ __device__ __forceinline__ int bsk_pos(int tl, int m) {
     return NttGeo<N, E>::template idx<NttGeo<N, E>::NPH - 1>(tl, m);
 }
 
-// minimum waves per SIMD (register cap 512 / w): 4 -> 128 VGPRs
-#ifndef FR_BR_MINW8
-#define FR_BR_MINW8 4
-#endif
-#ifndef FR_BR_MINW16
-#define FR_BR_MINW16 4
-#endif
-template <int E>
-constexpr int br_min_waves() {
-    return E == 16 ? FR_BR_MINW16 : FR_BR_MINW8;
-}
+// minimum waves per SIMD (register cap 512 / w): 4 -> 128 VGPRs, E = 8 and E = 16 alike
+constexpr int BR_MIN_WAVES = 4;
 
 // residue of sum_t d_t (X^pos_t A)[j] mod p from one residue row of A
 template <class G>
@@ -242,7 +233,7 @@ __device__ __forceinline__ void split_digits(uint32_t (&x)[E], const uint32_t (&
 }
 
 template <int N, int K, int E>
-__global__ void __launch_bounds__(2 * (K + 1) * (N / E), br_min_waves<E>())
+__global__ void __launch_bounds__(2 * (K + 1) * (N / E), BR_MIN_WAVES)
 k_blind_rotate(const uint64_t* __restrict__ ks, int ks_stride, int n, const DevGate* __restrict__ gates,
                const uint32_t* __restrict__ bsk, const uint32_t* __restrict__ tw, uint64_t* __restrict__ arena,
                int slot_stride) {
@@ -668,7 +659,7 @@ void Device::upload_rns_bsk(const std::vector<uint64_t>& bsk) {
 
 void Device::launch_br_rns(const DevGate* d_gates, const uint64_t* d_ks, size_t n, hipEvent_t ev_start, hipEvent_t ev_stop) {
     // small levels (at most one bootstrap per CU): more lanes per bootstrap for latency
-    const int E = n <= small_batch_ ? e_small_ : e_;
+    const int E = br_shape(n, false) == BrShape::Latency ? e_small_ : e_;
     dispatch(p_, E, [&](auto n_, auto k_, auto e_c) {
         constexpr int N = decltype(n_)::value, K = decltype(k_)::value, E = decltype(e_c)::value;
         hipExtLaunchKernelGGL(k_blind_rotate<N, K, E>, dim3((unsigned)n), dim3(br_threads<N, K, E>()),
