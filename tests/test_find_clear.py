@@ -5,11 +5,13 @@ checked against the selectors of an encrypted needle.  No device: the kernel and
 tests/test_find_clear_gpu.py."""
 import ctypes as C
 import random
+import time
 
 import numpy as np
 import pytest
 
 import fheregex as F
+import needle_limits as nl
 import oracle_ffi as of
 
 U = np.uint64
@@ -179,6 +181,67 @@ def test_plain_find_clear_against_python():
             assert starts == [int(content.find(bytes(needle), p, p + m) == p) for p in range(lo, hi)], case
         hits += any_
     assert 40 < hits < 180  # both answers occur often
+
+
+# ------------------------------------------------------------------ the needle-length limits
+@pytest.mark.parametrize("m", nl.LENGTHS)
+def test_plain_find_clear_at_the_length_limits(m):
+    """fr_plain_find_clear against py_starts on needle_limits.TEXT, as
+    tests/test_private_needle.py does for fr_plain_find; each of the 2 m terms is read"""
+    assert nl.check_plain(F.plain_find_clear, m) == nl.known_starts(m)[0]
+    nl.check_every_test_counts(F.plain_find_clear, m)
+
+
+@pytest.mark.parametrize("m", nl.LENGTHS)
+@pytest.mark.parametrize("starts", [False, True])
+def test_schedule_at_the_length_limits(m, starts):
+    """fr_schedule_find_clear's jobs per level and level count from balanced_chunks(2 m) and
+    or_tree: a sign gate of offset 1 - 2 len over each chunk's sum, a sum of its own each"""
+    n = len(nl.TEXT)
+    for lo, hi in ((0, n), (n - m - 1, n - m + 1), (n - m, n), (n - m + 1, n)):
+        S = F.schedule_find_clear(n, m, lo, hi, starts=starts)
+        fit = len(range(lo, min(hi, n - m + 1)))
+        lvl1 = nl.check_levels(S, m, fit, starts, clear=True)
+        assert all(j.kind == F.JOB_SIGN for j in S.jobs)
+        made = {j.out_gate[0] for j in S.jobs}
+        sums = [j.in_ref[0] for j in lvl1]
+        assert all(g >= 0 and g not in made for g in sums) and len(set(sums)) == len(sums) == fit * len(nl.chunk_lens(m))
+        assert [p[0] >= 0 for p in S.parts] == ([True] * fit + [False] * (hi - lo - fit) if starts else [fit > 0])
+
+
+@pytest.mark.parametrize("pid", list(POINTS))
+def test_oracle_alone_at_64_characters(request, key_blob, pid):
+    """The reference alone is right at the longest needle: Oracle.run_schedule on find_clear and
+    find_clear_starts of m = 64 over 66 bytes (three starts, eight sums of 16 terms each, an AND
+    of 8 and the OR), its sums from extract_sum over an encrypted needle's 128 selectors, decodes
+    to py_starts, every output's phase error below 2^53 (the bound of
+    tests/test_find_clear_gpu.py's check_outputs).  Measured on 8 threads, both needles: 1.2 s at
+    (1, 2048), 1.0 s at (2, 1024), plus the oracle's key generation where this test runs first
+    (5 s): not marked slow."""
+    import selector_cases as sc
+    import test_gate_programs as tg
+    k, N = POINTS[pid]
+    O = tg.oracle(request, pid)
+    ctx = F.Context(device=-1, params=F.default_params(k=k, N=N, ring=F.RING_FFT))
+    ctx.load_client_key(key_blob)
+    text = nl.DEVICE_TEXT[64]
+    assert len(text) - 64 + 1 == 3
+    t0 = time.perf_counter()
+    for name, masks in nl.cases(64, text):
+        if name not in ("plain", "absent"):
+            continue
+        sel = ctx.expand_needle(ctx.encrypt_needle(masks, K))
+        assert sel.shape == (128, k + 1, N)
+        words = np.concatenate([sc.oracle_find(O, sel, 64, text=text), sc.oracle_find(O, sel, 64, text=text, starts=True)])
+        want = nl.starts_of(text, masks)
+        assert want == ([2] if name == "plain" else [])
+        bits = [int(bool(want))] + [int(p in want) for p in range(len(text))]
+        assert [int(v) for v in O.decode16(words)] == bits, (pid, name)
+        err = (O.phase(words) - (np.array(bits, dtype=U) << U(59))).view(np.int64)
+        worst = int(np.abs(err).max())
+        print("%s %s: largest phase error 2^%.1f" % (pid, name, np.log2(max(worst, 1))))
+        assert worst < 2 ** 53, np.log2(worst)
+    print("oracle %s find_clear m = 64 over 66 bytes, two needles: %.2f s" % (pid, time.perf_counter() - t0))
 
 
 # ------------------------------------------------------------------ extraction

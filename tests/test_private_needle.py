@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import fheregex as F
+import needle_limits as nl
 
 K = bytes((41 * i + 7) & 0xFF for i in range(32))  # a fixed 256-bit generator key
 HEADER = 64
@@ -351,3 +352,58 @@ def test_plain_find_against_python():
             assert starts == by_find, case
         hits += any_
     assert 40 < hits < 180  # both answers occur often
+
+
+# ------------------------------------------------------------------ the needle-length limits
+@pytest.mark.parametrize("m", nl.LENGTHS)
+def test_plain_find_at_the_length_limits(m):
+    """fr_plain_find against py_starts on needle_limits.TEXT: the needle of m characters at the
+    last start that fits, as it is, case-insensitive, with wildcards and absent, over ranges that
+    cut through that start; the text holds the needle and its near miss where its period says;
+    and each of the 2 m selectors is read"""
+    occ = nl.check_plain(F.plain_find, m)
+    want, near = nl.known_starts(m)
+    assert occ == want and len(nl.TEXT) - m in occ
+    for p in near:
+        assert p not in occ and nl.TEXT[p:p + m - 1] == nl.needle(m)[:-1]
+    assert near or m > nl.DEVIANT + 1
+    nl.check_every_test_counts(F.plain_find, m)
+
+
+@pytest.mark.parametrize("m", nl.LENGTHS)
+@pytest.mark.parametrize("starts", [False, True])
+def test_schedule_at_the_length_limits(m, starts):
+    """fr_schedule_find's jobs per level and level count from balanced_chunks(2 m) and or_tree;
+    the sign gates' offsets; and every start's selector jobs carry the indices range(2 m), on
+    the content blocks of character p + i"""
+    n = len(nl.TEXT)
+    for lo, hi in ((0, n), (n - m - 1, n - m + 1), (n - m, n), (n - m + 1, n)):
+        S = F.schedule_find(n, m, lo, hi, starts=starts)
+        fit = len(range(lo, min(hi, n - m + 1)))
+        lvl1 = nl.check_levels(S, m, fit, starts, clear=False)
+        assert len(S.parts) == (hi - lo if starts else 1)
+        assert [p[0] >= 0 for p in S.parts] == ([True] * fit + [False] * (hi - lo - fit) if starts else [fit > 0])
+        for at, j in enumerate(lvl1):
+            p, t = lo + at // (2 * m), at % (2 * m)
+            assert (j.kind, j.n_out, j.n_in, j.offset) == (F.JOB_ACC, 1, 2, 0)
+            assert struct.unpack("<I", bytes(j.lut[0][:4]))[0] == t and not any(j.lut[0][4:])
+            assert (j.in_ref[0], j.in_w[0]) == (content_ref(p + t // 2, 2 * (t % 2) + 1), 4)
+            assert (j.in_ref[1], j.in_w[1]) == (content_ref(p + t // 2, 2 * (t % 2)), 1)
+        assert {struct.unpack("<I", bytes(j.lut[0][:4]))[0] for j in lvl1} == (set(range(2 * m)) if fit else set())
+
+
+def test_the_device_texts_hold_what_they_claim():
+    """the slices tests/test_needle_limits_gpu.py runs: each a slice of TEXT with its 0x00 and
+    bytes >= 0x80, the needle at the last start that fits (and where the comments say), the near
+    miss at m = 8 and 16, two and three starts at m = 64; the three evaluators agree on them"""
+    want = {8: ([0, 16], 8), 16: ([16], 0), 17: ([8], None), 64: ([2], None)}
+    for m, text in list(nl.DEVICE_TEXT.items()) + [(64, nl.TEXT_65)]:
+        assert text in nl.TEXT and len(text) <= 80 and text.count(0) == 1 and max(text) >= 0x80
+        for evaluator in (F.plain_find, F.plain_find_clear, F.plain_scan_clear):
+            occ = nl.check_plain(evaluator, m, text)
+        occ_want, near = want[m] if text is not nl.TEXT_65 else ([1], None)
+        assert occ == occ_want and occ[-1] == len(text) - m
+        if near is not None:
+            assert near not in occ and text[near:near + m - 1] == nl.needle(m, text)[:-1]
+    assert sorted(nl.DEVICE_TEXT) == nl.LIMITS
+    assert (len(nl.TEXT_65) - 63, len(nl.DEVICE_TEXT[64]) - 63) == (2, 3)

@@ -220,7 +220,8 @@ _E2E = {}
 
 
 def py_starts(content, masks):
-    b, m = content.encode(), len(masks)
+    """content: a str (its bytes) or the bytes themselves, every value valid"""
+    b, m = content.encode() if isinstance(content, str) else bytes(content), len(masks)
     return [p for p in range(len(b)) if p + m <= len(b) and all(
         (masks[i][0] >> (b[p + i] & 15)) & 1 and (masks[i][1] >> (b[p + i] >> 4)) & 1 for i in range(m))]
 

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import fheregex as F
+import needle_limits as nl
 from selector_cases import balanced_chunks
 from test_find_clear import or_tree, py_find
 from test_packed_results import POINTS, PSEED, host
@@ -211,6 +212,51 @@ def test_three_plain_evaluators_on_one_text():
             for f in evaluators:
                 assert f(text, masks, lo, hi) == (want, int(any(want))), (f.__name__, needle, lo, hi)
     assert py_find(text, F.needle_masks(b"abc"), 0, 12) == [1, 0, 0, 0, 1, 0, 0, 1, 0, 0, 0, 0]
+
+
+# ------------------------------------------------------------------ the needle-length limits
+@pytest.mark.parametrize("m", nl.LENGTHS)
+def test_plain_scan_clear_at_the_length_limits(m):
+    """fr_plain_scan_clear against py_starts on needle_limits.TEXT and on its continuation, whose
+    windows recur at every length: the window at d m of the compacted text is window d's"""
+    assert nl.check_plain(F.plain_scan_clear, m) == nl.known_starts(m)[0]
+    nl.check_every_test_counts(F.plain_scan_clear, m)
+    text = nl.SCAN_TEXT
+    occ = nl.check_plain(F.plain_scan_clear, m, text)
+    cls, D, Dpad, win = F.window_classes(text, m)
+    fit = len(text) - m + 1
+    assert len(occ) >= 3 and D < fit and Dpad == 64
+    assert all(win[c * m:(c + 1) * m] == text[p:p + m] for p, c in enumerate(cls[:fit]))
+
+
+def test_plain_scan_clear_past_64_windows_of_64_bytes():
+    """130 seeded bytes, m = 64: 67 distinct windows, padded to 128, so the plan's text is 8,192
+    bytes and window d's terms read d 64 .. d 64 + 63; the needle is the last window (class 66),
+    the first, one in the middle, and absent"""
+    text, m = nl.RANDOM_TEXT, 64
+    cls, D, Dpad, win = F.window_classes(text, m)
+    assert (D, Dpad, len(win)) == (67, 128, 67 * 64) and cls[:67] == list(range(67))
+    for at in (66, 0, 33):
+        masks = F.needle_masks(text[at:at + m])
+        assert nl.starts_of(text, masks) == [at]
+        for lo, hi in nl.ranges(len(text), m):
+            bits = [int(p == at) for p in range(lo, hi)]
+            assert F.plain_scan_clear(text, masks, lo, hi) == (bits, int(any(bits))), (at, lo, hi)
+    nl.check_every_test_counts(F.plain_scan_clear, m, text)
+    assert F.plain_scan_clear(text, F.needle_masks(nl.absent(text[66:])))[1] == 0
+
+
+@pytest.mark.parametrize("m", nl.LENGTHS)
+@pytest.mark.parametrize("Dpad", [64, 128])
+@pytest.mark.parametrize("starts", [False, True])
+def test_schedule_at_the_length_limits(Dpad, m, starts):
+    """fr_schedule_scan_clear is find_clear's shape over Dpad starts that all fit"""
+    S = F.schedule_scan_clear(Dpad, m, starts=starts)
+    lvl1 = nl.check_levels(S, m, Dpad, starts, clear=True)
+    made = {j.out_gate[0] for j in S.jobs}
+    sums = [j.in_ref[0] for j in lvl1]
+    assert all(g >= 0 and g not in made for g in sums) and len(set(sums)) == len(sums) == Dpad * len(nl.chunk_lens(m))
+    assert len(S.parts) == (Dpad if starts else 1) and all(p[0] >= 0 and p[1:] == (1, 0) for p in S.parts)
 
 
 # ------------------------------------------------------------------ the mapped pack on the host
