@@ -497,15 +497,20 @@ int fr_dev_blind_rotate_acc(fr_ctx* ctx, const uint64_t* in, const uint64_t* acc
 // A needle search on a plaintext, both lowered programs gate by gate: the per-start values from
 // the starts program, `any` from the boolean program's OR tree.  cls (a scan): start j reads the
 // output of its class (none, or past the classed starts: 0); else start j reads output j.
+// byte_tables: a byte-table needle's m sets of 256 bits instead of the 2 m masks.
 static void plain_needle(MatchKind kind, const uint8_t* text, size_t len, size_t n, size_t m, size_t lo, size_t hi,
-                         const uint16_t* masks, const std::vector<int32_t>* cls, uint8_t* starts_out, int32_t* any) {
+                         const uint16_t* masks, const std::vector<int32_t>* cls, uint8_t* starts_out, int32_t* any,
+                         const uint8_t* byte_tables = nullptr) {
     std::vector<int> vals;
-    eval_program_parts(needle_program(kind, n, m, lo, hi, true), text, len, vals, masks, 2 * m);
+    const bool bytes = byte_tables != nullptr;
+    const size_t n_tables = bytes ? m : 2 * m;
+    eval_program_parts(needle_program(kind, n, m, lo, hi, true, bytes), text, len, vals, masks, n_tables, byte_tables);
     for (size_t j = 0; j < (cls ? hi - lo : vals.size()); ++j) {
         const long o = !cls ? (long)j : j < cls->size() ? (*cls)[j] : -1;
         starts_out[j] = o >= 0 ? (uint8_t)vals[(size_t)o] : 0;
     }
-    *any = eval_program_parts(needle_program(kind, n, m, lo, hi, false), text, len, vals, masks, 2 * m);
+    *any = eval_program_parts(needle_program(kind, n, m, lo, hi, false, bytes), text, len, vals, masks, n_tables,
+                              byte_tables);
 }
 int fr_plain_find(const char* content, size_t len, const uint16_t* masks, size_t m, size_t start_lo, size_t start_hi,
                   uint8_t* starts_out, int32_t* any) {
@@ -553,6 +558,26 @@ int fr_plain_scan_clear(const uint8_t* content, size_t len, const uint16_t* mask
         pad_window_text(wc, m);
         plain_needle(MATCH_NEEDLE_WINDOWS, wc.text.data(), wc.text.size(), scan_padded(wc.first.size()), m, start_lo,
                      start_hi, masks, &wc.cls, starts_out, any);
+    })
+}
+int fr_plain_find_clear_bytes(const uint8_t* content, size_t len, const uint8_t* tables, size_t m, size_t start_lo,
+                              size_t start_hi, uint8_t* starts_out, int32_t* any) {
+    FR_TRY({
+        NEED((content || !len) && tables && any && start_lo <= start_hi && (starts_out || start_lo == start_hi));
+        NEED(m >= 1 && m <= NEEDLE_MAX_CHARS);
+        plain_needle(MATCH_NEEDLE_CLEAR, content, len, len, m, start_lo, start_hi, nullptr, nullptr, starts_out, any,
+                     tables);
+    })
+}
+int fr_plain_scan_clear_bytes(const uint8_t* content, size_t len, const uint8_t* tables, size_t m, size_t start_lo,
+                              size_t start_hi, uint8_t* starts_out, int32_t* any) {
+    FR_TRY({
+        NEED((content || !len) && tables && any && start_lo <= start_hi && (starts_out || start_lo == start_hi));
+        NEED(m >= 1 && m <= NEEDLE_MAX_CHARS && start_hi - start_lo <= ((size_t)1 << 24));
+        WindowClasses wc = window_classes(content, len, m, start_lo, start_hi);
+        pad_window_text(wc, m);
+        plain_needle(MATCH_NEEDLE_WINDOWS, wc.text.data(), wc.text.size(), scan_padded(wc.first.size()), m, start_lo,
+                     start_hi, nullptr, &wc.cls, starts_out, any, tables);
     })
 }
 int fr_dev_select_sum(fr_ctx* ctx, const fr_needle* needle, const uint8_t* content, size_t len, const int32_t* terms,

@@ -541,9 +541,61 @@ int fr_expand_needle(fr_ctx* ctx, const uint8_t* blob, size_t len, uint64_t* wor
     })
 }
 
+// ---- byte-table needles (keys.h): one 256-entry table per character, N/256 to a selector
+
+int fr_needle_bytes_size(fr_ctx* ctx, size_t m, size_t* bytes) {
+    FR_TRY({
+        NEED(ctx && bytes);
+        *bytes = needle_bytes_blob_size(ctx->p, m);
+    })
+}
+
+int fr_encrypt_needle_bytes_keyed(fr_ctx* ctx, const uint8_t* tables, size_t m, const uint8_t* key32, uint8_t* buf,
+                                  size_t cap, size_t* written) {
+    FR_TRY({
+        NEED(ctx && tables && written);
+        if (ctx->p.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "private search: FFT ring only");
+        if (!ctx->has_ck) throw Error(FR_ERR_NO_KEY, "client key not loaded");
+        const size_t need = needle_bytes_blob_size(ctx->p, m);
+        if (answer_size(written, need, buf, cap)) return FR_OK;
+        ScopedKey key(key32);
+        const std::vector<uint8_t> blob = encrypt_needle_bytes_blob(ctx->p, ctx->ck, tables, m, key.k);
+        std::memcpy(buf, blob.data(), need);
+    })
+}
+
+int fr_expand_needle_bytes(fr_ctx* ctx, const uint8_t* blob, size_t len, uint64_t* words, size_t cap_words,
+                           size_t* m) {
+    FR_TRY({
+        NEED(ctx && blob && m);
+        const NeedleBlob nb = check_needle_bytes_blob(ctx->p, blob, len);
+        *m = nb.m;
+        if (!words) return FR_OK;  // size query
+        NEED(cap_words >= needle_bytes_words(ctx->p, nb.m));
+        expand_needle_bytes(ctx->p, blob, len, words);
+    })
+}
+
+int fr_needle_form(const fr_needle* needle, int32_t* form) {
+    FR_TRY({
+        NEED(needle && form);
+        *form = (int32_t)needle->dev.form;
+    })
+}
+
 int fr_upload_needle(fr_ctx* ctx, const uint8_t* blob, size_t len, fr_needle** out) {
     FR_TRY({
         NEED(ctx && blob && out);
+        if (is_needle_bytes_blob(blob, len)) {  // the other form, told apart by its magic
+            const NeedleBlob nb = check_needle_bytes_blob(ctx->p, blob, len);
+            Device& dev = ctx->device();
+            std::vector<uint64_t> words(needle_bytes_words(ctx->p, nb.m));
+            expand_needle_bytes(ctx->p, blob, len, words.data());
+            auto nd = std::unique_ptr<fr_needle>(
+                new fr_needle{dev.upload_needle(words.data(), nb.m, NEEDLE_BYTES), ctx->p.k, ctx->p.N});
+            *out = nd.release();
+            return FR_OK;
+        }
         // the blob is checked before the device is asked for and before anything is allocated
         const NeedleBlob nb = check_needle_blob(ctx->p, blob, len);
         Device& dev = ctx->device();

@@ -62,6 +62,8 @@ inline void set_acc_selector(DevGate& g, uint32_t q) {
 // An extract-sum (private search over clear content, select_sum.hip): the big LWE in out_slot
 // is the sum over its terms (selector q, content position pos, half h) of the sample extract
 // of selector q at coefficient ((content[pos] >> 4 h) & 15) N/16.  No job: no keyswitch, no rotation.
+// Over a byte-table needle (NEEDLE_BYTES: the form is the bound selector table's, bind_selectors)
+// a term is (table i, pos, 0): selector i / (N/256) at coefficient (i % (N/256)) 256 + content[pos].
 constexpr int SUM_MAX_TERMS = 16;
 struct DevSum {
     int32_t out_slot;
@@ -93,12 +95,18 @@ class Device;
 // arena slots owned by a call, a plan or a handle in the making (owned.h)
 using Slots = gpu::SlotsOf<Device>;
 
-// A needle on the device (private search): its 2 m selectors, [selector][polynomial][N] u64.
+// The two forms of a needle: 2 m selectors of 16-entry nibble tables (fr_find* and the clear
+// searches), or m 256-entry byte tables, N/256 to a selector (the clear searches only).
+enum NeedleForm : int { NEEDLE_NIBBLES = FR_NEEDLE_NIBBLES, NEEDLE_BYTES = FR_NEEDLE_BYTES };
+// A needle on the device (private search): its selectors, [selector][polynomial][N] u64.
 // Move-only.  Finds on any lane may read it, so, by Plan's rule (plan.h), it waits for every
 // lane before its memory goes.
 struct DevNeedle {
     gpu::DevBuf<uint64_t> words;
-    size_t m = 0;  // characters: 2 m selectors
+    size_t m = 0;  // characters: 2 m selectors (bytes: m tables in ceil(256 m / N) selectors)
+    NeedleForm form = NEEDLE_NIBBLES;
+    // what bind_selectors takes as its count: the indices an extract-sum's or a job's first field may take
+    size_t tables() const { return form == NEEDLE_BYTES ? m : 2 * m; }
     Device* dev = nullptr;
     DevNeedle() = default;
     DevNeedle(DevNeedle&&) = default;
@@ -232,9 +240,11 @@ class Device {
     // one H2D copy, synchronous.  bind_selectors is to a selector launch what bind_content is to
     // a template plan: JOB_ACC jobs enqueued on the current lane after it read selector q < count
     // at table + q (k+1) N (the pointer is a launch argument: launches enqueued before keep
-    // theirs).  nullptr: none bound.
-    DevNeedle upload_needle(const uint64_t* words, size_t m);
-    void bind_selectors(const uint64_t* table, size_t count);
+    // theirs).  nullptr: none bound.  A byte-table needle is ceil(256 m / N) selectors of the same
+    // (k+1) N words, bound with count = m: its tables are what an extract-sum indexes, and no
+    // JOB_ACC job may read it.
+    DevNeedle upload_needle(const uint64_t* words, size_t m, NeedleForm form = NEEDLE_NIBBLES);
+    void bind_selectors(const uint64_t* table, size_t count, NeedleForm form = NEEDLE_NIBBLES);
     // Private search over clear content (select_sum.hip).  bind_text: the call's n content bytes,
     // copied before it returns and bound to the current lane in stream order through the lane's
     // staging ring, as bind_content binds a map.  run_sums / run_sums_resident: one launch of n
@@ -300,7 +310,8 @@ class Device {
         gpu::StagingRing<int> cmap;  // content map (bind_content)
         size_t cmap_n = 0;           // entries bound
         const uint64_t* sel = nullptr;  // selector table (bind_selectors)
-        size_t sel_n = 0;               // selectors bound
+        size_t sel_n = 0;               // selectors bound (bytes: tables)
+        NeedleForm sel_form = NEEDLE_NIBBLES;
         gpu::StagingRing<uint8_t> text;  // clear content bytes (bind_text)
         size_t text_n = 0;               // bytes bound
         gpu::Event done_ev;          // recorded on the lane's stream when it is left
@@ -383,7 +394,8 @@ class Device {
     void launch_jobs(const DevGate* d_gates, const DevGate* host, size_t n, bool acc);  // one keyswitch + rotation
     void run_br_jobs(const uint64_t* ks_in, std::vector<DevGate>& gates, uint64_t* out);  // the blind_rotate_*_host hooks
     // select_sum.hip
-    void validate_sums(const DevSum* sums, size_t n, size_t n_sel, size_t text_n) const;
+    void validate_sums(const DevSum* sums, size_t n, size_t n_sel, size_t text_n,
+                       NeedleForm form = NEEDLE_NIBBLES) const;
     void check_sums(const DevSum* host, size_t n) const;  // against what the current lane has bound
     void launch_select_sum(const uint64_t* table, const DevSum* d_sums, size_t n);
     gpu::StagingRing<DevSum> sums_;  // staged extract-sums (lane 0), as gates_

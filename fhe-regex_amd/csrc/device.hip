@@ -379,21 +379,25 @@ DevNeedle::~DevNeedle() {
     }
 }
 
-DevNeedle Device::upload_needle(const uint64_t* words, size_t m) {
+DevNeedle Device::upload_needle(const uint64_t* words, size_t m, NeedleForm form) {
     if (p_.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "private search: FFT ring only");
     if (!words || m < 1 || 2 * m > (size_t)MAX_SELECTORS) throw Error(FR_ERR_INVALID, "needle: 1 <= m <= 64");
     DevNeedle nd;
     nd.dev = this;
     nd.m = m;
-    nd.words.alloc(2 * m * (size_t)(p_.k + 1) * p_.N);
+    nd.form = form;
+    const size_t tpg = (size_t)p_.N / 256;  // byte tables per selector
+    if (form == NEEDLE_BYTES && !tpg) throw Error(FR_ERR_INVALID, "byte needle: N is not a multiple of 256");
+    nd.words.alloc((form == NEEDLE_BYTES ? (m + tpg - 1) / tpg : 2 * m) * (size_t)(p_.k + 1) * p_.N);
     HIP_CHECK(hipMemcpy(nd.words.get(), words, 8 * nd.words.size(), hipMemcpyHostToDevice));
     return nd;
 }
 
-void Device::bind_selectors(const uint64_t* table, size_t count) {
+void Device::bind_selectors(const uint64_t* table, size_t count, NeedleForm form) {
     if (table && p_.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "private search: FFT ring only");
     cur().sel = table;
     cur().sel_n = table ? count : 0;
+    cur().sel_form = table ? form : NEEDLE_NIBBLES;
 }
 
 size_t Device::leading_selector_jobs(const DevGate* host, size_t n) const {
@@ -405,6 +409,8 @@ size_t Device::leading_selector_jobs(const DevGate* host, size_t n) const {
     for (size_t i = 0; i < n; ++i) {
         if (host[i].direct != JOB_ACC) continue;
         if (i >= a) throw Error(FR_ERR_INVALID, "selector jobs must lead their level");
+        if (cur().sel_form != NEEDLE_NIBBLES)
+            throw Error(FR_ERR_INVALID, "selector job: a byte-table needle is read by extract-sums only");
         if ((size_t)acc_selector(host[i]) >= cur().sel_n)
             throw Error(FR_ERR_INVALID, "selector job: index past the selector table bound");
     }
@@ -620,15 +626,16 @@ void Device::blind_rotate_acc_host(const uint64_t* ks_in, const uint64_t* accs, 
     }
     const uint64_t* prev = cur().sel;
     const size_t prev_n = cur().sel_n;
+    const NeedleForm prev_form = cur().sel_form;
     bind_selectors(table.get(), count);
     try {
         run_br_jobs(ks_in, gates, out);  // (synchronises before it returns: the table may go)
     } catch (...) {
         (void)hipStreamSynchronize(cur().stream.get());
-        bind_selectors(prev, prev_n);
+        bind_selectors(prev, prev_n, prev_form);
         throw;
     }
-    bind_selectors(prev, prev_n);
+    bind_selectors(prev, prev_n, prev_form);
 }
 
 void Device::blind_rotate_host(const uint64_t* ks_in, const uint8_t* luts, size_t count, uint64_t* out) {

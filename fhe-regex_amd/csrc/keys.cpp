@@ -700,6 +700,38 @@ std::vector<uint8_t> encrypt_needle_blob(const Params& p, const ClientKey& ck, c
     return out;
 }
 
+std::vector<uint8_t> encrypt_needle_bytes_blob(const Params& p, const ClientKey& ck, const uint8_t* tables, size_t m,
+                                               const RngKey& key) {
+    if (p.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "private search: FFT ring only");
+    if (ck.s_big.size() != (size_t)p.big()) throw Error(FR_ERR_INVALID, "needle: client key size");
+    const int k = p.k, N = p.N;
+    std::vector<uint8_t> out(needle_bytes_blob_size(p, m));
+    const RngKey mk = derive_mask_key(key);  // public
+    write_needle_bytes_header(p, m, mk, out.data());
+    parallel_for((int)needle_bytes_selectors(p, m), [&](int q) {
+        Rng rm(mk, STREAM_NEEDLE_BYTES_MASK), rn(key, STREAM_NEEDLE_BYTES_NOISE);
+        std::vector<uint64_t> A((size_t)N), B((size_t)N, 0);
+        for (int c = 0; c < k; ++c) {
+            const uint64_t base = ((uint64_t)q * k + c) * N;
+            for (int t = 0; t < N; ++t) A[t] = rm.u64(base + t);
+            const uint64_t* S = ck.s_big.data() + (size_t)c * N;
+            for (int u = 0; u < N; ++u)
+                if (S[u]) add_rotated(B.data(), A.data(), u, N);
+        }
+        uint8_t* o = out.data() + NEEDLE_HEADER + 8 * (size_t)q * N;
+        for (int t = 0; t < N; ++t) {
+            // coefficient t is byte t % 256 of table q N/256 + t / 256 (past the last table: 0)
+            const size_t i = (size_t)q * (N / 256) + t / 256, b = t % 256;
+            const uint64_t bit = i < m ? (tables[32 * i + b / 8] >> (b % 8)) & 1 : 0;
+            B[t] += (bit << DELTA_LOG) + (uint64_t)rn.gaussian((uint64_t)q * N + t, p.glwe_sigma);
+            put_le64(o + 8 * (size_t)t, B[t]);
+        }
+        explicit_bzero(A.data(), 8 * A.size());  // (public) and the noisy body's scratch
+        explicit_bzero(B.data(), 8 * B.size());
+    });
+    return out;
+}
+
 uint32_t decode16(uint64_t phase) {
     const uint64_t delta = 1ULL << DELTA_LOG;
     uint64_t rounding = (phase & (delta >> 1)) << 1;

@@ -27,6 +27,8 @@ enum Stream : uint64_t {
     STREAM_PKSK_NOISE = 10,
     STREAM_NEEDLE_MASK = 11,
     STREAM_NEEDLE_NOISE = 12,
+    STREAM_NEEDLE_BYTES_MASK = 13,
+    STREAM_NEEDLE_BYTES_NOISE = 14,
 };
 
 class Rng {
@@ -199,6 +201,22 @@ uint64_t needle_test_poly(int N, int t, uint16_t table);
 // the needle blob of wire.h; masks: lo, hi per character (2 m tables); `key` is the caller's to wipe
 std::vector<uint8_t> encrypt_needle_blob(const Params& p, const ClientKey& ck, const uint16_t* masks, size_t m,
                                          const RngKey& key);
+// A byte-table needle (private search over clear content only): character i is one 0/1 table T_i
+// of the 256 byte values, 32 bytes, bit b at tables[32 i + b / 8] >> (b % 8).  N / 256 tables
+// share a selector: the phase of coefficient (i % (N/256)) 256 + b of selector i / (N/256) is
+// T_i[b] 2^59 -- no boxes, no recentring, no sign, because the server sample-extracts exactly that
+// coefficient; the coefficients past the last table encrypt 0.  Masks and noise as the nibble
+// needle's, on STREAM_NEEDLE_BYTES_MASK under M and STREAM_NEEDLE_BYTES_NOISE under K.
+inline size_t needle_bytes_per_selector(const Params& p) { return (size_t)p.N / 256; }
+inline size_t needle_bytes_selectors(const Params& p, size_t m) {
+    return (m + needle_bytes_per_selector(p) - 1) / needle_bytes_per_selector(p);
+}
+inline size_t needle_bytes_words(const Params& p, size_t m) {
+    return needle_bytes_selectors(p, m) * (size_t)(p.k + 1) * p.N;
+}
+// the byte-table needle blob of wire.h; `key` is the caller's to wipe
+std::vector<uint8_t> encrypt_needle_bytes_blob(const Params& p, const ClientKey& ck, const uint8_t* tables, size_t m,
+                                               const RngKey& key);
 uint64_t lwe_phase(const Params& p, const ClientKey& ck, const uint64_t* lwe);
 // tfhe-rs shortint decrypt_message_and_carry: round(phase / Delta) mod 16
 uint32_t decode16(uint64_t phase);

@@ -747,7 +747,7 @@ static int threshold_tree(Program& prog, bool is_and, std::vector<int> lits) {
 // stride: the content position of start p's first character is p * stride (1: the text itself;
 // m, clear only: window p of a compacted text, compile_needle_windows)
 static Program compile_needle_over(size_t n_chars, size_t m, size_t lo, size_t hi, bool starts, bool clear,
-                                   size_t stride = 1) {
+                                   size_t stride = 1, bool bytes = false) {
     if (m < 1 || m > NEEDLE_MAX_CHARS) throw Error(FR_ERR_INVALID, "needle: 1 <= m <= 64");
     if (lo > hi) throw Error(FR_ERR_INVALID, "needle: start range");
     if (n_chars > (size_t)1 << 24) throw Error(FR_ERR_INVALID, "needle: content too long");
@@ -765,11 +765,13 @@ static Program compile_needle_over(size_t n_chars, size_t m, size_t lo, size_t h
         std::vector<int> tests;
         if (clear) {
             // test 2 i + h is a term; a chunk of them, summed, feeds the SIGN gate that would AND them
-            for_balanced_chunks(2 * m, [&](size_t first, size_t len) {
+            // (a byte-table needle: test i is the term of table i, m of them)
+            for_balanced_chunks(bytes ? m : 2 * m, [&](size_t first, size_t len) {
                 PGate sum;
                 sum.kind = GATE_EXTRACT;
                 for (size_t t = first; t < first + len; ++t)
-                    sum.terms.push_back({(int32_t)t, (int32_t)(at + t / 2), (int32_t)(t % 2)});
+                    if (bytes) sum.terms.push_back({(int32_t)t, (int32_t)(at + t), 0});
+                    else sum.terms.push_back({(int32_t)t, (int32_t)(at + t / 2), (int32_t)(t % 2)});
                 PGate g;
                 g.kind = GATE_SIGN;
                 g.ins = {{(int32_t)prog.gates.size(), 1}};
@@ -807,19 +809,21 @@ static Program compile_needle_over(size_t n_chars, size_t m, size_t lo, size_t h
 Program compile_needle(size_t n_chars, size_t m, size_t lo, size_t hi, bool starts) {
     return compile_needle_over(n_chars, m, lo, hi, starts, false);
 }
-Program compile_needle_clear(size_t n_chars, size_t m, size_t lo, size_t hi, bool starts) {
-    return compile_needle_over(n_chars, m, lo, hi, starts, true);
+Program compile_needle_clear(size_t n_chars, size_t m, size_t lo, size_t hi, bool starts, bool bytes) {
+    return compile_needle_over(n_chars, m, lo, hi, starts, true, 1, bytes);
 }
-Program compile_needle_windows(size_t n_windows, size_t m, bool starts) {
+Program compile_needle_windows(size_t n_windows, size_t m, bool starts, bool bytes) {
     if (m < 1 || m > NEEDLE_MAX_CHARS) throw Error(FR_ERR_INVALID, "needle: 1 <= m <= 64");
     if (n_windows > ((size_t)1 << 24) / m) throw Error(FR_ERR_INVALID, "scan: more than 2^24 window bytes");
-    return compile_needle_over(n_windows * m, m, 0, n_windows, starts, true, m);
+    return compile_needle_over(n_windows * m, m, 0, n_windows, starts, true, m, bytes);
 }
-Program needle_program(MatchKind kind, size_t n, size_t m, size_t lo, size_t hi, bool starts) {
+Program needle_program(MatchKind kind, size_t n, size_t m, size_t lo, size_t hi, bool starts, bool bytes) {
     switch (kind) {
-        case MATCH_NEEDLE: return compile_needle(n, m, lo, hi, starts);
-        case MATCH_NEEDLE_CLEAR: return compile_needle_clear(n, m, lo, hi, starts);
-        case MATCH_NEEDLE_WINDOWS: return compile_needle_windows(n, m, starts);
+        case MATCH_NEEDLE:
+            if (bytes) throw Error(FR_ERR_INVALID, "needle: a byte-table needle searches clear content only");
+            return compile_needle(n, m, lo, hi, starts);
+        case MATCH_NEEDLE_CLEAR: return compile_needle_clear(n, m, lo, hi, starts, bytes);
+        case MATCH_NEEDLE_WINDOWS: return compile_needle_windows(n, m, starts, bytes);
         default: throw Error(FR_ERR_INVALID, "a pattern match has no needle program");
     }
 }
@@ -856,7 +860,7 @@ int eval_program(const Program& prog, const uint8_t* content, size_t L) {
 }
 
 int eval_program_parts(const Program& prog, const uint8_t* content, size_t L, std::vector<int>& parts,
-                       const uint16_t* tables, size_t n_tables) {
+                       const uint16_t* tables, size_t n_tables, const uint8_t* byte_tables) {
     std::vector<int> val(prog.gates.size(), 0);
     for (size_t g = 0; g < prog.gates.size(); ++g) {
         const PGate& G = prog.gates[g];
@@ -864,7 +868,8 @@ int eval_program_parts(const Program& prog, const uint8_t* content, size_t L, st
             for (const PTerm& t : G.terms) {
                 if (t.sel < 0 || (size_t)t.sel >= n_tables) throw Error(FR_ERR_INVALID, "extract-sum without its table");
                 if (t.pos < 0 || (size_t)t.pos >= L) throw Error(FR_ERR_INVALID, "program references content past its end");
-                val[g] += (tables[t.sel] >> ((content[t.pos] >> (4 * (t.half & 1))) & 15)) & 1;
+                if (byte_tables) val[g] += (byte_tables[32 * (size_t)t.sel + content[t.pos] / 8] >> (content[t.pos] % 8)) & 1;
+                else val[g] += (tables[t.sel] >> ((content[t.pos] >> (4 * (t.half & 1))) & 15)) & 1;
             }
             continue;
         }

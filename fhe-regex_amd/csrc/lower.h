@@ -18,6 +18,9 @@
 //           accepts that nibble of the clear content, an integer in [0, 16], formed as a sum of
 //           sample extracts of the selectors (device.h: DevSum).  No inputs, level 0: neither a
 //           job nor a rotation; only SIGN gates read it (weight 1), as they would read its terms.
+//           Over a byte-table needle (the form is the needle's, and so the bound selector table's,
+//           never the gate's) a term is (table, content position, 0) and counts when the table
+//           accepts that byte.
 //
 // FR_LOWER_FAITHFUL: one gate group per reference op (eq/gt/le = 3 PBS, and/or
 //   = 1 PBS, not = linear), the decomposition of SURVEY App. D.3.
@@ -80,9 +83,11 @@ Program lower(const ValueDag& dag, int root, int mode, int max_parts = 1);
 int eval_program(const Program& prog, const uint8_t* content, size_t L);
 // the same, and each output's value in `parts`; tables (n_tables 16-bit masks of accepted
 // values) are what the program's selector gates look up: bit s of tables[sel]; an extract-sum
-// counts its terms with bit (content[pos] >> 4 half) & 15 of tables[sel] set
+// counts its terms with bit (content[pos] >> 4 half) & 15 of tables[sel] set.  byte_tables (a
+// byte-table needle's program: n_tables sets of 256 bits, 32 bytes each, tables unused): an
+// extract-sum counts its terms with bit content[pos] of byte table `sel` set.
 int eval_program_parts(const Program& prog, const uint8_t* content, size_t L, std::vector<int>& parts,
-                       const uint16_t* tables = nullptr, size_t n_tables = 0);
+                       const uint16_t* tables = nullptr, size_t n_tables = 0, const uint8_t* byte_tables = nullptr);
 void compute_levels(Program& prog);
 // a gate's level: one past its deepest gate input (content blocks are level 0, and so is an
 // extract-sum, which is no bootstrap); level_of(g) gives the level of an earlier gate
@@ -141,7 +146,10 @@ Program compile_needle(size_t n_chars, size_t m, size_t lo, size_t hi, bool star
 // 2 m > 16 each balanced chunk of the tests gets its own sum and SIGN gate, and the chunks are
 // ANDed as before.  No gate reads an encrypted content block.  The program depends on
 // (n_chars, m, lo, hi, starts) alone, never on the content bytes.
-Program compile_needle_clear(size_t n_chars, size_t m, size_t lo, size_t hi, bool starts);
+// bytes: the needle is a byte-table needle (keys.h), one table per character: a start's tests are
+// the m terms (table i, position p + i, 0) -- one sum and one SIGN gate of offset 1 - 2 m for
+// m <= 16, else balanced chunks of the m tests.
+Program compile_needle_clear(size_t n_chars, size_t m, size_t lo, size_t hi, bool starts, bool bytes = false);
 
 // A scan of a long clear text (fr_scan_clear*): a start's result depends only on the m bytes of
 // its window, so the search runs once per distinct window and every start reads its class.
@@ -168,11 +176,13 @@ void pad_window_text(WindowClasses& wc, size_t m);
 // half t % 2); above the extract-sums the program is compile_needle_clear's for n_windows starts
 // that all fit.  m = 1 is compile_needle_clear(n_windows, 1, 0, n_windows, starts) gate for gate.
 // The program depends on (n_windows, m, starts) alone.  n_windows m <= 2^24.
-Program compile_needle_windows(size_t n_windows, size_t m, bool starts);
+// bytes: window d's term i is (table i, pos d m + i, 0), as compile_needle_clear's byte variant.
+Program compile_needle_windows(size_t n_windows, size_t m, bool starts, bool bytes = false);
 // What a match is over (match.cpp: the request), and the one place that maps a needle kind to its
 // compile function above; windows: n its windows, [lo, hi) not used.
 enum MatchKind : int { MATCH_PATTERN, MATCH_NEEDLE, MATCH_NEEDLE_CLEAR, MATCH_NEEDLE_WINDOWS };
-Program needle_program(MatchKind kind, size_t n, size_t m, size_t lo, size_t hi, bool starts);
+// bytes: the needle's form; only the clear kinds have a byte variant (MATCH_NEEDLE refuses it).
+Program needle_program(MatchKind kind, size_t n, size_t m, size_t lo, size_t hi, bool starts, bool bytes = false);
 
 // LUT builders
 void lut_eq(uint8_t* lut, int v);     // [x == v]

@@ -78,13 +78,14 @@ struct MatchRequest {
 // clear: that search over clear content (fr_find_clear*), whose plan does not depend on the
 // content's bytes either; the field keeps it apart from fr_find's plan for the same (m, n).  A
 // scan (fr_scan_clear*) is the field's third value with n its padded class count, so its plan is
-// never fr_find_clear's for the same numbers.
+// never fr_find_clear's for the same numbers.  form: the needle's (nibbles 0, byte tables 1), so a
+// byte needle of (m, n) never replays a nibble needle's plan.
 std::string match_key(const fr_ctx* ctx, const MatchRequest& rq, int lane) {
-    const size_t needle_m = rq.needle ? rq.needle->dev.m : 0;
+    const size_t needle_m = rq.needle ? rq.needle->dev.m : 0, form = rq.needle ? (size_t)rq.needle->dev.form : 0;
     const size_t clear = rq.kind == MATCH_NEEDLE_CLEAR ? 1 : rq.kind == MATCH_NEEDLE_WINDOWS ? 2 : 0;
     std::string k;
     for (size_t v : {(size_t)ctx->grammar, (size_t)ctx->engine, (size_t)ctx->lowering, (size_t)ctx->multi_value, rq.n,
-                     rq.M, rq.lo, rq.hi, rq.parts, (size_t)lane, (size_t)rq.starts, needle_m, clear})
+                     rq.M, rq.lo, rq.hi, rq.parts, (size_t)lane, (size_t)rq.starts, needle_m, clear, form})
         k += std::to_string(v) + "|";
     k += rq.pattern;
     return k;
@@ -192,6 +193,11 @@ void check_needle(fr_ctx* ctx, Device& dev, const fr_needle* needle) {
         throw Error(FR_ERR_INVALID, "needle: k, N do not match the context params");
     if (needle->dev.dev != &dev || !needle->dev.words) throw Error(FR_ERR_INVALID, "needle: uploaded to another context");
 }
+// ... and so is a byte-table needle over encrypted content: those searches rotate the tables
+void check_needle_kind(const MatchRequest& rq) {
+    if (rq.kind == MATCH_NEEDLE && rq.needle->dev.form == NEEDLE_BYTES)
+        throw Error(FR_ERR_INVALID, "needle: a byte-table needle searches clear content only");
+}
 
 // Every legality rule of a request, before anything is planned or launched.
 void validate(const MatchRequest& rq) {
@@ -214,7 +220,9 @@ struct Compiled {
 };
 Compiled program_for(const fr_ctx* ctx, const MatchRequest& rq) {
     if (rq.kind != MATCH_PATTERN)
-        return {needle_program(rq.kind, rq.n, rq.needle->dev.m, rq.lo, rq.hi, rq.starts), Recorded{}};
+        return {needle_program(rq.kind, rq.n, rq.needle->dev.m, rq.lo, rq.hi, rq.starts,
+                               rq.needle->dev.form == NEEDLE_BYTES),
+                Recorded{}};
     if (rq.starts) {
         CompiledStarts cs = compile_match_starts(match_spec(ctx, rq.pattern, rq.n, rq.lo, rq.hi));
         return {std::move(cs.prog), cs.rec};
@@ -316,7 +324,7 @@ struct Bound {
     // the needle's table and the clear content, for this match's launches on this lane only
     void search(const MatchRequest& rq) {
         selectors = rq.needle != nullptr, text = rq.clear();
-        if (selectors) d.bind_selectors(rq.needle->dev.words.get(), 2 * rq.needle->dev.m);
+        if (selectors) d.bind_selectors(rq.needle->dev.words.get(), rq.needle->dev.tables(), rq.needle->dev.form);
         // the call's bytes, copied now and in stream order on this lane: the caller's buffer may go
         if (text) d.bind_text(rq.text, rq.text_n);
     }
@@ -440,7 +448,7 @@ void run_match(fr_ctx* ctx, const MatchRequest& rq, fr_match_stats* st) {
     const double t0 = now_ms();
     Device& dev = ctx->keyed_device();
     validate(rq);
-    if (rq.needle) check_needle(ctx, dev, rq.needle);
+    if (rq.needle) check_needle(ctx, dev, rq.needle), check_needle_kind(rq);
     const DeviceTimers before = dev.timers();
     PlanView v = acquire_plan(ctx, dev, rq);
     Bound bound{dev};
@@ -908,6 +916,28 @@ int fr_schedule_scan_clear(size_t n_windows, size_t m, int32_t starts, fr_job* j
         NEED(n_windows <= ((size_t)1 << 24) && outs_cap >= (starts ? n_windows : 1));
         const Program prog = needle_program(MATCH_NEEDLE_WINDOWS, n_windows, m, 0, n_windows, starts != 0);
         // (the extract-sums read n_windows m bytes of compacted text)
+        schedule_program(prog, n_windows * m, 1, jobs, jobs_cap, n_jobs, level_off, level_cap, n_levels, outs3, n_outs);
+    })
+}
+
+int fr_schedule_find_clear_bytes(size_t n_chars, size_t m, size_t start_lo, size_t start_hi, int32_t starts,
+                                 fr_job* jobs, size_t jobs_cap, size_t* n_jobs, uint32_t* level_off, size_t level_cap,
+                                 size_t* n_levels, int32_t* outs3, size_t outs_cap, size_t* n_outs) {
+    FR_TRY({
+        NEED(n_jobs && n_levels && n_outs && outs3 && start_lo <= start_hi && (starts == 0 || starts == 1));
+        NEED(outs_cap >= (starts ? start_hi - start_lo : 1));
+        const Program prog = needle_program(MATCH_NEEDLE_CLEAR, n_chars, m, start_lo, start_hi, starts != 0, true);
+        schedule_program(prog, n_chars, 1, jobs, jobs_cap, n_jobs, level_off, level_cap, n_levels, outs3, n_outs);
+    })
+}
+
+int fr_schedule_scan_clear_bytes(size_t n_windows, size_t m, int32_t starts, fr_job* jobs, size_t jobs_cap,
+                                 size_t* n_jobs, uint32_t* level_off, size_t level_cap, size_t* n_levels,
+                                 int32_t* outs3, size_t outs_cap, size_t* n_outs) {
+    FR_TRY({
+        NEED(n_jobs && n_levels && n_outs && outs3 && (starts == 0 || starts == 1));
+        NEED(n_windows <= ((size_t)1 << 24) && outs_cap >= (starts ? n_windows : 1));
+        const Program prog = needle_program(MATCH_NEEDLE_WINDOWS, n_windows, m, 0, n_windows, starts != 0, true);
         schedule_program(prog, n_windows * m, 1, jobs, jobs_cap, n_jobs, level_off, level_cap, n_levels, outs3, n_outs);
     })
 }

@@ -13,13 +13,18 @@
 //                  consecutive words taken backwards (two runs where t passes j), as coalesced as
 //                  its stores.  The table (at most 128 selectors, 4 MB) stays in L2; the writes go
 //                  to HBM.
+//                  BYTES (a byte-table needle): term (i, pos, 0) reads table i of 256 entries, N/256
+//                  of them to a selector, whose bit b sits at coefficient j = (i % (N/256)) 256 + b
+//                  of selector i / (N/256) with no box around it, so every j of [0, N) occurs.  The
+//                  extraction formula, the access shape and everything after the two index words are
+//                  the same body; only the setup differs.
 #include <cstring>
 
 #include "device_impl.h"
 
 namespace fr {
 
-template <int N, int K>
+template <int N, int K, bool BYTES>
 __global__ void __launch_bounds__(256) k_select_sum(const uint64_t* __restrict__ table, const uint8_t* __restrict__ text,
                                                     const DevSum* __restrict__ sums, uint64_t* __restrict__ arena,
                                                     int stride) {
@@ -31,8 +36,15 @@ __global__ void __launch_bounds__(256) k_select_sum(const uint64_t* __restrict__
     const int nt = S.n_terms;
     if ((int)threadIdx.x < nt) {
         const int q = S.term[threadIdx.x][0], pos = S.term[threadIdx.x][1], h = S.term[threadIdx.x][2];
-        s_base[threadIdx.x] = q * W;
-        s_j[threadIdx.x] = (int)((text[pos] >> (4 * h)) & 15) * (N / 16);
+        if constexpr (BYTES) {
+            constexpr int TPG = N / 256;  // tables per selector
+            (void)h;
+            s_base[threadIdx.x] = (q / TPG) * W;
+            s_j[threadIdx.x] = (q % TPG) * 256 + (int)text[pos];
+        } else {
+            s_base[threadIdx.x] = q * W;
+            s_j[threadIdx.x] = (int)((text[pos] >> (4 * h)) & 15) * (N / 16);
+        }
     }
     __syncthreads();
     uint64_t acc[PASSES];
@@ -58,7 +70,7 @@ __global__ void __launch_bounds__(256) k_select_sum(const uint64_t* __restrict__
     }
 }
 
-void Device::validate_sums(const DevSum* sums, size_t n, size_t n_sel, size_t text_n) const {
+void Device::validate_sums(const DevSum* sums, size_t n, size_t n_sel, size_t text_n, NeedleForm form) const {
     for (size_t i = 0; i < n; ++i) {
         const DevSum& s = sums[i];
         if (s.n_terms < 1 || s.n_terms > SUM_MAX_TERMS) throw Error(FR_ERR_INVALID, "extract-sum: 1 <= n_terms <= 16");
@@ -69,6 +81,9 @@ void Device::validate_sums(const DevSum* sums, size_t n, size_t n_sel, size_t te
             if (s.term[t][1] < 0 || (size_t)s.term[t][1] >= text_n)
                 throw Error(FR_ERR_INVALID, "extract-sum: content position past the content bound");
             if (s.term[t][2] < 0 || s.term[t][2] > 1) throw Error(FR_ERR_INVALID, "extract-sum: half is 0 or 1");
+            // (a byte table's index was checked against m above: n_sel is the tables bound)
+            if (form == NEEDLE_BYTES && s.term[t][2] != 0)
+                throw Error(FR_ERR_INVALID, "extract-sum: a byte table has no half");
         }
     }
 }
@@ -88,10 +103,14 @@ void Device::bind_text(const uint8_t* text, size_t n) {
 void Device::launch_select_sum(const uint64_t* table, const DevSum* d_sums, size_t n) {
     const hipStream_t s = STREAM;
     const uint8_t* text = cur().text.device();
+    const bool bytes = cur().sel_form == NEEDLE_BYTES;  // the bound needle's form picks the variant
+    const auto launch = [&](auto kernel) {
+        kernel<<<(unsigned)n, 256, 0, s>>>(table, text, d_sums, d_arena_.get(), p_.slot_stride());
+    };
     if (p_.k == 1 && p_.N == 2048)
-        k_select_sum<2048, 1><<<(unsigned)n, 256, 0, s>>>(table, text, d_sums, d_arena_.get(), p_.slot_stride());
+        bytes ? launch(k_select_sum<2048, 1, true>) : launch(k_select_sum<2048, 1, false>);
     else if (p_.k == 2 && p_.N == 1024)
-        k_select_sum<1024, 2><<<(unsigned)n, 256, 0, s>>>(table, text, d_sums, d_arena_.get(), p_.slot_stride());
+        bytes ? launch(k_select_sum<1024, 2, true>) : launch(k_select_sum<1024, 2, false>);
     else
         throw Error(FR_ERR_INVALID, "extract-sum: (k, N) not compiled");
     HIP_CHECK(hipGetLastError());
@@ -101,7 +120,7 @@ void Device::check_sums(const DevSum* host, size_t n) const {
     if (p_.ring != FR_RING_FFT) throw Error(FR_ERR_INVALID, "private search: FFT ring only");
     if (n > (size_t)1 << 24) throw Error(FR_ERR_INVALID, "extract-sum: more than 2^24 sums");
     if (!cur().sel) throw Error(FR_ERR_INVALID, "extract-sum: no selector table bound");
-    validate_sums(host, n, cur().sel_n, cur().text_n);
+    validate_sums(host, n, cur().sel_n, cur().text_n, cur().sel_form);
 }
 
 void Device::run_sums(const DevSum* sums, size_t n) {
@@ -148,7 +167,8 @@ void Device::select_sum_host(const DevNeedle& needle, const uint8_t* text, size_
     }
     const uint64_t* prev = cur().sel;
     const size_t prev_n = cur().sel_n;
-    bind_selectors(needle.words.get(), 2 * needle.m);
+    const NeedleForm prev_form = cur().sel_form;
+    bind_selectors(needle.words.get(), needle.tables(), needle.form);
     try {
         bind_text(text, len);
         check_sums(sums.data(), n);  // before anything is staged or launched
@@ -164,10 +184,10 @@ void Device::select_sum_host(const DevNeedle& needle, const uint8_t* text, size_
         timer.read(&select_sum_ms_);
     } catch (...) {
         (void)hipStreamSynchronize(cur().stream.get());
-        bind_selectors(prev, prev_n);
+        bind_selectors(prev, prev_n, prev_form);
         throw;
     }
-    bind_selectors(prev, prev_n);
+    bind_selectors(prev, prev_n, prev_form);
     for (size_t i = 0; i < n; ++i) read_slot(slots[i], out + i * p_.lwe_len());
 }
 

@@ -83,7 +83,7 @@ struct Fields {
     bool radix = false;  // content: a string, whole characters only
 };
 
-// ---------------------------------------------------------------- the seven layouts
+// ---------------------------------------------------------------- the eight layouts
 constexpr void compact_layout(Cursor& c, const Params& p, Fields& f) {
     c.magic("FRCSKEY1", "compact server key: bad magic");
     c.params(p, "compact server key: parameters do not match the context params");
@@ -154,6 +154,18 @@ constexpr void needle_layout(Cursor& c, const Params& p, Fields& f) {
     c.zeros(8, "needle: reserved bytes are not zero");
 }
 
+const char NEEDLE_BYTES_MAGIC[] = "FRNEEDB1";
+const char NEEDLE_BYTES_LENGTH[] = "byte needle: length is not 64 + 8 ceil(256 m / N) N (fr_needle_bytes_size)";
+constexpr void needle_bytes_layout(Cursor& c, const Params& p, Fields& f) {
+    c.magic(NEEDLE_BYTES_MAGIC, "byte needle: bad magic");
+    c.k_N(p, "byte needle: k, N do not match the context params");
+    c.u64(f.count);
+    c.need([&] { return f.count >= 1 && f.count <= NEEDLE_MAX_CHARS; }, NEEDLE_RANGE);
+    c.need([&] { return f.len == needle_bytes_blob_size(p, (size_t)f.count); }, NEEDLE_BYTES_LENGTH);
+    c.key(f.mask_key);
+    c.zeros(8, "byte needle: reserved bytes are not zero");
+}
+
 using Layout = void (*)(Cursor&, const Params&, Fields&);
 constexpr size_t header_bytes(Layout layout) {
     Cursor c;
@@ -165,7 +177,7 @@ constexpr size_t header_bytes(Layout layout) {
 static_assert(header_bytes(compact_layout) == COMPACT_HEADER && header_bytes(pk_layout) == PK_HEADER &&
               header_bytes(pk_compact_layout) == PKC_HEADER && header_bytes(packed_result_layout) == PKRES_HEADER &&
               header_bytes(packed_compact_layout) == PKCRES_HEADER && header_bytes(content_layout) == CONTENT_HEADER &&
-              header_bytes(needle_layout) == NEEDLE_HEADER);
+              header_bytes(needle_layout) == NEEDLE_HEADER && header_bytes(needle_bytes_layout) == NEEDLE_HEADER);
 
 void write(Layout layout, const Params& p, Fields f, uint8_t* out) {
     Cursor c{nullptr, out};
@@ -374,6 +386,40 @@ void expand_needle(const Params& p, const uint8_t* blob, size_t len, uint64_t* o
     const size_t k = (size_t)p.k, N = (size_t)p.N;
     parallel_for((int)(2 * nb.m), [&](int q) {
         Rng rm(nb.mask_key, STREAM_NEEDLE_MASK);
+        uint64_t* o = out + (size_t)q * (k + 1) * N;
+        for (size_t t = 0; t < k * N; ++t) o[t] = rm.u64((uint64_t)q * k * N + t);
+        for (size_t t = 0; t < N; ++t) o[k * N + t] = get_le64(nb.bodies + 8 * ((size_t)q * N + t));
+    });
+}
+
+// ---------------------------------------------------------------- the byte-table needle
+size_t needle_bytes_blob_size(const Params& p, size_t m) {
+    need(m >= 1 && m <= NEEDLE_MAX_CHARS, NEEDLE_RANGE);
+    need(p.N >= 256 && p.N % 256 == 0, "byte needle: N is not a multiple of 256");
+    return NEEDLE_HEADER + 8 * needle_bytes_selectors(p, m) * (size_t)p.N;
+}
+
+bool is_needle_bytes_blob(const uint8_t* blob, size_t len) {
+    return blob && len >= 8 && !std::memcmp(blob, NEEDLE_BYTES_MAGIC, 8);
+}
+
+void write_needle_bytes_header(const Params& p, size_t m, const RngKey& mask_key, uint8_t* out) {
+    write(needle_bytes_layout, p, {m, 0, mask_key}, out);
+}
+
+NeedleBlob check_needle_bytes_blob(const Params& p, const uint8_t* blob, size_t len) {
+    need(p.ring == FR_RING_FFT, "private search: FFT ring only");
+    need(p.N >= 256 && p.N % 256 == 0, "byte needle: N is not a multiple of 256");
+    need(blob && len >= NEEDLE_HEADER, NEEDLE_BYTES_LENGTH);
+    const Fields f = read(needle_bytes_layout, p, blob, len);
+    return NeedleBlob{f.mask_key, (size_t)f.count, blob + NEEDLE_HEADER};
+}
+
+void expand_needle_bytes(const Params& p, const uint8_t* blob, size_t len, uint64_t* out) {
+    const NeedleBlob nb = check_needle_bytes_blob(p, blob, len);
+    const size_t k = (size_t)p.k, N = (size_t)p.N;
+    parallel_for((int)needle_bytes_selectors(p, nb.m), [&](int q) {
+        Rng rm(nb.mask_key, STREAM_NEEDLE_BYTES_MASK);
         uint64_t* o = out + (size_t)q * (k + 1) * N;
         for (size_t t = 0; t < k * N; ++t) o[t] = rm.u64((uint64_t)q * k * N + t);
         for (size_t t = 0; t < N; ++t) o[k * N + t] = get_le64(nb.bodies + 8 * ((size_t)q * N + t));

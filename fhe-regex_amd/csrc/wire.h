@@ -1,4 +1,4 @@
-// The seven wire blobs (include/fheregex.h states each format): header sizes, blob sizes,
+// The eight wire blobs (include/fheregex.h states each format): header sizes, blob sizes,
 // writers, checkers and the expansions that need no secret; little endian.  What the blobs carry
 // -- keys, ciphertexts, their randomness and rounding -- is keys.h's.  Every check_* throws
 // Error(FR_ERR_INVALID) unless the whole header and the exact length are the context's; it
@@ -103,5 +103,17 @@ NeedleBlob check_needle_blob(const Params& p, const uint8_t* blob, size_t len);
 // check_needle_blob, then every mask from the mask key around the blob's bodies: out has
 // needle_words(p, m) words, [selector][polynomial][N].  Needs no client key.
 void expand_needle(const Params& p, const uint8_t* blob, size_t len, uint64_t* out);
+
+// ---- "FRNEEDB1", the byte-table needle (FFT ring, clear content only): FRNEEDL1's header under
+// its own magic, then the G = ceil(256 m / N) body polynomials of N u64 (N / 256 tables of 256
+// coefficients each per polynomial); exactly 64 + 8 G N bytes
+size_t needle_bytes_blob_size(const Params& p, size_t m);  // Error(FR_ERR_INVALID) unless 1 <= m <= 64
+// true: the blob begins with this format's magic (fr_upload_needle tells the two needles apart)
+bool is_needle_bytes_blob(const uint8_t* blob, size_t len);
+void write_needle_bytes_header(const Params& p, size_t m, const RngKey& mask_key, uint8_t* out /* NEEDLE_HEADER bytes */);
+NeedleBlob check_needle_bytes_blob(const Params& p, const uint8_t* blob, size_t len);  // bodies: G N u64
+// check_needle_bytes_blob, then every mask from the mask key around the blob's bodies: out has
+// needle_bytes_words(p, m) words, [selector][polynomial][N].  Needs no client key.
+void expand_needle_bytes(const Params& p, const uint8_t* blob, size_t len, uint64_t* out);
 
 }  // namespace fr

@@ -222,6 +222,24 @@ _SIGS = {
                                          C.POINTER(C.c_size_t)]),
     "fr_plain_scan_clear": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint16), C.c_size_t, C.c_size_t,
                                       C.c_size_t, C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]),
+    "fr_needle_bytes_size": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fr_encrypt_needle_bytes_keyed": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p,
+                                                C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fr_expand_needle_bytes": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, u64p, C.c_size_t,
+                                         C.POINTER(C.c_size_t)]),
+    "fr_needle_form": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "fr_schedule_find_clear_bytes": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int32,
+                                               C.POINTER(FrJob), C.c_size_t, C.POINTER(C.c_size_t),
+                                               C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t),
+                                               C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fr_schedule_scan_clear_bytes": (C.c_int, [C.c_size_t, C.c_size_t, C.c_int32, C.POINTER(FrJob), C.c_size_t,
+                                               C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.c_size_t,
+                                               C.POINTER(C.c_size_t), C.POINTER(C.c_int32), C.c_size_t,
+                                               C.POINTER(C.c_size_t)]),
+    "fr_plain_find_clear_bytes": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_size_t,
+                                            C.c_size_t, C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]),
+    "fr_plain_scan_clear_bytes": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_size_t,
+                                            C.c_size_t, C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]),
     "fr_dev_pack_mapped": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_int32), C.c_size_t,
                                      C.c_int32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "fr_pack_lwes_mapped": (C.c_int, [C.c_void_p, u64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_size_t,
@@ -970,6 +988,33 @@ class Context:
         _check(lib().fr_expand_needle(self.h, blob, len(blob), _p(out), out.size, C.byref(m)))
         return out
 
+    # ---- byte-table needles: one 256-entry table per character, clear content only
+    def needle_bytes_size(self, m: int) -> int:
+        n = C.c_size_t()
+        _check(lib().fr_needle_bytes_size(self.h, m, C.byref(n)))
+        return n.value
+
+    def encrypt_needle_bytes(self, tables: Sequence[int], seed=None) -> bytes:
+        """fr_encrypt_needle_bytes_keyed: the byte-table needle blob of one 256-bit set per
+        character (needle_tables: bit b of the int accepts byte b); seed as in encrypt_needle"""
+        flat = _tables_bytes(tables)
+        n = C.c_size_t()
+        key = self._compact_key(seed)
+        _check(lib().fr_encrypt_needle_bytes_keyed(self.h, flat, len(tables), key, None, 0, C.byref(n)))
+        buf = C.create_string_buffer(n.value)
+        _check(lib().fr_encrypt_needle_bytes_keyed(self.h, flat, len(tables), key, buf, n.value, C.byref(n)))
+        return buf.raw[:n.value]
+
+    def expand_needle_bytes(self, blob: bytes) -> np.ndarray:
+        """fr_expand_needle_bytes: the selectors [ceil(256 m / N)][k + 1][N] of a byte-table needle
+        blob (no key needed)"""
+        m = C.c_size_t()
+        _check(lib().fr_expand_needle_bytes(self.h, blob, len(blob), None, 0, C.byref(m)))
+        tpg = self.params.N // 256
+        out = np.zeros(((m.value + tpg - 1) // tpg, self.params.k + 1, self.params.N), dtype=np.uint64)
+        _check(lib().fr_expand_needle_bytes(self.h, blob, len(blob), _p(out), out.size, C.byref(m)))
+        return out
+
     def upload_needle(self, blob: bytes) -> "Needle":
         h = C.c_void_p()
         _check(lib().fr_upload_needle(self.h, blob, len(blob), C.byref(h)))
@@ -1349,6 +1394,13 @@ class Needle:
         _check(lib().fr_needle_len(self.h, C.byref(m)))
         return m.value
 
+    @property
+    def form(self) -> int:
+        """fr_needle_form: NEEDLE_NIBBLES or NEEDLE_BYTES"""
+        f = C.c_int32()
+        _check(lib().fr_needle_form(self.h, C.byref(f)))
+        return f.value
+
     def close(self):
         if self.h is not None and self.ctx.h:
             _check(lib().fr_needle_free(self.ctx.h, self.h))
@@ -1381,6 +1433,130 @@ def needle_masks(s: bytes | str, ignore_case: bool = False, any_char: Optional[s
     return out
 
 
+NEEDLE_NIBBLES, NEEDLE_BYTES = 0, 1  # Needle.form
+NEEDLE_MAX_CHARS = 64
+_ALL_BYTES = (1 << 256) - 1
+_SHORTHAND = {
+    "d": sum(1 << b for b in range(0x30, 0x3A)),
+    "w": sum(1 << b for b in list(range(0x30, 0x3A)) + list(range(0x41, 0x5B)) + list(range(0x61, 0x7B)) + [0x5F]),
+    "s": sum(1 << b for b in b" \t\n\r\f\v"),
+}
+_CONTROL = {"t": 9, "n": 10, "r": 13, "f": 12, "v": 11, "0": 0}
+
+
+def _fold_case(t: int) -> int:
+    """a byte set with the other case of every ASCII letter it holds"""
+    for b in range(0x41, 0x5B):
+        if (t >> b | t >> (b | 0x20)) & 1:
+            t |= (1 << b) | (1 << (b | 0x20))
+    return t
+
+
+def needle_tables(pattern: bytes | str, ignore_case: bool = False) -> List[int]:
+    """One 256-bit set per position of a fixed-length pattern (bit b accepts byte b), for a
+    byte-table needle.  One character is consumed per item: a literal; `.`, any byte; `[...]` with
+    ranges and a leading `^` (a `]` placed first and a `-` placed first or last are literals);
+    \\d \\w \\s \\D \\W \\S (ASCII); \\xHH; \\t \\n \\r \\f \\v \\0; an escaped punctuation character.
+    ignore_case gives every ASCII letter of a set both cases, before a class is negated.  Whatever
+    makes the length variable or the form cannot hold raises ValueError naming the character:
+    * + ? | ( ) { }, the anchors ^ and $, an empty or unterminated class, a character past 0xFF,
+    and a pattern of 0 or more than 64 items."""
+    if isinstance(pattern, str):
+        for ch in pattern:
+            if ord(ch) > 255:
+                raise ValueError(f"needle pattern: character {ch!r} is not one byte")
+        s = pattern
+    else:
+        s = bytes(pattern).decode("latin-1")
+    fold = _fold_case if ignore_case else (lambda t: t)
+
+    def escape(i: int, in_class: bool) -> Tuple[int, int, bool]:
+        """the set of the escape whose backslash is at s[i]: (set, next index, is one literal byte)"""
+        if i + 1 >= len(s):
+            raise ValueError("needle pattern: '\\\\' at the end of the pattern")
+        c = s[i + 1]
+        if c.lower() in _SHORTHAND:
+            t = fold(_SHORTHAND[c.lower()])
+            return (t if c.islower() else _ALL_BYTES & ~t), i + 2, False
+        if c == "x":
+            hx = s[i + 2:i + 4]
+            if len(hx) != 2 or any(h not in "0123456789abcdefABCDEF" for h in hx):
+                raise ValueError(f"needle pattern: '\\\\x' at {i} is not followed by two hex digits")
+            return 1 << int(hx, 16), i + 4, True
+        if c in _CONTROL:
+            return 1 << _CONTROL[c], i + 2, True
+        if c.isalnum():
+            raise ValueError(f"needle pattern: escape '\\\\{c}' is not supported")
+        return 1 << ord(c), i + 2, True
+
+    out: List[int] = []
+    i = 0
+    while i < len(s):
+        c = s[i]
+        if c in "*+?|(){}":
+            raise ValueError(f"needle pattern: {c!r} at {i} would make the length variable; a needle is fixed-length")
+        if c in "^$":
+            raise ValueError(f"needle pattern: anchor {c!r} at {i}; a needle matches at every start")
+        if c == ".":
+            out.append(_ALL_BYTES)
+            i += 1
+        elif c == "\\":
+            t, i, lit = escape(i, False)
+            out.append(fold(t) if lit else t)
+        elif c == "[":
+            j = i + 1
+            neg = j < len(s) and s[j] == "^"
+            j += neg
+            t, first = 0, True
+            while True:
+                if j >= len(s):
+                    raise ValueError(f"needle pattern: class '[' at {i} is not closed")
+                if s[j] == "]" and not first:
+                    break
+                first = False
+                if s[j] == "\\":
+                    lo_set, j, lit = escape(j, True)
+                else:
+                    lo_set, j, lit = 1 << ord(s[j]), j + 1, True
+                # a range: a literal, '-', and a literal that is not the closing bracket
+                if lit and j + 1 < len(s) and s[j] == "-" and s[j + 1] != "]":
+                    if s[j + 1] == "\\":
+                        hi_set, j2, hi_lit = escape(j + 1, True)
+                    else:
+                        hi_set, j2, hi_lit = 1 << ord(s[j + 1]), j + 2, True
+                    if not hi_lit:
+                        raise ValueError(f"needle pattern: range at {j} ends in a class escape")
+                    lo, hi = lo_set.bit_length() - 1, hi_set.bit_length() - 1
+                    if hi < lo:
+                        raise ValueError(f"needle pattern: range {chr(lo)!r}-{chr(hi)!r} at {j} is reversed")
+                    lo_set, j = sum(1 << b for b in range(lo, hi + 1)), j2
+                t |= lo_set
+            t = fold(t)
+            t = _ALL_BYTES & ~t if neg else t
+            if not t:
+                raise ValueError(f"needle pattern: class '[' at {i} is empty")
+            out.append(t)
+            i = j + 1
+        elif c == "]":
+            raise ValueError(f"needle pattern: ']' at {i} closes no class")
+        else:
+            out.append(fold(1 << ord(c)))
+            i += 1
+        if len(out) > NEEDLE_MAX_CHARS:
+            raise ValueError(f"needle pattern: more than {NEEDLE_MAX_CHARS} items at {c!r}")
+    if not out:
+        raise ValueError("needle pattern: no item at all")
+    return out
+
+
+def _tables_bytes(tables: Sequence[int]) -> bytes:
+    """32 bytes per 256-bit set: bit b of table i at byte 32 i + b // 8, bit b % 8"""
+    for t in tables:
+        if not 0 <= int(t) <= _ALL_BYTES:
+            raise ValueError("a byte table is a set of the 256 byte values")
+    return b"".join(int(t).to_bytes(32, "little") for t in tables)
+
+
 def _text_bytes(text: bytes | str) -> bytes:
     """clear content as bytes: a str is its latin-1 bytes (one byte per character)"""
     return text.encode("latin-1") if isinstance(text, str) else bytes(text)
@@ -1411,6 +1587,27 @@ def plain_scan_clear(content: bytes | str, masks: Sequence[Tuple[int, int]], sta
     """fr_plain_scan_clear: plain_find_clear by the scan's route (windows classed, the lowered
     programs over the compacted text, every start its class's output): (starts, any)"""
     return _plain_needle(lib().fr_plain_scan_clear, content, masks, start_lo, start_hi)
+
+
+def _plain_needle_bytes(fn, content, tables, start_lo, start_hi) -> Tuple[List[int], int]:
+    b = _text_bytes(content)
+    hi = len(b) if start_hi is None else start_hi
+    out = (C.c_uint8 * max(hi - start_lo, 1))()
+    any_ = C.c_int32()
+    _check(fn(b, len(b), _tables_bytes(tables), len(tables), start_lo, hi, out, C.byref(any_)))
+    return list(out)[:max(hi - start_lo, 0)], any_.value
+
+
+def plain_find_clear_bytes(content: bytes | str, tables: Sequence[int], start_lo: int = 0,
+                           start_hi: Optional[int] = None) -> Tuple[List[int], int]:
+    """fr_plain_find_clear_bytes: plain_find_clear for a byte-table needle (needle_tables)"""
+    return _plain_needle_bytes(lib().fr_plain_find_clear_bytes, content, tables, start_lo, start_hi)
+
+
+def plain_scan_clear_bytes(content: bytes | str, tables: Sequence[int], start_lo: int = 0,
+                           start_hi: Optional[int] = None) -> Tuple[List[int], int]:
+    """fr_plain_scan_clear_bytes: plain_scan_clear for a byte-table needle (needle_tables)"""
+    return _plain_needle_bytes(lib().fr_plain_scan_clear_bytes, content, tables, start_lo, start_hi)
 
 
 def window_classes(text: bytes | str, m: int, start_lo: int = 0, start_hi: Optional[int] = None
@@ -1471,6 +1668,13 @@ class ClientKey:
         ServerKey.upload_needle takes: the server learns len(s) and nothing else.  ignore_case
         and any_char as in needle_masks; `seed` as in encrypt_str"""
         return self.ctx.encrypt_needle(needle_masks(s, ignore_case, any_char), seed)
+
+    def encrypt_needle_classes(self, pattern: bytes | str, ignore_case: bool = False, seed=None) -> bytes:
+        """the private-search query for a fixed-length pattern of byte classes (needle_tables:
+        literals, `.`, `[...]`, \\d \\w \\s, \\xHH) as a byte-table needle blob, for searches over the
+        server's clear text (ServerKey.find_clear*, scan_clear*): the server learns the number of
+        positions and nothing else.  `seed` as in encrypt_str"""
+        return self.ctx.encrypt_needle_bytes(needle_tables(pattern, ignore_case), seed)
 
     def decrypt(self, ct: int) -> int:
         return self.ctx.decrypt_radix(self.ctx.download_radix(ct))
@@ -2044,14 +2248,26 @@ def schedule_find_clear(n_chars: int, m: int, start_lo: int = 0, start_hi: Optio
     return schedule_find(n_chars, m, start_lo, start_hi, starts, _fn="fr_schedule_find_clear")
 
 
-def schedule_scan_clear(n_windows: int, m: int, starts: bool = False) -> Schedule:
+def schedule_find_clear_bytes(n_chars: int, m: int, start_lo: int = 0, start_hi: Optional[int] = None,
+                              starts: bool = False) -> Schedule:
+    """fr_schedule_find_clear_bytes: schedule_find_clear for a byte-table needle (m terms a start)"""
+    return schedule_find(n_chars, m, start_lo, start_hi, starts, _fn="fr_schedule_find_clear_bytes")
+
+
+def schedule_scan_clear_bytes(n_windows: int, m: int, starts: bool = False) -> Schedule:
+    """fr_schedule_scan_clear_bytes: schedule_scan_clear for a byte-table needle"""
+    return schedule_scan_clear(n_windows, m, starts, _fn="fr_schedule_scan_clear_bytes")
+
+
+def schedule_scan_clear(n_windows: int, m: int, starts: bool = False, _fn: str = "fr_schedule_scan_clear"
+                        ) -> Schedule:
     """fr_schedule_scan_clear: the schedule of scan_clear (one output) or of scan_clear_starts'
     plan (Schedule.parts: one output per window) over n_windows windows of m bytes"""
     nj, nl, ns = C.c_size_t(), C.c_size_t(), C.c_size_t()
     cap = max(n_windows, 1)
     outs3 = (C.c_int32 * (3 * cap))()
     args = (n_windows, m, int(starts))
-    fn = lib().fr_schedule_scan_clear
+    fn = getattr(lib(), _fn)
     _check(fn(*args, None, 0, C.byref(nj), None, 0, C.byref(nl), outs3, cap, C.byref(ns)))
     jobs = (FrJob * max(nj.value, 1))()
     off = (C.c_uint32 * (nl.value + 1))()

@@ -683,6 +683,36 @@ int fr_scan_clear_starts(fr_ctx* ctx, const uint8_t* content, size_t n_chars, co
                          size_t start_lo, size_t start_hi, int32_t compact, uint8_t* buf, size_t cap, size_t* written,
                          fr_match_stats* stats);
 int fr_scan_classes(fr_ctx* ctx, uint64_t* classes, uint64_t* padded);
+
+/* ----- byte-table needles: per-position byte classes over clear content (FFT ring) ----- */
+/* Over clear content no rotation touches the needle: the extract-sum reads one coefficient the
+ * server computes from a byte it knows, and that is exact at any coefficient.  A byte-table needle
+ * therefore carries one 0/1 table of the 256 byte values per character -- any class, [0-9], [^x],
+ * \w, not only a product lo_mask x hi_mask -- and N/256 tables share one selector: the phase of
+ * coefficient (i % (N/256)) 256 + b of selector i / (N/256) is T_i[b] 2^59, with no boxes, no
+ * recentring and no negacyclic sign; coefficients past the last table encrypt 0.  A start's AND
+ * reads m terms instead of 2 m: one rotation per start up to m = 16.
+ * Blob: "FRNEEDB1", int32 k, N, u64 m, the 32-byte public mask key, 8 zero bytes, then the
+ * G = ceil(256 m / N) body polynomials of N u64; little endian, exactly 64 + 8 G N bytes
+ * (fr_needle_bytes_size; 16,448 bytes for m = 8 at (1, 2048)).  Mask word t of mask polynomial c
+ * of selector q is u64 number (q k + c) N + t of ChaCha20 stream 13 under the mask key; the noise
+ * (GLWE sigma) is drawn from stream 14 under the call's secret key.  1 <= m <= 64.  The server
+ * learns m: literal, class, case-insensitive and wildcard positions look alike.
+ * fr_encrypt_needle_bytes_keyed (client key needed): 32 bytes per character, bit b of table i =
+ * tables[32 i + b / 8] >> (b % 8) & 1; key and size query as fr_encrypt_needle_keyed.
+ * fr_expand_needle_bytes (no key needed): the G (k+1) N words [selector][polynomial][N]; words
+ * NULL: *m only.  Refusals as the nibble needle's, before anything is allocated.
+ * fr_upload_needle takes either blob (told apart by the magic) and the needle remembers its form
+ * (fr_needle_form).  fr_find_clear, fr_find_clear_starts, fr_scan_clear and fr_scan_clear_starts
+ * accept either form; their plans are kept apart by form.  fr_find and fr_find_starts refuse a
+ * byte-table needle with FR_ERR_INVALID before anything is launched: those searches need rotations
+ * of the needle's tables, which only the nibble form allows. */
+enum { FR_NEEDLE_NIBBLES = 0, FR_NEEDLE_BYTES = 1 };
+int fr_needle_bytes_size(fr_ctx* ctx, size_t m, size_t* bytes);
+int fr_encrypt_needle_bytes_keyed(fr_ctx* ctx, const uint8_t* tables /* 32 per character */, size_t m,
+                                  const uint8_t* key /* NULL: OS CSPRNG */, uint8_t* buf, size_t cap, size_t* written);
+int fr_expand_needle_bytes(fr_ctx* ctx, const uint8_t* blob, size_t len, uint64_t* words, size_t cap_words, size_t* m);
+int fr_needle_form(const fr_needle* needle, int32_t* form);
 /* The classing alone, on the host: for the starts p of [start_lo, min(start_hi, n_chars)),
  * cls[p - start_lo] is the index of p's window text[p .. p + m) among the distinct windows in order
  * of first appearance, or -1 where p + m > n_chars; *n_cls entries are written (cls NULL: none).
@@ -793,6 +823,19 @@ int fr_schedule_scan_clear(size_t n_windows, size_t m, int32_t starts, fr_job* j
  * evaluated over the compacted text, every start given its class's output. */
 int fr_plain_scan_clear(const uint8_t* content, size_t len, const uint16_t* masks, size_t m, size_t start_lo,
                         size_t start_hi, uint8_t* starts_out, int32_t* any);
+/* The same four for a byte-table needle: a start's (a window's) tests are m terms (table i,
+ * position, 0), one extract-sum and one kind-2 job of offset 1 - 2 m per start for m <= 16, else
+ * balanced chunks of the m terms and their AND.  tables: 32 bytes per character. */
+int fr_schedule_find_clear_bytes(size_t n_chars, size_t m, size_t start_lo, size_t start_hi, int32_t starts,
+                                 fr_job* jobs, size_t jobs_cap, size_t* n_jobs, uint32_t* level_off, size_t level_cap,
+                                 size_t* n_levels, int32_t* outs3, size_t outs_cap, size_t* n_outs);
+int fr_schedule_scan_clear_bytes(size_t n_windows, size_t m, int32_t starts, fr_job* jobs, size_t jobs_cap,
+                                 size_t* n_jobs, uint32_t* level_off, size_t level_cap, size_t* n_levels,
+                                 int32_t* outs3, size_t outs_cap, size_t* n_outs);
+int fr_plain_find_clear_bytes(const uint8_t* content, size_t len, const uint8_t* tables, size_t m, size_t start_lo,
+                              size_t start_hi, uint8_t* starts_out, int32_t* any);
+int fr_plain_scan_clear_bytes(const uint8_t* content, size_t len, const uint8_t* tables, size_t m, size_t start_lo,
+                              size_t start_hi, uint8_t* starts_out, int32_t* any);
 
 /* ----- host-only introspection (tests; no device needed) ----- */
 /* Canonical AST string of parse(pattern) (parser.rs:146-185). */
@@ -922,6 +965,8 @@ int fr_dev_blind_rotate_acc(fr_ctx* ctx, const uint64_t* in /* count*(n+1) */, c
  * sum i - 1 in `terms`, and is the sum over them of the sample extract of the needle's selector q
  * at coefficient ((content[pos] >> 4 h) & 15) N/16 -> out: n_sums*(kN+1), wrapping u64, exact.
  * FR_ERR_INVALID for n_terms outside [1, 16], q >= 2 m, pos >= len, h > 1, before any launch.
+ * With a byte-table needle a term is (table i, pos, 0): the extract of selector i / (N/256) at
+ * coefficient (i % (N/256)) 256 + content[pos]; i >= m or a non-zero third word is refused.
  * fr_dev_select_sum_ms: the kernel's HIP-event ms of the last call under fr_set_profiling. */
 int fr_dev_select_sum(fr_ctx* ctx, const fr_needle* needle, const uint8_t* content, size_t len,
                       const int32_t* terms /* 3 per term */, const int32_t* n_terms, size_t n_sums, uint64_t* out);
