@@ -8,6 +8,7 @@
 
 #include "ctx.h"
 #include "rns.h"
+#include "step_sched.h"
 
 using namespace fr;
 
@@ -647,6 +648,8 @@ uint64_t fr_debug_scalar(int32_t op, uint64_t x, uint64_t y) {
             ks_decompose<3, 5>(x, d);
             return (uint64_t)(int64_t)d[y % 5];
         }
+        case 5: return step_sched::put(x, (int)((y >> step_sched::FIELD_BITS) % step_sched::FIELDS), (uint32_t)y);
+        case 6: return step_sched::get(x, (int)(y % step_sched::FIELDS));
         default: return 0;
     }
 }

@@ -28,6 +28,7 @@
 #include "device_impl.h"
 #include "fft.h"
 #include "geo.h"
+#include "step_sched.h"
 
 namespace fr {
 
@@ -456,7 +457,7 @@ __device__ __forceinline__ void key_products(const double (&bre)[2][NB], const d
 //  * latency with key products (k = 1, KP; launches of at most fft_kpre_): k_key_products forms
 //    every step's K_own, K_oth on the idle CUs first; the rotation loads the 2 E products of
 //    the next unskipped step right after the MAC and nothing inside a step: no key, no psi
-//    table, no slot factors; 491 instructions per wave-step against 722, 148 VGPRs.
+//    table, no slot factors; 483 instructions per wave-step against 713, 148 VGPRs.
 //  * pair (k = 1, B = 2; launches between the latency shape's limit and fft_pair_): the
 //    latency geometry with two bootstraps per workgroup.  One set of key loads, twiddle
 //    registers and barriers serves both (the two workgroups a CU would run side by side
@@ -544,6 +545,11 @@ struct FbrShape {
     // k = 1) by dropping the forward twiddle table (its registers load from global memory once)
     // and using the quadrant psi table; its multi-value terms live in the inverse rows after the
     // loop.  (KP: no psi table)
+    // The k = 1 latency shapes walk a packed step schedule (step_sched.h), built in the prologue
+    // from the live-step masks; once it stands, the loop reads abar no more, so the pair shape
+    // stages abar inside its inverse rows too (first written by the first step's inverse
+    // transform, after the barrier that closes the build) and spends the room on the schedule.
+    // (k = 2: its table of next unskipped steps, u16, in the schedule's region)
     struct Lds {
         static constexpr int XBUF = 0;  // B x (K+1) rows of NP complex: bootstrap b, row P at b BS + P NP
         static constexpr int IBUF = LAT ? XBUF + B * BS : XBUF;  // inverse-transform rows (latency shapes: separate)
@@ -551,19 +557,25 @@ struct FbrShape {
         static constexpr int PSI = TW + (B == 1 ? M : 0);        // psi^k, k < NPSI
         static constexpr int TWC = PSI + NPSI;                   // radix-4 products c ca
         static constexpr size_t LUT = 16 * (size_t)(TWC + NTWC);  // [B][16 * MAX_OUT]
-        static constexpr size_t ABAR = LUT + B * 16 * MAX_OUT;    // [B][1026] u16: n (<= 1024), zero-padded to even
+        // latency shapes: bit t % 64 of live[t / 64] is set when step t runs; sched: its entries
+        static constexpr size_t LIVE = LUT + B * 16 * MAX_OUT;  // [MAX_STEPS / 64] u64
+        static constexpr size_t SCHED = LIVE + (LAT ? 8 * (step_sched::MAX_STEPS / 64) : 0);  // [MAX_STEPS + 1] u64
+        static constexpr size_t SCHED_END = SCHED + (LAT ? 8 * (step_sched::MAX_STEPS + 1) : 0);
+        static constexpr size_t ABAR = B == 1 ? SCHED_END : 16 * (size_t)IBUF;  // [B][1026] u16: n (<= 1024), zero-padded to even
         static constexpr size_t ABAR_END = ABAR + B * 2 * 1026;
         // multi-value terms [B][16 MAX_OUT] u32 and their counts [B][MAX_OUT]
         static constexpr size_t WTERMS = B == 1 ? ABAR_END : 16 * (size_t)IBUF;
         static constexpr size_t WCNT = WTERMS + 4 * B * 16 * MAX_OUT;
         static constexpr size_t WCNT_END = WCNT + 4 * B * MAX_OUT;
-        static constexpr size_t NXT = B == 1 ? WCNT_END : ABAR_END;  // [514] u16 (latency shapes): next unskipped step
-        static constexpr size_t BYTES = NXT + 2 * 514;
+        static constexpr size_t BYTES = B == 1 ? WCNT_END : SCHED_END;
     };
-    static_assert(B == 1 || Lds::WCNT_END <= 16 * (size_t)(Lds::IBUF + B * BS),
-                  "pair shape: the terms inside the inverse rows");
-    static_assert(Lds::BYTES == 16 * (size_t)((LAT ? 2 : 1) * B * BS + (B == 1 ? M : 0) + NPSI + NTWC) +
-                                    B * (16 * MAX_OUT + 2 * 1026) + (B == 1 ? 4 * 17 * MAX_OUT : 0) + 2 * 514,
+    static_assert(B == 1 || (Lds::WCNT_END <= 16 * (size_t)(Lds::IBUF + B * BS) &&
+                             Lds::ABAR_END <= 16 * (size_t)(Lds::IBUF + B * BS)),
+                  "pair shape: abar (prologue) and the terms (tail) inside the inverse rows");
+    static_assert(Lds::LIVE % 8 == 0 && Lds::ABAR % 4 == 0 && Lds::WTERMS % 4 == 0, "u64 / u32 regions aligned");
+    static_assert(Lds::BYTES == 16 * (size_t)((LAT ? 2 : 1) * B * BS + (B == 1 ? M : 0) + NPSI + NTWC) + B * 16 * MAX_OUT +
+                                    (LAT ? 8 * (step_sched::MAX_STEPS / 64 + step_sched::MAX_STEPS + 1) : 0) +
+                                    (B == 1 ? 2 * 1026 + 4 * 17 * MAX_OUT : 0),
                   "LDS total: the end of the last region is the sum of the regions");
     static_assert(Lds::BYTES <= (LAT ? 160 * 1024 : 160 * 1024 / TP_GROUPS), "LDS per workgroup of the shape");
 };
@@ -730,7 +742,8 @@ __device__ __forceinline__ void fbr_rotate(const uint64_t* ks, int ks_stride, in
     uint16_t* abar = (uint16_t*)(fsb + L::ABAR);
     uint32_t* wterms = (uint32_t*)(fsb + L::WTERMS);
     int* wcnt = (int*)(fsb + L::WCNT);
-    uint16_t* nxt = (uint16_t*)(fsb + L::NXT);
+    uint64_t* live = (uint64_t*)(fsb + L::LIVE);
+    uint64_t* sched = (uint64_t*)(fsb + L::SCHED);
 
     const int tid = threadIdx.x;
     const int P = __builtin_amdgcn_readfirstlane(tid / T), tl = tid % T;  // wave-uniform polynomial
@@ -867,11 +880,30 @@ __device__ __forceinline__ void fbr_rotate(const uint64_t* ks, int ks_stride, in
     // step ahead -- right after the previous step's MAC, when their registers are dead --
     // so that they have the inverse FFT, the accumulate and the forward FFT to land (a
     // single CU streams ~50 GB/s of key at 3.9 us per step); the others across the
-    // step's own forward FFT.  The next unskipped step comes from the table nxt (no
+    // step's own forward FFT.  The next unskipped step comes from the schedule (no
     // control flow around the prefetch, which keeps it after the MAC's last use).
     // KP: the whole of the next unskipped step's products in that place, nothing loaded inside
     // a step.
     constexpr bool LATPF = NPF > 0;
+    // The latency shapes (every one of them prefetches: LATPF or KP) walk the packed schedule
+    // of step_sched.h, one entry per unskipped step: the entry of the next step is read right
+    // after the MAC, where its step index addresses the prefetch, and is scalar from there on,
+    // so a step starts with t, e_i and e_j in SGPRs and no LDS read in front of its digits.
+    // k = 2 keeps the table of next unskipped steps (nxt, in the schedule's region) and reads
+    // its pairs at the top of the step: walking the schedule, its kernel took 256 VGPRs and
+    // spilled 52 bytes (profiles/step_schedule/README.md).
+    constexpr bool WALK = LAT && K == 1;
+    static_assert(LAT == (LATPF || KP), "every latency shape prefetches the next unskipped step");
+    static_assert(!KP || WALK, "key products: addressed by the schedule's step index, first loaded after its build");
+    uint16_t* nxt = (uint16_t*)sched;  // [MAX_STEPS + 2] u16 (k = 2)
+    static_assert(2 * (step_sched::MAX_STEPS + 2) <= 8 * (step_sched::MAX_STEPS + 1), "nxt inside the schedule's region");
+    auto sched_entry = [&](int i) {  // entry i, wave-uniform
+        const uint64_t v = sched[i];
+        // (the builtin returns int: through uint32_t, or the low half's bit 31 would sign-extend)
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v);
+        const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+        return ((uint64_t)hi << 32) | lo;
+    };
     // step t is skipped when every bootstrap's pair is (0, 0): X^0 acc - acc = 0.  The pair
     // shape runs a step that is zero for one bootstrap only: its factors c - 1 are exact
     // zeros, so its MAC output is 0 and the accumulate adds +-0.
@@ -881,7 +913,29 @@ __device__ __forceinline__ void fbr_rotate(const uint64_t* ks, int ks_stride, in
         for (int b = 0; b < B; ++b) z |= abar[b * 1026 + 2 * t] | abar[b * 1026 + 2 * t + 1];
         return z == 0;
     };
-    if constexpr (LATPF || KP) {
+    uint64_t ent = step_sched::END_ENTRY;  // the entry of the step at hand, then of the next one (uniform)
+    int si = 0;                            // its index in the schedule
+    if constexpr (WALK) {
+        static_assert(NT % 64 == 0, "whole waves: a wave's ballot covers 64 consecutive steps");
+        // the live steps, 64 per wave ballot (uniform trip count: every lane votes)
+        for (int t0 = 0; t0 < steps; t0 += NT) {
+            const int t = t0 + tid;
+            const uint64_t m = __ballot(t < steps && !idle(t));
+            if ((tid & 63) == 0 && t < steps) live[t >> 6] = m;
+        }
+        __syncthreads();
+        // a live step's entry goes to its rank among the live steps; t = steps: the end entry
+        for (int t = tid; t <= steps; t += NT) {
+            const int rank = step_sched::rank_below(live, t);
+            if (t == steps) sched[rank] = step_sched::END_ENTRY;
+            else if (!idle(t)) sched[rank] = step_sched::entry_of<B>(abar, 1026, t);
+        }
+        __syncthreads();
+        ent = sched_entry(0);
+        const int t0 = (int)step_sched::step(ent);
+        for (int gg = 0; gg < NPF; ++gg) load_ggsw(gg, t0 != (int)step_sched::END ? t0 : 0);
+        load_kp(t0 != (int)step_sched::END ? t0 : 0);
+    } else if constexpr (LATPF) {
         for (int t = tid; t <= steps; t += NT) {
             int tt = t;
             while (tt < steps && idle(tt)) ++tt;
@@ -890,10 +944,16 @@ __device__ __forceinline__ void fbr_rotate(const uint64_t* ks, int ks_stride, in
         __syncthreads();
         const int t0 = __builtin_amdgcn_readfirstlane((int)nxt[0]);
         for (int gg = 0; gg < NPF; ++gg) load_ggsw(gg, t0 < steps ? t0 : 0);
-        load_kp(t0 < steps ? t0 : 0);
     }
-    for (int t = 0; t < steps; ++t) {
-        if (idle(t)) continue;  // (uniform branch)
+    // One loop for both forms (the step's body as a function of its own, called from a loop per
+    // form, spilled in every shape).  WALK: the step of the entry at hand, until the end entry; the
+    // post-MAC block leaves the next entry in ent.  Otherwise (k = 2 and the throughput shapes)
+    // every step in turn, skipped behind a uniform branch when idle.
+    auto step_from = [&](int t) { return WALK ? (int)step_sched::step(ent) : t; };
+    auto more = [&](int t) { return WALK ? t != (int)step_sched::END : t < steps; };
+    for (int t = step_from(0); more(t); t = step_from(t + 1)) {
+        if constexpr (!WALK)
+            if (idle(t)) continue;
         BR_STAMP(0);
         // the step's byte offset in the key (uniform: soffset of every load)
         const uint32_t sbase = (uint32_t)__builtin_amdgcn_readfirstlane(t) * ggsw_step_bytes<K, M>();
@@ -908,8 +968,13 @@ __device__ __forceinline__ void fbr_rotate(const uint64_t* ks, int ks_stride, in
         uint32_t ei[B], ej[B];
 #pragma unroll
         for (int b = 0; b < B; ++b) {
-            ei[b] = __builtin_amdgcn_readfirstlane((uint32_t)abar[b * 1026 + 2 * t]);
-            ej[b] = __builtin_amdgcn_readfirstlane((uint32_t)abar[b * 1026 + 2 * t + 1]);
+            if constexpr (WALK) {
+                ei[b] = step_sched::pair_i(ent, b);
+                ej[b] = step_sched::pair_j(ent, b);
+            } else {
+                ei[b] = __builtin_amdgcn_readfirstlane((uint32_t)abar[b * 1026 + 2 * t]);
+                ej[b] = __builtin_amdgcn_readfirstlane((uint32_t)abar[b * 1026 + 2 * t + 1]);
+            }
         }
         double bre[B][2][NB], bim[B][2][NB];
         auto psi_factors = [&]() {
@@ -1006,11 +1071,18 @@ __device__ __forceinline__ void fbr_rotate(const uint64_t* ks, int ks_stride, in
                     for (int r = 0; r <= K; ++r) Bc[gg][r] = Bn[gg][r];
             }
         }
-        if constexpr (LATPF || KP) {  // the next step's key, into the registers the MAC just freed
+        if constexpr (LATPF && !WALK) {
             const int tn = __builtin_amdgcn_readfirstlane((int)nxt[t + 1]);
             __builtin_amdgcn_sched_barrier(0);
             for (int gg = 0; gg < NPF; ++gg) load_ggsw(gg, tn < steps ? tn : t);
-            load_kp(tn < steps ? tn : t);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (WALK) {  // the next step's key, into the registers the MAC just freed
+            ent = sched_entry(++si);  // (this step's pairs were last used by the MAC)
+            const int tn = (int)step_sched::step(ent);
+            __builtin_amdgcn_sched_barrier(0);
+            for (int gg = 0; gg < NPF; ++gg) load_ggsw(gg, tn != (int)step_sched::END ? tn : t);
+            load_kp(tn != (int)step_sched::END ? tn : t);
             __builtin_amdgcn_sched_barrier(0);
         }
         BR_STAMP(3);

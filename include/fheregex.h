@@ -994,7 +994,9 @@ int fr_device_info(fr_ctx* ctx, char* buf, size_t buflen);
 /* Scalar maps shared by host and device code (test hook): op 0 = CRT of the
  * residues of x (identity on [0, Q)), 1 = PBS gadget digit of x mod Q (signed,
  * as u64), 2 = Z_Q -> 2^64 torus of x mod Q (from its residues),
- * 3 = modulus switch of x to 2^y, 4 = keyswitch digit y (0..4) of x (signed, as u64). */
+ * 3 = modulus switch of x to 2^y, 4 = keyswitch digit y (0..4) of x (signed, as u64),
+ * 5 = the step-schedule entry x with its field y >> 12 (0..4) set to y & 0xFFF,
+ * 6 = field y (0..4) of the step-schedule entry x. */
 uint64_t fr_debug_scalar(int32_t op, uint64_t x, uint64_t y);
 /* The slot arena (test hook): synchronises every lane, so that slots whose release was
  * deferred are recycled, then *slots = the slots ever handed out (the high-water mark) and
