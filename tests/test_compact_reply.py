@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import fheregex as F
+from pack_oracle import round16  # the rule, restated: ((x + 2^47) >> 48) mod 2^16
 
 POINTS = [(1, 2048), (2, 1024)]
 POINT_IDS = ["k1n2048", "k2n1024"]
@@ -44,11 +45,6 @@ def weight(ctx):
 
 def signed(x):
     return np.asarray(x, dtype=np.uint64).astype(np.int64)
-
-
-def round16(words):
-    """the rule, restated: ((x + 2^47) >> 48) mod 2^16 (uint64 arithmetic wraps mod 2^64)"""
-    return ((np.asarray(words, dtype=np.uint64) + np.uint64(1 << 47)) >> np.uint64(48)).astype(np.uint16)
 
 
 class Keyed:

@@ -4,7 +4,9 @@ restatement, the wire blobs, and the match-starts front end.
 The packing key has 3 kN rows; row 3 i + l is a GLWE encryption, under the big key read as k
 polynomials, of the constant polynomial s_big[i] 2^(64 - 7 (l + 1)) (include/fheregex.h).
 pack_lwes is the plain-loop packing keyswitch the device must reproduce word for word
-(tests/test_packed_results_gpu.py); here it is pinned by its algebra and by decryption.
+(tests/test_packed_results_gpu.py); here it is pinned by its algebra and by decryption, and
+tests/test_pack_oracle.py holds it word for word to oracle/pack_oracle.py, which shares no code
+with it.
 
 The phase-error bound is derived, not tuned: rounding a mask coefficient to 21 bits leaves a
 uniform error of std 2^43 / sqrt(3), summed over the ~kN/2 set key bits: sqrt(kN/2) 2^43 /
